@@ -16,7 +16,10 @@ relays rank 0's single JSON line.  Documented weak-scaling lines beside the head
     python bench.py --gpus N --workload nba --batch 1024        (BASELINE configs[4]: 1024 trajectories per GPU, 8192 at N=8)
     python bench.py --gpus N --workload peptide --batch 8       (BASELINE configs[3]: 1000-step SDE, 8 trajectories per GPU)
 
-Extra legs on rank 0 at N=1: ``roofline`` / ``roofline2`` (HIP-event timing of every launch of the dominant kernel, the linear1
+A plain run sets up, warms up, times ``--steps`` steps and prints the result line (``--dump-outputs DIR`` also writes the final
+latents of the last timed step as DIR/latents.npy).  Everything else it can measure runs only with ``--full``.
+
+Extra legs on rank 0 at N=1 with ``--full``: ``roofline`` / ``roofline2`` (HIP-event timing of every launch of the dominant kernel, the linear1
 MFMA GEMM, and of linear2, in a separate un-overlapped pass after the timed region), ``roofline_step`` (the whole step's HBM-side bytes, from
 the committed PMC profile, over this run's step time: the step as it is cut into kernels is HBM-bound), ``gpu_small_batch`` (the
 same call at B = 1, 8 and 64), ``stage1`` (device encode / decode
@@ -53,6 +56,7 @@ WORKLOADS = {
                 {"num_steps": 1000}, 8),
 }
 PEAK_BF16_DENSE_TFLOPS = 2500.0  # MI355X_MICROARCH.md, chip-level parameters (dense, no sparsity)
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs writes at most this much
 
 
 def flops_per_eval_per_traj(kw, T, L):
@@ -61,11 +65,31 @@ def flops_per_eval_per_traj(kw, T, L):
     return 6 * n * Cc * D + kw["depth"] * 4 * n * D * (4 * D + 2 * M + L + T)
 
 
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: every array as outdir/<name>.npy in float32.  Above DUMP_LIMIT_BYTES only a fixed seeded sample of whole trajectories
+    (rows of dim 0, in their original order) is written, so two runs with the same arguments write the same rows."""
+    import numpy as np
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if t.numel() * 4 > DUMP_LIMIT_BYTES:
+            keep = max(1, DUMP_LIMIT_BYTES // (t[0].numel() * 4))
+            rows = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            t = t[rows.to(t.device)]
+        np.save(os.path.join(outdir, name + ".npy"), t.cpu().numpy())
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run the extra legs (roofline passes, the whole step against the "
+                                                         "HBM roof, small batches, stage 1, the CPU baseline with its parity check); off: the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step (rank 0: the final latents of the whole job) as DIR/latents.npy, float32; "
+                         f"above {DUMP_LIMIT_BYTES >> 20} MiB a fixed seeded sample of whole trajectories")
     ap.add_argument("--workload", default="md17_bench", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="trajectories per GPU per step (0 = workload default)")
     ap.add_argument("--chunk", type=int, default=0, help="trajectories per pass inside the library (0 = default)")
@@ -77,11 +101,11 @@ def parse_args(argv=None):
     ap.add_argument("--ln-fuse", default="auto", choices=("auto", "on", "off"),
                     help="LayerNorm + modulate inside linear1's activation load (lam_slide_amd.LatentSIV3.set_ln_fuse): auto = on at >= 131 072 tokens "
                          "per GPU (where it is faster) for handles that do not run the tail form, off elsewhere")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-extras", action="store_true", help="skip the small-batch and stage-1 legs")
-    ap.add_argument("--no-roofline", action="store_true", help="skip the per-kernel HIP-event passes (rocprofv3 runs: every launch of the trace then belongs to a warm-up or timed sampling call)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the small-batch and stage-1 legs")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the per-kernel HIP-event passes (rocprofv3 runs: every launch of the trace then belongs to a warm-up or timed sampling call)")
     ap.add_argument("--profile-kernel", type=int, default=0, help="kernel class timed with HIP events (lsl_api.h)")
-    ap.add_argument("--breakdown", action="store_true", help="extra untimed passes: per-kernel-class time shares")
+    ap.add_argument("--breakdown", action="store_true", help="with --full: extra untimed passes, per-kernel-class time shares")
     ap.add_argument("--backend", default="nccl", choices=("nccl", "gloo"), help="gloo only with --stub-compute (launcher test on CPU)")
     ap.add_argument("--stub-compute", action="store_true",
                     help="launcher / collective plumbing test without a GPU: the sampling call is replaced by a trivial CPU op and the "
@@ -91,7 +115,12 @@ def parse_args(argv=None):
     ap.add_argument("--stub-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)  # launcher test: this rank exits with code 7 before the rendezvous
     ap.add_argument("--cpu-worker", type=int, default=0, help=argparse.SUPPRESS)  # internal: one worker of the all-core CPU leg
     ap.add_argument("--cpu-threads", type=int, default=1, help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.breakdown and not args.full:
+        ap.error("--breakdown is a leg of --full")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -291,6 +320,7 @@ def run_rank(args) -> int:
     # batch is world x B trajectories and rank r owns [r B, (r + 1) B); its inputs were generated on its own device above, so the
     # "global" tensor handed to sample_sharded only carries the batch shape (an expanded view, no memory).
     global_shape = torch.empty(1, device=dev).expand(B * world, *init.shape[1:])
+    last = {}  # what the last step handed its caller (--dump-outputs)
 
     def one_step():
         box = {}
@@ -300,7 +330,7 @@ def run_rank(args) -> int:
             box["final"] = sample_call(lo)
             return box["final"]
 
-        sample_sharded(shard_fn, global_shape, dst=0)  # rank 0 gets the [world * B, T, L, C] result, the others None
+        last["latents"] = sample_sharded(shard_fn, global_shape, dst=0)  # rank 0 gets the [world * B, T, L, C] result, the others None
         return box["final"]
 
     def gather_final(final):  # the collective alone (timed outside the timed region): the same call with the sampling replaced by its result
@@ -353,6 +383,8 @@ def run_rank(args) -> int:
         if world > 1:
             dist.destroy_process_group()
         return 0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"latents": last["latents"]})
 
     traj = B * world * args.steps
     value = traj / dt
@@ -397,13 +429,20 @@ def run_rank(args) -> int:
 
     profiled_pass.name = ""
 
-    if not resident and not args.no_roofline:
-        total_ms.value, launches.value = profiled_pass(args.profile_kernel)
     out["config"]["kernels"] = "trajectory-resident (k_resident)" if resident else "general"
-    f_eval = flops_per_eval_per_traj(kw, T, L)
     ws_bytes = lib.lsl_workspace_bytes(net._handle, B, T, L)
     pass_size = lib.lsl_pass_size(net._handle, B, T, L)
     out["config"].update({"trajectories_per_pass": pass_size, "workspace_mib": round(ws_bytes / 2 ** 20, 1)})
+    if not args.full:  # a plain run: the headline figure only, every other leg is --full's
+        out.update({"roofline": None, "cpu_baseline": None})
+        print(json.dumps(out))
+        if world > 1:
+            dist.destroy_process_group()
+        return 0
+
+    if not resident and not args.no_roofline:
+        total_ms.value, launches.value = profiled_pass(args.profile_kernel)
+    f_eval = flops_per_eval_per_traj(kw, T, L)
     passes = -(-B // pass_size)
     block_evals = 2 * kw["depth"] * n_evals                       # launches of each block kernel per pass and sampling call
     launches_total = passes * block_evals

@@ -1,3 +1,4 @@
+import glob
 import os
 import sys
 
@@ -15,11 +16,29 @@ def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
 
 
+class _Parts:
+    """The arrays of one fixture, stored as <stem>.npz alone or followed by <stem>.part2.npz, <stem>.part3.npz, ... (so that no committed
+    file exceeds 1 MiB); ``files`` and ``[name]`` as on one npz file."""
+
+    def __init__(self, path):
+        stem = path[:-len(".npz")]
+        self._where = {}
+        for p in [path] + sorted(glob.glob(glob.escape(stem) + ".part*.npz")):
+            z = np.load(p)
+            for k in z.files:
+                assert k not in self._where, (p, k)
+                self._where[k] = z
+        self.files = list(self._where)
+
+    def __getitem__(self, k):
+        return self._where[k][k]
+
+
 class Fixture:
     """npz fixture with 'group/key' names exposed as nested dicts of torch tensors."""
 
     def __init__(self, name):
-        self.raw = np.load(os.path.join(GOLDEN, name))
+        self.raw = _Parts(os.path.join(GOLDEN, name))
 
     def group(self, prefix):
         out = {}

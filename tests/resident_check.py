@@ -2,9 +2,9 @@
 shape, batch independence of a trajectory's bits, and wall time per 10-update call at B = 1 / 20 / 160 / 1280.
 Usage (GPU box): python tests/resident_check.py   (LSL_LIB=<path> selects another build of the library)"""
 import sys, time, os, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo")); sys.path.insert(0, os.path.join(os.environ.get("GRAFT_REPO_ROOT", "/root/repo"), "tests"))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 from lam_slide_amd import _lib
-if os.environ.get('LSL_LIB'): _lib.LIB_PATH = os.path.join(os.environ.get('GRAFT_REPO_ROOT', '/root/repo'), os.environ['LSL_LIB'])
+if os.environ.get('LSL_LIB'): _lib.LIB_PATH = os.path.join(ROOT, os.environ['LSL_LIB'])
 from lam_slide_amd import CreateTransport, LatentSIV3, SecondStageSampler, Sampler
 from lam_slide_amd.synthetic import seeded_state_dict
 from oracle import harness, latent_net, transport as otr

@@ -2,7 +2,7 @@
 results that differ from the first one (must be 0).  CASES="[(T, L, C, normalize, depth), ...]" selects shapes, LSL_LIB=<path> another
 build of the library.  Usage (GPU box): python tests/resident_reruns.py"""
 import sys, os, torch
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo"); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 from lam_slide_amd import _lib
 if os.environ.get('LSL_LIB'): _lib.LIB_PATH = os.path.join(ROOT, os.environ['LSL_LIB'])
 from lam_slide_amd import CreateTransport, LatentSIV3, Sampler

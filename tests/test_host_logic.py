@@ -230,9 +230,9 @@ def test_two_rank_sharding_over_gloo(tmp_path):
         assert p.returncode == 0, o
 
 
-def test_min_ade_fde_matches_reference_formula():
-    """Executes the reference's own `_compute_errors` (pedestrian.py:178-185, extracted with ast) against the product and the oracle.
-    /root/reference only exists in the build container, so the comparison against the source is skipped elsewhere."""
+def test_min_ade_fde_matches_reference_formula(golden):
+    """The product against the oracle and a brute-force loop, and against what the reference's own `_compute_errors`
+    (pedestrian.py:178-185) returned for these inputs (tests/golden/f14_compute_errors.npz)."""
     from lam_slide_amd import min_ade_fde
     g = torch.Generator().manual_seed(3)
     traj, target = torch.randn(7, 5, 12, 2, generator=g), torch.randn(7, 12, 2, generator=g)
@@ -241,15 +241,9 @@ def test_min_ade_fde_matches_reference_formula():
     assert torch.equal(a, oa) and torch.equal(f, of)
     brute = torch.stack([torch.stack([(traj[n, k] - target[n]).norm(dim=-1).mean() for k in range(5)]).min() for n in range(7)])
     assert torch.allclose(a, brute, atol=1e-6)
-    ref_file = "/root/reference/src/models/composites/second_stage/pedestrian.py"
-    if os.path.exists(ref_file):
-        import ast
-        tree = ast.parse(open(ref_file).read())
-        fn = next(n for n in ast.walk(tree) if isinstance(n, ast.FunctionDef) and n.name == "_compute_errors")
-        ns = {"torch": torch}
-        exec(compile(ast.Module(body=[fn], type_ignores=[]), "<ref:_compute_errors>", "exec"), ns)
-        ra, rf = ns["_compute_errors"](traj, target)
-        assert torch.equal(a, ra) and torch.equal(f, rf)
+    ref = golden("f14_compute_errors.npz")
+    ra, rf = min_ade_fde(ref["traj"], ref["target"])
+    assert torch.equal(ra, ref["ade"]) and torch.equal(rf, ref["fde"])
 
 
 def test_stage1_decoder_packing_on_cpu(golden):
@@ -347,6 +341,49 @@ def test_bench_self_launches_its_ranks(tmp_path):
     # the product path refuses gloo / CPU
     bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--backend", "gloo", "--no-cpu"], env=env, capture_output=True, text=True, timeout=120)
     assert bad.returncode != 0
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain `bench.py` run prints one line with the headline keys and times exactly --steps steps; `--dump-outputs DIR` writes what the
+    last step returned as DIR/latents.npy (float32), the same bytes in two runs with the same arguments.  Sampling call stubbed (no GPU)."""
+    import json
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    dumped = []
+    for run in ("a", "b"):
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--stub-compute",
+                              "--batch", "3", "--dump-outputs", str(tmp_path / run)], env=env, capture_output=True, text=True, timeout=300)
+        assert res.returncode == 0, res.stdout + res.stderr
+        lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, res.stdout
+        out = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in out, k
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0
+        assert out["value"] == pytest.approx(3 * 3 / (out["ms_per_step"] * 3 * 1e-3), rel=1e-9)  # trajectories / timed seconds
+        assert sorted(os.listdir(tmp_path / run)) == ["latents.npy"]
+        dumped.append(np.load(tmp_path / run / "latents.npy"))
+    assert dumped[0].dtype == np.float32 and dumped[0].shape == (3, 4, 4, 32)
+    assert dumped[0].tobytes() == dumped[1].tobytes()
+    for bad in (["--steps", "0"], ["--breakdown"]):  # no timed step to report; --breakdown is a leg of --full
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--stub-compute"] + bad, env=env, capture_output=True, text=True, timeout=120)
+        assert res.returncode == 2 and "error" in res.stderr, (bad, res.stderr)
+
+
+def test_bench_dump_outputs_samples_whole_trajectories_above_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1000)
+    t = torch.arange(50 * 10 * 4, dtype=torch.float64).reshape(50, 10, 4)  # 160 bytes per trajectory in float32: 6 fit
+    bench.dump_outputs(str(tmp_path / "a"), {"latents": t})
+    bench.dump_outputs(str(tmp_path / "b"), {"latents": t})
+    a, b = np.load(tmp_path / "a" / "latents.npy"), np.load(tmp_path / "b" / "latents.npy")
+    assert a.dtype == np.float32 and a.shape == (6, 10, 4) and a.nbytes <= 1000 and a.tobytes() == b.tobytes()
+    rows = (a[:, 0, 0] / 40).astype(int)
+    assert (np.diff(rows) > 0).all() and all(np.array_equal(a[i], t[r].float().numpy()) for i, r in enumerate(rows))
+    small = torch.ones(2, 3)
+    bench.dump_outputs(str(tmp_path / "c"), {"x": small})
+    assert np.array_equal(np.load(tmp_path / "c" / "x.npy"), small.numpy())
 
 
 def test_bench_launcher_fails_fast_when_a_rank_dies_before_the_rendezvous():

@@ -91,7 +91,7 @@ pmcbin)
 workloads)
   cd "$root"
   run() {
-    python3 bench.py --no-cpu --no-extras "$@" 2>&1 | tail -1 | python3 -c "
+    python3 bench.py --full --no-cpu --no-extras "$@" 2>&1 | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read()); c=d['config']; r=d['roofline']
 print('%-18s B=%-5d updates=%-4d  %10.2f traj/s  %9.3f ms/call  whole-path %6.1f TFLOP/s (%.1f %% of bf16 peak)' % (c['workload'], c['batch_per_gpu'], c['state_updates'], d['value'], d['ms_per_step'], r['whole_path_tflops'], 100*r['whole_path_frac']))"
@@ -113,7 +113,7 @@ ab)
   args=$1; shift
   script=bench.py; [ -n "${EXP:-}" ] && script=tools/bench_exp.py   # EXP=1: the -DLSL_EXPERIMENTS build (tuning knobs, probes)
   for arm in "$@"; do  # `env` scopes every variable of the arm to its own process
-    env $arm python3 $script $args --no-cpu --no-extras --breakdown 2>&1 | tail -1 | short_line "[$arm]"
+    env $arm python3 $script $args --full --no-cpu --no-extras --breakdown 2>&1 | tail -1 | short_line "[$arm]"
   done
   ;;
 libab)
@@ -125,7 +125,7 @@ libab)
   for round in 1 2; do
     for lib in "$@"; do
       if [ "$lib" = product ]; then cp "$keep" lam_slide_amd/liblamslide_hip.so; else cp "$lib" lam_slide_amd/liblamslide_hip.so; fi
-      python3 bench.py $args --no-cpu --no-extras --breakdown 2>&1 | tail -1 | short_line "$lib"
+      python3 bench.py $args --full --no-cpu --no-extras --breakdown 2>&1 | tail -1 | short_line "$lib"
     done
   done
   ;;

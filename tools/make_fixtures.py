@@ -24,6 +24,7 @@ Fixture families:
                     stand-ins): stage-1 inputs -> encode -> conditioning -> 5 Euler updates -> decode, with the initial noise fixed
 """
 import ast
+import glob
 import os
 import sys
 import tempfile
@@ -69,6 +70,9 @@ os.makedirs(OUT, exist_ok=True)
 torch.set_grad_enabled(False)
 
 
+PART_BYTES = 900_000  # raw bytes of arrays per fixture file (random fp32 compresses to ~90 %)
+
+
 def npz(name, **arrays):
     flat = {}
     for k, v in arrays.items():
@@ -77,9 +81,22 @@ def npz(name, **arrays):
                 flat[f"{k}/{kk}"] = vv.detach().cpu().numpy() if torch.is_tensor(vv) else np.asarray(vv)
         else:
             flat[k] = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
-    path = os.path.join(OUT, name)
-    np.savez_compressed(path, **flat)
-    print(f"wrote {name}: {os.path.getsize(path)/1024:.0f} KiB, {len(flat)} arrays")
+    # above PART_BYTES of arrays the fixture is stored as <stem>.npz, <stem>.part2.npz, ... (tests/conftest.py merges them): no committed
+    # file exceeds 1 MiB.  Arrays go to the first part with room, largest first.
+    stem = os.path.join(OUT, name[:-len(".npz")])
+    for old in glob.glob(glob.escape(stem) + ".part*.npz"):
+        os.remove(old)
+    parts = []
+    for k in sorted(flat, key=lambda k: -flat[k].nbytes):
+        part = next((q for q in parts if sum(a.nbytes for a in q.values()) + flat[k].nbytes <= PART_BYTES), None)
+        if part is None:
+            part = {}
+            parts.append(part)
+        part[k] = flat[k]
+    for i, part in enumerate(parts):
+        path = stem + (".npz" if i == 0 else f".part{i + 1}.npz")
+        np.savez_compressed(path, **part)
+        print(f"wrote {os.path.basename(path)}: {os.path.getsize(path)/1024:.0f} KiB, {len(part)} arrays")
 
 
 def rel(a, b):
