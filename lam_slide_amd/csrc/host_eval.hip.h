@@ -1,5 +1,6 @@
-// Host side, part 3 of 4: the kernel sequence of one network evaluation (conditioning tables, sub-blocks, embedding, head), of a pass, and
-// of the trajectory-resident sampler; argument checks of a call.  Inside the anonymous namespace opened by host_common.hip.h.
+// Host side, part 3 of 4: the plan of a pass (which kernels its sub-blocks run, checked before the first launch); the kernel sequence of one
+// network evaluation (conditioning tables, sub-blocks, embedding, head), of a pass, and of the trajectory-resident sampler; argument checks of
+// a call.  Inside the anonymous namespace opened by host_common.hip.h.
 #pragma once
 
 // ---- pieces of one evaluation ----------------------------------------------------------------------
@@ -86,71 +87,139 @@ void run_tables(const lsl_model *m, const Workspace &ws, int T, int L, hipStream
     }
 }
 
-// one ParallelMLPAttentionV2 sub-block on h (in place): LN+modulate -> linear1 -> attention -> linear2
-// a_ready: ws.a already holds this sub-block's LayerNorm + modulate (written by the previous sub-block's linear2); fuse_next: let this
-// sub-block's linear2 write the next one's when the launch allows it (*a_written reports whether it did)
-int run_block(lsl_model *m, const Workspace &ws, int bi, float *h, const float *mods, int mod_stride, int bc, int T, int L,
-              hipStream_t st, bool a_ready = false, bool fuse_next = false, bool *a_written = nullptr, bool stop_before_linear2 = false,
-              bool stats_ready = false, bool *stats_written = nullptr) {
+// ---- the plan of a pass: which kernels every sub-block runs -----------------------------------------
+
+// A network evaluation (lsl_forward, lsl_sample*), lsl_debug_block (one sub-block) or lsl_debug_taps (one sub-block up to its attention)
+enum class PlanMode { eval, debug_block, debug_taps };
+enum class Lin2Kind { none, tail, ws, gemm };  // k_tail (the whole back half), k_linear2_ws, the tile GEMM (EpiLinear2)
+
+// Decided once per pass size, before the call's first launch; run_eval / run_block only read it.  Every choice depends on the model, the
+// handle's forms (tail, ln_fuse), T, L, the pass size and the mode - the forms whose rounding differs (tail, ln_fuse) never on the batch.
+struct PassPlan {
+    PlanMode mode;
+    int bc, n, npad, T, L, mod_stride, blocks;  // (npad: n rounded up to whole 256-token tiles; blocks: 2 * depth)
+    bool tail;  // k_tail runs the back half of every sub-block and writes the next one's LayerNorm + modulate; linear1 computes q | k | v only
+    int F1;     // linear1's output features
+    bool lin1_ts;    // token-stationary linear1 (k_linear1_ts), else the tile GEMM (EpiLinear1)
+    int lin1_waves;  // its waves per workgroup (linear1_ts_waves)
+    bool ln_stats;   // ln_fuse handles: k_linear2_ws leaves the rows' statistics for the next sub-block, whose linear1 normalises on load
+    bool emb_stats;  // ... and the embedding leaves them for the first sub-block
+    bool planes[2];  // q / k / v as head-major planes: [spatial, temporal] sub-blocks
+    Lin2Kind lin2;
+    Lin2Grid l2grid;  // lin2 == ws
+
+    bool a_from_tail(int bi) const { return mode == PlanMode::eval && tail && bi > 0; }  // ws.a written by the previous sub-block's k_tail
+    bool lin1_lnf(int bi) const { return mode == PlanMode::eval && ln_stats && (bi > 0 || emb_stats); }  // no LayerNorm launch, ws.a unused
+    bool lin2_stats(int bi) const { return ln_stats && bi + 1 < blocks; }
+};
+
+// The plan of a pass of bc trajectories through sub-blocks [0, 2 depth) (eval) or sub-block `block` (the debug modes).  Refuses (-3) a pass
+// too large for the kernels' 32-bit arithmetic, with the message of the first check a sub-block's launches would meet.
+int plan_pass(const lsl_model *m, const Workspace &ws, int bc, int T, int L, int mod_stride, PlanMode mode, int block, PassPlan &p) {
+    const lsl_model_desc &d = m->d;
+    const int D = d.hidden, n = bc * T * L;
+    p = PassPlan{};
+    p.mode = mode;
+    p.bc = bc;
+    p.n = n;
+    p.npad = (n + 255) & ~255;
+    p.T = T;
+    p.L = L;
+    p.mod_stride = mod_stride;
+    p.blocks = 2 * d.depth;
+    p.tail = m->tail && mode != PlanMode::debug_taps;  // (the taps hand out the GELU'd mlp half of z)
+    p.F1 = p.tail ? 3 * m->HHD : m->F1;
+    p.lin1_ts = linear1_ts_ok(d.head_dim_pad, D, p.F1, m->HHD, n);
+    p.lin1_waves = linear1_ts_waves(D, n);
+    // (never with tail: k_tail reads `a` itself; the statistics come from k_linear2_ws)
+    p.ln_stats = m->ln_fuse && !m->tail && ws.w2p && mode != PlanMode::debug_taps &&
+                 linear1_lnf_ok(d.head_dim_pad, D, m->F1, m->HHD, n, T * L, mod_stride);
+    // (models without the in-place LayerNorm behind the embedding)
+    p.emb_stats = p.ln_stats && mode == PlanMode::eval && !d.normalize && embed_stats_ok(d.in_dim, D);
+    for (int t = 0; t < 2; ++t) p.planes[t] = !m->attention_linear && qkv_planes_ok(d.head_dim_pad, D, d.heads, t ? T : L, t != 0, p.lin1_ts);
+    const bool ws_reach = ws.w2p && (unsigned long long)n * (unsigned)(4 * D) < (1ull << 32);  // (k_linear2_ws: 32-bit byte offsets into h)
+    if (ws_reach) p.l2grid = linear2_ws_grid(D, n, T * L, mod_stride == 0);
+    const bool on_ws = ws_reach && p.l2grid.gate_rows <= linear2_ws_max_gate_rows(m->K2);
+    p.lin2 = mode == PlanMode::debug_taps ? Lin2Kind::none : p.tail ? Lin2Kind::tail : on_ws ? Lin2Kind::ws : Lin2Kind::gemm;
+
+    const int b0 = mode == PlanMode::eval ? 0 : block, b1 = mode == PlanMode::eval ? p.blocks : block + 1;  // the sub-blocks the call runs
+    for (int bi = b0; bi < b1; ++bi) {
+        const int temporal = bi & 1, pdiv = temporal ? L : 1, pmod = temporal ? T : L;
+        // position of token n along the attended axis = (n / pdiv) % pmod, done with multiply-high in the epilogue: exact while n * d < 2^32
+        if ((unsigned long long)n * (unsigned)std::max(pdiv, pmod) >= (1ull << 32)) return fail(-3, "pass too large for the position arithmetic");
+        // head-major planes are addressed with 32-bit per-lane byte offsets over the whole q | k | v buffer (k_lin1.hip.h flush, k_attn.hip.h
+        // stream requests): a pass set larger than that through lsl_model_set_chunk / LSL_CHUNK_TRAJ is refused, never wrapped
+        if (p.planes[temporal] && (unsigned long long)p.npad * 3ull * (unsigned)m->HHD * 2ull >= (1ull << 32))
+            return fail(-3, "pass too large for the q/k/v plane offsets (%d tokens: at most %llu with this model)", n, (unsigned long long)((1ull << 32) / (6ull * (unsigned)m->HHD)) - 256);
+        if (p.lin2 == Lin2Kind::none) continue;
+        if ((unsigned long long)n * (unsigned)(T * L) >= (1ull << 32)) return fail(-3, "pass too large for the trajectory arithmetic");
+        if (p.tail && (unsigned long long)p.npad * (unsigned)(4 * D) >= (1ull << 32)) return fail(-3, "pass too large for the residual-stream offsets");
+        // (which LayerNorm form the next sub-block runs must not depend on the launch: a pass the weight-stationary kernel cannot take - more
+        // trajectories per token range than its gate table holds - is refused on ln_fuse handles, never served by the other form)
+        if (p.lin2_stats(bi) && !on_ws) {
+            if (ws_reach) return fail(-3, "ln_fuse: a pass of %d tokens has too many trajectories per token range for k_linear2_ws; use smaller passes (lsl_model_set_chunk)", n);
+            return fail(-3, "ln_fuse: pass too large for the residual-stream offsets (%d tokens)", n);
+        }
+    }
+    return 0;
+}
+
+// The plans of a call's passes: `chunk` trajectories, and the rest of the batch when B is not a multiple of it
+struct CallPlans {
+    PassPlan full, rest;
+    const PassPlan &of(int bc) const { return bc == full.bc ? full : rest; }
+};
+int plan_call(const lsl_model *m, const Workspace &ws, const lsl_io *io, int chunk, int mod_stride, CallPlans &cp) {
+    if (int rc = plan_pass(m, ws, chunk, io->T, io->L, mod_stride, PlanMode::eval, 0, cp.full)) return rc;
+    if (io->B % chunk) return plan_pass(m, ws, io->B % chunk, io->T, io->L, mod_stride, PlanMode::eval, 0, cp.rest);
+    return 0;
+}
+
+// one ParallelMLPAttentionV2 sub-block on ws.h (in place): LN+modulate -> linear1 -> attention -> linear2
+int run_block(lsl_model *m, const Workspace &ws, const PassPlan &p, int bi, const float *mods, hipStream_t st) {
     const lsl_model_desc &d = m->d;
     const lsl_block_weights &bw = m->blocks[bi];
-    const int D = d.hidden, n = bc * T * L, layer = bi / 2, temporal = bi & 1;
+    const int D = d.hidden, n = p.n, T = p.T, L = p.L, mod_stride = p.mod_stride, layer = bi / 2, temporal = bi & 1;
     const float *mbase = mods + (size_t)layer * 6 * D + (temporal ? 3 * D : 0);  // shift, scale, gate
-    // handles with lsl_model_set_ln_fuse: linear1 normalises the fp32 residual stream on load (no LayerNorm launch, ws.a unused); never for
-    // the debug taps (which hand out `a`) and only on the workspace's own padded stream
-    const bool tail_m = m->tail && ws.wtail && !stop_before_linear2;
-    // (every condition depends on the model and on T, L only - never on the batch: a trajectory's bits must not)
-    const bool lnf_shape = m->ln_fuse && !tail_m && ws.lnstat && ws.w2p && h == ws.h &&  // (k_tail reads `a` itself; the statistics come from k_linear2_ws)
-                           linear1_lnf_ok(d.head_dim_pad, D, m->F1, m->HHD, n, T * L, mod_stride);
-    const bool lnf = lnf_shape && stats_ready && !a_ready && !stop_before_linear2;  // ws.lnstat holds the statistics of h (the previous linear2's)
-    if (stats_written) *stats_written = false;
-    if (!a_ready && !lnf) {
+    const bool lnf = p.lin1_lnf(bi);  // (ws.lnstat holds the statistics of h)
+    if (!p.a_from_tail(bi) && !lnf) {
         m->prof.begin(3, st);
-        DISPATCH_D(D, launch_ln_mod_t, ws.a, h, mbase, mbase + D, mod_stride, n, T * L, st);
+        DISPATCH_D(D, launch_ln_mod_t, ws.a, ws.h, mbase, mbase + D, mod_stride, n, T * L, st);
         m->prof.end(3, st);
     }
     m->prof.begin(0, st);
 
     // softmax attention: log2(e) / sqrt(head_dim) rides on q (the kernels use exp2); attention_linear takes the plain normalised, rotated q
     const float premul = m->attention_linear ? 1.0f : (float)(1.4426950408889634 / std::sqrt((double)d.head_dim));
-    // position of token n along the attended axis = (n / pdiv) % pmod, done with multiply-high in the epilogue: exact while
-    // n * d < 2^32, and n < 2^18 (pass size) with d <= T or L
-    const int pdiv = temporal ? L : 1, pmod = temporal ? T : L;
+    const int pdiv = temporal ? L : 1, pmod = temporal ? T : L;  // position of token n = (n / pdiv) % pmod (plan_pass: the range check)
     auto magic_of = [](int dv) { return dv == 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)dv + 1); };
-    if ((unsigned long long)n * (unsigned)std::max(pdiv, pmod) >= (1ull << 32)) return fail(-3, "pass too large for the position arithmetic");
-    // tail models (and never the debug taps, which hand out the GELU'd mlp half of z): linear1 computes q | k | v only
-    const bool tail = tail_m;
-    const int F1 = tail ? 3 * m->HHD : m->F1;
-    const bool lin1_ts = linear1_ts_ok(d.head_dim_pad, D, F1, m->HHD, n);
-    const int npad = (n + 255) & ~255;
-    const bool planes = !m->attention_linear && qkv_planes_ok(d.head_dim_pad, D, d.heads, temporal ? T : L, temporal != 0, lin1_ts);
-    // head-major planes are addressed with 32-bit per-lane byte offsets over the whole q | k | v buffer (k_lin1.hip.h flush, k_attn.hip.h
-    // stream requests): a pass set larger than that through lsl_model_set_chunk / LSL_CHUNK_TRAJ is refused, never wrapped
-    if (planes && (unsigned long long)npad * 3ull * (unsigned)m->HHD * 2ull >= (1ull << 32)) return fail(-3, "pass too large for the q/k/v plane offsets (%d tokens: at most %llu with this model)", n, (unsigned long long)((1ull << 32) / (6ull * (unsigned)m->HHD)) - 256);
-    if (lin1_ts) {
-        const Lin1Args la{(const u16 *)bw.w1, lnf ? (const u16 *)h : ws.a, bw.b1, ws.rope_qk + (size_t)(2 * bi) * ws.rope_qk_stride,
-                          ws.rope_qk + (size_t)(2 * bi + 1) * ws.rope_qk_stride, ws.qkv, ws.z, F1, n, m->HHD, d.mlp_dim,
-                          pdiv, pmod, magic_of(pdiv), magic_of(pmod), 1.0f / d.head_dim, premul, 1, 0, planes ? 1 : 0, npad,
+    const bool planes = p.planes[temporal];
+    if (p.lin1_ts) {
+        const Lin1Args la{(const u16 *)bw.w1, lnf ? (const u16 *)ws.h : ws.a, bw.b1, ws.rope_qk + (size_t)(2 * bi) * ws.rope_qk_stride,
+                          ws.rope_qk + (size_t)(2 * bi + 1) * ws.rope_qk_stride, ws.qkv, ws.z, p.F1, n, m->HHD, d.mlp_dim,
+                          pdiv, pmod, magic_of(pdiv), magic_of(pmod), 1.0f / d.head_dim, premul, 1, 0, planes ? 1 : 0, p.npad,
                           ws.lnstat, mbase, mbase + D, mod_stride, T * L, magic_of(T * L)};
         if (lnf) {
             launch_linear1_lnf(d.head_dim_pad, D, la, st);
-            m->prof.label(0, "k_linear1_ts<%d, %d, 8, true>%s", d.head_dim_pad, D, tail ? " (LayerNorm | q | k | v)" : " (LayerNorm fused)");
+            m->prof.label(0, "k_linear1_ts<%d, %d, 8, true> (LayerNorm fused)", d.head_dim_pad, D);
         } else {
-            launch_linear1_ts(d.head_dim_pad, D, la, st);
-            m->prof.label(0, "k_linear1_ts<%d, %d, %d>%s", d.head_dim_pad, D, linear1_ts_waves(D, n), tail ? " (q | k | v)" : "");
+            launch_linear1_ts(d.head_dim_pad, D, p.lin1_waves, la, st);
+            m->prof.label(0, "k_linear1_ts<%d, %d, %d>%s", d.head_dim_pad, D, p.lin1_waves, p.tail ? " (q | k | v)" : "");
         }
-    } else if (d.head_dim_pad == 32) {
-        EpiLinear1<32> e{bw.b1, bw.qs, bw.ks, temporal ? ws.rope_t : ws.rope_l, ws.rope_qk + (size_t)(2 * bi) * ws.rope_qk_stride,
-                         ws.rope_qk + (size_t)(2 * bi + 1) * ws.rope_qk_stride, ws.qkv, ws.z, m->HHD, d.mlp_dim,
-                         pdiv, pmod, magic_of(pdiv), magic_of(pmod), 1.0f / d.head_dim, premul, 0};
-        launch_gemm((const u16 *)bw.w1, ws.a, F1, n, D, e, st, m->HHD);
     } else {
-        EpiLinear1<16> e{bw.b1, bw.qs, bw.ks, temporal ? ws.rope_t : ws.rope_l, ws.rope_qk + (size_t)(2 * bi) * ws.rope_qk_stride,
-                         ws.rope_qk + (size_t)(2 * bi + 1) * ws.rope_qk_stride, ws.qkv, ws.z, m->HHD, d.mlp_dim,
-                         pdiv, pmod, magic_of(pdiv), magic_of(pmod), 1.0f / d.head_dim, premul, 0};
-        launch_gemm((const u16 *)bw.w1, ws.a, F1, n, D, e, st, m->HHD);
+        if (d.head_dim_pad == 32) {
+            EpiLinear1<32> e{bw.b1, bw.qs, bw.ks, temporal ? ws.rope_t : ws.rope_l, ws.rope_qk + (size_t)(2 * bi) * ws.rope_qk_stride,
+                             ws.rope_qk + (size_t)(2 * bi + 1) * ws.rope_qk_stride, ws.qkv, ws.z, m->HHD, d.mlp_dim,
+                             pdiv, pmod, magic_of(pdiv), magic_of(pmod), 1.0f / d.head_dim, premul, 0};
+            launch_gemm((const u16 *)bw.w1, ws.a, p.F1, n, D, e, st, m->HHD);
+        } else {
+            EpiLinear1<16> e{bw.b1, bw.qs, bw.ks, temporal ? ws.rope_t : ws.rope_l, ws.rope_qk + (size_t)(2 * bi) * ws.rope_qk_stride,
+                             ws.rope_qk + (size_t)(2 * bi + 1) * ws.rope_qk_stride, ws.qkv, ws.z, m->HHD, d.mlp_dim,
+                             pdiv, pmod, magic_of(pdiv), magic_of(pmod), 1.0f / d.head_dim, premul, 0};
+            launch_gemm((const u16 *)bw.w1, ws.a, p.F1, n, D, e, st, m->HHD);
+        }
+        m->prof.label(0, "k_gemm_glds<EpiLinear1<%d>> (tiling %d)", d.head_dim_pad, gemm_variant<EpiLinear1<32>>(p.F1, D, n));
     }
-    if (!lin1_ts) m->prof.label(0, "k_gemm_glds<EpiLinear1<%d>> (tiling %d)", d.head_dim_pad, gemm_variant<EpiLinear1<32>>(F1, D, n));
     m->prof.end(0, st);
     static const int nt_mask = tune_int("LSL_NT", 3);
     AttnArgs aa{};
@@ -166,12 +235,12 @@ int run_block(lsl_model *m, const Workspace &ws, int bi, float *h, const float *
     aa.qmax2 = ws.kmax2 + 2 * d.depth + bi;
     aa.premul = premul;
     aa.planes = planes ? 1 : 0;
-    aa.npad = npad;
+    aa.npad = p.npad;
     aa.bound = attn_bound == 2 || (attn_bound == 1 && (temporal ? T : L) > 96);  // short axes: the max pass is one or two tiles, cheaper than the norms
     if (!temporal) {  // sequences (b,t), positions l
-        aa.S = L; aa.n_seq = bc * T; aa.inner = 1; aa.outer_stride = L; aa.pos_stride = 1;
+        aa.S = L; aa.n_seq = p.bc * T; aa.inner = 1; aa.outer_stride = L; aa.pos_stride = 1;
     } else {          // sequences (b,l), positions t
-        aa.S = T; aa.n_seq = bc * L; aa.inner = L; aa.outer_stride = T * L; aa.pos_stride = L;
+        aa.S = T; aa.n_seq = p.bc * L; aa.inner = L; aa.outer_stride = T * L; aa.pos_stride = L;
     }
     m->prof.begin(2, st);
     if (m->attention_linear) {
@@ -182,98 +251,82 @@ int run_block(lsl_model *m, const Workspace &ws, int bi, float *h, const float *
     m->prof.label(2, "%s", m->attention_linear ? "k_attention_linear" : attention_stream_mode(aa.S, aa.H) || attention_grouped_ok(aa) ? "k_attention_stream" : "k_attention_rows / k_attention_tiny / k_attention");
     m->prof.end(2, st);
 
-    if (stop_before_linear2) {  // (lsl_debug_taps)
+    if (p.lin2 == Lin2Kind::none) {  // (lsl_debug_taps)
         LSL_CHECK_LAUNCH("block");
         return 0;
     }
     m->prof.begin(1, st);
-    if ((unsigned long long)n * (unsigned)(T * L) >= (1ull << 32)) return fail(-3, "pass too large for the trajectory arithmetic");
-    if (tail) {  // up-projection -> GELU -> down-projection + out-projection + gated residual + the next sub-block's LayerNorm + modulate
-        if (h != ws.h) return fail(-3, "the tail kernel runs on the workspace's residual stream");
-        if ((unsigned long long)npad * (unsigned)(4 * D) >= (1ull << 32)) return fail(-3, "pass too large for the residual-stream offsets");
+    if (p.lin2 == Lin2Kind::tail) {  // up-projection -> GELU -> down-projection + out-projection + gated residual + the next sub-block's LayerNorm + modulate
         const bool next = bi + 1 < 2 * d.depth;
         const float *nb = mods + (size_t)((bi + 1) / 2) * 6 * D + (((bi + 1) & 1) ? 3 * D : 0);  // next sub-block: shift, scale
-        const TailArgs ta{ws.wtail + (size_t)bi * ws.wtail_stride, ws.a, ws.z, bw.b1 + 3 * m->HHD, bw.b2, mbase + 2 * D, h, next ? ws.a : nullptr,
+        const TailArgs ta{ws.wtail + (size_t)bi * ws.wtail_stride, ws.a, ws.z, bw.b1 + 3 * m->HHD, bw.b2, mbase + 2 * D, ws.h, next ? ws.a : nullptr,
                           nb, nb + D, n, d.mlp_dim, m->K2, mod_stride, T * L, magic_of(T * L)};
         launch_tail(ta, st);
         m->prof.label(1, "k_tail<%d, %d>", D, m->HHD);
-        if (a_written) *a_written = next;
         m->prof.end(1, st);
         LSL_CHECK_LAUNCH("block (tail)");
         return 0;
     }
-    const bool fuse = fuse_next && !lnf_shape && bi + 1 < 2 * d.depth && linear2_can_fuse_ln(D, n, m->K2);  // (where the ln_fuse form applies, linear1 normalises)
-    const float *nbase = mods + (size_t)((bi + 1) / 2) * 6 * D + (((bi + 1) & 1) ? 3 * D : 0);  // next sub-block: shift, scale
-    bool on_ws = false;
-    if (ws.w2p && !fuse && (unsigned long long)n * (unsigned)(4 * D) < (1ull << 32)) {  // (32-bit byte offsets into h)
+    if (p.lin2 == Lin2Kind::ws) {
         // ln_fuse handles: the rows' statistics for the NEXT sub-block's LayerNorm (inside its linear1) leave with the update
-        const bool stats = lnf_shape && bi + 1 < 2 * d.depth && !stop_before_linear2;
-        const Lin2Args l2{ws.w2p + (size_t)bi * D * m->K2, ws.z, bw.b2, mbase + 2 * D, h, D, n, mod_stride, T * L, magic_of(T * L), 0, 0, 0,
-                          stats ? ws.lnparts : nullptr, npad};
-        on_ws = launch_linear2_ws(m->K2, l2, mod_stride == 0, st);
-        if (on_ws) m->prof.label(1, stats ? "k_linear2_ws<%d> (+ row statistics)" : "k_linear2_ws<%d>", m->K2);
-        if (on_ws && stats) {
-            hipLaunchKernelGGL(k_ln_finalize, dim3((n + 255) / 256), dim3(256), 0, st, ws.lnstat, ws.lnparts, D / 32, npad, n, 32.0f);
-            if (stats_written) *stats_written = true;
-        }
-        // (which LayerNorm form the next sub-block runs must not depend on the launch: a pass the weight-stationary kernel cannot take - more
-        // trajectories per token range than its gate table holds - is refused on ln_fuse handles, never served by the other form)
-        if (stats && !on_ws) return fail(-3, "ln_fuse: a pass of %d tokens has too many trajectories per token range for k_linear2_ws; use smaller passes (lsl_model_set_chunk)", n);
-    } else if (lnf_shape && bi + 1 < 2 * d.depth && !stop_before_linear2 && !fuse) {
-        return fail(-3, "ln_fuse: pass too large for the residual-stream offsets (%d tokens)", n);
-    }
-    if (!on_ws) {
-        EpiLinear2 e2{bw.b2, mbase + 2 * D, h, D, mod_stride, T * L, 0, magic_of(T * L), fuse ? ws.a : nullptr, nbase, nbase + D};
-        launch_gemm((const u16 *)bw.w2, ws.z, D, n, m->K2, e2, st, 32, fuse);
+        const bool stats = p.lin2_stats(bi);
+        const Lin2Args l2{ws.w2p + (size_t)bi * D * m->K2, ws.z, bw.b2, mbase + 2 * D, ws.h, D, n, mod_stride, T * L, magic_of(T * L),
+                          p.l2grid.slices, p.l2grid.rpx, p.l2grid.gate_rows, stats ? ws.lnparts : nullptr, p.npad};
+        launch_linear2_ws(m->K2, l2, st);
+        m->prof.label(1, stats ? "k_linear2_ws<%d> (+ row statistics)" : "k_linear2_ws<%d>", m->K2);
+        if (stats) hipLaunchKernelGGL(k_ln_finalize, dim3((n + 255) / 256), dim3(256), 0, st, ws.lnstat, ws.lnparts, D / 32, p.npad, n, 32.0f);
+    } else {
+        const EpiLinear2 e2{bw.b2, mbase + 2 * D, ws.h, D, mod_stride, T * L, 0, magic_of(T * L)};
+        launch_gemm((const u16 *)bw.w2, ws.z, D, n, m->K2, e2, st);
         m->prof.label(1, "k_gemm_glds<EpiLinear2> (tiling %d)", gemm_variant<EpiLinear2>(D, m->K2, n));
     }
-    if (a_written) *a_written = fuse && !on_ws;
     m->prof.end(1, st);
     LSL_CHECK_LAUNCH("block");
     return 0;
 }
 
-// One evaluation for a pass of bc trajectories; state already embedded?  No: embeds x first.
-// do_step: fuse the affine update into the head; else write the network output to `out`.
-int run_eval(lsl_model *m, const Workspace &ws, float *x, float *out, const float *t_dev, float t_scalar, bool have_y, int bc,
-             int T, int L, int do_step, float ax, float am, float aw, const float *noise, uint64_t seed, unsigned step,
-             uint64_t elem_off, float *trace, hipStream_t st, float as = 0.0f, const float *saved = nullptr, float *save_out = nullptr,
-             const float *mods_ready = nullptr) {
+// What one evaluation reads besides its pass: lsl_forward's per-trajectory times and output buffer, or a sampler record (lsl_sample_ex)
+// whose state update the head applies, with the slices of noise / trace / saved state it uses
+struct EvalArgs {
+    float *x = nullptr;
+    float *out = nullptr;              // network output (lsl_forward)
+    const float *t = nullptr;          // per-trajectory times (lsl_forward); nullptr: the record's scalar time
+    bool have_y = false;
+    const lsl_step_ex *rec = nullptr;  // nullptr: no state update
+    const float *noise = nullptr;
+    uint64_t seed = 0, elem_off = 0;
+    float *trace = nullptr;
+    const float *saved = nullptr;
+    float *save_out = nullptr;
+    const float *mods_ready = nullptr;  // this record's row of the group table (run_mods_steps), or nullptr
+};
+
+// One evaluation for a pass: embeds x, runs the sub-blocks and the head (write the network output, or fuse the record's update into it)
+int run_eval(lsl_model *m, const Workspace &ws, const PassPlan &p, const EvalArgs &e, hipStream_t st) {
     const lsl_model_desc &d = m->d;
-    const int D = d.hidden, n = bc * T * L;
-    // modulation rows: one per trajectory, or a single shared row when t is a scalar and there is no y
-    const bool shared = (t_dev == nullptr) && !have_y;
-    const int rows = shared ? 1 : bc;
-    const int mod_stride = shared ? 0 : m->MODW;
+    const int D = d.hidden, n = p.n;
+    const lsl_step_ex r = e.rec ? *e.rec : lsl_step_ex{};
+    // modulation rows: one per trajectory, or a single shared row when t is a scalar and there is no y (plan: mod_stride 0)
+    const bool shared = p.mod_stride == 0;
     int rc = 0;
     const float *mods = ws.mods;
-    if (mods_ready && shared) mods = mods_ready;  // this record's row of the group table (run_mods_steps)
-    else rc = run_mods(m, ws, t_dev, t_scalar, have_y ? ws.yemb : nullptr, rows, ws.vec, ws.mods, st);
+    if (e.mods_ready && shared) mods = e.mods_ready;
+    else rc = run_mods(m, ws, e.t, r.t, e.have_y ? ws.yemb : nullptr, shared ? 1 : p.bc, ws.vec, ws.mods, st);
     if (rc) return rc;
     m->prof.begin(5, st);
-    // ln_fuse handles (models without the in-place LayerNorm behind the embedding): the embedding leaves the rows' statistics, so that the
-    // FIRST sub-block's LayerNorm runs inside its linear1 too (the same shape conditions as run_block's, which decide there again)
-    const int npad_e = (n + 255) & ~255;
-    const bool emb_stats = m->ln_fuse && !m->tail && !d.normalize && ws.lnstat && ws.w2p && embed_stats_ok(d.in_dim, D) &&
-                           linear1_lnf_ok(d.head_dim_pad, D, m->F1, m->HHD, n, T * L, mod_stride);
-    launch_embed<1>(ws.h, x, m->w.x_in_w, nullptr, nullptr, nullptr, nullptr, ws.cond_emb, n, d.in_dim, D, st, emb_stats ? ws.lnparts : nullptr, npad_e);
-    if (emb_stats) hipLaunchKernelGGL(k_ln_finalize, dim3((n + 255) / 256), dim3(256), 0, st, ws.lnstat, ws.lnparts, D / 256, npad_e, n, 256.0f);
+    // ln_fuse handles: the embedding leaves the rows' statistics, so that the FIRST sub-block's LayerNorm runs inside its linear1 too
+    launch_embed<1>(ws.h, e.x, m->w.x_in_w, nullptr, nullptr, nullptr, nullptr, ws.cond_emb, n, d.in_dim, D, st, p.emb_stats ? ws.lnparts : nullptr, p.npad);
+    if (p.emb_stats) hipLaunchKernelGGL(k_ln_finalize, dim3((n + 255) / 256), dim3(256), 0, st, ws.lnstat, ws.lnparts, D / 256, p.npad, n, 256.0f);
     if (d.normalize) { DISPATCH_D(D, launch_ln_inplace_t, ws.h, n, 1e-5f, st); }
     m->prof.end(5, st);
     LSL_CHECK_LAUNCH("embed");
-    bool a_ready = false;  // the first sub-block of an evaluation runs the standalone LayerNorm; later ones get `a` from the previous linear2
-    bool stats_ready = emb_stats;  // ... or (ln_fuse handles) the rows' statistics, and normalise inside their linear1
-    for (int bi = 0; bi < 2 * d.depth; ++bi) {
-        bool wrote = false, wrote_stats = false;
-        rc = run_block(m, ws, bi, ws.h, mods, mod_stride, bc, T, L, st, a_ready, true, &wrote, false, stats_ready, &wrote_stats);
-        if (rc) return rc;
-        a_ready = wrote;
-        stats_ready = wrote_stats;
-    }
+    for (int bi = 0; bi < 2 * d.depth; ++bi)
+        if ((rc = run_block(m, ws, p, bi, mods, st))) return rc;
     const float *fm = mods + (size_t)d.depth * 6 * D;  // adaLN: shift, scale
     m->prof.begin(4, st);
-    DISPATCH_D(D, launch_head_t, x, out, ws.h, fm, fm + D, mod_stride, m->w.out_w, m->w.out_b, n, d.in_dim, T * L, do_step, ax, am, aw,
-               noise, (unsigned long long)seed, step, (unsigned long long)elem_off, trace, as, saved, save_out, st);
+    DISPATCH_D(D, launch_head_t, e.x, e.out, ws.h, fm, fm + D, p.mod_stride, m->w.out_w, m->w.out_b, n, d.in_dim, p.T * p.L, e.rec ? 1 : 0,
+               r.ax, r.am, r.aw, e.noise, (unsigned long long)e.seed, (unsigned)r.noise_index, (unsigned long long)e.elem_off, e.trace, r.as,
+               e.saved, e.save_out, st);
     m->prof.end(4, st);
     LSL_CHECK_LAUNCH("head");
     return 0;

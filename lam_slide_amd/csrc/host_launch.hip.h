@@ -151,33 +151,16 @@ void launch_gemm_glds(const GemmArgs &g, const Epi &epi, hipStream_t st) {
     // + the bias vector of the whole GEMM, kept in LDS by epilogues that start the accumulators from it (k_gemm.hip.h)
     const size_t lds = GemmCfg<BF, BT, NWF, NWT, BK, NS, PERSIST, Epi>::lds_bytes + (Epi::lds_bias ? (size_t)((g.F + BF - 1) / BF) * BF * 4 : 0);
     LSL_ALLOW_LDS(kern, (size_t)163840);
-    const int ntt = (g.N + BT - 1) / BT, tiles = ntt * ((g.F + BF - 1) / BF);
+    const int tiles = ((g.N + BT - 1) / BT) * ((g.F + BF - 1) / BF);
     int grid = tiles;
-    GemmArgs ga = g;
-    ga.rows = 0;
     if (PERSIST) {  // as many workgroups as fit at once (LDS-limited), a multiple of 8 so the XCD mapping stays regular
         const int per_cu = (int)(163840 / lds) < 1 ? 1 : (int)(163840 / lds);
         grid = device_cus() * per_cu;
         grid -= grid % 8;
         if (grid > tiles) grid = tiles;
-        // row-owner walk (the epilogue finishes whole token rows: fused LayerNorm of linear2) only when there are at least as many
-        // token tiles as workgroups; smaller launches keep the flat list, which spreads the feature tiles over more CUs
-        if (Epi::row_owner && g.rows && ntt >= grid) ga.rows = 1;
     }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NWF * NWT * 64), lds, st, ga, epi);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(NWF * NWT * 64), lds, st, g, epi);
 }
-// whether launch_gemm_glds would take the row-owner walk for this launch (the caller then lets the epilogue write the next LayerNorm)
-template <int BF, int BT, int NWF, int NWT, int BK, int NS, class Epi>
-bool gemm_rows_walk(int F, int N) {
-    const size_t lds = GemmCfg<BF, BT, NWF, NWT, BK, NS, true, Epi>::lds_bytes;
-    const int per_cu = (int)(163840 / lds) < 1 ? 1 : (int)(163840 / lds);
-    int grid = device_cus() * per_cu;
-    grid -= grid % 8;
-    const int ntt = (N + BT - 1) / BT, tiles = ntt * ((F + BF - 1) / BF);
-    if (grid > tiles) grid = tiles;
-    return ntt >= grid;
-}
-
 
 #ifdef LSL_EXPERIMENTS
 #include "host_launch_experiments.hip.h"  // (needs launch_gemm_glds / device_cus above)
@@ -209,11 +192,6 @@ int linear1_ts_waves(int D, int N) {
     static const int nw4_max = tune_int("LSL_LIN1_NW4_MAX", 10240);
     return D == 512 && N <= nw4_max ? 4 : 8;
 }
-template <int HDP>
-void launch_linear1_ts_512(const Lin1Args &a, hipStream_t st) {
-    if (linear1_ts_waves(512, a.N) == 4) return launch_linear1_ts_t<HDP, 512, 4>(a, st);
-    return launch_linear1_ts_t<HDP, 512, 8>(a, st);
-}
 bool linear1_ts_ok(int hdp, int D, int F1, int HHD, int N) {
     static const int on = tune_int("LSL_LIN1_TS", 1);
     if (!on || (hdp != 16 && hdp != 32) || (D != 128 && D != 256 && D != 384 && D != 512) || F1 % 64 != 0 || HHD % 64 != 0 || N < 1) return false;
@@ -244,16 +222,16 @@ void launch_linear1_lnf(int hdp, int D, const Lin1Args &a, hipStream_t st) {
         default: return launch_linear1_ts_t<16, 512, 8, true>(a, st);
     }
 }
-void launch_linear1_ts(int hdp, int D, const Lin1Args &a, hipStream_t st) {
+void launch_linear1_ts(int hdp, int D, int waves, const Lin1Args &a, hipStream_t st) {  // (waves: linear1_ts_waves)
     switch ((hdp == 32 ? 0 : 4) + D / 128 - 1) {
         case 0: return launch_linear1_ts_t<32, 128>(a, st);
         case 1: return launch_linear1_ts_t<32, 256>(a, st);
         case 2: return launch_linear1_ts_t<32, 384>(a, st);
-        case 3: return launch_linear1_ts_512<32>(a, st);
+        case 3: return waves == 4 ? launch_linear1_ts_t<32, 512, 4>(a, st) : launch_linear1_ts_t<32, 512, 8>(a, st);
         case 4: return launch_linear1_ts_t<16, 128>(a, st);
         case 5: return launch_linear1_ts_t<16, 256>(a, st);
         case 6: return launch_linear1_ts_t<16, 384>(a, st);
-        default: return launch_linear1_ts_512<16>(a, st);
+        default: return waves == 4 ? launch_linear1_ts_t<16, 512, 4>(a, st) : launch_linear1_ts_t<16, 512, 8>(a, st);
     }
 }
 
@@ -264,41 +242,48 @@ bool linear2_ws_shape_ok(int D, int K2) {
     static const int on = env_int("LSL_LIN2_WS", 1);
     return on && D % 128 == 0 && D <= 512 && (K2 == 1536 || K2 == 1280 || K2 == 768 || K2 == 384);
 }
-template <int K, int NCH, int NS, bool LNS = false>
-bool launch_linear2_ws_t(Lin2Args a, int shared, hipStream_t st) {
-    using C = Lin2Cfg<K, NCH, NS, true>;
-    auto kern = k_linear2_ws<K, NCH, NS, true, LNS>;
-    // grid = 8 x slices x rpx workgroups, at most one per CU; fewer token ranges than 32-token blocks
-    const int slices = a.F / 128, cus = device_cus(), NBLK = (a.N + 31) / 32;
+// The grid of a k_linear2_ws launch: 8 x slices x rpx workgroups, at most one per CU, fewer token ranges than 32-token blocks; the LDS gate
+// table holds the trajectories one token range can span.  The kernel takes the launch only if they fit (linear2_ws_max_gate_rows).
+struct Lin2Grid {
+    int slices, rpx, gate_rows;
+};
+Lin2Grid linear2_ws_grid(int F, int N, int tpt, bool shared) {
+    const int slices = F / 128, cus = device_cus(), NBLK = (N + 31) / 32;
     int rpx = std::max(1, cus / (8 * slices));
     while (rpx > 1 && 8 * rpx > NBLK) --rpx;
     const int ranges = 8 * rpx, max_blocks = (NBLK + ranges - 1) / ranges + 1;
-    const int gate_rows = shared ? 1 : (max_blocks * 32 + a.tpt - 1) / a.tpt + 1;  // trajectories one range can span
-    if (gate_rows > C::max_gate_rows) return false;
-    a.slices = slices;
-    a.rpx = rpx;
-    a.gate_rows = gate_rows;
-    LSL_ALLOW_LDS(kern, (size_t)163840);
-    hipLaunchKernelGGL(kern, dim3(8 * slices * rpx), dim3(512), C::lds_bytes(gate_rows), st, a);
-    return true;
+    return {slices, rpx, shared ? 1 : (max_blocks * 32 + tpt - 1) / tpt + 1};
 }
-bool launch_linear2_ws(int K2, const Lin2Args &a, int shared, hipStream_t st) {
-    if (a.stats) {  // LNS instances: per-wave row statistics of the updated rows beside h (the next sub-block's LayerNorm runs inside linear1)
-        switch (K2) {
-            case 1536: return launch_linear2_ws_t<1536, 3, 3, true>(a, shared, st);
-            case 1280: return launch_linear2_ws_t<1280, 4, 4, true>(a, shared, st);
-            case 768: return launch_linear2_ws_t<768, 3, 3, true>(a, shared, st);
-            case 384: return launch_linear2_ws_t<384, 3, 3, true>(a, shared, st);
-            default: return false;
-        }
-    }
+// (the instances: K2, NCH chunks, NS ring slots - the same in launch_linear2_ws)
+int linear2_ws_max_gate_rows(int K2) {
     switch (K2) {
-        case 1536: return launch_linear2_ws_t<1536, 3, 3>(a, shared, st);
-        case 1280: return launch_linear2_ws_t<1280, 4, 4>(a, shared, st);  // (4 chunks of 160 columns: 40 of 64 lanes per LDS-DMA instruction instead of 32; round 5: 0.168-0.171 -> 0.165 ms at 163 840 tokens, 18.6 -> 17.1 us at 10 240)
-        case 768: return launch_linear2_ws_t<768, 3, 3>(a, shared, st);
-        case 384: return launch_linear2_ws_t<384, 3, 3>(a, shared, st);
-        default: return false;
+        case 1536: return Lin2Cfg<1536, 3, 3, true>::max_gate_rows;
+        case 1280: return Lin2Cfg<1280, 4, 4, true>::max_gate_rows;
+        case 768: return Lin2Cfg<768, 3, 3, true>::max_gate_rows;
+        case 384: return Lin2Cfg<384, 3, 3, true>::max_gate_rows;
+        default: return 0;
     }
+}
+template <int K, int NCH, int NS, bool LNS = false>
+void launch_linear2_ws_t(const Lin2Args &a, hipStream_t st) {  // (a.slices / rpx / gate_rows: linear2_ws_grid)
+    using C = Lin2Cfg<K, NCH, NS, true>;
+    auto kern = k_linear2_ws<K, NCH, NS, true, LNS>;
+    LSL_ALLOW_LDS(kern, (size_t)163840);
+    hipLaunchKernelGGL(kern, dim3(8 * a.slices * a.rpx), dim3(512), C::lds_bytes(a.gate_rows), st, a);
+}
+template <bool LNS>
+void launch_linear2_ws_k(int K2, const Lin2Args &a, hipStream_t st) {
+    switch (K2) {
+        case 1536: return launch_linear2_ws_t<1536, 3, 3, LNS>(a, st);
+        case 1280: return launch_linear2_ws_t<1280, 4, 4, LNS>(a, st);  // (4 chunks of 160 columns: 40 of 64 lanes per LDS-DMA instruction instead of 32; round 5: 0.168-0.171 -> 0.165 ms at 163 840 tokens, 18.6 -> 17.1 us at 10 240)
+        case 768: return launch_linear2_ws_t<768, 3, 3, LNS>(a, st);
+        case 384: return launch_linear2_ws_t<384, 3, 3, LNS>(a, st);
+    }
+}
+// LNS instances (a.stats): per-wave row statistics of the updated rows beside h (the next sub-block's LayerNorm runs inside linear1)
+void launch_linear2_ws(int K2, const Lin2Args &a, hipStream_t st) {
+    if (a.stats) launch_linear2_ws_k<true>(K2, a, st);
+    else launch_linear2_ws_k<false>(K2, a, st);
 }
 
 // The back half of a sub-block on the row-owning tail kernel (k_tail.hip.h): up-projection -> GELU in registers -> down-projection + attention
@@ -368,20 +353,12 @@ int gemm_variant(int F, int K, int N = 1 << 30) {
     return std::is_same<Epi, EpiLinear2>::value ? (K % 128 == 0 ? 7 : 15) : (K % 128 == 0 ? 12 : 5);
 }
 
-// linear2 can also write the next sub-block's LayerNorm + modulate (EpiLinear2::finish_rows) when it runs as the persistent
-// row-owner kernel over whole rows of D = 256 or 512 features and the launch has at least as many token tiles as workgroups
-bool linear2_can_fuse_ln(int D, int N, int K2) {
-    static const int off = tune_int("LSL_LN_FUSE", 0) == 0;  // measured and rejected (k_gemm.hip.h: EpiLinear2): experiments builds only
-    if (off || D % 256 != 0 || gemm_variant<EpiLinear2>(D, K2) != 7 || K2 % 128 != 0) return false;
-    return gemm_rows_walk<256, 256, 2, 4, 64, 2, EpiPieces<EpiLinear2>>(D, N);
-}
-
 template <class Epi>
-void launch_gemm(const u16 *W, const u16 *X, int F, int N, int K, const Epi &epi_in, hipStream_t st, int hhd = 32, bool rows = false) {
+void launch_gemm(const u16 *W, const u16 *X, int F, int N, int K, const Epi &epi_in, hipStream_t st, int hhd = 32) {
     const int variant = gemm_variant<Epi>(F, K, N);
     static const int probe = tune_int("LSL_PROBE", 0);
     static const int stagger = tune_int("LSL_STAGGER", 0);
-    GemmArgs g{W, X, F, N, K, rows ? 1 : 0, stagger, probe};
+    GemmArgs g{W, X, F, N, K, stagger, probe};
     // LSL_NT bit 0: linear1 output, bit 1: linear2 residual update, bit 2: attention output, bit 3: LayerNorm+modulate output
     static const int nt = tune_int("LSL_NT", 3);
     Epi epi = epi_in;

@@ -237,15 +237,20 @@ int lsl_forward(lsl_model *m, const lsl_io *io, void *workspace, size_t workspac
     if (!io->t || !io->out) return fail(-3, "t and out are required");
     hipStream_t st = (hipStream_t)stream;
     const Workspace ws = carve(m, (char *)workspace, chunk, io->T, io->L);
+    CallPlans plans;
+    if (int rc = plan_call(m, ws, io, chunk, m->MODW, plans)) return rc;  // (per-trajectory times: a modulation row per trajectory)
     run_tables(m, ws, io->T, io->L, st);
     const size_t per = (size_t)io->T * io->L * m->d.in_dim;
     for (int b0 = 0; b0 < io->B; b0 += chunk) {
         const int bc = io->B - b0 < chunk ? io->B - b0 : chunk;
         const float *y = io->y ? io->y + (size_t)b0 * m->d.vec_in_dim : nullptr;
         if (int rc = prepare_pass(m, ws, io->x_cond + b0 * per, io->mask + (size_t)b0 * io->T * io->L, y, bc, io->T, io->L, st)) return rc;
-        if (int rc = run_eval(m, ws, io->x + b0 * per, io->out + b0 * per, io->t + b0, 0.0f, y != nullptr, bc, io->T, io->L, 0, 0, 0, 0,
-                              nullptr, 0, 0, 0, nullptr, st))
-            return rc;
+        EvalArgs e;
+        e.x = io->x + b0 * per;
+        e.out = io->out + b0 * per;
+        e.t = io->t + b0;
+        e.have_y = y != nullptr;
+        if (int rc = run_eval(m, ws, plans.of(bc), e, st)) return rc;
     }
     return 0;
 } catch (const std::bad_alloc &) {
@@ -378,6 +383,8 @@ int lsl_sample_ex(lsl_model *m, const lsl_io *io, const lsl_step_ex *steps, int3
 static int sample_enqueue(lsl_model *m, const lsl_io *io, const lsl_step_ex *steps, int32_t n_steps, const float *noise, uint64_t seed,
                           uint64_t elem_offset, float *trace, void *workspace, int chunk, hipStream_t st) {
     const Workspace ws = carve(m, (char *)workspace, chunk, io->T, io->L);
+    CallPlans plans;
+    if (int rc = plan_call(m, ws, io, chunk, io->y ? m->MODW : 0, plans)) return rc;  // (a scalar time: one shared row without class conditioning)
     run_tables(m, ws, io->T, io->L, st);
     const size_t per = (size_t)io->T * io->L * m->d.in_dim;
     const size_t total = per * io->B;
@@ -402,31 +409,33 @@ static int sample_enqueue(lsl_model *m, const lsl_io *io, const lsl_step_ex *ste
         if (int rc = prepare_pass(m, ws, io->x_cond + b0 * per, io->mask + (size_t)b0 * io->T * io->L, y, bc, io->T, io->L, st)) return rc;
         for (int s = 0; s < n_steps; ++s) {
             const lsl_step_ex &sp = steps[s];
-            const float *nz = nullptr;
-            if (sp.aw != 0.0f && noise) nz = noise + (size_t)sp.noise_index * total + b0 * per;
-            float *tr = trace && sp.trace_index >= 0 ? trace + (size_t)sp.trace_index * total + b0 * per : nullptr;
-            const float *saved = sp.as != 0.0f ? ws.saved : nullptr;        // (the pass's own copy: a pass runs all records for its trajectories)
-            float *save_out = (sp.flags & LSL_STEP_SAVE) ? ws.saved : nullptr;
+            EvalArgs e;
+            e.x = io->x + b0 * per;
+            e.have_y = io->y != nullptr;
+            e.rec = &sp;
+            if (sp.aw != 0.0f && noise) e.noise = noise + (size_t)sp.noise_index * total + b0 * per;
+            e.seed = seed;
+            e.elem_off = elem_offset + b0 * per;
+            e.trace = trace && sp.trace_index >= 0 ? trace + (size_t)sp.trace_index * total + b0 * per : nullptr;
+            e.saved = sp.as != 0.0f ? ws.saved : nullptr;  // (the pass's own copy: a pass runs all records for its trajectories)
+            e.save_out = (sp.flags & LSL_STEP_SAVE) ? ws.saved : nullptr;
             if (sp.flags & LSL_STEP_NO_NETWORK) {
                 const unsigned long long ne = (unsigned long long)bc * per;
                 hipLaunchKernelGGL(k_state_affine, dim3((unsigned)std::min<unsigned long long>((ne + 255) / 256, 2048)), dim3(256), 0, st,
-                                   io->x + b0 * per, ne, sp.ax, sp.aw, sp.as, nz, (unsigned long long)seed, (unsigned)sp.noise_index,
-                                   (unsigned long long)(elem_offset + b0 * per), saved, save_out, tr);
+                                   e.x, ne, sp.ax, sp.aw, sp.as, e.noise, (unsigned long long)seed, (unsigned)sp.noise_index,
+                                   (unsigned long long)e.elem_off, e.saved, e.save_out, e.trace);
                 LSL_CHECK_LAUNCH("state update");
                 continue;
             }
-            const float *mods_ready = nullptr;
             if (G) {
                 const int k = net_idx[s], g = k / G;
                 if (cur_group != g) {
                     if (int rc = run_mods_steps(m, ws, net_t.data() + (size_t)g * G, std::min(G, (int)net_t.size() - g * G), st)) return rc;
                     cur_group = g;
                 }
-                mods_ready = ws.mods_all + (size_t)(k - g * G) * m->MODW;
+                e.mods_ready = ws.mods_all + (size_t)(k - g * G) * m->MODW;
             }
-            if (int rc = run_eval(m, ws, io->x + b0 * per, nullptr, nullptr, sp.t, io->y != nullptr, bc, io->T, io->L, 1, sp.ax, sp.am, sp.aw,
-                                  nz, seed, (unsigned)sp.noise_index, elem_offset + b0 * per, tr, st, sp.as, saved, save_out, mods_ready))
-                return rc;
+            if (int rc = run_eval(m, ws, plans.of(bc), e, st)) return rc;
         }
     }
     return 0;
@@ -510,11 +519,13 @@ int lsl_debug_block(lsl_model *m, int32_t bi, const float *h_in, float *h_out, c
     if (!workspace || workspace_bytes < need) return fail(-4, "workspace too small: need %zu bytes", need);
     hipStream_t st = (hipStream_t)stream;
     const Workspace ws = carve(m, (char *)workspace, B, T, L);
+    PassPlan plan;
+    if (int rc = plan_pass(m, ws, B, T, L, m->MODW, PlanMode::debug_block, bi, plan)) return rc;
     run_tables(m, ws, T, L, st);
     const size_t bytes = (size_t)B * T * L * m->d.hidden * 4;
     // (on the workspace's residual stream, like an evaluation: its rows are padded to whole tiles)
     hipMemcpyAsync(ws.h, h_in, bytes, hipMemcpyDeviceToDevice, st);
-    if (int rc = run_block(m, ws, bi, ws.h, mods, m->MODW, B, T, L, st)) return rc;
+    if (int rc = run_block(m, ws, plan, bi, mods, st)) return rc;
     hipMemcpyAsync(h_out, ws.h, bytes, hipMemcpyDeviceToDevice, st);
     return 0;
 } catch (const std::bad_alloc &) {
@@ -533,12 +544,13 @@ int lsl_debug_taps(lsl_model *m, int32_t bi, const float *h_in, const float *mod
     if (!workspace || workspace_bytes < need) return fail(-4, "workspace too small: need %zu bytes", need);
     hipStream_t st = (hipStream_t)stream;
     const Workspace ws = carve(m, (char *)workspace, B, T, L);
+    PassPlan plan;
+    if (int rc = plan_pass(m, ws, B, T, L, m->MODW, PlanMode::debug_taps, bi, plan)) return rc;
     run_tables(m, ws, T, L, st);
     const size_t n = (size_t)B * T * L;
     hipMemcpyAsync(ws.h, h_in, n * m->d.hidden * 4, hipMemcpyDeviceToDevice, st);
-    if (int rc = run_block(m, ws, bi, ws.h, mods, m->MODW, B, T, L, st, false, false, nullptr, true)) return rc;
-    const bool temporal = bi & 1;
-    if (qkv_planes_ok(m->d.head_dim_pad, m->d.hidden, m->d.heads, temporal ? T : L, temporal, linear1_ts_ok(m->d.head_dim_pad, m->d.hidden, m->F1, m->HHD, (int)n))) {
+    if (int rc = run_block(m, ws, plan, bi, mods, st)) return rc;
+    if (plan.planes[bi & 1]) {
         const long chunks = (long)n * 3 * m->d.heads * (m->d.head_dim_pad / 8);  // the block left q / k / v as head-major planes: hand them out as token-major rows
         hipLaunchKernelGGL(k_planes_to_rows, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, st, (u16 *)qkv_out, ws.qkv, (int)n,
                            (int)((n + 255) & ~(size_t)255), 3 * m->d.heads, m->d.head_dim_pad);

@@ -78,7 +78,7 @@ void run_case(int N, int D, int H, int mlp_ratio, int iters, int grid_new, int p
     // ---- old kernel ----
     using Epi = EpiLinear1<HDP>;
     Epi e{b, nullptr, nullptr, nullptr, rq, rk, qkv0, z0, HHD, M, pdiv, pmod, magic_of(pdiv), magic_of(pmod), inv_hd, premul, 32};
-    GemmArgs ga{W, X, F, N, K, 0, 0, 0};
+    GemmArgs ga{W, X, F, N, K, 0, 0};
     auto kold = k_gemm_glds<256, 256, 2, 4, 64, 2, true, Epi>;
     const size_t lds_old = GemmCfg<256, 256, 2, 4, 64, 2, true, Epi>::lds_bytes + (size_t)Fpad * 4;
     CK(hipFuncSetAttribute(reinterpret_cast<const void *>(kold), hipFuncAttributeMaxDynamicSharedMemorySize, 163840));

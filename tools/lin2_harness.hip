@@ -71,9 +71,9 @@ void run_case(int N, int F, int tpt, int shared, int iters, int rpx_arg) {
     const float *gate = gt + 2 * F;  // (shift, scale, gate of a sub-block: the gate is the third F-vector of the row)
 
     // ---- old kernel ----
-    EpiLinear2 e2{b, gate, h0, F, mod_stride, tpt, 32, magic_of(tpt), nullptr, nullptr, nullptr};
+    EpiLinear2 e2{b, gate, h0, F, mod_stride, tpt, 32, magic_of(tpt)};
     using Epi = EpiPieces<EpiLinear2>;
-    GemmArgs ga{W, Z, F, N, K, 0, 0, 0};
+    GemmArgs ga{W, Z, F, N, K, 0, 0};
     auto kold = k_gemm_glds<256, 256, 2, 4, 64, 2, true, Epi>;
     const size_t lds_old = GemmCfg<256, 256, 2, 4, 64, 2, true, Epi>::lds_bytes;
     CK(hipFuncSetAttribute(reinterpret_cast<const void *>(kold), hipFuncAttributeMaxDynamicSharedMemorySize, 163840));
