@@ -58,8 +58,10 @@ def main():
     ade, fde = min_ade_fde(pos, target)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    val = drv.model_step(latents)["loss"].mean()                          # what validation_step logs as val/loss: one lsl_si_loss call
     print(f"{B} scenes x {K} samples x {T} frames x {A} agents: {dt * 1e3:.1f} ms  ({B * K / dt:.0f} trajectories/s)  "
-          f"min-ADE {float(ade.mean()):.3f}  min-FDE {float(fde.mean()):.3f}  (random weights: the numbers only show the plumbing)")
+          f"min-ADE {float(ade.mean()):.3f}  min-FDE {float(fde.mean()):.3f}  val/loss {float(val):.3f}  "
+          f"(random weights: the numbers only show the plumbing)")
 
 
 if __name__ == "__main__":

@@ -36,7 +36,9 @@ extern "C" {
  *    no signature of version 2 changed.
  * 4: lsl_model_set_attention_mode exists (attention_linear, mmdit.py:58-72); nothing else changed.
  * 5: lsl_model_set_tail, lsl_model_tail, lsl_profile_kernel_name exist; no signature of version 4 changed.
- * 6: lsl_model_set_ln_fuse, lsl_model_ln_fuse exist; no signature of version 5 changed. */
+ * 6: lsl_model_set_ln_fuse, lsl_model_ln_fuse exist; no signature of version 5 changed.
+ * 6, later: lsl_si_loss, lsl_si_reduce, lsl_si_loss_workspace_bytes added, no signature changed (a binding that needs them finds out by
+ *    looking the symbols up: a library without them is stale). */
 #define LSL_VERSION 6
 
 typedef struct lsl_model lsl_model;
@@ -186,6 +188,30 @@ size_t lsl_workspace_bytes(const lsl_model *m, int32_t B, int32_t T, int32_t L);
 
 /* LatentSIV3.forward: io->out = network(io->x, io->t, io->x_cond, io->mask, io->y). */
 int lsl_forward(lsl_model *m, const lsl_io *io, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Stochastic-interpolant objective without gradients: Transport.training_losses (modules/transport/transport.py:116-156), the loss every
+ * validation_step evaluates through Loss.forward (second_stage/md17.py:221) before it samples.  For every path (path.py:21-206), prediction
+ * and loss weight the reference's loss of trajectory b is affine in three arrays; one record per trajectory carries the coefficients:
+ *      xt     = alpha x1 + sigma x0                                            (path.py:124-134, ICPlan.compute_mu_t)
+ *      r      = p pred + q1 x1 + q0 x0,      loss_b = w mean_{T,L,C}(r^2)       (transport.py:135-154, mean_flat)
+ *   velocity: p = 1, q1 = -d_alpha, q0 = -d_sigma, w = 1        data:  p = 1, q1 = -1, q0 = 0, w = 1
+ *   noise:    p = 1, q1 = 0, q0 = -1, w = W                     score: p = sigma, q1 = 0, q0 = 1, w = W
+ *   W = 1 | (drift_var / sigma)^2 | drift_var / sigma^2 for loss_weight None | "velocity" | "likelihood"
+ * lam_slide_amd/transport.py derives the records in float64 (Transport.si_rows).  Sums run in a fixed order (slabs of LSL_SI_SLAB elements
+ * of one trajectory, no atomics): a trajectory's loss has the same bits in any batch, shard or pass. */
+typedef struct lsl_si_row { float alpha, sigma, p, q1, q0, w; } lsl_si_row;
+#define LSL_SI_SLAB 4096
+/* lsl_workspace_bytes of the same sizes + one float per trajectory and slab. */
+size_t lsl_si_loss_workspace_bytes(const lsl_model *m, int32_t B, int32_t T, int32_t L);
+/* Transport.training_losses on given draws: io->x receives xt, io->t = device [B] times, io->out receives pred = network(xt, t, x_cond, mask, y)
+ * exactly as lsl_forward computes it; x1, x0 device [B,T,L,C]; rows device [B]; loss device [B].  A refused call enqueues nothing. */
+int lsl_si_loss(lsl_model *m, const lsl_io *io, const float *x1, const float *x0, const lsl_si_row *rows, float *loss,
+                void *workspace, size_t workspace_bytes, void *stream);
+/* The reduction alone, for predictions that came from somewhere else (any callable that left its output on the GPU, tests):
+ * loss[b] = w_b mean(r^2) over the per_trajectory elements of trajectory b.  scratch: device, at least
+ * B * ceil(per_trajectory / LSL_SI_SLAB) floats. */
+int lsl_si_reduce(const float *pred, const float *x1, const float *x0, const lsl_si_row *rows, int32_t B, uint64_t per_trajectory,
+                  float *loss, void *scratch, size_t scratch_bytes, void *stream);
 
 /* Sampler loop (Sampler.sample_ode / sample_sde inner loops): applies n_steps affine updates to io->x
  * in place.  noise: device [n_noise, B*T*L*C] standard-normal draws, slice s belongs to step s (the

@@ -3,7 +3,7 @@
 Public surface (mirrors the reference's for this path only):
   LatentSIV3                       <- src.models.components.latent.latent_si_v31.LatentSIV3
   CreateTransport, Transport, Sampler, ModelType, PathType
-                                   <- src.modules.transport
+                                   <- src.modules.transport (samplers, and Transport.training_losses without gradients)
   SecondStageSampler, setup_conditioning, sample_sharded
                                    <- SecondStageCondLightningBase.{sample, setup_conditioning} + batch sharding
   Stage1Decoder                    <- first_stage.decode = Decoder(post_quant(latents), entities) (frozen, after the sampler)
@@ -21,8 +21,8 @@ from .latent_si import LatentSIV3
 from .sampling import (RolloutSampler, SecondStageSampler, best_of_k_errors, min_ade_fde, sample_rollout, sample_sharded,
                        setup_conditioning, shard_bounds)
 from .transport import (CreateTransport, ModelType, PathType, Sampler, SampleResult, Transport, WeightType, as_transport, device_randn,
-                        mix_seed)
+                        mix_seed, si_reduce)
 
 __all__ = ["LatentSIV3", "CreateTransport", "Transport", "Sampler", "SampleResult", "ModelType", "PathType", "WeightType",
            "SecondStageSampler", "setup_conditioning", "sample_sharded", "shard_bounds", "min_ade_fde", "sample_rollout", "best_of_k_errors",
-           "RolloutSampler", "Stage1Decoder", "Stage1Encoder", "as_transport", "device_randn", "mix_seed", "install", "uninstall", "dropin", "_lib"]
+           "RolloutSampler", "Stage1Decoder", "Stage1Encoder", "as_transport", "device_randn", "mix_seed", "si_reduce", "install", "uninstall", "dropin", "_lib"]

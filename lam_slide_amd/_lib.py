@@ -19,10 +19,12 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 
 ABI_VERSION = 6  # LSL_VERSION of include/lsl_api.h this binding was written against
 RK_SCRATCH_BYTES = 8192  # LSL_RK_SCRATCH_BYTES
+SI_SLAB = 4096  # LSL_SI_SLAB: elements of one trajectory per partial sum of lsl_si_reduce
 
 EXPORTED = (
     "lsl_version", "lsl_build_info", "lsl_last_error", "lsl_model_create", "lsl_model_set_weights", "lsl_model_destroy",
     "lsl_model_set_chunk", "lsl_model_set_attention_mode", "lsl_model_set_tail", "lsl_model_tail", "lsl_model_set_ln_fuse", "lsl_model_ln_fuse", "lsl_profile_kernel_name", "lsl_pass_size", "lsl_sampler_path", "lsl_workspace_bytes", "lsl_forward", "lsl_sample", "lsl_sample_ex", "lsl_debug_block", "lsl_debug_taps", "lsl_debug_mods",
+    "lsl_si_loss_workspace_bytes", "lsl_si_loss", "lsl_si_reduce",
     "lsl_profile_enable", "lsl_profile_read", "lsl_randn", "lsl_rk_lincomb", "lsl_rk_dense", "lsl_rk_error_ratio",
     "lsl_decoder_create", "lsl_decoder_destroy", "lsl_decode_workspace_bytes", "lsl_decode",
     "lsl_encoder_create", "lsl_encoder_destroy", "lsl_encode_workspace_bytes", "lsl_encode",
@@ -85,6 +87,10 @@ class StepEx(C.Structure):  # lsl_step_ex
                 ("noise_index", C.c_int32), ("trace_index", C.c_int32)]
 
 
+class SiRow(C.Structure):  # lsl_si_row
+    _fields_ = [(n, C.c_float) for n in ("alpha", "sigma", "p", "q1", "q0", "w")]
+
+
 STEP_NO_NETWORK, STEP_SAVE = 1, 2
 
 
@@ -122,6 +128,10 @@ def load() -> C.CDLL:
         raise LibraryMissing(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(the HIP extension is the only compute path of lam_slide_amd)")
     lib = C.CDLL(LIB_PATH)
+    # LSL_VERSION stayed 6 when entry points were added without changing a signature: a library built before them is found by the symbols
+    missing = [s for s in EXPORTED if not hasattr(lib, s)]
+    if missing:
+        raise RuntimeError(f"{LIB_PATH} is stale: it lacks {', '.join(missing)}; rebuild it (python -c 'import __graft_entry__ as g; g.build()')")
     lib.lsl_version.restype = C.c_int
     lib.lsl_build_info.restype = C.c_char_p
     lib.lsl_last_error.restype = C.c_char_p
@@ -152,6 +162,11 @@ def load() -> C.CDLL:
                                    C.c_void_p, C.c_size_t, C.c_void_p]
     lib.lsl_debug_mods.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                    C.c_void_p]
+    lib.lsl_si_loss_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+    lib.lsl_si_loss_workspace_bytes.restype = C.c_size_t
+    lib.lsl_si_loss.argtypes = [C.c_void_p, C.POINTER(IO), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.lsl_si_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t,
+                                  C.c_void_p]
     lib.lsl_randn.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
     lib.lsl_rk_lincomb.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.c_int32, C.c_uint64, C.c_void_p]
     lib.lsl_rk_dense.argtypes = [C.c_void_p] * 6 + [C.c_float, C.c_uint64, C.c_void_p]

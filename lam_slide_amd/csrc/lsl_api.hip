@@ -2,7 +2,7 @@
 // network evaluation (latent_si_v31.py:168-188) and of the sampler loops (integrators.py:67-78,103-120)
 // on the caller's stream.  No allocation, no synchronisation, no host<->device copies.
 // One translation unit: this file = the entry points of the sampling path (model handle, forward, fused sampler + opt-in hipGraph replay,
-// noise, Runge-Kutta state arithmetic, debug taps); host_common / host_launch / host_eval.hip.h = what they enqueue; decode_host.hip.h +
+// noise, Runge-Kutta state arithmetic, the stochastic-interpolant objective around one evaluation, debug taps); host_common / host_launch / host_eval.hip.h = what they enqueue; decode_host.hip.h +
 // stage1_api.hip.h = the frozen stage-1 encode / decode beside the path.
 #include "../../include/lsl_api.h"
 
@@ -27,6 +27,7 @@
 #include "k_tail.hip.h"
 #include "k_small.hip.h"
 #include "k_resident.hip.h"
+#include "k_siloss.hip.h"
 #ifdef LSL_EXPERIMENTS  // measured-and-rejected GEMM structures, built only by tools/build_experiments.sh (never in the product library)
 #include "k_gemm_pp.hip.h"        // tools/experiments/ (on the include path of tools/build_experiments.sh only)
 #include "k_gemm_drain.hip.h"
@@ -230,15 +231,8 @@ size_t lsl_workspace_bytes(const lsl_model *m, int32_t B, int32_t T, int32_t L) 
     return need;
 }
 
-int lsl_forward(lsl_model *m, const lsl_io *io, void *workspace, size_t workspace_bytes, void *stream) try {
-    DeviceGuard dev_guard_((hipStream_t)stream);
-    int chunk = 0;
-    if (int rc = check_call(m, io, workspace_bytes, workspace, &chunk)) return rc;
-    if (!io->t || !io->out) return fail(-3, "t and out are required");
-    hipStream_t st = (hipStream_t)stream;
-    const Workspace ws = carve(m, (char *)workspace, chunk, io->T, io->L);
-    CallPlans plans;
-    if (int rc = plan_call(m, ws, io, chunk, m->MODW, plans)) return rc;  // (per-trajectory times: a modulation row per trajectory)
+// the passes of one network evaluation at per-trajectory times: io->out = network(io->x, io->t, ...) (lsl_forward, and the middle of lsl_si_loss)
+static int forward_passes(lsl_model *m, const lsl_io *io, const Workspace &ws, const CallPlans &plans, int chunk, hipStream_t st) {
     run_tables(m, ws, io->T, io->L, st);
     const size_t per = (size_t)io->T * io->L * m->d.in_dim;
     for (int b0 = 0; b0 < io->B; b0 += chunk) {
@@ -253,6 +247,98 @@ int lsl_forward(lsl_model *m, const lsl_io *io, void *workspace, size_t workspac
         if (int rc = run_eval(m, ws, plans.of(bc), e, st)) return rc;
     }
     return 0;
+}
+
+int lsl_forward(lsl_model *m, const lsl_io *io, void *workspace, size_t workspace_bytes, void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    int chunk = 0;
+    if (int rc = check_call(m, io, workspace_bytes, workspace, &chunk)) return rc;
+    if (!io->t || !io->out) return fail(-3, "t and out are required");
+    hipStream_t st = (hipStream_t)stream;
+    const Workspace ws = carve(m, (char *)workspace, chunk, io->T, io->L);
+    CallPlans plans;
+    if (int rc = plan_call(m, ws, io, chunk, m->MODW, plans)) return rc;  // (per-trajectory times: a modulation row per trajectory)
+    return forward_passes(m, io, ws, plans, chunk, st);
+} catch (const std::bad_alloc &) {
+    return fail(-5, "out of host memory");
+} catch (...) {
+    return fail(-11, "unexpected C++ exception");
+}
+
+// ---- stochastic-interpolant objective (k_siloss.hip.h) ----
+static_assert(sizeof(lsl_si_row) == sizeof(SiRow) && sizeof(SiRow) == 24 && LSL_SI_SLAB == LSL_SI_SLAB_ELEMS, "lsl_si_row layout / slab size");
+static size_t si_slabs(uint64_t per) { return (size_t)((per + LSL_SI_SLAB_ELEMS - 1) / LSL_SI_SLAB_ELEMS); }
+static bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+// the two reduction launches; arguments already checked
+static int si_reduce_enqueue(const float *pred, const float *x1, const float *x0, const lsl_si_row *rows, int B, uint64_t per, float *loss,
+                             float *partial, hipStream_t st) {
+    const size_t slabs = si_slabs(per);
+    const bool vec = per % 4 == 0 && aligned16(pred) && aligned16(x1) && aligned16(x0);
+    for (int b0 = 0; b0 < B; b0 += 65535) {  // (a grid has at most 65535 rows)
+        const dim3 grid((unsigned)slabs, (unsigned)std::min(B - b0, 65535));
+        const size_t o = (size_t)b0 * per;
+        if (vec)
+            hipLaunchKernelGGL(k_si_loss_partial<true>, grid, dim3(256), 0, st, partial + (size_t)b0 * slabs, pred + o, x1 + o, x0 + o,
+                               (const SiRow *)rows + b0, (unsigned long long)per);
+        else
+            hipLaunchKernelGGL(k_si_loss_partial<false>, grid, dim3(256), 0, st, partial + (size_t)b0 * slabs, pred + o, x1 + o, x0 + o,
+                               (const SiRow *)rows + b0, (unsigned long long)per);
+    }
+    hipLaunchKernelGGL(k_si_loss_final, dim3((unsigned)B), dim3(64), 0, st, loss, (const float *)partial, (const SiRow *)rows, (int)slabs,
+                       (unsigned long long)per);
+    LSL_CHECK_LAUNCH("si loss reduction");
+    return 0;
+}
+
+static size_t si_scratch_bytes(int32_t B, uint64_t per_trajectory) {  // one float per (trajectory, slab)
+    if (B <= 0 || per_trajectory == 0 || per_trajectory > ((uint64_t)1 << 31)) return 0;
+    return (size_t)B * si_slabs(per_trajectory) * sizeof(float);
+}
+
+size_t lsl_si_loss_workspace_bytes(const lsl_model *m, int32_t B, int32_t T, int32_t L) {
+    const size_t fwd = lsl_workspace_bytes(m, B, T, L);
+    if (!fwd) return 0;
+    return align_up(fwd, 256) + align_up(si_scratch_bytes(B, (uint64_t)T * L * m->d.in_dim), 256);  // (the partial sums live behind the forward's scratch)
+}
+
+int lsl_si_reduce(const float *pred, const float *x1, const float *x0, const lsl_si_row *rows, int32_t B, uint64_t per_trajectory, float *loss,
+                  void *scratch, size_t scratch_bytes, void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!pred || !x1 || !x0 || !rows || !loss) return fail(-1, "null argument");
+    if (B <= 0 || per_trajectory == 0) return fail(-3, "B and per_trajectory must be positive");
+    if (per_trajectory > ((uint64_t)1 << 31)) return fail(-3, "per_trajectory too large");
+    const size_t need = si_scratch_bytes(B, per_trajectory);
+    if (!scratch || scratch_bytes < need) return fail(-4, "scratch too small: need %zu bytes, got %zu", need, scratch_bytes);
+    return si_reduce_enqueue(pred, x1, x0, rows, B, per_trajectory, loss, (float *)scratch, (hipStream_t)stream);
+} catch (...) {
+    return fail(-11, "unexpected C++ exception");
+}
+
+int lsl_si_loss(lsl_model *m, const lsl_io *io, const float *x1, const float *x0, const lsl_si_row *rows, float *loss, void *workspace,
+                size_t workspace_bytes, void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    int chunk = 0;
+    if (int rc = check_call(m, io, workspace_bytes, workspace, &chunk)) return rc;
+    if (!io->t || !io->out) return fail(-3, "t and out are required");
+    if (!x1 || !x0 || !rows || !loss) return fail(-1, "null argument");
+    const size_t need = lsl_si_loss_workspace_bytes(m, io->B, io->T, io->L);
+    if (workspace_bytes < need) return fail(-4, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    hipStream_t st = (hipStream_t)stream;
+    const Workspace ws = carve(m, (char *)workspace, chunk, io->T, io->L);
+    CallPlans plans;
+    if (int rc = plan_call(m, ws, io, chunk, m->MODW, plans)) return rc;  // (before the first launch: a refused call enqueues nothing)
+    const uint64_t per = (uint64_t)io->T * io->L * m->d.in_dim, total = per * (uint64_t)io->B;
+    const bool vec = per % 4 == 0 && aligned16(io->x) && aligned16(x1) && aligned16(x0);
+    const unsigned grid = (unsigned)std::min<uint64_t>(((vec ? total / 4 : total) + 255) / 256, (uint64_t)device_cus() * 16);
+    if (vec)
+        hipLaunchKernelGGL(k_si_mix<true>, dim3(grid), dim3(256), 0, st, io->x, x1, x0, (const SiRow *)rows, (unsigned long long)per, (unsigned long long)total);
+    else
+        hipLaunchKernelGGL(k_si_mix<false>, dim3(grid), dim3(256), 0, st, io->x, x1, x0, (const SiRow *)rows, (unsigned long long)per, (unsigned long long)total);
+    LSL_CHECK_LAUNCH("k_si_mix");
+    if (int rc = forward_passes(m, io, ws, plans, chunk, st)) return rc;
+    float *partial = (float *)((char *)workspace + align_up(lsl_workspace_bytes(m, io->B, io->T, io->L), 256));
+    return si_reduce_enqueue(io->out, x1, x0, rows, io->B, per, loss, partial, st);
 } catch (const std::bad_alloc &) {
     return fail(-5, "out of host memory");
 } catch (...) {

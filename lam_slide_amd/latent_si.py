@@ -220,11 +220,12 @@ class LatentSIV3(nn.Module):
         if self._handle:
             _lib.load().lsl_model_set_chunk(self._handle, self._chunk)
 
-    def workspace(self, B: int, T: int, L: int, device) -> Tensor:
+    def workspace(self, B: int, T: int, L: int, device, need: Optional[int] = None) -> Tensor:
         """Scratch of one call.  One buffer per (device, stream): two sampling calls of one model in flight on different streams
-        never share scratch (calls on ONE stream are ordered by the stream).  At most 4 buffers are kept."""
+        never share scratch (calls on ONE stream are ordered by the stream).  At most 4 buffers are kept.  ``need``: the bytes of a call
+        that wants more than a forward (``lsl_si_loss_workspace_bytes``)."""
         device = torch.device(device)
-        need = _lib.load().lsl_workspace_bytes(self._handle, B, T, L)
+        need = max(_lib.load().lsl_workspace_bytes(self._handle, B, T, L), need or 0)
         key = (device, torch.cuda.current_stream(device).cuda_stream)
         ws = self._workspaces.get(key)
         if ws is None or ws.numel() < need:

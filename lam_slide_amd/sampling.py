@@ -61,6 +61,7 @@ class SecondStageSampler:
         self.seed = seed
         self.calls = 0  # sampling calls made so far: call k draws its noise from stream mix_seed(seed, k)
         self.last_sampler: Optional[Sampler] = None
+        self.last_draws: Optional[Tuple[Tensor, Tensor]] = None  # (t, x0) of the most recent model_step
 
     def reseed(self, seed: Optional[int] = None):
         """Restart the noise streams: the next call is call 0 of ``seed`` (default: the current seed) again."""
@@ -108,6 +109,32 @@ class SecondStageSampler:
         out = fn(init, self.forward, **mk)[-1]
         self.last_sampler = sampler
         return out
+
+    @torch.no_grad()
+    def model_step(self, latents: Tensor, y: Optional[Tensor] = None, *, t: Optional[Tensor] = None, x0: Optional[Tensor] = None,
+                   first_index: int = 0) -> Dict[str, Tensor]:
+        """The validation loss of ``SecondStageCondLightningBase.model_step`` (lightning_base.py:190-193 -> Loss.forward ->
+        ``si.training_losses``) without Lightning: {"loss" [B], "pred"} for stage-1 latents [B,T,L,C], conditioning as in
+        :meth:`sample_latents`.  Without explicit draws, call k of this object takes ``x0`` from the counter stream ``mix_seed(seed, k)``
+        at the GLOBAL element index and ``t_b`` from ``mix_seed(call_seed, first_index + b)`` on the host (53 bits -> [0, 1) -> the
+        training interval): a rank that holds rows [first_index, first_index + B) draws what the unsharded call draws for them.  The
+        draws are kept in ``last_draws``."""
+        call_seed = self._next_call_seed()
+        B = latents.shape[0]
+        if B == 0:  # an empty shard: the call is counted, nothing to evaluate
+            return {"loss": latents.new_zeros(0), "pred": latents.new_zeros(latents.shape)}
+        x_cond, mask = setup_conditioning(latents, self.cond_idx, self.mask_cond_mean)
+        if x0 is None:
+            x0 = device_randn(latents.shape, latents.device, call_seed, int(first_index) * latents[0].numel()).to(latents.dtype)
+        if t is None:
+            t0, t1 = self.si.check_interval(self.si.train_eps, self.si.sample_eps)
+            u = [(mix_seed(call_seed, int(first_index) + b) >> 11) / float(1 << 53) for b in range(B)]
+            t = torch.tensor([v * (t1 - t0) + t0 for v in u], dtype=torch.float64).to(latents)
+        mk = {"x_cond": x_cond, "x_cond_mask": mask}
+        if y is not None:
+            mk["y"] = y
+        self.last_draws = (t, x0)
+        return self.si.training_losses(self.forward, latents, mk, t=t, x0=x0)
 
     @torch.no_grad()
     def sample_latents_k(self, latents: Tensor, K: int, y: Optional[Tensor] = None, inits: Optional[Tensor] = None) -> Tensor:

@@ -29,20 +29,34 @@ from . import _lib
 from .latent_si import LatentSIV3
 
 
-class ModelType(enum.Enum):
+class _ByName(enum.Enum):
+    """Members compare and hash by NAME against any enum class of the same class name, so ``model.si.model_type == ModelType.DATA`` holds
+    with the reference's own ``ModelType`` on the other side (second_stage/md17.py:232-234 asserts exactly that) and either enum finds the
+    other's entry in a dict (``Enum.__hash__`` is the hash of the member name there too)."""
+
+    def __eq__(self, other):
+        if isinstance(other, enum.Enum) and type(other).__name__ == type(self).__name__:
+            return self.name == other.name
+        return NotImplemented
+
+    def __hash__(self):
+        return hash(self._name_)
+
+
+class ModelType(_ByName):
     NOISE = enum.auto()
     SCORE = enum.auto()
     VELOCITY = enum.auto()
     DATA = enum.auto()
 
 
-class PathType(enum.Enum):
+class PathType(_ByName):
     LINEAR = enum.auto()
     GVP = enum.auto()
     VP = enum.auto()
 
 
-class WeightType(enum.Enum):
+class WeightType(_ByName):
     NONE = enum.auto()
     VELOCITY = enum.auto()
     LIKELIHOOD = enum.auto()
@@ -92,6 +106,25 @@ class _Schedule:
         s, ds = self.sigma(t)
         return -ratio, ratio * s * s - s * ds
 
+    def coeffs(self, t: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+        """(alpha, d_alpha, sigma, d_sigma, drift_var) of every entry of the float64 tensor ``t``: the formulas above, vectorised
+        (path.py: compute_alpha_t / compute_sigma_t / compute_drift of ICPlan, GVPCPlan, VPCPlan)."""
+        one = torch.ones_like(t)
+        if self.kind is PathType.VP:
+            lm, dlm = self._lm(t), self._dlm(t)
+            a = torch.exp(lm)
+            e2 = torch.exp(2 * lm)
+            s = torch.sqrt(1 - e2)
+            return a, a * dlm, s, e2 * (2 * dlm) / (-2 * s), (_SMIN + (1 - t) * (_SMAX - _SMIN)) / 2
+        if self.kind is PathType.LINEAR:
+            a, da, s, ds = t, one, 1 - t, -one
+            ratio = 1 / t
+        else:
+            h = t * (math.pi / 2)
+            a, da, s, ds = torch.sin(h), math.pi / 2 * torch.cos(h), torch.cos(h), -math.pi / 2 * torch.sin(h)
+            ratio = math.pi / (2 * torch.tan(h))
+        return a, da, s, ds, ratio * s * s - s * ds
+
     def diffusion(self, t: float, form: str, norm: float) -> float:
         if form == "constant":
             return norm
@@ -116,6 +149,7 @@ class Transport:
         self.schedule = _Schedule(path_type)
         self.train_eps = train_eps
         self.sample_eps = sample_eps
+        self.last_path: Optional[str] = None  # "fused" | "generic" after a training_losses / si_loss call
 
     def check_interval(self, train_eps, sample_eps, *, diffusion_form="SBDM", sde=False, reverse=False, eval=False,
                        last_step_size=0.0):
@@ -153,6 +187,135 @@ class Transport:
         rev = a / da
         var = s * s - rev * ds * s
         return -1.0 / var, rev / var
+
+
+    # ---- the stochastic-interpolant objective without gradients (transport.py:103-156) ---------------------------------------------
+    def sample(self, x1: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+        """(t, x0, x1) with the reference's draws in the reference's order (transport.py:103-114): the noise first, then one uniform per
+        trajectory from the CPU generator scaled into the training interval.  Same seed, same device: the reference's ``t`` and ``x0``."""
+        x0 = torch.randn_like(x1)
+        t0, t1 = self.check_interval(self.train_eps, self.sample_eps)
+        t = torch.rand((x1.shape[0],)) * (t1 - t0) + t0
+        t = t.to(x1)
+        return t, x0, x1
+
+    def si_rows(self, t: Tensor) -> Tensor:
+        """The ``[B, 6]`` float32 table (alpha, sigma, p, q1, q0, w) of ``lsl_si_row`` (include/lsl_api.h) on the host: for trajectory b
+            xt = alpha x1 + sigma x0,   r = p pred + q1 x1 + q0 x0,   loss_b = w mean(r^2)
+        restates transport.py:135-154 for this transport's prediction and loss weight.  Derived once per call, vectorised over ``t``, in
+        float64 from the float32 times and rounded to float32 (as ``velocity_coeffs`` does for the samplers)."""
+        t64 = t.detach().to(device="cpu", dtype=torch.float32).double()
+        a, da, s, ds, var = self.schedule.coeffs(t64)
+        one, zero = torch.ones_like(t64), torch.zeros_like(t64)
+        if self.model_type == ModelType.VELOCITY:
+            p, q1, q0, w = one, -da, -ds, one
+        elif self.model_type == ModelType.DATA:
+            p, q1, q0, w = one, -one, zero, one
+        else:
+            if self.loss_type == WeightType.VELOCITY:
+                w = (var / s) ** 2
+            elif self.loss_type == WeightType.LIKELIHOOD:
+                w = var / (s * s)
+            elif self.loss_type == WeightType.NONE:
+                w = one
+            else:
+                raise NotImplementedError()
+            p, q1, q0 = (one, zero, -one) if self.model_type == ModelType.NOISE else (s, zero, one)
+        return torch.stack([a, s, p, q1, q0, w], dim=1).float()
+
+    def si_loss(self, model: Callable, x1: Tensor, t: Tensor, x0: Tensor, model_kwargs: Optional[Dict[str, Any]] = None) -> Dict[str, Tensor]:
+        """``training_losses`` on given draws: {"pred", "loss" [B], "xt"}.  A ``lam_slide_amd.LatentSIV3`` behind ``model`` (the module, its
+        bound ``forward``, a LightningModule or its bound ``forward``, through ``torch.compile`` wrappers) with a contiguous float32 GPU
+        ``x1`` runs as ONE library call (``lsl_si_loss``: interpolant, network, reduction); any other callable goes through the same affine
+        table in torch.  No backward exists on the HIP path: with grad mode on and a trainable backbone this raises instead of returning
+        a loss that trains nothing."""
+        model_kwargs = {} if model_kwargs is None else model_kwargs
+        net = resolve_backbone(model)
+        if net is None:  # Loss.forward hands over the LightningModule itself (second_stage/md17.py:221): its bound forward is the trusted case
+            net = resolve_backbone(getattr(model, "forward", None))
+        if net is not None and torch.is_grad_enabled() and any(p.requires_grad for p in net.parameters()):
+            raise RuntimeError("lam_slide_amd evaluates the stochastic-interpolant loss without gradients (the HIP path has no backward): call "
+                               "training_losses under torch.no_grad() (as every validation_step does), or freeze the backbone")
+        rows = self.si_rows(t)
+        if net is not None and x1.is_cuda and x1.dtype == torch.float32 and x1.is_contiguous():
+            self.last_path = "fused"
+            return self._si_loss_fused(net, x1, t, x0, rows, model_kwargs)
+        self.last_path = "generic"
+        bshape = (x1.shape[0],) + (1,) * (x1.dim() - 1)
+        alpha, sigma, p, q1, q0, w = (rows[:, i].to(x1).reshape(bshape) for i in range(6))
+        xt = alpha * x1 + sigma * x0
+        pred = model(xt, t, **model_kwargs)
+        B, *_, Cc = xt.shape
+        assert pred.size() == (B, *xt.size()[1:-1], Cc)
+        r = p * pred + q1 * x1 + q0 * x0
+        loss = w.reshape(-1) * (r ** 2).mean(dim=list(range(1, r.dim())))
+        return {"pred": pred, "loss": loss, "xt": xt}
+
+    def _si_loss_fused(self, net: "LatentSIV3", x1: Tensor, t: Tensor, x0: Tensor, rows: Tensor, model_kwargs: Dict[str, Any]) -> Dict[str, Tensor]:
+        extra = set(model_kwargs) - {"x_cond", "x_cond_mask", "y"}
+        if extra:
+            raise TypeError(f"unexpected model kwargs {sorted(extra)}")
+        for name in ("x_cond", "x_cond_mask"):
+            if name not in model_kwargs:
+                raise TypeError(f"missing model kwarg {name!r}")
+        lib = _lib.load()
+        dev = x1.device
+        B = x1.shape[0]
+        if tuple(x0.shape) != tuple(x1.shape) or tuple(t.shape) != (B,):
+            raise ValueError(f"x0 must be shaped like x1 {tuple(x1.shape)} and t ({B},), got {tuple(x0.shape)} and {tuple(t.shape)}")
+        for name, ten in (("t", t), ("x0", x0)):
+            if ten.device != dev:
+                raise RuntimeError(f"Expected all tensors to be on the same device, but {name} is on {ten.device} and x1 is on {dev}")
+        with torch.cuda.device(dev):
+            net.ensure_packed(dev)
+            x1 = x1.detach()
+            x0 = x0.detach().float().contiguous()
+            tt = t.detach().float().contiguous()
+            xt, pred = torch.empty_like(x1), torch.empty_like(x1)
+            loss = torch.empty(B, dtype=torch.float32, device=dev)
+            table = rows.contiguous().to(dev)
+            io, keep = net.make_io(xt, model_kwargs["x_cond"], model_kwargs["x_cond_mask"], model_kwargs.get("y"), tt, pred)
+            ws = net.workspace(io.B, io.T, io.L, dev, need=lib.lsl_si_loss_workspace_bytes(net._handle, io.B, io.T, io.L))
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.lsl_si_loss(net._handle, C.byref(io), x1.data_ptr(), x0.data_ptr(), table.data_ptr(), loss.data_ptr(), ws.data_ptr(),
+                                       ws.numel(), stream))
+        net.last_path = "hip"
+        del keep
+        return {"pred": pred, "loss": loss, "xt": xt}
+
+    def training_losses(self, model: Callable, x1: Tensor, model_kwargs: Optional[Dict[str, Any]] = None, *, t: Optional[Tensor] = None,
+                        x0: Optional[Tensor] = None) -> Dict[str, Tensor]:
+        """``Transport.training_losses`` of the reference (transport.py:116-156) evaluated without gradients: {"pred", "loss"} with ``loss``
+        of shape [B].  ``t`` / ``x0`` (keyword only) fix the draws; whichever is missing comes from :meth:`sample`."""
+        if t is None or x0 is None:
+            td, x0d, _ = self.sample(x1)
+            t = td if t is None else t
+            x0 = x0d if x0 is None else x0
+        out = self.si_loss(model, x1, t, x0, model_kwargs)
+        return {"pred": out["pred"], "loss": out["loss"]}
+
+
+def si_reduce(pred: Tensor, x1: Tensor, x0: Tensor, rows: Tensor) -> Tensor:
+    """The reduction of the objective alone on the device (``lsl_si_reduce``): loss[b] = w_b mean((p_b pred + q1_b x1 + q0_b x0)^2) for
+    contiguous float32 GPU tensors [B, ...] and a ``Transport.si_rows`` table.  Deterministic, and independent of the batch a trajectory
+    is in."""
+    if not pred.is_cuda:
+        raise RuntimeError("si_reduce runs on the GPU (HIP kernel); there is no CPU fallback")
+    B = pred.shape[0]
+    per = pred[0].numel()
+    for name, ten in (("pred", pred), ("x1", x1), ("x0", x0)):
+        if ten.shape != pred.shape or ten.dtype != torch.float32 or not ten.is_contiguous() or ten.device != pred.device:
+            raise ValueError(f"{name} must be a contiguous float32 tensor shaped like pred on pred's device")
+    if tuple(rows.shape) != (B, 6):
+        raise ValueError(f"rows must be [{B}, 6], got {tuple(rows.shape)}")
+    dev = pred.device
+    with torch.cuda.device(dev):
+        table = rows.float().contiguous().to(dev)
+        loss = torch.empty(B, dtype=torch.float32, device=dev)
+        scratch = torch.empty(B * ((per + _lib.SI_SLAB - 1) // _lib.SI_SLAB), dtype=torch.float32, device=dev)
+        _lib.check(_lib.load().lsl_si_reduce(pred.data_ptr(), x1.data_ptr(), x0.data_ptr(), table.data_ptr(), B, per, loss.data_ptr(),
+                                             scratch.data_ptr(), scratch.numel() * 4, torch.cuda.current_stream(dev).cuda_stream))
+    return loss
 
 
 class CreateTransport:

@@ -19,6 +19,10 @@ Fixture families:
   f11_pedestrian_k.npz  the reference's REAL pedestrian CondWrapper: prepare_batch (class vector y) and the K = 20 test_step loop (ADE / FDE)
   f13_peptide.npz       the reference's REAL peptide Wrapper at T = 1000: encode -> sample -> decode to atom14 positions
   f12_nba_k.npz         the reference's REAL NBA CondWrapper at the NBA shape: prepare_batch and the K = 60 / num_runs = 20 test_step loop
+  f15_si_loss.npz   Transport.training_losses for all 36 path x prediction x loss-weight combinations on stored draws (closed-form model), and
+                    what Transport.sample draws under torch.manual_seed(1234)
+  f16_model_step.npz  the reference's REAL md17 Wrapper.model_step (prepare_batch, Loss.forward with calc_additional_losses, decode, the three
+                    masked losses) in the F9 environment, draws fixed; F9's weights
   f9_sample.npz     the reference's REAL LightningModule (second_stage/md17.py Wrapper built by its own __init__ from the reference YAML,
                     lightning_base.py sample / prepare_batch / setup_conditioning unchanged; tools/ref_env.py supplies the Lightning / Hydra
                     stand-ins): stage-1 inputs -> encode -> conditioning -> 5 Euler updates -> decode, with the initial noise fixed
@@ -517,6 +521,115 @@ def f9():
         meta=np.array([F["B"], F["T"], F["A"], F["L"], F["cond_idx"][0], F["cond_idx"][1], F["num_steps"]]))
 
 
+# ------------------------------------------------------------------------------------------- F15
+F15_PATHS, F15_PREDS, F15_WEIGHTS = ("Linear", "GVP", "VP"), ("velocity", "data", "noise", "score"), (None, "velocity", "likelihood")
+
+
+def f15_model(xt, t, **kw):
+    """The closed-form "network" of F15 (restated in tests/test_si_loss.py)."""
+    return 0.7 * torch.tanh(xt) + 0.3 * torch.sin(3 * xt + t.reshape(-1, *([1] * (xt.dim() - 1))))
+
+
+def f15():
+    """Transport.training_losses (transport.py:116-156) of the reference for all 36 combinations, with Transport.sample pinned to stored t, x0.
+    t is spread over [0.05, 0.9]: next to t1 = 1 - 1e-5 the reference's fp32 sigma_t = sqrt(1 - exp(2 lmc)) of the VP path loses the value
+    itself (its own rounding, not something a restatement can follow).  Plus the draws of Transport.sample under torch.manual_seed(1234)."""
+    import lam_slide_amd
+    g = torch.Generator().manual_seed(150)
+    B, T, L, Cc = 6, 3, 4, 8
+    x1 = torch.randn(B, T, L, Cc, generator=g)
+    x0 = torch.randn(B, T, L, Cc, generator=g)
+    t = torch.linspace(0.05, 0.9, B)[torch.randperm(B, generator=g)].contiguous()
+    arrays, worst = {}, 0.0
+    for path in F15_PATHS:
+        for pred in F15_PREDS:
+            for lw in F15_WEIGHTS:
+                tr = CreateTransport(path, pred, lw)()
+                tr.sample = lambda x, t=t, x0=x0: (t, x0, x)
+                out = tr.training_losses(f15_model, x1)
+                mine = lam_slide_amd.CreateTransport(path, pred, lw)().training_losses(f15_model, x1, t=t, x0=x0)
+                worst = max(worst, float(((mine["loss"] - out["loss"]).abs() / out["loss"].abs()).max()))
+                assert rel(mine["pred"], out["pred"]) < 1e-6
+                arrays[f"{path}_{pred}_{lw}"] = {"loss": out["loss"], "pred": out["pred"]}
+    print(f"F15: 36 combinations, worst per-trajectory relative loss error of the package's generic path {worst:.2e}")
+    assert worst < 1e-5
+    draws = {}
+    for path, pred in (("GVP", "data"), ("Linear", "velocity")):
+        torch.manual_seed(1234)
+        td, x0d, _ = CreateTransport(path, pred)().sample(x1)
+        draws[f"{path}_{pred}_t"] = td
+        draws[f"{path}_{pred}_x0"] = x0d[0, 0, 0, :4].clone()
+    npz("f15_si_loss.npz", t=t, x0=x0, x1=x1, draws=draws, **arrays)
+
+
+# ------------------------------------------------------------------------------------------- F16
+def f16():
+    """SecondStageCondLightningBase.model_step (lightning_base.py:190-193) executed UNCHANGED on the reference's real md17 Wrapper: its own
+    prepare_batch, Loss.forward with calc_additional_losses as configs/model/md17/second-stage.yaml says, decode and the three masked losses.
+    The F9 environment with positions [B, T, A, 3] lifted to the stage-1 input width.  Run twice: the reference's CreateTransport, and
+    transport._target_ = lam_slide_amd.CreateTransport (the reference backbone then goes through this package's generic path); the two loss
+    dicts must agree, the first is the fixture.  Weights are F9's (asserted), so none are stored."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import ref_env
+    import lam_slide_amd  # noqa: F401
+    from lam_slide_amd import dropin
+    dropin.uninstall()
+    ns = ref_env.setup()
+    F = ref_env.F9
+    lift = torch.randn(3, 128, generator=torch.Generator().manual_seed(160)) * 0.5
+    batch = ref_env.f9_batch()
+    batch["pos"] = torch.randn(F["B"], F["T"], F["A"], 3, generator=torch.Generator().manual_seed(161))
+    g = torch.Generator().manual_seed(162)
+    x0 = torch.randn(F["B"], F["T"], F["L"], 32, generator=g)
+
+    def run(transport_target):
+        first, first_cls = ref_env.build_first_stage(ns, lift=lift)
+        w = ref_env.build_wrapper(ns, "src.models.components.latent.latent_si_v31.LatentSIV3", transport_target, first, first_cls)
+        w.eval()
+        t0, t1 = w.si.check_interval(w.si.train_eps, w.si.sample_eps)
+        t = torch.tensor([0.37, 0.81])[: F["B"]] * (t1 - t0) + t0
+        w.si.sample = lambda x1: (t, x0.to(x1), x1)
+        seen = {}
+        real = w.si.training_losses
+
+        def tap(model, x1, model_kwargs=None):
+            assert model is w  # (Loss.forward hands over the LightningModule itself)
+            out = real(model=model, x1=x1, model_kwargs=model_kwargs)
+            seen.update(loss=out["loss"].clone(), pred=out["pred"].clone(), x1=x1.clone(), x_cond=model_kwargs["x_cond"].clone(),
+                        mask=model_kwargs["x_cond_mask"].clone())
+            return out
+
+        w.si.training_losses = tap
+        with torch.no_grad():
+            losses, _ = w.model_step({k: v.clone() for k, v in batch.items()})
+        return w, first, t, seen, {k: v.detach().clone() for k, v in losses.items()}
+
+    w, first, t, seen, losses = run("src.modules.transport.CreateTransport")
+    w2, _, t2, seen2, losses2 = run("lam_slide_amd.CreateTransport")
+    dropin.uninstall()
+    assert type(w2.si).__module__.startswith("lam_slide_amd") and w2.si.last_path == "generic" and torch.equal(t, t2)
+    assert set(losses) == {"si_loss", "pos_loss", "inter_dist_loss", "dist", "loss"} == set(losses2)
+    e_swap = max(float((losses2[k] - losses[k]).abs() / losses[k].abs()) for k in losses)
+    print(f"F16 real md17 Wrapper.model_step: " + " ".join(f"{k} {float(v):.6f}" for k, v in losses.items()) + f"; transport swap rel {e_swap:.2e}")
+    assert e_swap < 2e-6 and rel(seen2["pred"], seen["pred"]) < 2e-6
+    # the weights are F9's: the tests take them from f9_sample.npz
+    f9 = {}
+    for part in [os.path.join(OUT, "f9_sample.npz")] + sorted(glob.glob(os.path.join(OUT, "f9_sample.part*.npz"))):
+        z = np.load(part)
+        f9.update({k: z[k] for k in z.files})
+    sd = w.backbone.state_dict()
+    assert all(np.array_equal(f9["backbone/" + k], v.numpy()) for k, v in sd.items()) and len(sd) == sum(k.startswith("backbone/") for k in f9)
+    extra = {}
+    for k, v in first.backbone.state_dict().items():
+        if not np.array_equal(f9["stage1/" + k], v.numpy()):
+            assert k.endswith("entity_embedding.embedding.weight"), k  # (nn.Embedding(max_norm=1) renormalises the looked-up rows in place)
+            extra[k] = v.clone()
+    print(f"F16: backbone = f9_sample.npz ({len(sd)} tensors, bit-equal); stage-1 tensors that differ from the stored ones: {sorted(extra)}")
+    npz("f16_model_step.npz", lift=lift, pos=batch["pos"], entities=batch["entities"], attention_mask=batch["attention_mask"], t=t, x0=x0,
+        latents=seen["x1"], x_cond=seen["x_cond"], mask=seen["mask"], pred=seen["pred"], loss=seen["loss"], losses=losses,
+        **({"stage1_tables": extra} if extra else {}))
+
+
 # ------------------------------------------------------------------------------------------- F10
 F10_CASES = {
     # attention_mode="linear" (mmdit.py:50-53, 58-72; no shipped config selects it).  name: (NetShape kwargs, B, T, L, weight seed)
@@ -733,6 +846,6 @@ def f13():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["f1", "f2", "f3", "f4", "f5", "f6", "f7", "f8", "f9", "f10", "f11", "f12", "f13"]
+    which = sys.argv[1:] or ["f1", "f2", "f3", "f4", "f5", "f6", "f7", "f8", "f9", "f10", "f11", "f12", "f13", "f15", "f16"]
     for w in which:
         globals()[w]()

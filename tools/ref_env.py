@@ -18,7 +18,7 @@ stand-ins that let those files import:
     src.datasets.md17              only ``dataset_cond_indices`` (a dict of 8 molecule names; the real module imports the dataset stack)
     lightning_utilities.core.rank_zero   the two names pylogger imports
 
-Used by ``tools/make_fixtures.py f9 f11``.  Nothing here ships.
+Used by ``tools/make_fixtures.py f9 f11 f12 f13 f16``.  Nothing here ships.
 """
 from __future__ import annotations
 
