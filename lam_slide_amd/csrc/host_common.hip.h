@@ -1,5 +1,6 @@
-// Host side, part 1 of 4: error convention, the model handle, the scratch layout of a pass (carve), pass size, per-device one-time kernel
-// attributes and the device guard.  Included by lsl_api.hip only (one translation unit; everything here has internal linkage).
+// Host side, part 1 of 4: error convention (fail, LSL_API_CATCH: the exception tail of every entry point), the model handle, the scratch
+// layout of a pass (carve), pass size, per-device one-time kernel attributes and the device guard.  Included by lsl_api.hip only (one
+// translation unit; everything here has internal linkage).
 #pragma once
 
 namespace {
@@ -19,6 +20,14 @@ int fail(int code, const char *fmt, ...) {
         hipError_t e_ = hipGetLastError();                                         \
         if (e_ != hipSuccess) return fail(-10, "%s: %s", name, hipGetErrorString(e_)); \
     } while (0)
+
+// Behind the function-try-block of every C entry point: no exception crosses the ABI
+#define LSL_API_CATCH                                \
+    catch (const std::bad_alloc &) {                 \
+        return fail(-5, "out of host memory");       \
+    } catch (...) {                                  \
+        return fail(-11, "unexpected C++ exception"); \
+    }
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -49,6 +58,8 @@ struct Profiler {
     }
 };
 
+#include "host_graph.hip.h"
+
 struct lsl_model {
     Profiler prof;
     lsl_model_desc d;
@@ -60,20 +71,7 @@ struct lsl_model {
     int HHD, F1, K2, MODW;
     bool ln_fuse = false;  // LayerNorm + modulate inside linear1's activation load (k_lin1.hip.h LNF): lsl_model_set_ln_fuse, a property of the HANDLE
     bool tail = false;  // the back half of every sub-block runs k_tail (k_tail.hip.h): a property of the HANDLE (lsl_model_set_tail), never of the batch
-    // hipGraph cache of lsl_sample: a call whose arguments (pointers, sizes, step table) repeat is captured once and replayed; the
-    // small-batch configs are launch-bound (~700 launches of a few microseconds per sampling call)
-    struct GraphEntry {
-        std::vector<unsigned char> key;
-        hipGraphExec_t exec = nullptr;
-        unsigned long long last_use = 0;
-    };
-    std::vector<GraphEntry> graphs;
-    std::vector<std::vector<unsigned char>> seen;  // argument sets that ran eagerly once (capture happens on their second appearance)
-    std::vector<std::vector<unsigned char>> uncapturable;  // argument sets whose capture failed: never tried again
-    bool graph_stream_failed = false;                      // the internal capture stream could not be created: no further attempts
-    unsigned long long graph_clock = 0;
-    hipStream_t graph_stream = nullptr;  // capture happens on this internal stream (the caller's may be the legacy default stream, which
-                                         // cannot be captured); the instantiated graph is launched on the caller's stream
+    GraphCache graphs;  // hipGraph replay of lsl_sample / lsl_sample_ex calls whose arguments repeat (host_graph.hip.h)
 };
 
 namespace {
@@ -97,8 +95,7 @@ struct Workspace {
     size_t bytes;
 };
 
-int env_int(const char *name, int dflt);
-int tune_int(const char *name, int dflt);
+// (host_launch.hip.h)
 bool linear2_ws_shape_ok(int D, int K2);
 size_t tail_stream_bytes(const lsl_model *m);
 

@@ -1,6 +1,6 @@
-// Host side, part 3 of 4: the plan of a pass (which kernels its sub-blocks run, checked before the first launch); the kernel sequence of one
-// network evaluation (conditioning tables, sub-blocks, embedding, head), of a pass, and of the trajectory-resident sampler; argument checks of
-// a call.  Inside the anonymous namespace opened by host_common.hip.h.
+// Host side, part 3 of 4: the plan of a pass (which kernel and instance every launch of its sub-blocks runs, decided and checked before the
+// first launch; the profiler's labels are read off it); the kernel sequence of one network evaluation (conditioning tables, sub-blocks,
+// embedding, head), of a pass, of a call's passes, and of the trajectory-resident sampler; argument checks of a call.  Inside the anonymous namespace opened by host_common.hip.h.
 #pragma once
 
 // ---- pieces of one evaluation ----------------------------------------------------------------------
@@ -104,9 +104,12 @@ struct PassPlan {
     int lin1_waves;  // its waves per workgroup (linear1_ts_waves)
     bool ln_stats;   // ln_fuse handles: k_linear2_ws leaves the rows' statistics for the next sub-block, whose linear1 normalises on load
     bool emb_stats;  // ... and the embedding leaves them for the first sub-block
+    int gemm1;       // !lin1_ts: the tiling of the tile GEMM (gemm_variant)
     bool planes[2];  // q / k / v as head-major planes: [spatial, temporal] sub-blocks
+    AttnPlan attn[2];  // the attention form of the [spatial, temporal] sub-blocks
     Lin2Kind lin2;
     Lin2Grid l2grid;  // lin2 == ws
+    int gemm2;        // lin2 == gemm: its tiling
 
     bool a_from_tail(int bi) const { return mode == PlanMode::eval && tail && bi > 0; }  // ws.a written by the previous sub-block's k_tail
     bool lin1_lnf(int bi) const { return mode == PlanMode::eval && ln_stats && (bi > 0 || emb_stats); }  // no LayerNorm launch, ws.a unused
@@ -136,11 +139,16 @@ int plan_pass(const lsl_model *m, const Workspace &ws, int bc, int T, int L, int
                  linear1_lnf_ok(d.head_dim_pad, D, m->F1, m->HHD, n, T * L, mod_stride);
     // (models without the in-place LayerNorm behind the embedding)
     p.emb_stats = p.ln_stats && mode == PlanMode::eval && !d.normalize && embed_stats_ok(d.in_dim, D);
-    for (int t = 0; t < 2; ++t) p.planes[t] = !m->attention_linear && qkv_planes_ok(d.head_dim_pad, D, d.heads, t ? T : L, t != 0, p.lin1_ts);
+    if (!p.lin1_ts) p.gemm1 = gemm_variant(false, p.F1, D, n);
+    for (int t = 0; t < 2; ++t) {
+        p.attn[t] = plan_attention(m->attention_linear, d.head_dim_pad, d.heads, d.head_dim, bc, T, L, t != 0);
+        p.planes[t] = qkv_planes_ok(d.head_dim_pad, d.heads, t ? T : L, t != 0, p.lin1_ts, p.attn[t]);
+    }
     const bool ws_reach = ws.w2p && (unsigned long long)n * (unsigned)(4 * D) < (1ull << 32);  // (k_linear2_ws: 32-bit byte offsets into h)
     if (ws_reach) p.l2grid = linear2_ws_grid(D, n, T * L, mod_stride == 0);
     const bool on_ws = ws_reach && p.l2grid.gate_rows <= linear2_ws_max_gate_rows(m->K2);
     p.lin2 = mode == PlanMode::debug_taps ? Lin2Kind::none : p.tail ? Lin2Kind::tail : on_ws ? Lin2Kind::ws : Lin2Kind::gemm;
+    if (p.lin2 == Lin2Kind::gemm) p.gemm2 = gemm_variant(true, D, m->K2, n);
 
     const int b0 = mode == PlanMode::eval ? 0 : block, b1 = mode == PlanMode::eval ? p.blocks : block + 1;  // the sub-blocks the call runs
     for (int bi = b0; bi < b1; ++bi) {
@@ -175,82 +183,91 @@ int plan_call(const lsl_model *m, const Workspace &ws, const lsl_io *io, int chu
     return 0;
 }
 
-// one ParallelMLPAttentionV2 sub-block on ws.h (in place): LN+modulate -> linear1 -> attention -> linear2
+// What sub-block bi's launch of the profiled class (0 linear1, 1 linear2 / tail, 2 attention) runs, for lsl_profile_kernel_name: read off the plan
+void label_block(lsl_model *m, const PassPlan &p, int bi) {
+    const lsl_model_desc &d = m->d;
+    Profiler &pr = m->prof;
+    switch (pr.kernel) {
+        case 0:
+            if (!p.lin1_ts) pr.label(0, "k_gemm_glds<EpiLinear1<%d>> (tiling %d)", d.head_dim_pad, p.gemm1);
+            else if (p.lin1_lnf(bi)) pr.label(0, "k_linear1_ts<%d, %d, 8, true> (LayerNorm fused)", d.head_dim_pad, d.hidden);
+            else pr.label(0, "k_linear1_ts<%d, %d, %d>%s", d.head_dim_pad, d.hidden, p.lin1_waves, p.tail ? " (q | k | v)" : "");
+            break;
+        case 1:
+            if (p.lin2 == Lin2Kind::tail) pr.label(1, "k_tail<%d, %d>", d.hidden, m->HHD);
+            else if (p.lin2 == Lin2Kind::ws) pr.label(1, p.lin2_stats(bi) ? "k_linear2_ws<%d> (+ row statistics)" : "k_linear2_ws<%d>", m->K2);
+            else if (p.lin2 == Lin2Kind::gemm) pr.label(1, "k_gemm_glds<EpiLinear2> (tiling %d)", p.gemm2);
+            break;
+        case 2: {
+            const AttnPlan &a = p.attn[bi & 1];
+            pr.label(2, "%s", a.form == AttnForm::linear ? "k_attention_linear" : a.stream() ? "k_attention_stream" : "k_attention_rows / k_attention_tiny / k_attention");
+            break;
+        }
+        default: break;
+    }
+}
+
+unsigned magic_of(int dv) { return dv == 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)dv + 1); }  // floor(2^32 / dv) + 1: division by multiply-high
+
+template <int HDP>
+void launch_linear1_gemm(const lsl_model *m, const Workspace &ws, const PassPlan &p, int bi, int pdiv, int pmod, float premul, hipStream_t st) {
+    const lsl_block_weights &bw = m->blocks[bi];
+    const EpiLinear1<HDP> e{bw.b1, bw.qs, bw.ks, (bi & 1) ? ws.rope_t : ws.rope_l, ws.rope_qk + (size_t)(2 * bi) * ws.rope_qk_stride,
+                            ws.rope_qk + (size_t)(2 * bi + 1) * ws.rope_qk_stride, ws.qkv, ws.z, m->HHD, m->d.mlp_dim,
+                            pdiv, pmod, magic_of(pdiv), magic_of(pmod), 1.0f / m->d.head_dim, premul, 0};
+    launch_gemm(p.gemm1, (const u16 *)bw.w1, ws.a, p.F1, p.n, m->d.hidden, e, st, m->HHD);
+}
+
+AttnArgs attention_args(const lsl_model *m, const Workspace &ws, const PassPlan &p, int bi, float premul) {
+    const lsl_model_desc &d = m->d;
+    const AttnPlan &ap = p.attn[bi & 1];
+    static const int nt_mask = tune_int("LSL_NT", 3);
+    static const int attn_bound = tune_int("LSL_ATTN_BOUND", 1);
+    AttnArgs aa{};
+    aa.nt = (nt_mask >> 2) & 1;
+    aa.qkv = ws.qkv; aa.z = ws.z; aa.HHD = m->HHD; aa.zw = m->K2; aa.H = d.heads; aa.hd = d.head_dim; aa.premul = premul;
+    aa.kmax2 = ws.kmax2 + bi;
+    aa.qmax2 = ws.kmax2 + 2 * d.depth + bi;
+    aa.planes = p.planes[bi & 1] ? 1 : 0;
+    aa.npad = p.npad;
+    aa.bound = attn_bound == 2 || (attn_bound == 1 && ((bi & 1) ? p.T : p.L) > 96);  // short axes: the max pass is one or two tiles, cheaper than the norms
+    aa.S = ap.S; aa.n_seq = ap.n_seq; aa.inner = ap.inner; aa.outer_stride = ap.outer_stride; aa.pos_stride = ap.pos_stride;
+    aa.blk = ap.blk; aa.n_tok = ap.n_tok;
+    return aa;
+}
+
+// one ParallelMLPAttentionV2 sub-block on ws.h (in place): LN+modulate -> linear1 -> attention -> linear2; which kernels: the plan
 int run_block(lsl_model *m, const Workspace &ws, const PassPlan &p, int bi, const float *mods, hipStream_t st) {
     const lsl_model_desc &d = m->d;
     const lsl_block_weights &bw = m->blocks[bi];
-    const int D = d.hidden, n = p.n, T = p.T, L = p.L, mod_stride = p.mod_stride, layer = bi / 2, temporal = bi & 1;
-    const float *mbase = mods + (size_t)layer * 6 * D + (temporal ? 3 * D : 0);  // shift, scale, gate
+    const int D = d.hidden, n = p.n, tpt = p.T * p.L, mod_stride = p.mod_stride, temporal = bi & 1;
+    const float *mbase = mods + (size_t)(bi / 2) * 6 * D + (temporal ? 3 * D : 0);  // shift, scale, gate
     const bool lnf = p.lin1_lnf(bi);  // (ws.lnstat holds the statistics of h)
+    // softmax attention: log2(e) / sqrt(head_dim) rides on q (the kernels use exp2); attention_linear takes the plain normalised, rotated q
+    const float premul = m->attention_linear ? 1.0f : (float)(1.4426950408889634 / std::sqrt((double)d.head_dim));
+    const int pdiv = temporal ? p.L : 1, pmod = temporal ? p.T : p.L;  // position of token n = (n / pdiv) % pmod (plan_pass: the range check)
+    label_block(m, p, bi);
     if (!p.a_from_tail(bi) && !lnf) {
         m->prof.begin(3, st);
-        DISPATCH_D(D, launch_ln_mod_t, ws.a, ws.h, mbase, mbase + D, mod_stride, n, T * L, st);
+        DISPATCH_D(D, launch_ln_mod_t, ws.a, ws.h, mbase, mbase + D, mod_stride, n, tpt, st);
         m->prof.end(3, st);
     }
     m->prof.begin(0, st);
-
-    // softmax attention: log2(e) / sqrt(head_dim) rides on q (the kernels use exp2); attention_linear takes the plain normalised, rotated q
-    const float premul = m->attention_linear ? 1.0f : (float)(1.4426950408889634 / std::sqrt((double)d.head_dim));
-    const int pdiv = temporal ? L : 1, pmod = temporal ? T : L;  // position of token n = (n / pdiv) % pmod (plan_pass: the range check)
-    auto magic_of = [](int dv) { return dv == 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)dv + 1); };
-    const bool planes = p.planes[temporal];
     if (p.lin1_ts) {
         const Lin1Args la{(const u16 *)bw.w1, lnf ? (const u16 *)ws.h : ws.a, bw.b1, ws.rope_qk + (size_t)(2 * bi) * ws.rope_qk_stride,
                           ws.rope_qk + (size_t)(2 * bi + 1) * ws.rope_qk_stride, ws.qkv, ws.z, p.F1, n, m->HHD, d.mlp_dim,
-                          pdiv, pmod, magic_of(pdiv), magic_of(pmod), 1.0f / d.head_dim, premul, 1, 0, planes ? 1 : 0, p.npad,
-                          ws.lnstat, mbase, mbase + D, mod_stride, T * L, magic_of(T * L)};
-        if (lnf) {
-            launch_linear1_lnf(d.head_dim_pad, D, la, st);
-            m->prof.label(0, "k_linear1_ts<%d, %d, 8, true> (LayerNorm fused)", d.head_dim_pad, D);
-        } else {
-            launch_linear1_ts(d.head_dim_pad, D, p.lin1_waves, la, st);
-            m->prof.label(0, "k_linear1_ts<%d, %d, %d>%s", d.head_dim_pad, D, p.lin1_waves, p.tail ? " (q | k | v)" : "");
-        }
-    } else {
-        if (d.head_dim_pad == 32) {
-            EpiLinear1<32> e{bw.b1, bw.qs, bw.ks, temporal ? ws.rope_t : ws.rope_l, ws.rope_qk + (size_t)(2 * bi) * ws.rope_qk_stride,
-                             ws.rope_qk + (size_t)(2 * bi + 1) * ws.rope_qk_stride, ws.qkv, ws.z, m->HHD, d.mlp_dim,
-                             pdiv, pmod, magic_of(pdiv), magic_of(pmod), 1.0f / d.head_dim, premul, 0};
-            launch_gemm((const u16 *)bw.w1, ws.a, p.F1, n, D, e, st, m->HHD);
-        } else {
-            EpiLinear1<16> e{bw.b1, bw.qs, bw.ks, temporal ? ws.rope_t : ws.rope_l, ws.rope_qk + (size_t)(2 * bi) * ws.rope_qk_stride,
-                             ws.rope_qk + (size_t)(2 * bi + 1) * ws.rope_qk_stride, ws.qkv, ws.z, m->HHD, d.mlp_dim,
-                             pdiv, pmod, magic_of(pdiv), magic_of(pmod), 1.0f / d.head_dim, premul, 0};
-            launch_gemm((const u16 *)bw.w1, ws.a, p.F1, n, D, e, st, m->HHD);
-        }
-        m->prof.label(0, "k_gemm_glds<EpiLinear1<%d>> (tiling %d)", d.head_dim_pad, gemm_variant<EpiLinear1<32>>(p.F1, D, n));
-    }
+                          pdiv, pmod, magic_of(pdiv), magic_of(pmod), 1.0f / d.head_dim, premul, 1, 0, p.planes[temporal] ? 1 : 0, p.npad,
+                          ws.lnstat, mbase, mbase + D, mod_stride, tpt, magic_of(tpt)};
+        launch_linear1_ts(d.head_dim_pad, D, p.lin1_waves, lnf, la, st);
+    } else if (d.head_dim_pad == 32) launch_linear1_gemm<32>(m, ws, p, bi, pdiv, pmod, premul, st);
+    else launch_linear1_gemm<16>(m, ws, p, bi, pdiv, pmod, premul, st);
     m->prof.end(0, st);
-    static const int nt_mask = tune_int("LSL_NT", 3);
-    AttnArgs aa{};
-    aa.nt = (nt_mask >> 2) & 1;
-    aa.qkv = ws.qkv;
-    aa.z = ws.z;
-    aa.HHD = m->HHD;
-    aa.zw = m->K2;
-    aa.H = d.heads;
-    aa.hd = d.head_dim;
-    static const int attn_bound = tune_int("LSL_ATTN_BOUND", 1);
-    aa.kmax2 = ws.kmax2 + bi;
-    aa.qmax2 = ws.kmax2 + 2 * d.depth + bi;
-    aa.premul = premul;
-    aa.planes = planes ? 1 : 0;
-    aa.npad = p.npad;
-    aa.bound = attn_bound == 2 || (attn_bound == 1 && (temporal ? T : L) > 96);  // short axes: the max pass is one or two tiles, cheaper than the norms
-    if (!temporal) {  // sequences (b,t), positions l
-        aa.S = L; aa.n_seq = p.bc * T; aa.inner = 1; aa.outer_stride = L; aa.pos_stride = 1;
-    } else {          // sequences (b,l), positions t
-        aa.S = T; aa.n_seq = p.bc * L; aa.inner = L; aa.outer_stride = T * L; aa.pos_stride = L;
-    }
-    m->prof.begin(2, st);
-    if (m->attention_linear) {
-        if (d.head_dim_pad == 32) launch_attention_linear_t<32>(aa, st);
-        else launch_attention_linear_t<16>(aa, st);
-    } else if (d.head_dim_pad == 32) launch_attention_t<32>(aa, st);
-    else launch_attention_t<16>(aa, st);
-    m->prof.label(2, "%s", m->attention_linear ? "k_attention_linear" : attention_stream_mode(aa.S, aa.H) || attention_grouped_ok(aa) ? "k_attention_stream" : "k_attention_rows / k_attention_tiny / k_attention");
-    m->prof.end(2, st);
 
+    const AttnArgs aa = attention_args(m, ws, p, bi, premul);
+    m->prof.begin(2, st);
+    if (d.head_dim_pad == 32) launch_attention_t<32>(p.attn[temporal], aa, st);
+    else launch_attention_t<16>(p.attn[temporal], aa, st);
+    m->prof.end(2, st);
     if (p.lin2 == Lin2Kind::none) {  // (lsl_debug_taps)
         LSL_CHECK_LAUNCH("block");
         return 0;
@@ -260,28 +277,21 @@ int run_block(lsl_model *m, const Workspace &ws, const PassPlan &p, int bi, cons
         const bool next = bi + 1 < 2 * d.depth;
         const float *nb = mods + (size_t)((bi + 1) / 2) * 6 * D + (((bi + 1) & 1) ? 3 * D : 0);  // next sub-block: shift, scale
         const TailArgs ta{ws.wtail + (size_t)bi * ws.wtail_stride, ws.a, ws.z, bw.b1 + 3 * m->HHD, bw.b2, mbase + 2 * D, ws.h, next ? ws.a : nullptr,
-                          nb, nb + D, n, d.mlp_dim, m->K2, mod_stride, T * L, magic_of(T * L)};
+                          nb, nb + D, n, d.mlp_dim, m->K2, mod_stride, tpt, magic_of(tpt)};
         launch_tail(ta, st);
-        m->prof.label(1, "k_tail<%d, %d>", D, m->HHD);
-        m->prof.end(1, st);
-        LSL_CHECK_LAUNCH("block (tail)");
-        return 0;
-    }
-    if (p.lin2 == Lin2Kind::ws) {
+    } else if (p.lin2 == Lin2Kind::ws) {
         // ln_fuse handles: the rows' statistics for the NEXT sub-block's LayerNorm (inside its linear1) leave with the update
         const bool stats = p.lin2_stats(bi);
-        const Lin2Args l2{ws.w2p + (size_t)bi * D * m->K2, ws.z, bw.b2, mbase + 2 * D, ws.h, D, n, mod_stride, T * L, magic_of(T * L),
+        const Lin2Args l2{ws.w2p + (size_t)bi * D * m->K2, ws.z, bw.b2, mbase + 2 * D, ws.h, D, n, mod_stride, tpt, magic_of(tpt),
                           p.l2grid.slices, p.l2grid.rpx, p.l2grid.gate_rows, stats ? ws.lnparts : nullptr, p.npad};
         launch_linear2_ws(m->K2, l2, st);
-        m->prof.label(1, stats ? "k_linear2_ws<%d> (+ row statistics)" : "k_linear2_ws<%d>", m->K2);
         if (stats) hipLaunchKernelGGL(k_ln_finalize, dim3((n + 255) / 256), dim3(256), 0, st, ws.lnstat, ws.lnparts, D / 32, p.npad, n, 32.0f);
     } else {
-        const EpiLinear2 e2{bw.b2, mbase + 2 * D, ws.h, D, mod_stride, T * L, 0, magic_of(T * L)};
-        launch_gemm((const u16 *)bw.w2, ws.z, D, n, m->K2, e2, st);
-        m->prof.label(1, "k_gemm_glds<EpiLinear2> (tiling %d)", gemm_variant<EpiLinear2>(D, m->K2, n));
+        const EpiLinear2 e2{bw.b2, mbase + 2 * D, ws.h, D, mod_stride, tpt, 0, magic_of(tpt)};
+        launch_gemm(p.gemm2, (const u16 *)bw.w2, ws.z, D, n, m->K2, e2, st);
     }
     m->prof.end(1, st);
-    LSL_CHECK_LAUNCH("block");
+    LSL_CHECK_LAUNCH(p.lin2 == Lin2Kind::tail ? "block (tail)" : "block");
     return 0;
 }
 
@@ -461,6 +471,15 @@ int resident_sample(lsl_model *m, const lsl_io *io, const lsl_step *steps, int n
     return 0;
 }
 
+// The workspace a call on B trajectories needs: the general path's pass, and the resident path's whole batch where it can take the call
+size_t workspace_need(const lsl_model *m, int B, int T, int L, int *chunk_out = nullptr) {
+    const int chunk = default_chunk(m, B, T, L);
+    size_t need = carve(m, nullptr, chunk, T, L).bytes;
+    if (resident_ok(m, T, L)) need = std::max(need, carve_resident(m, nullptr, B, T, L, m->d.vec_in_dim > 0).bytes);
+    if (chunk_out) *chunk_out = chunk;
+    return need;
+}
+
 int check_call(const lsl_model *m, const lsl_io *io, size_t ws_bytes, void *ws, int *chunk_out) {
     if (!m || !io) return fail(-1, "null model or io");
     if (!m->has_weights) return fail(-2, "weights not set");
@@ -468,11 +487,36 @@ int check_call(const lsl_model *m, const lsl_io *io, size_t ws_bytes, void *ws, 
     if (!io->x || !io->x_cond || !io->mask) return fail(-3, "x, x_cond and mask are required");
     if ((io->y != nullptr) != (m->d.vec_in_dim > 0) && io->y != nullptr) return fail(-3, "y given but the model has no vec_in");
     if ((size_t)io->T * io->L > (1u << 24)) return fail(-3, "T*L too large");
-    const int chunk = default_chunk(m, io->B, io->T, io->L);
-    size_t need = carve(m, nullptr, chunk, io->T, io->L).bytes;
-    if (resident_ok(m, io->T, io->L)) need = std::max(need, carve_resident(m, nullptr, io->B, io->T, io->L, m->d.vec_in_dim > 0).bytes);
+    const size_t need = workspace_need(m, io->B, io->T, io->L, chunk_out);
     if (!ws || ws_bytes < need) return fail(-4, "workspace too small: need %zu bytes, got %zu", need, ws_bytes);
-    *chunk_out = chunk;
+    return 0;
+}
+
+// The lsl_debug_* calls: a handle with weights, a sub-block index, the call's own pointers and sizes (args_ok), a workspace for one pass of B
+int check_debug(const lsl_model *m, int bi, bool args_ok, int B, int T, int L, const void *ws, size_t ws_bytes) {
+    if (!m || !m->has_weights) return fail(-2, "weights not set");
+    if (bi < 0 || bi >= 2 * m->d.depth) return fail(-3, "block index out of range");
+    if (!args_ok) return fail(-3, "invalid arguments");
+    const size_t need = carve(m, nullptr, B, T, L).bytes;
+    if (!ws || ws_bytes < need) return fail(-4, "workspace too small: need %zu bytes", need);
+    return 0;
+}
+
+// The passes of a call: `chunk` trajectories each (the last one the rest), as offsets into the call's arrays.  Per pass: the conditioning
+// embedding (prepare_pass), then body(pass).
+struct Pass {
+    int b0, bc;
+    size_t elem;  // b0 trajectories of x / x_cond / out / noise / trace, in elements
+    const float *y;
+};
+template <class Body>
+int for_each_pass(lsl_model *m, const Workspace &ws, const lsl_io *io, int chunk, hipStream_t st, Body &&body) {
+    const size_t per = (size_t)io->T * io->L * m->d.in_dim;
+    for (int b0 = 0; b0 < io->B; b0 += chunk) {
+        const Pass ps{b0, std::min(chunk, io->B - b0), b0 * per, io->y ? io->y + (size_t)b0 * m->d.vec_in_dim : nullptr};
+        if (int rc = prepare_pass(m, ws, io->x_cond + ps.elem, io->mask + (size_t)b0 * io->T * io->L, ps.y, ps.bc, io->T, io->L, st)) return rc;
+        if (int rc = body(ps)) return rc;
+    }
     return 0;
 }
 

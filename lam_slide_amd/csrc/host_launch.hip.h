@@ -1,8 +1,10 @@
-// Host side, part 2 of 4: one launch helper per kernel family - grid / LDS arithmetic and the choice between instances (which depends on
-// the model and on T, L only where results could differ, never on the batch).  Inside the anonymous namespace opened by host_common.hip.h.
+// Host side, part 2 of 4: one launch helper per kernel family - grid / LDS arithmetic of a chosen kernel - and, next to it, the rule that
+// chooses among the family's instances (which depends on the model and on T, L only where results could differ, never on the batch).  The
+// sub-block's rules (linear1, attention, linear2 / tail) are asked by plan_pass (host_eval.hip.h) only: their launchers are a switch over
+// what the plan says.  Each family's instances are listed ONCE (LSL_LIN1_TS_INSTANCES, LSL_LIN2_WS_INSTANCES; the switches of launch_gemm
+// and launch_attention_t), and a gate that depends on a kernel's LDS need asks the kernel's own config for it.
+// Inside the anonymous namespace opened by host_common.hip.h.
 #pragma once
-
-// ---- launch helpers -------------------------------------------------------------------------------
 
 // Rejected structures and A/B arms (ping-pong / drain GEMMs, tilings 6 / 8 / 13-18 / 23-26 / 29, the scalar output head, every LSL_* tuning knob)
 // live in tools/experiments/host_launch_experiments.hip.h, on the include path of tools/build_experiments.sh only; the product has empty hooks.
@@ -21,8 +23,30 @@ template <class Epi>
 bool launch_gemm_experiment(int, const GemmArgs &, const Epi &, hipStream_t, bool) { return false; }
 #endif
 
-int device_cus();
-int env_int(const char *name, int dflt);
+int env_int(const char *name, int dflt) {
+    const char *e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+// Kernel-selection / timing knobs (LSL_GEMM*, LSL_NT, LSL_STAGGER, LSL_PROBE, ...): read from the environment only in
+// -DLSL_EXPERIMENTS builds; the product library always runs its measured defaults.
+int tune_int(const char *name, int dflt) { return lsl_experiments ? env_int(name, dflt) : dflt; }
+
+int device_cus() {  // of the current device (entry points switch to the stream's device first)
+    static std::atomic<int> cache[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 256;
+    int n = cache[dev & 63].load(std::memory_order_relaxed);
+    if (n > 0) return n;
+    n = 256;
+    (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+    if (n <= 0) n = 256;
+    cache[dev & 63].store(n, std::memory_order_relaxed);
+    return n;
+}
+
+constexpr size_t LDS_BUDGET = 160 * 1024;  // LDS a workgroup may use (gfx950: 160 KiB per CU)
+
+// ---- launch helpers -------------------------------------------------------------------------------
 
 template <int NE, int VEC>
 void launch_ln_mod_t(u16 *a, const float *h, const float *shift, const float *scale, int stride, int n, int tpt, hipStream_t st) {
@@ -41,9 +65,6 @@ template <int NE, int VEC>
 void launch_ln_inplace_t(float *h, int n, float eps, hipStream_t st) {
     hipLaunchKernelGGL((k_ln_inplace<NE, VEC>), dim3((n + 3) / 4), dim3(256), 0, st, h, n, eps);
 }
-int device_cus();
-int env_int(const char *name, int dflt);
-
 template <int NE, int VEC>
 void launch_head_mfma(float *x, float *out, const float *h, const float *shift, const float *scale, int stride, const float *Wo,
                       const float *bo, int n, int C, int tpt, int do_step, float ax, float am, float aw, const float *noise,
@@ -54,7 +75,7 @@ void launch_head_mfma(float *x, float *out, const float *h, const float *shift, 
     LSL_ALLOW_LDS(kern, head_mfma_lds_bytes<NE>(false));
     // two workgroups per CU where the LDS image allows it (any hidden size with <= 32 channels): one workgroup's LayerNorm / weight-load latencies under the other's MFMAs
     static const int per_cu = tune_int("LSL_HEAD_PER_CU", 2);
-    const int wgs = device_cus() * (per_cu >= 2 && 2 * lds <= (size_t)160 * 1024 ? 2 : 1);
+    const int wgs = device_cus() * (per_cu >= 2 && 2 * lds <= LDS_BUDGET ? 2 : 1);
     hipLaunchKernelGGL(kern, dim3(std::min((n + HEAD_TOK - 1) / HEAD_TOK, wgs)), dim3(256), lds, st, x, out, h, shift, scale, stride,
                        Wo, bo, n, C, tpt, do_step, ax, am, aw, noise, seed, step, eo, trace, as, saved, save_out);
 }
@@ -79,8 +100,6 @@ void launch_head_t(float *x, float *out, const float *h, const float *shift, con
         case 7: FN<7, 1>(__VA_ARGS__); break;           \
         default: FN<8, 2>(__VA_ARGS__); break;          \
     }
-
-int device_cus();
 
 // (stats / npad: ln_fuse handles, launch_embed<1> only - the rows' statistics for the first sub-block's fused LayerNorm; embed_stats_ok says where)
 bool embed_stats_ok(int C, int D) { return C <= 32 && D % 256 == 0 && D <= 512; }
@@ -124,37 +143,16 @@ int launch_embed(float *out, const float *in, const float *W, const float *b, co
     return 0;
 }
 
-int env_int(const char *name, int dflt) {
-    const char *e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-// Kernel-selection / timing knobs (LSL_GEMM*, LSL_NT, LSL_STAGGER, LSL_PROBE, ...): read from the environment only in
-// -DLSL_EXPERIMENTS builds; the product library always runs its measured defaults.
-int tune_int(const char *name, int dflt) { return lsl_experiments ? env_int(name, dflt) : dflt; }
-
-int device_cus() {  // of the current device (entry points switch to the stream's device first)
-    static std::atomic<int> cache[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    int n = cache[dev & 63].load(std::memory_order_relaxed);
-    if (n > 0) return n;
-    n = 256;
-    (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    if (n <= 0) n = 256;
-    cache[dev & 63].store(n, std::memory_order_relaxed);
-    return n;
-}
-
 template <int BF, int BT, int NWF, int NWT, int BK, int NS, bool PERSIST, class Epi>
 void launch_gemm_glds(const GemmArgs &g, const Epi &epi, hipStream_t st) {
     auto kern = k_gemm_glds<BF, BT, NWF, NWT, BK, NS, PERSIST, Epi>;
     // + the bias vector of the whole GEMM, kept in LDS by epilogues that start the accumulators from it (k_gemm.hip.h)
     const size_t lds = GemmCfg<BF, BT, NWF, NWT, BK, NS, PERSIST, Epi>::lds_bytes + (Epi::lds_bias ? (size_t)((g.F + BF - 1) / BF) * BF * 4 : 0);
-    LSL_ALLOW_LDS(kern, (size_t)163840);
+    LSL_ALLOW_LDS(kern, LDS_BUDGET);
     const int tiles = ((g.N + BT - 1) / BT) * ((g.F + BF - 1) / BF);
     int grid = tiles;
     if (PERSIST) {  // as many workgroups as fit at once (LDS-limited), a multiple of 8 so the XCD mapping stays regular
-        const int per_cu = (int)(163840 / lds) < 1 ? 1 : (int)(163840 / lds);
+        const int per_cu = (int)std::max<size_t>(1, LDS_BUDGET / lds);
         grid = device_cus() * per_cu;
         grid -= grid % 8;
         if (grid > tiles) grid = tiles;
@@ -168,11 +166,22 @@ void launch_gemm_glds(const GemmArgs &g, const Epi &epi, hipStream_t st) {
 
 // linear1 on the token-stationary kernel (k_lin1.hip.h): hidden sizes 128 / 256 / 384 / 512, sections (q | k | v | mlp) on multiples of 64
 // features.  Same bits as the tile kernels below (tools/lin1_harness.hip), so the choice between them may depend on the launch size.
+// THE instance list (head width, hidden): gates and launch go through it.  Per entry: 8 waves; 4 waves as well at hidden 512; the LNF form at 8.
+#define LSL_LIN1_TS_INSTANCES(X) X(32, 128) X(32, 256) X(32, 384) X(32, 512) X(16, 128) X(16, 256) X(16, 384) X(16, 512)
+template <int V>
+using int_c = std::integral_constant<int, V>;
+template <class Fn>
+bool with_linear1_ts_instance(int hdp, int D, Fn &&fn) {  // fn(head width, hidden) as integral constants; false: no such instance
+#define X(H, K) if (hdp == H && D == K) return fn(int_c<H>{}, int_c<K>{}), true;
+    LSL_LIN1_TS_INSTANCES(X)
+#undef X
+    return false;
+}
 template <int HDP, int K, int NW = 8, bool LNF = false>
 void launch_linear1_ts_t(const Lin1Args &a, hipStream_t st) {
     using C = Lin1Cfg<HDP, K, NW>;
     auto kern = k_linear1_ts<HDP, K, NW, LNF>;
-    LSL_ALLOW_LDS(kern, (size_t)163840);
+    LSL_ALLOW_LDS(kern, LDS_BUDGET);
     const int ntile = (a.N + C::TT - 1) / C::TT, nb = a.F / 32;
     const long units = (long)ntile * nb;
     int grid = (int)std::min<long>(device_cus(), units / 2);
@@ -194,53 +203,56 @@ int linear1_ts_waves(int D, int N) {
 }
 bool linear1_ts_ok(int hdp, int D, int F1, int HHD, int N) {
     static const int on = tune_int("LSL_LIN1_TS", 1);
-    if (!on || (hdp != 16 && hdp != 32) || (D != 128 && D != 256 && D != 384 && D != 512) || F1 % 64 != 0 || HHD % 64 != 0 || N < 1) return false;
-    return (size_t)(D <= 256 ? 4 : 3) * 32 * (2 * D + 16) + 8 * 4096 + (size_t)F1 * 4 <= (size_t)163840;  // weight ring (Lin1Cfg::NS slots) + staging + bias vector (Lin1Cfg::lds_bytes)
+    if (!on || F1 % 64 != 0 || HHD % 64 != 0 || N < 1) return false;
+    size_t lds = 0;  // of the 8-wave instance: weight ring + staging + bias vector
+    return with_linear1_ts_instance(hdp, D, [&](auto h, auto k) { lds = Lin1Cfg<decltype(h)::value, decltype(k)::value, 8>::lds_bytes(F1); }) && lds <= LDS_BUDGET;
 }
 // LayerNorm + modulate inside linear1's activation load (k_lin1.hip.h, LNF instances): no LayerNorm launch, no bf16 `a` buffer - the kernel reads
 // the fp32 residual stream.  Per HANDLE (lsl_model_set_ln_fuse; LSL_LN_FUSE=1 makes it the default of new handles, 0 disables it), never per
 // batch: its rounding differs from the standalone kernel's.  Shapes: the token-stationary kernel's, with the (1 + scale | shift) rows of every
-// trajectory a 256-token tile can touch in LDS - one shared row, or tokens per trajectory >= 128 (hidden <= 256) / >= 256 (wider).
+// trajectory a 256-token tile can touch in LDS (Lin1Cfg::LN_SLOTS) - one shared row, or tokens per trajectory >= half a tile (3 slots) / a tile (2).
 int ln_fuse_env() {
     static const int v = env_int("LSL_LN_FUSE", -1);
     return v;
 }
 bool linear1_lnf_ok(int hdp, int D, int F1, int HHD, int N, int tpt, int mod_stride) {
-    if (ln_fuse_env() == 0 || !linear1_ts_ok(hdp, D, F1, HHD, N) || D % 128 != 0) return false;
-    if (mod_stride != 0 && tpt < (D <= 256 ? 128 : 256)) return false;
-    return (size_t)(D <= 256 ? 4 : 3) * 32 * (2 * D + 16) + 8 * 4096 + (size_t)F1 * 4 + (size_t)(D <= 256 ? 3 : 2) * 2 * D * 4 <= (size_t)163840;
+    if (ln_fuse_env() == 0 || !linear1_ts_ok(hdp, D, F1, HHD, N)) return false;
+    size_t lds = 0;
+    int min_tpt = 0;
+    with_linear1_ts_instance(hdp, D, [&](auto h, auto k) {
+        using C = Lin1Cfg<decltype(h)::value, decltype(k)::value, 8>;
+        lds = C::lds_bytes_lnf(F1);
+        min_tpt = C::LN_SLOTS >= 3 ? C::TT / 2 : C::TT;
+    });
+    return (mod_stride == 0 || tpt >= min_tpt) && lds <= LDS_BUDGET;
 }
-void launch_linear1_lnf(int hdp, int D, const Lin1Args &a, hipStream_t st) {
-    switch ((hdp == 32 ? 0 : 4) + D / 128 - 1) {
-        case 0: return launch_linear1_ts_t<32, 128, 8, true>(a, st);
-        case 1: return launch_linear1_ts_t<32, 256, 8, true>(a, st);
-        case 2: return launch_linear1_ts_t<32, 384, 8, true>(a, st);
-        case 3: return launch_linear1_ts_t<32, 512, 8, true>(a, st);
-        case 4: return launch_linear1_ts_t<16, 128, 8, true>(a, st);
-        case 5: return launch_linear1_ts_t<16, 256, 8, true>(a, st);
-        case 6: return launch_linear1_ts_t<16, 384, 8, true>(a, st);
-        default: return launch_linear1_ts_t<16, 512, 8, true>(a, st);
-    }
-}
-void launch_linear1_ts(int hdp, int D, int waves, const Lin1Args &a, hipStream_t st) {  // (waves: linear1_ts_waves)
-    switch ((hdp == 32 ? 0 : 4) + D / 128 - 1) {
-        case 0: return launch_linear1_ts_t<32, 128>(a, st);
-        case 1: return launch_linear1_ts_t<32, 256>(a, st);
-        case 2: return launch_linear1_ts_t<32, 384>(a, st);
-        case 3: return waves == 4 ? launch_linear1_ts_t<32, 512, 4>(a, st) : launch_linear1_ts_t<32, 512, 8>(a, st);
-        case 4: return launch_linear1_ts_t<16, 128>(a, st);
-        case 5: return launch_linear1_ts_t<16, 256>(a, st);
-        case 6: return launch_linear1_ts_t<16, 384>(a, st);
-        default: return waves == 4 ? launch_linear1_ts_t<16, 512, 4>(a, st) : launch_linear1_ts_t<16, 512, 8>(a, st);
-    }
+void launch_linear1_ts(int hdp, int D, int waves, bool lnf, const Lin1Args &a, hipStream_t st) {  // (waves: linear1_ts_waves; lnf: 8 waves)
+    with_linear1_ts_instance(hdp, D, [&](auto h, auto k) {
+        constexpr int H = decltype(h)::value, K = decltype(k)::value;
+        if (lnf) return launch_linear1_ts_t<H, K, 8, true>(a, st);
+        if constexpr (K == 512) {
+            if (waves == 4) return launch_linear1_ts_t<H, K, 4>(a, st);
+        }
+        launch_linear1_ts_t<H, K, 8>(a, st);
+    });
 }
 
 // linear2 + gated residual update on the weight-stationary kernel (k_lin2.hip.h): F a multiple of 128, K2 one of the instantiated widths
 // (K2 / 8 stationary registers per wave: 2 048, peptide, does not fit).  Same bits as the tile kernels (tools/lin2_harness.hip), so the
 // choice may depend on the launch.  LSL_LIN2_WS=0 (read in the product too: the GPU suite compares the two paths bit for bit) turns it off.
+// THE instance list (K2, chunks, ring slots).  (1280: 4 chunks of 160 columns - 40 of 64 lanes per LDS-DMA instruction instead of 32; round 5:
+// 0.168-0.171 -> 0.165 ms at 163 840 tokens, 18.6 -> 17.1 us at 10 240)
+#define LSL_LIN2_WS_INSTANCES(X) X(1536, 3, 3) X(1280, 4, 4) X(768, 3, 3) X(384, 3, 3)
+template <class Fn>
+bool with_linear2_ws_instance(int K2, Fn &&fn) {
+#define X(K, NCH, NS) if (K2 == K) return fn(int_c<K>{}, int_c<NCH>{}, int_c<NS>{}), true;
+    LSL_LIN2_WS_INSTANCES(X)
+#undef X
+    return false;
+}
 bool linear2_ws_shape_ok(int D, int K2) {
     static const int on = env_int("LSL_LIN2_WS", 1);
-    return on && D % 128 == 0 && D <= 512 && (K2 == 1536 || K2 == 1280 || K2 == 768 || K2 == 384);
+    return on && D % 128 == 0 && D <= 512 && with_linear2_ws_instance(K2, [](auto, auto, auto) {});
 }
 // The grid of a k_linear2_ws launch: 8 x slices x rpx workgroups, at most one per CU, fewer token ranges than 32-token blocks; the LDS gate
 // table holds the trajectories one token range can span.  The kernel takes the launch only if they fit (linear2_ws_max_gate_rows).
@@ -254,36 +266,25 @@ Lin2Grid linear2_ws_grid(int F, int N, int tpt, bool shared) {
     const int ranges = 8 * rpx, max_blocks = (NBLK + ranges - 1) / ranges + 1;
     return {slices, rpx, shared ? 1 : (max_blocks * 32 + tpt - 1) / tpt + 1};
 }
-// (the instances: K2, NCH chunks, NS ring slots - the same in launch_linear2_ws)
 int linear2_ws_max_gate_rows(int K2) {
-    switch (K2) {
-        case 1536: return Lin2Cfg<1536, 3, 3, true>::max_gate_rows;
-        case 1280: return Lin2Cfg<1280, 4, 4, true>::max_gate_rows;
-        case 768: return Lin2Cfg<768, 3, 3, true>::max_gate_rows;
-        case 384: return Lin2Cfg<384, 3, 3, true>::max_gate_rows;
-        default: return 0;
-    }
+    int rows = 0;
+    with_linear2_ws_instance(K2, [&](auto k, auto nch, auto ns) { rows = Lin2Cfg<decltype(k)::value, decltype(nch)::value, decltype(ns)::value, true>::max_gate_rows; });
+    return rows;
 }
-template <int K, int NCH, int NS, bool LNS = false>
+template <int K, int NCH, int NS, bool LNS>
 void launch_linear2_ws_t(const Lin2Args &a, hipStream_t st) {  // (a.slices / rpx / gate_rows: linear2_ws_grid)
     using C = Lin2Cfg<K, NCH, NS, true>;
     auto kern = k_linear2_ws<K, NCH, NS, true, LNS>;
-    LSL_ALLOW_LDS(kern, (size_t)163840);
+    LSL_ALLOW_LDS(kern, LDS_BUDGET);
     hipLaunchKernelGGL(kern, dim3(8 * a.slices * a.rpx), dim3(512), C::lds_bytes(a.gate_rows), st, a);
-}
-template <bool LNS>
-void launch_linear2_ws_k(int K2, const Lin2Args &a, hipStream_t st) {
-    switch (K2) {
-        case 1536: return launch_linear2_ws_t<1536, 3, 3, LNS>(a, st);
-        case 1280: return launch_linear2_ws_t<1280, 4, 4, LNS>(a, st);  // (4 chunks of 160 columns: 40 of 64 lanes per LDS-DMA instruction instead of 32; round 5: 0.168-0.171 -> 0.165 ms at 163 840 tokens, 18.6 -> 17.1 us at 10 240)
-        case 768: return launch_linear2_ws_t<768, 3, 3, LNS>(a, st);
-        case 384: return launch_linear2_ws_t<384, 3, 3, LNS>(a, st);
-    }
 }
 // LNS instances (a.stats): per-wave row statistics of the updated rows beside h (the next sub-block's LayerNorm runs inside linear1)
 void launch_linear2_ws(int K2, const Lin2Args &a, hipStream_t st) {
-    if (a.stats) launch_linear2_ws_k<true>(K2, a, st);
-    else launch_linear2_ws_k<false>(K2, a, st);
+    with_linear2_ws_instance(K2, [&](auto k, auto nch, auto ns) {
+        constexpr int K = decltype(k)::value, NCH = decltype(nch)::value, NS = decltype(ns)::value;
+        if (a.stats) launch_linear2_ws_t<K, NCH, NS, true>(a, st);
+        else launch_linear2_ws_t<K, NCH, NS, false>(a, st);
+    });
 }
 
 // The back half of a sub-block on the row-owning tail kernel (k_tail.hip.h): up-projection -> GELU in registers -> down-projection + attention
@@ -296,13 +297,13 @@ int tail_env() {
     return v;
 }
 bool tail_shape_ok(int D, int HHD, int M) {
-    return tail_env() != 0 && D == 256 && HHD == 256 && M % 64 == 0 && M >= 64 && TailCfg<256, 256>::lds_bytes(M) <= (size_t)163840;  // (an even number of 32-feature mlp blocks: the kernel's pipeline has no parity branches)
+    return tail_env() != 0 && D == 256 && HHD == 256 && M % 64 == 0 && M >= 64 && TailCfg<256, 256>::lds_bytes(M) <= LDS_BUDGET;  // (an even number of 32-feature mlp blocks: the kernel's pipeline has no parity branches)
 }
 size_t tail_stream_bytes(const lsl_model *m) { return TailCfg<256, 256>::stream_bytes(m->d.mlp_dim); }
 void launch_tail(const TailArgs &a, hipStream_t st) {
     using C = TailCfg<256, 256>;
     auto kern = k_tail<256, 256>;
-    LSL_ALLOW_LDS(kern, (size_t)163840);
+    LSL_ALLOW_LDS(kern, LDS_BUDGET);
     const int nwt = (a.N + 31) / 32;  // wave tiles of 32 tokens: every workgroup gets at least one
     hipLaunchKernelGGL(kern, dim3(std::min(nwt, device_cus())), dim3(512), C::lds_bytes(a.M), st, a);
 }
@@ -321,22 +322,22 @@ void launch_tail(const TailArgs &a, hipStream_t st) {
 //      extra occupancy hides load / store latency)
 // 20-22: ping-pong halves (k_gemm_pp.hip.h).  Default (-1): 12 for linear1 (5 when K < 512 or not a multiple of 128, 6 when not a multiple of 64), 7 for linear2: the fastest pair measured on MI355X (profiles/r01_gemm_variants.txt lists
 // every variant that was tried, including the ones no longer compiled in).
-template <class Epi>
-int gemm_variant(int F, int K, int N = 1 << 30) {
+// Called by plan_pass only, once per GEMM (lin2: linear2's, else linear1's); launch_gemm takes the answer.
+int gemm_variant(bool lin2, int F, int K, int N) {
     static const int forced_all = tune_int("LSL_GEMM", -1);
     static const int forced_1 = tune_int("LSL_GEMM1", -1), forced_2 = tune_int("LSL_GEMM2", -1);  // per GEMM: linear1 / linear2
-    const int forced_one = std::is_same<Epi, EpiLinear2>::value ? forced_2 : forced_1;
+    const int forced_one = lin2 ? forced_2 : forced_1;
     const int forced = forced_one >= 0 ? forced_one : forced_all;
     // 256-wide feature tiles waste MFMA work when F is not a multiple of 256 (D = 128 / 384 models): use 128 x 128 there
     const bool ragged = F % 256 != 0 && (F % 256 <= 128);
-    const int ragged_variant = std::is_same<Epi, EpiLinear2>::value && K % 64 == 0 ? 11 : 10;  // measured on the D = 384 / 128 models
+    const int ragged_variant = lin2 && K % 64 == 0 ? 11 : 10;  // measured on the D = 384 / 128 models
     if (forced >= 0) return forced;
     // linear2 of the 384-wide models (peptide: F = 384, K = 2 048, which no weight-stationary instance holds): the launch is bound by the
     // operand bytes each CU pulls through its L1 miss path (measured 49 GB/s per CU with two 128 x 128 workgroups per CU: the per-CU limit);
     // 192 x 128 tiles move 17 % fewer operand bytes per FLOP with as many workgroups as CUs, and a third ring slot covers the latency one
     // workgroup per CU leaves exposed: 63.5 -> 54.3 ms per 100 evaluations at 16 000 tokens (profiles/r05_experiments.txt).  Same bits as
     // every other tiling (same k order per element).  Only when the tiles fill at least half of the CUs.
-    if (std::is_same<Epi, EpiLinear2>::value && F % 192 == 0 && F % 256 != 0 && K % 64 == 0 && (long)((N + 127) / 128) * (F / 192) * 2 >= (long)device_cus())
+    if (lin2 && F % 192 == 0 && F % 256 != 0 && K % 64 == 0 && (long)((N + 127) / 128) * (F / 192) * 2 >= (long)device_cus())
         return 28;
     if (ragged) return ragged_variant;
     // Small launches (one or two trajectories of the MD17 models, the reference's own B = 4 case): 256 x 256 tiles leave most of the chip
@@ -348,25 +349,27 @@ int gemm_variant(int F, int K, int N = 1 << 30) {
     static const int small_rule = tune_int("LSL_SMALL_TILES", 1);
     const long tiles256 = (long)((N + 255) / 256) * ((F + 255) / 256);
     const int cus = device_cus();
-    if (small_rule && K % 64 == 0 && tiles256 * (std::is_same<Epi, EpiLinear2>::value ? 2 : 4) <= (long)cus * (std::is_same<Epi, EpiLinear2>::value ? 1 : 5))
+    if (small_rule && K % 64 == 0 && tiles256 * (lin2 ? 2 : 4) <= (long)cus * (lin2 ? 1 : 5))
         return 11;  // linear2: tiles <= CUs / 2; linear1: tiles <= 1.25 CUs
-    return std::is_same<Epi, EpiLinear2>::value ? (K % 128 == 0 ? 7 : 15) : (K % 128 == 0 ? 12 : 5);
+    return lin2 ? (K % 128 == 0 ? 7 : 15) : (K % 128 == 0 ? 12 : 5);
 }
 
+// (variant: the plan's, gemm_variant.  The shape conditions below only keep a tiling FORCED in the experiments build inside what its kernel
+// covers - gemm_variant itself never answers 12 or 7 outside them - and send it to tiling 5 otherwise.)
 template <class Epi>
-void launch_gemm(const u16 *W, const u16 *X, int F, int N, int K, const Epi &epi_in, hipStream_t st, int hhd = 32) {
-    const int variant = gemm_variant<Epi>(F, K, N);
+void launch_gemm(int variant, const u16 *W, const u16 *X, int F, int N, int K, const Epi &epi_in, hipStream_t st, int hhd = 32) {
+    constexpr bool lin2 = std::is_same<Epi, EpiLinear2>::value;
     static const int probe = tune_int("LSL_PROBE", 0);
     static const int stagger = tune_int("LSL_STAGGER", 0);
     GemmArgs g{W, X, F, N, K, stagger, probe};
     // LSL_NT bit 0: linear1 output, bit 1: linear2 residual update, bit 2: attention output, bit 3: LayerNorm+modulate output
     static const int nt = tune_int("LSL_NT", 3);
     Epi epi = epi_in;
-    epi.probe = probe | ((nt >> (std::is_same<Epi, EpiLinear2>::value ? 1 : 0)) & 1 ? 32 : 0);
-    const bool pp_ok = !std::is_same<Epi, EpiLinear2>::value ? hhd % 32 == 0 : true;  // linear1 sections start on 32-feature tiles
+    epi.probe = probe | ((nt >> (lin2 ? 1 : 0)) & 1 ? 32 : 0);
+    const bool pp_ok = lin2 || hhd % 32 == 0;  // linear1 sections start on 32-feature tiles
     if (launch_gemm_experiment(variant, g, epi, st, pp_ok)) return;  // (rejected structures: -DLSL_EXPERIMENTS builds only)
     if (variant == 12 && K % 128 == 0) return launch_gemm_glds<256, 256, 2, 4, 64, 2, true>(g, epi, st);  // 5 made persistent (staging in ring slot 1)
-    if constexpr (lsl_experiments || std::is_same<Epi, EpiLinear2>::value) {  // (linear1's piece epilogue exists in the experiments build only)
+    if constexpr (lsl_experiments || lin2) {  // (linear1's piece epilogue exists in the experiments build only)
         if (variant == 7 && F % 32 == 0 && pp_ok && K % 128 == 0) return launch_gemm_glds<256, 256, 2, 4, 64, 2, true>(g, EpiPieces<Epi>(epi), st);  // persistent, 64-deep k-tiles, piece epilogue
     }
     switch (variant) {
@@ -374,21 +377,14 @@ void launch_gemm(const u16 *W, const u16 *X, int F, int N, int K, const Epi &epi
         case 10: return launch_gemm_glds<128, 128, 2, 2, 32, 3, false>(g, epi, st);
         case 11: return launch_gemm_glds<128, 128, 2, 2, 64, 2, false>(g, epi, st);
         case 28:  // 192 features x 128 tokens, 8 waves of 96 x 32, three 64-deep ring slots (linear2 of the 384-wide models)
-            if constexpr (std::is_same<Epi, EpiLinear2>::value) return launch_gemm_glds<192, 128, 2, 4, 64, 3, false>(g, epi, st);
+            if constexpr (lin2) return launch_gemm_glds<192, 128, 2, 4, 64, 3, false>(g, epi, st);
             else break;
         case 15: return launch_gemm_glds<256, 256, 4, 4, 64, 2, false>(g, epi, st);
         default: return launch_gemm_glds<256, 256, 2, 4, 64, 2, false>(g, epi, st);  // (K is a multiple of 64: hidden sizes are)
     }
 }
 
-template <int HDP, int NW, int ITEMS, int NKT>
-void launch_attention_rows(const AttnArgs &a, hipStream_t st) {
-    auto kern = k_attention_rows<HDP, NW, ITEMS, NKT>;
-    const size_t lds = (size_t)ITEMS * 2 * (NKT > 0 ? NKT * 32 : (a.S + 31) & ~31) * HDP * 2 + NW * sizeof(float);  // K, V, key-norm slots
-    LSL_ALLOW_LDS(kern, NKT > 0 ? lds : (size_t)160 * 1024);
-    const long items = (long)a.n_seq * a.H;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((items + ITEMS - 1) / ITEMS)), dim3(NW * 64), lds, st, a);
-}
+// ---- attention: the form of an axis (plan_attention, called by plan_pass), then one launcher per form ---------------------------------
 
 // persistent, double-buffered form (k_attention_stream): axes of more than 128 positions (unit = (sequence, head, group of 256 queries), keys in
 // chunks of 256: peptide's T = 1000 is 4 groups x 4 chunks) and of 9 .. 32 positions
@@ -402,101 +398,154 @@ int attention_stream_mode(int S, int H) {  // 0: k_attention_rows / tiny / onlin
     if (S > 8 && S <= 32 && H % 8 == 0) return 1;
     return 0;
 }
-// q / k / v as head-major planes (k_lin1.hip.h, Lin1Args::planes): spatial sub-blocks (positions = consecutive tokens) whose attention
-// runs the LONG stream kernel, token-stationary linear1.  LSL_QKV_PLANES=0 keeps token-major rows (A/B runs).
-bool qkv_planes_ok(int hdp, int hidden, int heads, int S, bool temporal, bool lin1_ts) {
-    static const int on = env_int("LSL_QKV_PLANES", 1);
-    (void)hidden;
-    return on && !temporal && lin1_ts && heads % (64 / hdp) == 0 && S <= 256 && attention_stream_mode(S, heads) == 2;
-}
+
+enum class AttnForm {
+    linear,           // k_attention_linear
+    stream_short,     // k_attention_stream: 9 .. 32 positions, 8 heads of a sequence per unit
+    stream_grouped,   // ... tiny spatial axes, 32 / S sequences to a 32-row tile (geometry rewritten below)
+    stream_long,      // ... up to 256 positions: one key chunk
+    stream_chunked,   // ... longer: keys in chunks of 256, queries in groups of 8 tiles
+    stream_chunked_den,  // ... with the padded head's spare V column carrying the softmax denominator (peptide: head_dim 24 of 32)
+    tiny,             // k_attention_tiny: one lane per (query, head)
+    rows,             // k_attention_rows<nw, items, nkt>: two-pass softmax, K / V of `items` (sequence, head)s in LDS
+    online            // k_attention<nw, items>: online softmax
+};
+// What the attention of one axis runs: the form, the sequence geometry the kernel is given (AttnArgs) and the instance of rows / online
+struct AttnPlan {
+    AttnForm form;
+    int stream_mode;  // what attention_stream_mode said for this axis (2: q / k / v may travel as planes, qkv_planes_ok)
+    int S, n_seq, inner, outer_stride, pos_stride, blk, n_tok;
+    int nw, items, nkt;
+    bool stream() const { return form >= AttnForm::stream_short && form <= AttnForm::stream_chunked_den; }
+};
 // tiny SPATIAL axes (L = 2, 4, 8: positions and sequences are consecutive tokens) on the SHORT stream kernel, 32 / L sequences to a tile with
 // the scores outside the block diagonal masked (AttnArgs::blk): replaces k_attention_tiny.  LSL_ATTN_GROUP=0 keeps the lane-per-query kernel.
-bool attention_grouped_ok(const AttnArgs &a) {
+bool attention_grouped_ok(const AttnPlan &a, int H) {
     static const int on = env_int("LSL_ATTN_GROUP", 1), stream_on = env_int("LSL_ATTN_STREAM", 1);
-    return on && stream_on && a.S >= 2 && a.S <= 8 && (a.S & (a.S - 1)) == 0 && a.inner == 1 && a.pos_stride == 1 && a.outer_stride == a.S && a.H % 8 == 0 &&
-           a.kmax2 != nullptr;
+    return on && stream_on && a.S >= 2 && a.S <= 8 && (a.S & (a.S - 1)) == 0 && a.inner == 1 && a.pos_stride == 1 && a.outer_stride == a.S && H % 8 == 0;
 }
-template <int HDP>
-bool launch_attention_stream(const AttnArgs &a_in, hipStream_t st) {
-    AttnArgs a = a_in;
-    a.blk = 0;
-    a.n_tok = 0;
-    if (attention_grouped_ok(a)) {  // present the tokens as sequences of 32 rows
-        a.blk = a.S;
-        a.n_tok = a.n_seq * a.S;
-        a.n_seq = (a.n_tok + 31) / 32;
-        a.S = 32;
-        a.outer_stride = 32;
+// LDS of the forms: stream - two images of K | V, 256 rows each, and a 32-row query image per wave; rows - K, V of every item (key tiles of
+// 32 rows) and the key-norm slots; online - K, V of every item
+constexpr size_t attention_stream_lds(int hdp) { return (size_t)2 * 2 * 256 * hdp * 2 + (size_t)8 * 32 * hdp * 2; }
+constexpr size_t attention_rows_lds(int hdp, int nw, int items, int key_rows) { return (size_t)items * 2 * key_rows * hdp * 2 + nw * sizeof(float); }
+constexpr size_t attention_online_lds(int hdp, int items, int key_rows) { return (size_t)items * 2 * key_rows * hdp * 2; }
+
+AttnPlan plan_attention(bool linear, int hdp, int H, int hd, int bc, int T, int L, bool temporal) {
+    AttnPlan p{};
+    if (!temporal) {  // sequences (b,t), positions l
+        p.S = L; p.n_seq = bc * T; p.inner = 1; p.outer_stride = L; p.pos_stride = 1;
+    } else {          // sequences (b,l), positions t
+        p.S = T; p.n_seq = bc * L; p.inner = L; p.outer_stride = T * L; p.pos_stride = L;
     }
-    const int mode = attention_stream_mode(a.S, a.H);
-    const bool is_long = mode == 2;
-    if (!mode || !a.kmax2) return false;
-    const size_t lds = (size_t)2 * 2 * 256 * HDP * 2 + (size_t)8 * 32 * HDP * 2;  // two images of K | V, 256 rows each; a 32-row query image per wave
-    const long n_units = is_long ? (long)a.n_seq * a.H * (((a.S + 31) / 32 + 7) / 8) : (long)a.n_seq * (a.H / 8);  // LONG: (sequence, head, group of 8 query tiles)
-    if (n_units + 2L * device_cus() >= (1L << 31)) return false;  // (the kernel counts units in 32 bits)
-    const int grid = (int)std::min<long>(2L * device_cus(), n_units);  // two workgroups per CU (2 x 80 KiB of LDS at 32-wide heads)
-    // plain stores: behind streaming stores the in-order vector-memory queue reports the next unit's requests late (measured: 0.78 vs 0.27 ms)
-    AttnArgs b = a;
-    b.nt = 0;
-    auto go2 = [&](auto kern) {
-        LSL_ALLOW_LDS(kern, lds);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, b);
-    };
-    if (!is_long && a.blk > 0) go2(k_attention_stream<HDP, false, false, false, true>);
-    else if (!is_long) go2(k_attention_stream<HDP, false>);
-    else if (a.S <= 256) go2(k_attention_stream<HDP, true>);
-    else if constexpr (HDP == 32) {  // keys in chunks of 256, queries in groups of 8 tiles
-        if (a.hd == 24) go2(k_attention_stream<HDP, true, true, true>);  // (peptide: the padded head's spare V column carries the softmax denominator)
-        else go2(k_attention_stream<HDP, true, true>);
-    } else go2(k_attention_stream<HDP, true, true>);
-    return true;
-}
-
-template <int HDP>
-void launch_attention_linear_t(const AttnArgs &a, hipStream_t st) {
-    const long units = (long)a.n_seq * a.H;
-    hipLaunchKernelGGL((k_attention_linear<HDP>), dim3((unsigned)std::min<long>(units, 8L * device_cus())), dim3(256), 0, st, a);
-}
-
-template <int HDP>
-void launch_attention_t(const AttnArgs &a, hipStream_t st) {
-    if (launch_attention_stream<HDP>(a, st)) return;
-    const int Sp = (a.S + 31) & ~31;
+    p.form = AttnForm::linear;
+    if (linear) return p;
+    const AttnPlan axis = p;
+    const bool grouped = attention_grouped_ok(p, H);
+    if (grouped) {  // present the tokens as sequences of 32 rows
+        p.blk = p.S;
+        p.n_tok = p.n_seq * p.S;
+        p.n_seq = (p.n_tok + 31) / 32;
+        p.S = 32;
+        p.outer_stride = 32;
+    }
+    p.stream_mode = attention_stream_mode(p.S, H);
+    const bool is_long = p.stream_mode == 2;
+    const long n_units = is_long ? (long)p.n_seq * H * (((p.S + 31) / 32 + 7) / 8) : (long)p.n_seq * (H / 8);  // LONG: (sequence, head, group of 8 query tiles)
+    if (p.stream_mode && n_units + 2L * device_cus() < (1L << 31)) {  // (the kernel counts units in 32 bits: more go to the forms below)
+        p.form = !is_long ? (grouped ? AttnForm::stream_grouped : AttnForm::stream_short)
+                 : p.S <= 256 ? AttnForm::stream_long
+                 : hdp == 32 && hd == 24 ? AttnForm::stream_chunked_den : AttnForm::stream_chunked;
+        return p;
+    }
+    const int mode = p.stream_mode;
+    p = axis;  // (not on the stream kernel: the axis as it is)
+    p.stream_mode = mode;
+    const int Sp = (p.S + 31) & ~31;
     static const int online = tune_int("LSL_ATTN_ONLINE", 0);  // 1: force the online-softmax kernel (A/B measurements)
-    if (!online && a.S <= 8) {  // one lane per (query, head), no MFMA padding
-        const long lanes = (long)a.n_seq * a.S * a.H;
-        hipLaunchKernelGGL((k_attention_tiny<HDP>), dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, a);
-        return;
-    }
-    if (!online && (size_t)2 * Sp * HDP * 2 + 64 <= (size_t)160 * 1024) {  // two-pass softmax, K/V of one (sequence, head) in LDS
+    auto inst = [&](AttnForm f, int nw, int items, int nkt) { p.form = f; p.nw = nw; p.items = items; p.nkt = nkt; return p; };
+    if (!online && p.S <= 8) return inst(AttnForm::tiny, 4, 1, 0);  // one lane per (query, head), no MFMA padding
+    if (!online && attention_rows_lds(hdp, 16, 1, Sp) <= LDS_BUDGET) {  // two-pass softmax, K/V of one (sequence, head) in LDS
         // long axes (peptide T = 1000): 16 waves - with the max pass gone (AttnArgs::bound) the kernel is a chain of MFMA -> exp2 -> MFMA per
         // tile, and four waves per SIMD hide it better than two (attention 320.6 -> 303.8 ms per 1000-step call; with the max pass
         // 8 waves were as fast, profiles/r02_experiments.txt)
         static const int nw16 = tune_int("LSL_ATTN_NW16", 1);
-        if (Sp > 256 && nw16) return launch_attention_rows<HDP, 16, 1, 0>(a, st);
-        if (Sp > 256) return launch_attention_rows<HDP, 8, 1, 0>(a, st);
-        if (Sp <= 32) return launch_attention_rows<HDP, 4, 4, 1>(a, st);
-        if (Sp <= 64) return launch_attention_rows<HDP, 4, 2, 2>(a, st);
-        if (Sp <= 128) return launch_attention_rows<HDP, 4, 1, 4>(a, st);
-        if (Sp <= 192) return launch_attention_rows<HDP, 4, 1, 6>(a, st);
-        return launch_attention_rows<HDP, 4, 1, 8>(a, st);
+        if (Sp > 256) return inst(AttnForm::rows, nw16 ? 16 : 8, 1, 0);
+        if (Sp <= 32) return inst(AttnForm::rows, 4, 4, 1);
+        if (Sp <= 64) return inst(AttnForm::rows, 4, 2, 2);
+        if (Sp <= 128) return inst(AttnForm::rows, 4, 1, 4);
+        return inst(AttnForm::rows, 4, 1, Sp <= 192 ? 6 : 8);
     }
+    if (Sp <= 32) return inst(AttnForm::online, 4, 4, 0);
+    if (Sp <= 64) return inst(AttnForm::online, 4, 2, 0);
+    return inst(AttnForm::online, Sp <= 512 ? 4 : 8, 1, 0);
+}
+// q / k / v as head-major planes (k_lin1.hip.h, Lin1Args::planes): spatial sub-blocks (positions = consecutive tokens) whose attention
+// runs the LONG stream kernel, token-stationary linear1.  LSL_QKV_PLANES=0 keeps token-major rows (A/B runs).
+bool qkv_planes_ok(int hdp, int heads, int S, bool temporal, bool lin1_ts, const AttnPlan &attn) {
+    static const int on = env_int("LSL_QKV_PLANES", 1);
+    return on && !temporal && lin1_ts && heads % (64 / hdp) == 0 && S <= 256 && attn.form != AttnForm::linear && attn.stream_mode == 2;
+}
+
+template <auto KERN>
+void launch_attention_stream(bool is_long, size_t lds, AttnArgs a, hipStream_t st) {
+    LSL_ALLOW_LDS(KERN, lds);
+    const long n_units = is_long ? (long)a.n_seq * a.H * (((a.S + 31) / 32 + 7) / 8) : (long)a.n_seq * (a.H / 8);  // (< 2^31 - 2 CUs: plan_attention)
+    const int grid = (int)std::min<long>(2L * device_cus(), n_units);  // two workgroups per CU (2 x 80 KiB of LDS at 32-wide heads)
+    a.nt = 0;  // plain stores: behind streaming stores the in-order vector-memory queue reports the next unit's requests late (measured: 0.78 vs 0.27 ms)
+    hipLaunchKernelGGL(KERN, dim3(grid), dim3(512), lds, st, a);
+}
+template <int HDP, int NW, int ITEMS, int NKT>
+void launch_attention_rows(const AttnArgs &a, hipStream_t st) {
+    auto kern = k_attention_rows<HDP, NW, ITEMS, NKT>;
+    const size_t lds = attention_rows_lds(HDP, NW, ITEMS, NKT > 0 ? NKT * 32 : (a.S + 31) & ~31);
+    LSL_ALLOW_LDS(kern, NKT > 0 ? lds : LDS_BUDGET);
     const long items = (long)a.n_seq * a.H;
-    const size_t per_item = (size_t)2 * Sp * HDP * 2;
-    if (Sp <= 32) {
-        auto kern = k_attention<HDP, 4, 4>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)((items + 3) / 4)), dim3(256), 4 * per_item, st, a);
-    } else if (Sp <= 64) {
-        auto kern = k_attention<HDP, 4, 2>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)((items + 1) / 2)), dim3(256), 2 * per_item, st, a);
-    } else if (Sp <= 512) {
-        auto kern = k_attention<HDP, 4, 1>;
-        LSL_ALLOW_LDS(kern, 65536);
-        hipLaunchKernelGGL(kern, dim3((unsigned)items), dim3(256), per_item, st, a);
-    } else {
-        auto kern = k_attention<HDP, 8, 1>;
-        LSL_ALLOW_LDS(kern, 160 * 1024);
-        hipLaunchKernelGGL(kern, dim3((unsigned)items), dim3(512), per_item, st, a);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((items + ITEMS - 1) / ITEMS)), dim3(NW * 64), lds, st, a);
+}
+template <int HDP, int NW, int ITEMS>
+void launch_attention_online(const AttnArgs &a, hipStream_t st) {
+    auto kern = k_attention<HDP, NW, ITEMS>;
+    const size_t lds = attention_online_lds(HDP, ITEMS, (a.S + 31) & ~31);
+    if (ITEMS == 1) LSL_ALLOW_LDS(kern, NW == 8 ? LDS_BUDGET : (size_t)65536);
+    const long items = (long)a.n_seq * a.H;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((items + ITEMS - 1) / ITEMS)), dim3(NW * 64), lds, st, a);
+}
+
+// (a: the plan's geometry already in it - run_block)
+template <int HDP>
+void launch_attention_t(const AttnPlan &p, const AttnArgs &a, hipStream_t st) {
+    constexpr size_t slds = attention_stream_lds(HDP);
+    switch (p.form) {
+        case AttnForm::linear:
+            hipLaunchKernelGGL((k_attention_linear<HDP>), dim3((unsigned)std::min<long>((long)a.n_seq * a.H, 8L * device_cus())), dim3(256), 0, st, a);
+            return;
+        case AttnForm::stream_short: return launch_attention_stream<k_attention_stream<HDP, false>>(false, slds, a, st);
+        case AttnForm::stream_grouped: return launch_attention_stream<k_attention_stream<HDP, false, false, false, true>>(false, slds, a, st);
+        case AttnForm::stream_long: return launch_attention_stream<k_attention_stream<HDP, true>>(true, slds, a, st);
+        case AttnForm::stream_chunked: return launch_attention_stream<k_attention_stream<HDP, true, true>>(true, slds, a, st);
+        case AttnForm::stream_chunked_den:
+            if constexpr (HDP == 32) return launch_attention_stream<k_attention_stream<HDP, true, true, true>>(true, slds, a, st);
+            else return;  // (plan_attention: 32-wide heads only)
+        case AttnForm::tiny:
+            hipLaunchKernelGGL((k_attention_tiny<HDP>), dim3((unsigned)(((long)a.n_seq * a.S * a.H + 255) / 256)), dim3(256), 0, st, a);
+            return;
+        case AttnForm::rows:
+            switch (p.nw * 100 + p.items * 10 + p.nkt) {
+                case 1610: return launch_attention_rows<HDP, 16, 1, 0>(a, st);
+                case 810: return launch_attention_rows<HDP, 8, 1, 0>(a, st);
+                case 441: return launch_attention_rows<HDP, 4, 4, 1>(a, st);
+                case 422: return launch_attention_rows<HDP, 4, 2, 2>(a, st);
+                case 414: return launch_attention_rows<HDP, 4, 1, 4>(a, st);
+                case 416: return launch_attention_rows<HDP, 4, 1, 6>(a, st);
+                default: return launch_attention_rows<HDP, 4, 1, 8>(a, st);
+            }
+        case AttnForm::online:
+            switch (p.nw * 10 + p.items) {
+                case 44: return launch_attention_online<HDP, 4, 4>(a, st);
+                case 42: return launch_attention_online<HDP, 4, 2>(a, st);
+                case 41: return launch_attention_online<HDP, 4, 1>(a, st);
+                default: return launch_attention_online<HDP, 8, 1>(a, st);
+            }
     }
 }
 

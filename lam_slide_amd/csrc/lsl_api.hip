@@ -2,7 +2,7 @@
 // network evaluation (latent_si_v31.py:168-188) and of the sampler loops (integrators.py:67-78,103-120)
 // on the caller's stream.  No allocation, no synchronisation, no host<->device copies.
 // One translation unit: this file = the entry points of the sampling path (model handle, forward, fused sampler + opt-in hipGraph replay,
-// noise, Runge-Kutta state arithmetic, the stochastic-interpolant objective around one evaluation, debug taps); host_common / host_launch / host_eval.hip.h = what they enqueue; decode_host.hip.h +
+// noise, Runge-Kutta state arithmetic, the stochastic-interpolant objective around one evaluation, debug taps); host_common / host_launch / host_eval.hip.h = what they enqueue (host_graph.hip.h: the replay cache); decode_host.hip.h +
 // stage1_api.hip.h = the frozen stage-1 encode / decode beside the path.
 #include "../../include/lsl_api.h"
 
@@ -74,11 +74,7 @@ int lsl_model_create(const lsl_model_desc *desc, lsl_model **out) try {
     m->ln_fuse = ln_fuse_env() == 1;
     *out = m;
     return 0;
-} catch (const std::bad_alloc &) {
-    return fail(-5, "out of host memory");
-} catch (...) {
-    return fail(-11, "unexpected C++ exception");
-}
+} LSL_API_CATCH
 
 int lsl_model_set_weights(lsl_model *m, const lsl_weights *w) try {
     if (!m || !w || !w->blocks) return fail(-1, "null argument");
@@ -93,26 +89,13 @@ int lsl_model_set_weights(lsl_model *m, const lsl_weights *w) try {
     m->w = *w;
     m->w.blocks = m->blocks.data();
     m->has_weights = true;
-    for (auto &g : m->graphs)  // captured launches hold the old weight pointers
-        if (g.exec) hipGraphExecDestroy(g.exec);
-    m->graphs.clear();
-    m->seen.clear();
-    m->uncapturable.clear();
+    m->graphs.clear();  // (captured launches hold the old weight pointers)
     return 0;
-} catch (const std::bad_alloc &) {
-    return fail(-5, "out of host memory");
-} catch (...) {
-    return fail(-11, "unexpected C++ exception");
-}
+} LSL_API_CATCH
 
 void lsl_model_destroy(lsl_model *m) {
-    if (m) {
-        m->prof.clear();
-        for (auto &g : m->graphs)
-            if (g.exec) hipGraphExecDestroy(g.exec);
-        if (m->graph_stream) hipStreamDestroy(m->graph_stream);
-    }
-    delete m;
+    if (m) m->prof.clear();
+    delete m;  // (~GraphCache: the captured graphs and the capture stream)
 }
 
 int lsl_profile_enable(lsl_model *m, int32_t kernel, int32_t max_launches) try {
@@ -125,11 +108,7 @@ int lsl_profile_enable(lsl_model *m, int32_t kernel, int32_t max_launches) try {
     m->prof.kernel = kernel;
     m->prof.cap = max_launches;
     return 0;
-} catch (const std::bad_alloc &) {
-    return fail(-5, "out of host memory");
-} catch (...) {
-    return fail(-11, "unexpected C++ exception");
-}
+} LSL_API_CATCH
 
 int lsl_profile_read(lsl_model *m, double *total_ms, int32_t *launches) {
     if (!m || !total_ms || !launches) return fail(-1, "null argument");
@@ -146,60 +125,36 @@ int lsl_profile_read(lsl_model *m, double *total_ms, int32_t *launches) {
     return 0;
 }
 
-static void drop_graphs(lsl_model *m) {
-    for (auto &g : m->graphs)
-        if (g.exec) hipGraphExecDestroy(g.exec);
-    m->graphs.clear();
-    m->seen.clear();
-    m->uncapturable.clear();
-}
-
 int lsl_model_set_chunk(lsl_model *m, int32_t c) try {
     if (!m || c < 0) return fail(-1, "bad argument");
     m->chunk = c;
-    drop_graphs(m);
+    m->graphs.clear();
     return 0;
-} catch (const std::bad_alloc &) {
-    return fail(-5, "out of host memory");
-} catch (...) {
-    return fail(-11, "unexpected C++ exception");
-}
+} LSL_API_CATCH
 
 int lsl_model_set_attention_mode(lsl_model *m, int32_t mode) try {
     if (!m || (mode != 0 && mode != 1)) return fail(-1, "attention mode must be 0 (scaled_dot_product) or 1 (linear)");
     m->attention_linear = mode == 1;
-    drop_graphs(m);
+    m->graphs.clear();
     return 0;
-} catch (const std::bad_alloc &) {
-    return fail(-5, "out of host memory");
-} catch (...) {
-    return fail(-11, "unexpected C++ exception");
-}
+} LSL_API_CATCH
 
 int lsl_model_set_tail(lsl_model *m, int32_t on) try {
     if (!m || (on != 0 && on != 1)) return fail(-1, "tail must be 0 or 1");
     if (on && !tail_shape_ok(m->d.hidden, m->HHD, m->d.mlp_dim))
         return fail(-21, "no tail kernel for this model (hidden 256 with heads * head_dim_pad = 256, mlp_dim a multiple of 64; LSL_TAIL=0 disables it)");
-    if (m->tail != (on == 1)) drop_graphs(m);
+    if (m->tail != (on == 1)) m->graphs.clear();
     m->tail = on == 1;
     return 0;
-} catch (const std::bad_alloc &) {
-    return fail(-5, "out of host memory");
-} catch (...) {
-    return fail(-11, "unexpected C++ exception");
-}
+} LSL_API_CATCH
 int32_t lsl_model_tail(const lsl_model *m) { return m && m->tail ? 1 : 0; }
 int lsl_model_set_ln_fuse(lsl_model *m, int32_t on) try {
     if (!m || (on != 0 && on != 1)) return fail(-1, "ln_fuse must be 0 or 1");
     if (on && ln_fuse_env() == 0) return fail(-21, "LayerNorm fusion is disabled (LSL_LN_FUSE=0)");
-    if (m->ln_fuse != (on == 1)) drop_graphs(m);
+    if (m->ln_fuse != (on == 1)) m->graphs.clear();
     m->ln_fuse = on == 1;
     return 0;
-} catch (const std::bad_alloc &) {
-    return fail(-5, "out of host memory");
-} catch (...) {
-    return fail(-11, "unexpected C++ exception");
-}
+} LSL_API_CATCH
 int32_t lsl_model_ln_fuse(const lsl_model *m) { return m && m->ln_fuse ? 1 : 0; }
 const char *lsl_profile_kernel_name(const lsl_model *m) { return m ? m->prof.name : ""; }
 
@@ -226,27 +181,20 @@ int32_t lsl_sampler_path(const lsl_model *m, int32_t T, int32_t L) {
 
 size_t lsl_workspace_bytes(const lsl_model *m, int32_t B, int32_t T, int32_t L) {
     if (!m || B <= 0 || T <= 0 || L <= 0) return 0;
-    size_t need = carve(m, nullptr, default_chunk(m, B, T, L), T, L).bytes;
-    if (resident_ok(m, T, L)) need = std::max(need, carve_resident(m, nullptr, B, T, L, m->d.vec_in_dim > 0).bytes);
-    return need;
+    return workspace_need(m, B, T, L);
 }
 
 // the passes of one network evaluation at per-trajectory times: io->out = network(io->x, io->t, ...) (lsl_forward, and the middle of lsl_si_loss)
 static int forward_passes(lsl_model *m, const lsl_io *io, const Workspace &ws, const CallPlans &plans, int chunk, hipStream_t st) {
     run_tables(m, ws, io->T, io->L, st);
-    const size_t per = (size_t)io->T * io->L * m->d.in_dim;
-    for (int b0 = 0; b0 < io->B; b0 += chunk) {
-        const int bc = io->B - b0 < chunk ? io->B - b0 : chunk;
-        const float *y = io->y ? io->y + (size_t)b0 * m->d.vec_in_dim : nullptr;
-        if (int rc = prepare_pass(m, ws, io->x_cond + b0 * per, io->mask + (size_t)b0 * io->T * io->L, y, bc, io->T, io->L, st)) return rc;
+    return for_each_pass(m, ws, io, chunk, st, [&](const Pass &ps) {
         EvalArgs e;
-        e.x = io->x + b0 * per;
-        e.out = io->out + b0 * per;
-        e.t = io->t + b0;
-        e.have_y = y != nullptr;
-        if (int rc = run_eval(m, ws, plans.of(bc), e, st)) return rc;
-    }
-    return 0;
+        e.x = io->x + ps.elem;
+        e.out = io->out + ps.elem;
+        e.t = io->t + ps.b0;
+        e.have_y = ps.y != nullptr;
+        return run_eval(m, ws, plans.of(ps.bc), e, st);
+    });
 }
 
 int lsl_forward(lsl_model *m, const lsl_io *io, void *workspace, size_t workspace_bytes, void *stream) try {
@@ -259,11 +207,7 @@ int lsl_forward(lsl_model *m, const lsl_io *io, void *workspace, size_t workspac
     CallPlans plans;
     if (int rc = plan_call(m, ws, io, chunk, m->MODW, plans)) return rc;  // (per-trajectory times: a modulation row per trajectory)
     return forward_passes(m, io, ws, plans, chunk, st);
-} catch (const std::bad_alloc &) {
-    return fail(-5, "out of host memory");
-} catch (...) {
-    return fail(-11, "unexpected C++ exception");
-}
+} LSL_API_CATCH
 
 // ---- stochastic-interpolant objective (k_siloss.hip.h) ----
 static_assert(sizeof(lsl_si_row) == sizeof(SiRow) && sizeof(SiRow) == 24 && LSL_SI_SLAB == LSL_SI_SLAB_ELEMS, "lsl_si_row layout / slab size");
@@ -311,9 +255,7 @@ int lsl_si_reduce(const float *pred, const float *x1, const float *x0, const lsl
     const size_t need = si_scratch_bytes(B, per_trajectory);
     if (!scratch || scratch_bytes < need) return fail(-4, "scratch too small: need %zu bytes, got %zu", need, scratch_bytes);
     return si_reduce_enqueue(pred, x1, x0, rows, B, per_trajectory, loss, (float *)scratch, (hipStream_t)stream);
-} catch (...) {
-    return fail(-11, "unexpected C++ exception");
-}
+} LSL_API_CATCH
 
 int lsl_si_loss(lsl_model *m, const lsl_io *io, const float *x1, const float *x0, const lsl_si_row *rows, float *loss, void *workspace,
                 size_t workspace_bytes, void *stream) try {
@@ -339,11 +281,7 @@ int lsl_si_loss(lsl_model *m, const lsl_io *io, const float *x1, const float *x0
     if (int rc = forward_passes(m, io, ws, plans, chunk, st)) return rc;
     float *partial = (float *)((char *)workspace + align_up(lsl_workspace_bytes(m, io->B, io->T, io->L), 256));
     return si_reduce_enqueue(io->out, x1, x0, rows, io->B, per, loss, partial, st);
-} catch (const std::bad_alloc &) {
-    return fail(-5, "out of host memory");
-} catch (...) {
-    return fail(-11, "unexpected C++ exception");
-}
+} LSL_API_CATCH
 
 static int sample_enqueue(lsl_model *m, const lsl_io *io, const lsl_step_ex *steps, int32_t n_steps, const float *noise, uint64_t seed,
                           uint64_t elem_offset, float *trace, void *workspace, int chunk, hipStream_t st);
@@ -354,11 +292,7 @@ int lsl_sample(lsl_model *m, const lsl_io *io, const lsl_step *steps, int32_t n_
     std::vector<lsl_step_ex> ex((size_t)n_steps);
     for (int s = 0; s < n_steps; ++s) ex[s] = lsl_step_ex{steps[s].t, steps[s].ax, steps[s].am, steps[s].aw, 0.0f, 0, s, s};
     return lsl_sample_ex(m, io, ex.data(), n_steps, noise, n_noise, seed, elem_offset, trace, n_steps, workspace, workspace_bytes, stream);
-} catch (const std::bad_alloc &) {
-    return fail(-5, "out of host memory");
-} catch (...) {
-    return fail(-11, "unexpected C++ exception");
-}
+} LSL_API_CATCH
 
 int lsl_sample_ex(lsl_model *m, const lsl_io *io, const lsl_step_ex *steps, int32_t n_steps, const float *noise, int32_t n_noise, uint64_t seed,
                   uint64_t elem_offset, float *trace, int32_t n_trace, void *workspace, size_t workspace_bytes, void *stream) try {
@@ -383,9 +317,8 @@ int lsl_sample_ex(lsl_model *m, const lsl_io *io, const lsl_step_ex *steps, int3
         for (int s = 0; s < n_steps; ++s) ps[s] = lsl_step{steps[s].t, steps[s].ax, steps[s].am, steps[s].aw};
         return resident_sample(m, io, ps.data(), n_steps, noise, seed, elem_offset, trace, workspace, st);
     }
-    // hipGraph replay.  LSL_GRAPH: 1 (default since round 6) for launch-bound calls (at most 64 Ki tokens per pass and 4096 launches) whose
-    // arguments repeat, 2 for every call of at most 4096 launches, 0 off: the first appearance of an argument set runs eagerly (it also
-    // initialises the per-kernel attributes), the second is captured, later ones are replayed.  Bit-identical to the eager path
+    // hipGraph replay (host_graph.hip.h).  LSL_GRAPH: 1 (default since round 6) for launch-bound calls (at most 64 Ki tokens per pass and 4096
+    // launches) whose arguments repeat, 2 for every call of at most 4096 launches, 0 off.  Bit-identical to the eager path
     // (test_graph_replay_matches_eager_bits).  Measured on MI355X (tools/latency_small_batch.py, profiles/r06_small_launches.txt): a
     // 10-update pedestrian call (~600 launches) 3.38 -> 3.23 ms, md17_bench B = 1 (50 updates) 30.0 -> 29.2 ms: the floor of the small-batch
     // configs is the GPU-side cost of their dependent tiny kernels, replay removes the host-side gaps between them (0-4 %).
@@ -394,7 +327,7 @@ int lsl_sample_ex(lsl_model *m, const lsl_io *io, const lsl_step_ex *steps, int3
     const long est_launches = (long)passes * n_steps * (8L * m->d.depth + 6);
     const bool launch_bound = (size_t)chunk * io->T * io->L <= 65536;
     if (use_graph && (launch_bound || use_graph >= 2) && m->prof.kernel < 0 && est_launches <= 4096) {
-        std::vector<unsigned char> key;
+        GraphCache::Key key;  // everything the enqueued launches depend on
         auto put = [&](const void *p, size_t n) { key.insert(key.end(), (const unsigned char *)p, (const unsigned char *)p + n); };
         put(io, sizeof(*io));
         put(steps, sizeof(lsl_step_ex) * n_steps);
@@ -405,66 +338,11 @@ int lsl_sample_ex(lsl_model *m, const lsl_io *io, const lsl_step_ex *steps, int3
         put(&workspace, sizeof(workspace));
         put(&chunk, sizeof(chunk));
         put(&st, sizeof(st));
-        for (auto &g : m->graphs)
-            if (g.key == key) {
-                g.last_use = ++m->graph_clock;
-                if (hipGraphLaunch(g.exec, st) != hipSuccess) return fail(-10, "hipGraphLaunch failed");
-                return 0;
-            }
-        bool second = false, bad = m->graph_stream_failed;
-        for (auto &k : m->uncapturable) bad |= (k == key);
-        for (auto &k : m->seen) second |= (k == key);
-        if (bad) {
-            // capture failed before for this argument set (or no capture stream): eager from now on
-        } else if (second) {
-            hipGraph_t graph = nullptr;
-            if (!m->graph_stream && hipStreamCreateWithFlags(&m->graph_stream, hipStreamNonBlocking) != hipSuccess) {
-                m->graph_stream = nullptr;
-                m->graph_stream_failed = true;
-            }
-            hipStream_t cs = m->graph_stream;
-            if (cs && hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                const int rc = sample_enqueue(m, io, steps, n_steps, noise, seed, elem_offset, trace, workspace, chunk, cs);
-                const hipError_t e = hipStreamEndCapture(cs, &graph);
-                hipGraphExec_t exec = nullptr;
-                if (rc == 0 && e == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-                    hipGraphDestroy(graph);
-                    if (m->graphs.size() >= 8) {  // evict the least recently used
-                        size_t lru = 0;
-                        for (size_t i = 1; i < m->graphs.size(); ++i)
-                            if (m->graphs[i].last_use < m->graphs[lru].last_use) lru = i;
-                        hipGraphExecDestroy(m->graphs[lru].exec);
-                        m->graphs.erase(m->graphs.begin() + lru);
-                    }
-                    lsl_model::GraphEntry ge;
-                    ge.key = key;
-                    ge.exec = exec;
-                    ge.last_use = ++m->graph_clock;
-                    m->graphs.push_back(std::move(ge));
-                    if (hipGraphLaunch(exec, st) != hipSuccess) return fail(-10, "hipGraphLaunch failed");
-                    return 0;
-                }
-                if (graph) hipGraphDestroy(graph);
-            }
-            (void)hipGetLastError();  // capture not possible: forget the error, run eagerly, and never try this argument set again
-            for (size_t i = 0; i < m->seen.size(); ++i)
-                if (m->seen[i] == key) {
-                    m->seen.erase(m->seen.begin() + i);
-                    break;
-                }
-            if (m->uncapturable.size() >= 16) m->uncapturable.erase(m->uncapturable.begin());
-            m->uncapturable.push_back(key);
-        } else {
-            if (m->seen.size() >= 16) m->seen.erase(m->seen.begin());
-            m->seen.push_back(key);
-        }
+        const int rc = m->graphs.run(key, st, [&](hipStream_t cs) { return sample_enqueue(m, io, steps, n_steps, noise, seed, elem_offset, trace, workspace, chunk, cs); });
+        if (rc) return rc < 0 ? rc : 0;  // (replayed, or captured and launched; 0: eagerly)
     }
     return sample_enqueue(m, io, steps, n_steps, noise, seed, elem_offset, trace, workspace, chunk, st);
-} catch (const std::bad_alloc &) {
-    return fail(-5, "out of host memory");
-} catch (...) {
-    return fail(-11, "unexpected C++ exception");
-}
+} LSL_API_CATCH
 
 static int sample_enqueue(lsl_model *m, const lsl_io *io, const lsl_step_ex *steps, int32_t n_steps, const float *noise, uint64_t seed,
                           uint64_t elem_offset, float *trace, void *workspace, int chunk, hipStream_t st) {
@@ -489,24 +367,21 @@ static int sample_enqueue(lsl_model *m, const lsl_io *io, const lsl_step_ex *ste
         }
     }
     int cur_group = -1;
-    for (int b0 = 0; b0 < io->B; b0 += chunk) {  // one pass = all records for `bc` trajectories
-        const int bc = io->B - b0 < chunk ? io->B - b0 : chunk;
-        const float *y = io->y ? io->y + (size_t)b0 * m->d.vec_in_dim : nullptr;
-        if (int rc = prepare_pass(m, ws, io->x_cond + b0 * per, io->mask + (size_t)b0 * io->T * io->L, y, bc, io->T, io->L, st)) return rc;
+    return for_each_pass(m, ws, io, chunk, st, [&](const Pass &ps) -> int {  // one pass = all records for its trajectories
         for (int s = 0; s < n_steps; ++s) {
             const lsl_step_ex &sp = steps[s];
             EvalArgs e;
-            e.x = io->x + b0 * per;
+            e.x = io->x + ps.elem;
             e.have_y = io->y != nullptr;
             e.rec = &sp;
-            if (sp.aw != 0.0f && noise) e.noise = noise + (size_t)sp.noise_index * total + b0 * per;
+            if (sp.aw != 0.0f && noise) e.noise = noise + (size_t)sp.noise_index * total + ps.elem;
             e.seed = seed;
-            e.elem_off = elem_offset + b0 * per;
-            e.trace = trace && sp.trace_index >= 0 ? trace + (size_t)sp.trace_index * total + b0 * per : nullptr;
+            e.elem_off = elem_offset + ps.elem;
+            e.trace = trace && sp.trace_index >= 0 ? trace + (size_t)sp.trace_index * total + ps.elem : nullptr;
             e.saved = sp.as != 0.0f ? ws.saved : nullptr;  // (the pass's own copy: a pass runs all records for its trajectories)
             e.save_out = (sp.flags & LSL_STEP_SAVE) ? ws.saved : nullptr;
             if (sp.flags & LSL_STEP_NO_NETWORK) {
-                const unsigned long long ne = (unsigned long long)bc * per;
+                const unsigned long long ne = (unsigned long long)ps.bc * per;
                 hipLaunchKernelGGL(k_state_affine, dim3((unsigned)std::min<unsigned long long>((ne + 255) / 256, 2048)), dim3(256), 0, st,
                                    e.x, ne, sp.ax, sp.aw, sp.as, e.noise, (unsigned long long)seed, (unsigned)sp.noise_index,
                                    (unsigned long long)e.elem_off, e.saved, e.save_out, e.trace);
@@ -521,10 +396,10 @@ static int sample_enqueue(lsl_model *m, const lsl_io *io, const lsl_step_ex *ste
                 }
                 e.mods_ready = ws.mods_all + (size_t)(k - g * G) * m->MODW;
             }
-            if (int rc = run_eval(m, ws, plans.of(bc), e, st)) return rc;
+            if (int rc = run_eval(m, ws, plans.of(ps.bc), e, st)) return rc;
         }
-    }
-    return 0;
+        return 0;
+    });
 }
 
 // x_0 ~ N(0, 1) from the documented counter stream (k_small.hip.h: k_randn); the reference draws torch.randn_like(x_cond)
@@ -539,9 +414,7 @@ int lsl_randn(float *x, uint64_t n, uint64_t seed, uint64_t elem_offset, void *s
                        (unsigned long long)elem_offset);
     LSL_CHECK_LAUNCH("lsl_randn");
     return 0;
-} catch (...) {
-    return fail(-11, "unexpected C++ exception");
-}
+} LSL_API_CATCH
 
 // ---- Runge-Kutta arithmetic of the adaptive sampler (k_small.hip.h: k_rk_*) ----
 static int rk_terms(RkTerms &t, const float *const *x, const float *c, int32_t n_x) {
@@ -565,9 +438,7 @@ int lsl_rk_lincomb(float *out, const float *const *x, const float *c, int32_t n_
     hipLaunchKernelGGL(k_rk_lincomb, dim3(rk_grid(n)), dim3(256), 0, (hipStream_t)stream, out, t, (unsigned long long)n);
     LSL_CHECK_LAUNCH("lsl_rk_lincomb");
     return 0;
-} catch (...) {
-    return fail(-11, "unexpected C++ exception");
-}
+} LSL_API_CATCH
 
 int lsl_rk_dense(float *out, const float *a, const float *b, const float *c, const float *d, const float *e, float x, uint64_t n, void *stream) try {
     DeviceGuard dev_guard_((hipStream_t)stream);
@@ -576,9 +447,7 @@ int lsl_rk_dense(float *out, const float *a, const float *b, const float *c, con
     hipLaunchKernelGGL(k_rk_poly4, dim3(rk_grid(n)), dim3(256), 0, (hipStream_t)stream, out, a, b, c, d, e, x, (unsigned long long)n);
     LSL_CHECK_LAUNCH("lsl_rk_dense");
     return 0;
-} catch (...) {
-    return fail(-11, "unexpected C++ exception");
-}
+} LSL_API_CATCH
 
 int lsl_rk_error_ratio(float *ratio, const float *y0, const float *y1, const float *const *k, const float *c, int32_t n_k, float atol, float rtol,
                        uint64_t n, void *scratch, void *stream) try {
@@ -592,17 +461,12 @@ int lsl_rk_error_ratio(float *ratio, const float *y0, const float *y1, const flo
     hipLaunchKernelGGL(k_rk_error_final, dim3(1), dim3(256), 0, (hipStream_t)stream, ratio, (const float *)scratch, (int)grid, (unsigned long long)n);
     LSL_CHECK_LAUNCH("lsl_rk_error_ratio");
     return 0;
-} catch (...) {
-    return fail(-11, "unexpected C++ exception");
-}
+} LSL_API_CATCH
 
 int lsl_debug_block(lsl_model *m, int32_t bi, const float *h_in, float *h_out, const float *mods, int32_t B, int32_t T, int32_t L,
                     void *workspace, size_t workspace_bytes, void *stream) try {
     DeviceGuard dev_guard_((hipStream_t)stream);
-    if (!m || !m->has_weights) return fail(-2, "weights not set");
-    if (bi < 0 || bi >= 2 * m->d.depth) return fail(-3, "block index out of range");
-    const size_t need = carve(m, nullptr, B, T, L).bytes;
-    if (!workspace || workspace_bytes < need) return fail(-4, "workspace too small: need %zu bytes", need);
+    if (int rc = check_debug(m, bi, true, B, T, L, workspace, workspace_bytes)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const Workspace ws = carve(m, (char *)workspace, B, T, L);
     PassPlan plan;
@@ -614,20 +478,13 @@ int lsl_debug_block(lsl_model *m, int32_t bi, const float *h_in, float *h_out, c
     if (int rc = run_block(m, ws, plan, bi, mods, st)) return rc;
     hipMemcpyAsync(h_out, ws.h, bytes, hipMemcpyDeviceToDevice, st);
     return 0;
-} catch (const std::bad_alloc &) {
-    return fail(-5, "out of host memory");
-} catch (...) {
-    return fail(-11, "unexpected C++ exception");
-}
+} LSL_API_CATCH
 
 int lsl_debug_taps(lsl_model *m, int32_t bi, const float *h_in, const float *mods, int32_t B, int32_t T, int32_t L, void *qkv_out,
                    void *z_out, void *workspace, size_t workspace_bytes, void *stream) try {
     DeviceGuard dev_guard_((hipStream_t)stream);
-    if (!m || !m->has_weights) return fail(-2, "weights not set");
-    if (bi < 0 || bi >= 2 * m->d.depth) return fail(-3, "block index out of range");
-    if (!h_in || !mods || !qkv_out || !z_out || B <= 0 || T <= 0 || L <= 0) return fail(-3, "invalid arguments");
-    const size_t need = carve(m, nullptr, B, T, L).bytes;
-    if (!workspace || workspace_bytes < need) return fail(-4, "workspace too small: need %zu bytes", need);
+    const bool args_ok = h_in && mods && qkv_out && z_out && B > 0 && T > 0 && L > 0;
+    if (int rc = check_debug(m, bi, args_ok, B, T, L, workspace, workspace_bytes)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const Workspace ws = carve(m, (char *)workspace, B, T, L);
     PassPlan plan;
@@ -645,29 +502,19 @@ int lsl_debug_taps(lsl_model *m, int32_t bi, const float *h_in, const float *mod
     hipMemcpyAsync(z_out, ws.z, n * m->K2 * 2, hipMemcpyDeviceToDevice, st);
     LSL_CHECK_LAUNCH("debug taps");
     return 0;
-} catch (const std::bad_alloc &) {
-    return fail(-5, "out of host memory");
-} catch (...) {
-    return fail(-11, "unexpected C++ exception");
-}
+} LSL_API_CATCH
 
 int lsl_debug_mods(lsl_model *m, const float *t, const float *y, int32_t B, float *vec_out, float *mods_out, void *workspace,
                    size_t workspace_bytes, void *stream) try {
     DeviceGuard dev_guard_((hipStream_t)stream);
-    if (!m || !m->has_weights) return fail(-2, "weights not set");
-    const size_t need = carve(m, nullptr, B, 1, 1).bytes;
-    if (!workspace || workspace_bytes < need) return fail(-4, "workspace too small: need %zu bytes", need);
+    if (int rc = check_debug(m, 0, true, B, 1, 1, workspace, workspace_bytes)) return rc;  // (no sub-block: index 0 always exists)
     hipStream_t st = (hipStream_t)stream;
     const Workspace ws = carve(m, (char *)workspace, B, 1, 1);
     if (y) {
         if (int rc = run_yemb(m, ws, y, B, st)) return rc;
     }
     return run_mods(m, ws, t, 0.0f, y ? ws.yemb : nullptr, B, vec_out, mods_out, st);
-} catch (const std::bad_alloc &) {
-    return fail(-5, "out of host memory");
-} catch (...) {
-    return fail(-11, "unexpected C++ exception");
-}
+} LSL_API_CATCH
 
 #include "stage1_api.hip.h"
 

@@ -22,11 +22,7 @@ int lsl_decoder_create(const lsl_decoder_desc *desc, const lsl_decoder_weights *
     dec->w.cross_blocks = dec->cross_blocks.data();
     *out = dec;
     return 0;
-} catch (const std::bad_alloc &) {
-    return fail(-5, "out of host memory");
-} catch (...) {
-    return fail(-11, "unexpected C++ exception");
-}
+} LSL_API_CATCH
 
 void lsl_decoder_destroy(lsl_decoder *d) { delete d; }
 
@@ -70,11 +66,7 @@ int lsl_decode(lsl_decoder *dec, const float *z, const int64_t *entities, int32_
     dec_dense(0, out, ws.hid, w.head_w2, w.head_b2, nullptr, na, d.dim_query, d.out_dim, st);
     LSL_CHECK_LAUNCH("lsl_decode");
     return 0;
-} catch (const std::bad_alloc &) {
-    return fail(-5, "out of host memory");
-} catch (...) {
-    return fail(-11, "unexpected C++ exception");
-}
+} LSL_API_CATCH
 
 int lsl_encoder_create(const lsl_encoder_desc *desc, const lsl_encoder_weights *w, lsl_encoder **out) try {
     if (!desc || !w || !out) return fail(-1, "null encoder argument");
@@ -94,11 +86,7 @@ int lsl_encoder_create(const lsl_encoder_desc *desc, const lsl_encoder_weights *
     enc->w.self_blocks = enc->self_blocks.data();
     *out = enc;
     return 0;
-} catch (const std::bad_alloc &) {
-    return fail(-5, "out of host memory");
-} catch (...) {
-    return fail(-11, "unexpected C++ exception");
-}
+} LSL_API_CATCH
 
 void lsl_encoder_destroy(lsl_encoder *e) { delete e; }
 
@@ -136,8 +124,4 @@ int lsl_encode(lsl_encoder *enc, const float *x, const int64_t *entities, const 
     dec_ln(out, ws.hid, nullptr, nullptr, nl, d.dim_latent, st);
     LSL_CHECK_LAUNCH("lsl_encode");
     return 0;
-} catch (const std::bad_alloc &) {
-    return fail(-5, "out of host memory");
-} catch (...) {
-    return fail(-11, "unexpected C++ exception");
-}
+} LSL_API_CATCH

@@ -399,7 +399,7 @@ def test_batch_independence_across_the_linear2_tiling_threshold_384(dev):
 
 def test_batch_independence_across_the_linear1_wave_count_threshold_512(dev):
     """512-wide models: linear1 runs 4-wave workgroups on 128-token tiles up to 10 240 tokens per pass and 8-wave workgroups on 256-token
-    tiles above (host_launch.hip.h, launch_linear1_ts_512; tools/lin1_harness.hip -DLIN1_NW=4 compares both with the tile kernel bit for
+    tiles above (host_launch.hip.h, linear1_ts_waves; tools/lin1_harness.hip -DLIN1_NW=4 compares both with the tile kernel bit for
     bit).  Here through the sampler: trajectory k of a 3-trajectory call (23 040 tokens: 8 waves) against the same trajectory sampled alone
     (7 680 tokens - md17_bench B = 1 -: 4 waves), and a ragged length whose last 128-token tile is partial."""
     from lam_slide_amd import CreateTransport, SecondStageSampler
