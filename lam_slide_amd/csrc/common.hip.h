@@ -25,6 +25,19 @@ typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
+// A pointer that is wave-uniform by construction, made provably so (two v_readfirstlane) for the "s" operands of asm statements - where the
+// compiler cannot see it, e.g. behind a ring-slot or unit counter that lives in a VGPR
+__device__ __forceinline__ const char *uni_ptr(const char *q) {
+    const unsigned long long v = (unsigned long long)q;
+    const unsigned lo32 = __builtin_amdgcn_readfirstlane((unsigned)v), hi32 = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    return reinterpret_cast<const char *>(((unsigned long long)hi32 << 32) | lo32);
+}
+// One LDS-DMA request of 16 bytes per lane: lane l's 16 bytes at base + voff land at LDS byte address dst + 16 l (base, dst wave-uniform; m0
+// carries dst, the s_nop covers the m0 write -> use hazard).  Counted by vmcnt like a load.
+__device__ __forceinline__ void lds_dma16(unsigned voff, const void *base, unsigned dst) {
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(base), "s"(dst) : "memory");
+}
+
 // 32x32x16 bf16 MFMA, fp32 accumulate.  Operand maps (lane l: r = l & 31, hf = l >> 5):
 //   A[row r][k = 8 hf + j], B[k = 8 hf + j][col r], j = 0..7
 //   C/D: col = l & 31, row = (reg & 3) + 8 (reg >> 2) + 4 hf, reg = 0..15

@@ -117,7 +117,7 @@ struct PassPlan {
 };
 
 // The plan of a pass of bc trajectories through sub-blocks [0, 2 depth) (eval) or sub-block `block` (the debug modes).  Refuses (-3) a pass
-// too large for the kernels' 32-bit arithmetic, with the message of the first check a sub-block's launches would meet.
+// too large for the kernels' 32-bit arithmetic or an attention axis no kernel takes, with the message of the first check a sub-block's launches would meet.
 int plan_pass(const lsl_model *m, const Workspace &ws, int bc, int T, int L, int mod_stride, PlanMode mode, int block, PassPlan &p) {
     const lsl_model_desc &d = m->d;
     const int D = d.hidden, n = bc * T * L;
@@ -159,6 +159,10 @@ int plan_pass(const lsl_model *m, const Workspace &ws, int bc, int T, int L, int
         // stream requests): a pass set larger than that through lsl_model_set_chunk / LSL_CHUNK_TRAJ is refused, never wrapped
         if (p.planes[temporal] && (unsigned long long)p.npad * 3ull * (unsigned)m->HHD * 2ull >= (1ull << 32))
             return fail(-3, "pass too large for the q/k/v plane offsets (%d tokens: at most %llu with this model)", n, (unsigned long long)((1ull << 32) / (6ull * (unsigned)m->HHD)) - 256);
+        // an axis that is not on the stream kernel (LSL_ATTN_STREAM=0, or a pass of 2^31 stream units) needs K | V of a whole (sequence, head) in LDS
+        if (p.attn[temporal].form == AttnForm::none)
+            return fail(-3, "attention axis of %d positions is not on the stream kernel and too long for k_attention_rows (at most %d positions at %d-wide heads)",
+                        pmod, attention_rows_max_s(d.head_dim_pad), d.head_dim_pad);
         if (p.lin2 == Lin2Kind::none) continue;
         if ((unsigned long long)n * (unsigned)(T * L) >= (1ull << 32)) return fail(-3, "pass too large for the trajectory arithmetic");
         if (p.tail && (unsigned long long)p.npad * (unsigned)(4 * D) >= (1ull << 32)) return fail(-3, "pass too large for the residual-stream offsets");
@@ -200,7 +204,7 @@ void label_block(lsl_model *m, const PassPlan &p, int bi) {
             break;
         case 2: {
             const AttnPlan &a = p.attn[bi & 1];
-            pr.label(2, "%s", a.form == AttnForm::linear ? "k_attention_linear" : a.stream() ? "k_attention_stream" : "k_attention_rows / k_attention_tiny / k_attention");
+            pr.label(2, "%s", a.form == AttnForm::linear ? "k_attention_linear" : a.stream() ? "k_attention_stream" : "k_attention_rows / k_attention_tiny");
             break;
         }
         default: break;

@@ -390,7 +390,7 @@ void launch_gemm(int variant, const u16 *W, const u16 *X, int F, int N, int K, c
 // chunks of 256: peptide's T = 1000 is 4 groups x 4 chunks) and of 9 .. 32 positions
 // with a multiple of 8 heads (8 heads of a sequence per unit).  The choice depends on the model and on T, L only - never on the batch - so a
 // trajectory's bits are the same in any batch.  LSL_ATTN_STREAM=0 (read in the product too: A/B runs) keeps k_attention_rows.
-int attention_stream_mode(int S, int H) {  // 0: k_attention_rows / tiny / online, 1: stream SHORT, 2: stream LONG
+int attention_stream_mode(int S, int H) {  // 0: k_attention_rows / tiny, 1: stream SHORT, 2: stream LONG
     static const int on = env_int("LSL_ATTN_STREAM", 1);
     if (!on) return 0;
     static const int long_min = tune_int("LSL_ATTN_LONG_MIN", 129);  // shortest axis on the LONG form
@@ -408,9 +408,9 @@ enum class AttnForm {
     stream_chunked_den,  // ... with the padded head's spare V column carrying the softmax denominator (peptide: head_dim 24 of 32)
     tiny,             // k_attention_tiny: one lane per (query, head)
     rows,             // k_attention_rows<nw, items, nkt>: two-pass softmax, K / V of `items` (sequence, head)s in LDS
-    online            // k_attention<nw, items>: online softmax
+    none              // not on the stream kernel and too long for k_attention_rows: plan_pass refuses the pass
 };
-// What the attention of one axis runs: the form, the sequence geometry the kernel is given (AttnArgs) and the instance of rows / online
+// What the attention of one axis runs: the form, the sequence geometry the kernel is given (AttnArgs) and the instance of rows
 struct AttnPlan {
     AttnForm form;
     int stream_mode;  // what attention_stream_mode said for this axis (2: q / k / v may travel as planes, qkv_planes_ok)
@@ -425,10 +425,12 @@ bool attention_grouped_ok(const AttnPlan &a, int H) {
     return on && stream_on && a.S >= 2 && a.S <= 8 && (a.S & (a.S - 1)) == 0 && a.inner == 1 && a.pos_stride == 1 && a.outer_stride == a.S && H % 8 == 0;
 }
 // LDS of the forms: stream - two images of K | V, 256 rows each, and a 32-row query image per wave; rows - K, V of every item (key tiles of
-// 32 rows) and the key-norm slots; online - K, V of every item
+// 32 rows) and the key-norm slots
 constexpr size_t attention_stream_lds(int hdp) { return (size_t)2 * 2 * 256 * hdp * 2 + (size_t)8 * 32 * hdp * 2; }
 constexpr size_t attention_rows_lds(int hdp, int nw, int items, int key_rows) { return (size_t)items * 2 * key_rows * hdp * 2 + nw * sizeof(float); }
-constexpr size_t attention_online_lds(int hdp, int items, int key_rows) { return (size_t)items * 2 * key_rows * hdp * 2; }
+// the longest axis k_attention_rows takes: K | V of one (sequence, head) in whole key tiles, 16 waves' key-norm slots
+constexpr int attention_rows_max_s(int hdp) { return (int)((LDS_BUDGET - 16 * sizeof(float)) / (4 * hdp)) & ~31; }
+static_assert(attention_rows_lds(32, 16, 1, attention_rows_max_s(32)) <= LDS_BUDGET && attention_rows_lds(32, 16, 1, attention_rows_max_s(32) + 32) > LDS_BUDGET);
 
 AttnPlan plan_attention(bool linear, int hdp, int H, int hd, int bc, int T, int L, bool temporal) {
     AttnPlan p{};
@@ -461,10 +463,9 @@ AttnPlan plan_attention(bool linear, int hdp, int H, int hd, int bc, int T, int 
     p = axis;  // (not on the stream kernel: the axis as it is)
     p.stream_mode = mode;
     const int Sp = (p.S + 31) & ~31;
-    static const int online = tune_int("LSL_ATTN_ONLINE", 0);  // 1: force the online-softmax kernel (A/B measurements)
     auto inst = [&](AttnForm f, int nw, int items, int nkt) { p.form = f; p.nw = nw; p.items = items; p.nkt = nkt; return p; };
-    if (!online && p.S <= 8) return inst(AttnForm::tiny, 4, 1, 0);  // one lane per (query, head), no MFMA padding
-    if (!online && attention_rows_lds(hdp, 16, 1, Sp) <= LDS_BUDGET) {  // two-pass softmax, K/V of one (sequence, head) in LDS
+    if (p.S <= 8) return inst(AttnForm::tiny, 4, 1, 0);  // one lane per (query, head), no MFMA padding
+    if (Sp <= attention_rows_max_s(hdp)) {  // two-pass softmax, K/V of one (sequence, head) in LDS
         // long axes (peptide T = 1000): 16 waves - with the max pass gone (AttnArgs::bound) the kernel is a chain of MFMA -> exp2 -> MFMA per
         // tile, and four waves per SIMD hide it better than two (attention 320.6 -> 303.8 ms per 1000-step call; with the max pass
         // 8 waves were as fast, profiles/r02_experiments.txt)
@@ -475,9 +476,7 @@ AttnPlan plan_attention(bool linear, int hdp, int H, int hd, int bc, int T, int 
         if (Sp <= 128) return inst(AttnForm::rows, 4, 1, 4);
         return inst(AttnForm::rows, 4, 1, Sp <= 192 ? 6 : 8);
     }
-    if (Sp <= 32) return inst(AttnForm::online, 4, 4, 0);
-    if (Sp <= 64) return inst(AttnForm::online, 4, 2, 0);
-    return inst(AttnForm::online, Sp <= 512 ? 4 : 8, 1, 0);
+    return inst(AttnForm::none, 0, 0, 0);  // (reachable with LSL_ATTN_STREAM=0, or 2^31 stream units: plan_pass refuses)
 }
 // q / k / v as head-major planes (k_lin1.hip.h, Lin1Args::planes): spatial sub-blocks (positions = consecutive tokens) whose attention
 // runs the LONG stream kernel, token-stationary linear1.  LSL_QKV_PLANES=0 keeps token-major rows (A/B runs).
@@ -499,14 +498,6 @@ void launch_attention_rows(const AttnArgs &a, hipStream_t st) {
     auto kern = k_attention_rows<HDP, NW, ITEMS, NKT>;
     const size_t lds = attention_rows_lds(HDP, NW, ITEMS, NKT > 0 ? NKT * 32 : (a.S + 31) & ~31);
     LSL_ALLOW_LDS(kern, NKT > 0 ? lds : LDS_BUDGET);
-    const long items = (long)a.n_seq * a.H;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((items + ITEMS - 1) / ITEMS)), dim3(NW * 64), lds, st, a);
-}
-template <int HDP, int NW, int ITEMS>
-void launch_attention_online(const AttnArgs &a, hipStream_t st) {
-    auto kern = k_attention<HDP, NW, ITEMS>;
-    const size_t lds = attention_online_lds(HDP, ITEMS, (a.S + 31) & ~31);
-    if (ITEMS == 1) LSL_ALLOW_LDS(kern, NW == 8 ? LDS_BUDGET : (size_t)65536);
     const long items = (long)a.n_seq * a.H;
     hipLaunchKernelGGL(kern, dim3((unsigned)((items + ITEMS - 1) / ITEMS)), dim3(NW * 64), lds, st, a);
 }
@@ -539,13 +530,7 @@ void launch_attention_t(const AttnPlan &p, const AttnArgs &a, hipStream_t st) {
                 case 416: return launch_attention_rows<HDP, 4, 1, 6>(a, st);
                 default: return launch_attention_rows<HDP, 4, 1, 8>(a, st);
             }
-        case AttnForm::online:
-            switch (p.nw * 10 + p.items) {
-                case 44: return launch_attention_online<HDP, 4, 4>(a, st);
-                case 42: return launch_attention_online<HDP, 4, 2>(a, st);
-                case 41: return launch_attention_online<HDP, 4, 1>(a, st);
-                default: return launch_attention_online<HDP, 8, 1>(a, st);
-            }
+        case AttnForm::none: return;  // (plan_pass has refused the pass)
     }
 }
 

@@ -3,17 +3,17 @@
 // reference materialises "(B T) L D" / "(B L) T D" copies (latent_si_v31.py:51-61); here the axis is a
 // stride pattern over the token-major q/k/v buffer written by linear1's epilogue.
 //
-// One workgroup per ITEMS (sequence, head) pairs.  K and V of the pair are staged once in LDS
-// (K XOR-swizzled for ds_read_b128 fragments, V plain for ds_read_b64_tr_b16 transposed fragments).
-// Each wave owns 32-query tiles:
+// Four kernels, chosen per axis by plan_attention (host_launch.hip.h):
+//     k_attention_stream  persistent workgroups, K / V by LDS-DMA into double-buffered images: every shipped workload
+//     k_attention_rows    one workgroup per ITEMS (sequence, head)s, K / V staged once: the axes the stream kernel does not take (33 .. 128
+//                         positions, heads not a multiple of 8), and the form it is tested against
+//     k_attention_tiny    S <= 8: one lane per (query, head), no MFMA;    k_attention_linear  attention_mode "linear": no S^2 term
+// The two MFMA kernels work on 32-query x 32-key tiles, K XOR-swizzled in LDS for ds_read_b128, V plain for ds_read_b64_tr_b16 transposed reads:
 //     St = K Q^T     (A = K rows, B = Q rows)   -> lane (q = l&31, hf) holds 16 of the tile's 32 keys
-//     online softmax in registers: running max / sum are per lane, one lane^32 exchange per tile
 //     Ot = V^T P^T   (A = V via transposed LDS read, B = P straight from the accumulator registers)
 // so every per-query quantity lives on the query's own lane.  q arrives pre-multiplied by
-// hd^-0.5 * log2(e) (linear1 epilogue), so probabilities are exp2(s - max).
+// hd^-0.5 * log2(e) (linear1 epilogue), so probabilities are exp2 of the scores.
 #pragma once
-#include <type_traits>
-
 #include "common.hip.h"
 
 struct AttnArgs {
@@ -44,118 +44,82 @@ __device__ __forceinline__ int k_swz(int row, int chunk) {
     return row * 32 + ((chunk ^ ((row >> 3) & 1)) << 4);
 }
 
-template <int HDP, int NW, int ITEMS>
-__global__ void __launch_bounds__(NW * 64, 2) k_attention(AttnArgs a) {  // (min waves/SIMD: MFMA results stay in VGPRs, see k_attention_rows)
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int ROWB = HDP * 2;         // bytes per K/V row
-    constexpr int CPR = ROWB / 16;        // 16-byte chunks per row
-    constexpr int KS = HDP / 16;          // k-steps of the QK^T contraction
-    constexpr int WPI = NW / ITEMS;       // waves per (seq, head) item
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, hf = lane >> 5;
-    const int S = a.S, Sp = (S + 31) & ~31, nkt = Sp >> 5;
-    const int item_local = wave / WPI, wsub = wave % WPI;
-    const long item = (long)blockIdx.x * ITEMS + item_local;
-    const bool item_ok = item < (long)a.n_seq * a.H;
-    const int seq = item_ok ? (int)(item / a.H) : 0, head = item_ok ? (int)(item % a.H) : 0;
-    const size_t tok0 = (size_t)(seq / a.inner) * a.outer_stride + (seq % a.inner);
-    const size_t rs = (size_t)3 * a.HHD;  // qkv row stride (elements)
-    char *Ks = smem + (size_t)item_local * 2 * Sp * ROWB;
-    char *Vs = Ks + (size_t)Sp * ROWB;
+// ---- fragments of a 32 x 32 tile, shared by k_attention_rows and k_attention_stream (lane l: query r = l & 31, half hf = l >> 5) ---------
+// The score MFMA leaves lane (r, hf) with the scores of query r against keys acc_row(e, hf), e = 0 .. 15, of the tile; the P.V MFMAs
+// contract over those keys in two k-steps s = 0, 1 of 16, element j of k-step s <-> accumulator register 8 s + j <-> key
+// 16 s + 8 (j >> 2) + 4 hf + (j & 3).  The helpers take values, not references to the accumulators, and call sites keep one statement per step:
+// hipcc simplifies caller and helper apart before it inlines, and k_attention_rows schedules differently once an accumulator's address escapes
+// or an address is computed in front of a pack (profiles/attn_refactor.txt; the softmax denominator stays written out in both kernels for that).
 
-    // stage K (swizzled) and V (plain); rows >= S are zero so padded keys contribute exactly 0 * 0
-    {
-        const int ltid = wsub * 64 + lane, lthreads = WPI * 64;
-        const u16 *kbase = a.qkv + tok0 * rs + a.HHD + head * HDP;
-        const u16 *vbase = kbase + a.HHD;
-        for (int i = ltid; i < Sp * CPR; i += lthreads) {
-            const int row = i / CPR, ch = i % CPR;
-            u32x4 kv = {0, 0, 0, 0}, vv = {0, 0, 0, 0};
-            if (row < S && item_ok) {
-                const size_t off = (size_t)row * a.pos_stride * rs + ch * 8;
-                kv = *reinterpret_cast<const u32x4 *>(kbase + off);
-                vv = *reinterpret_cast<const u32x4 *>(vbase + off);
-            }
-            *reinterpret_cast<u32x4 *>(Ks + k_swz<HDP>(row, ch)) = kv;
-            *reinterpret_cast<u32x4 *>(Vs + row * ROWB + ch * 16) = vv;
+// the two bf16 of a 32-bit word as fp32
+__device__ __forceinline__ float bf_lo(unsigned w) { return __uint_as_float(w << 16); }
+__device__ __forceinline__ float bf_hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
+
+// squared norm of the 8 KS bf16 in a lane's fragments of a row, for the Cauchy-Schwarz softmax bound |q| max |k| (k_attention_rows has the
+// argument): a query's half row (the caller adds the other half's), or one 16-byte chunk of a key row (KS = 1)
+template <int KS>
+__device__ __forceinline__ float sq_norm(const bf16x8 (&q)[KS]) {
+    float qq = 0.0f;
+#pragma unroll
+    for (int s2 = 0; s2 < KS; ++s2) {
+        const u32x4 w = __builtin_bit_cast(u32x4, q[s2]);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float lo = bf_lo(w[k]), hi = bf_hi(w[k]);
+            qq = fmaf(lo, lo, fmaf(hi, hi, qq));
         }
     }
-    __syncthreads();
+    return qq;
+}
 
-    // transposed-read lane geometry (ds_read_b64_tr_b16, per 16-lane group: lane 4q+p supplies row q,
-    // columns 4p..4p+3 of a 4x16 block; lane i receives column i of the 4 rows)
+// B operand of a P.V k-step: P[q = r][key], 8 probabilities (two runs of 4 accumulator registers) rounded to bf16.  P needs no
+// exchange between lanes: it is used in the register order the score MFMA left it in.
+__device__ __forceinline__ u32x4 p_frag(const float *a, const float *b) {
+    return u32x4{pack2(a[0], a[1]), pack2(a[2], a[3]), pack2(b[0], b[1]), pack2(b[2], b[3])};
+}
+
+// Transposed-read lane geometry (ds_read_b64_tr_b16, per 16-lane group: lane 4q+p supplies row q, columns 4p..4p+3 of a 4x16 block;
+// lane i receives column i of the 4 rows): byte offset of the lane's source inside a 16-key block of plain V rows
+template <int HDP>
+__device__ __forceinline__ int v_frag_off(int lane) {
     const int gi = lane & 15, gq = gi >> 2, gp = gi & 3, grp = lane >> 4;
-    const int v_col = (HDP == 32 ? (grp & 1) * 16 : 0) + 4 * gp;
-    const int v_row0 = 4 * (grp >> 1) + gq;  // + 16*s + 8*half + 32*kt
+    return (4 * (grp >> 1) + gq) * (HDP * 2) + ((HDP == 32 ? (grp & 1) * 16 : 0) + 4 * gp) * 2;
+}
+// A operand of a P.V k-step: V^T[hd = r][key] in p_frag's key order: two transposed reads 8 rows apart, vb = first V row + v_frag_off
+typedef __attribute__((ext_vector_type(8))) short s16x8;
+template <int ROWB>
+__device__ __forceinline__ bf16x8 v_frag(const char *vb) {
+    const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(vb));
+    const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(vb + 8 * ROWB));
+    const s16x8 vv = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+    return __builtin_bit_cast(bf16x8, vv);
+}
 
-    for (int qt = wsub; qt < nkt; qt += WPI) {
-        // Q fragments straight from global memory (B operand: Q[q = r][hd = 16 s + 8 hf + j])
-        const int qpos = min(qt * 32 + r, S - 1);
-        const u16 *qrow = a.qkv + (tok0 + (size_t)qpos * a.pos_stride) * rs + head * HDP;
-        bf16x8 qf[KS];
-#pragma unroll
-        for (int s = 0; s < KS; ++s) qf[s] = as_bf16x8(*reinterpret_cast<const u32x4 *>(qrow + 16 * s + 8 * hf));
+// the lane's piece q4 of its query's output row: channels 8 q4 + 4 hf .. + 3 = accumulator registers 4 q4 .. + 3, normalised, 4 bf16
+__device__ __forceinline__ u32x2 o_pack(f32x16 o, float inv_l, int q4) {
+    return u32x2{pack2(o[4 * q4] * inv_l, o[4 * q4 + 1] * inv_l), pack2(o[4 * q4 + 2] * inv_l, o[4 * q4 + 3] * inv_l)};
+}
 
-        f32x16 o;
+// ---- a bf16 row <-> fp32 registers (k_attention_tiny, k_attention_linear: one lane owns a whole head row) ----------------------------------
+__device__ __forceinline__ void unpack8(u32x4 w, float *x) {
 #pragma unroll
-        for (int e = 0; e < 16; ++e) o[e] = 0.0f;
-        float m_run = -INFINITY, l_run = 0.0f;
-
-        for (int kt = 0; kt < nkt; ++kt) {
-            f32x16 sacc;
+    for (int k = 0; k < 4; ++k) {
+        x[2 * k] = bf_lo(w[k]);
+        x[2 * k + 1] = bf_hi(w[k]);
+    }
+}
+template <int HDP>
+__device__ __forceinline__ void row_unpack(const u16 *row, float (&x)[HDP]) {
 #pragma unroll
-            for (int e = 0; e < 16; ++e) sacc[e] = 0.0f;
+    for (int c = 0; c < HDP / 8; ++c) unpack8(*reinterpret_cast<const u32x4 *>(row + 8 * c), x + 8 * c);
+}
+template <int HDP>
+__device__ __forceinline__ void row_pack(u16 *dst, const float (&o)[HDP], float sc) {  // dst <- bf16(o * sc)
 #pragma unroll
-            for (int s = 0; s < KS; ++s) {
-                const bf16x8 kf = as_bf16x8(*reinterpret_cast<const u32x4 *>(Ks + k_swz<HDP>(kt * 32 + r, (KS == 2 ? 2 * s : 0) + hf)));
-                sacc = mfma32(kf, qf[s], sacc);
-            }
-            if (kt * 32 + 32 > S) {  // wave-uniform: mask the zero-padded keys of the last tile
-#pragma unroll
-                for (int e = 0; e < 16; ++e)
-                    if (kt * 32 + acc_row(e, hf) >= S) sacc[e] = -INFINITY;
-            }
-            float mt = sacc[0];
-#pragma unroll
-            for (int e = 1; e < 16; ++e) mt = fmaxf(mt, sacc[e]);
-            mt = fmaxf(mt, xhalf(mt));
-            const float m_new = fmaxf(m_run, mt);
-            const float alpha = exp2f(m_run - m_new);
-            float psum = 0.0f;
-            float p[16];
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                p[e] = exp2f(sacc[e] - m_new);
-                psum += p[e];
-            }
-            l_run = l_run * alpha + psum;
-            m_run = m_new;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) o[e] *= alpha;
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                // B operand: P[q][key], element j of k-step s = accumulator register 8 s + j
-                u32x4 pw = {pack2(p[8 * s], p[8 * s + 1]), pack2(p[8 * s + 2], p[8 * s + 3]),
-                            pack2(p[8 * s + 4], p[8 * s + 5]), pack2(p[8 * s + 6], p[8 * s + 7])};
-                // A operand: V^T[hd = r][key], same key order: element j <-> key 16 s + 8 (j>>2) + 4 hf + (j&3)
-                const int vr = kt * 32 + 16 * s + v_row0;
-                const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(Vs + vr * ROWB + v_col * 2));
-                const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(Vs + (vr + 8) * ROWB + v_col * 2));
-                typedef __attribute__((ext_vector_type(8))) short s16x8;
-                const s16x8 vv = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-                o = mfma32(__builtin_bit_cast(bf16x8, vv), as_bf16x8(pw), o);
-            }
-        }
-        const float inv_l = 1.0f / (l_run + xhalf(l_run));
-        const int qglob = qt * 32 + r;
-        if (qglob < S && item_ok) {
-            u16 *dst = a.z + (tok0 + (size_t)qglob * a.pos_stride) * a.zw + head * HDP;
-#pragma unroll
-            for (int q4 = 0; q4 < HDP / 8; ++q4) {
-                u32x2 pk = {pack2(o[4 * q4] * inv_l, o[4 * q4 + 1] * inv_l), pack2(o[4 * q4 + 2] * inv_l, o[4 * q4 + 3] * inv_l)};
-                store8(dst + 8 * q4 + 4 * hf, pk, a.nt);
-            }
-        }
+    for (int c = 0; c < HDP / 8; ++c) {
+        const u32x4 w = {pack2(o[8 * c] * sc, o[8 * c + 1] * sc), pack2(o[8 * c + 2] * sc, o[8 * c + 3] * sc),
+                         pack2(o[8 * c + 4] * sc, o[8 * c + 5] * sc), pack2(o[8 * c + 6] * sc, o[8 * c + 7] * sc)};
+        *reinterpret_cast<u32x4 *>(dst + 8 * c) = w;
     }
 }
 
@@ -163,8 +127,8 @@ __global__ void __launch_bounds__(NW * 64, 2) k_attention(AttnArgs a) {  // (min
 // Short sequences (S <= 32 * NKT <= 256: every axis of the MD17 / pedestrian / NBA configs, both axes of peptide's
 // spatial attention): softmax is the plain two-pass form (one max pass, one exp/sum/PV pass, no running rescale of
 // O) -- per score element: max, sub, exp2, add, half a cvt; the scores are recomputed in the second pass.  Measured on
-// MI355X the online form above spent 17 VALU instructions per score element (profiles/r01_rocprof_summary.txt:
-// VALU : MFMA = 68 : 1), which is what bounds attention at head_dim 32, not the MFMAs.
+// MI355X an online-softmax form (running max / sum, O rescaled per key tile; retired) spent 17 VALU instructions per score
+// element (profiles/r01_rocprof_summary.txt: VALU : MFMA = 68 : 1), which is what bounds attention at head_dim 32, not the MFMAs.
 template <int HDP, int NW, int ITEMS, int NKT>
 __global__ void __launch_bounds__(NW * 64, 4) k_attention_rows(AttnArgs a) {  // >= 4 waves/SIMD: keeps the MFMA results in VGPRs (with the
     // whole 512-register budget hipcc parks them in AGPRs and spends a v_accvgpr_read per score element to get them back)
@@ -221,12 +185,8 @@ __global__ void __launch_bounds__(NW * 64, 4) k_attention_rows(AttnArgs a) {  //
             *reinterpret_cast<u32x4 *>(Ks + k_swz<HDP>(row, ch)) = kv;
             *reinterpret_cast<u32x4 *>(Vs + row * ROWB + ch * 16) = vv;
             if (a.bound) {  // squared norm of the key row: its CPR chunks sit on CPR neighbouring lanes
-                float ss = 0.0f;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float lo = __uint_as_float(kv[k] << 16), hi = __uint_as_float(kv[k] & 0xffff0000u);
-                    ss = fmaf(lo, lo, fmaf(hi, hi, ss));
-                }
+                const bf16x8 kr[1] = {as_bf16x8(kv)};
+                float ss = sq_norm(kr);
                 ss += __shfl_xor(ss, 1, 64);
                 if (CPR == 4) ss += __shfl_xor(ss, 2, 64);
                 kmax2 = fmaxf(kmax2, ss);
@@ -245,8 +205,7 @@ __global__ void __launch_bounds__(NW * 64, 4) k_attention_rows(AttnArgs a) {  //
         for (int w = 1; w < WPI; ++w) kmax2 = fmaxf(kmax2, red[item_local * WPI + w]);
     }
 
-    const int gi = lane & 15, gq = gi >> 2, gp = gi & 3, grp = lane >> 4;
-    const int v_off = (4 * (grp >> 1) + gq) * ROWB + ((HDP == 32 ? (grp & 1) * 16 : 0) + 4 * gp) * 2;
+    const int v_off = v_frag_off<HDP>(lane);
     f32x16 zero;
 #pragma unroll
     for (int e = 0; e < 16; ++e) zero[e] = 0.0f;
@@ -279,16 +238,7 @@ __global__ void __launch_bounds__(NW * 64, 4) k_attention_rows(AttnArgs a) {  //
         float mx = -INFINITY;
         bool shifted = false;
         if (a.bound) {
-            float qq = 0.0f;
-#pragma unroll
-            for (int s2 = 0; s2 < KS; ++s2) {
-                const u32x4 w = __builtin_bit_cast(u32x4, qf[s2]);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float lo = __uint_as_float(w[k] << 16), hi = __uint_as_float(w[k] & 0xffff0000u);
-                    qq = fmaf(lo, lo, fmaf(hi, hi, qq));
-                }
-            }
+            float qq = sq_norm(qf);
             qq += xhalf(qq);
             const float m = sqrtf(qq * kmax2) * 1.001f;
             shifted = __ballot(m > 60.0f) == 0;  // (wave-uniform)
@@ -319,14 +269,10 @@ __global__ void __launch_bounds__(NW * 64, 4) k_attention_rows(AttnArgs a) {  //
             for (int e = 0; e < 16; ++e) p[e] = __builtin_amdgcn_exp2f(t[e]);
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
-                u32x4 pw = {pack2(p[8 * s], p[8 * s + 1]), pack2(p[8 * s + 2], p[8 * s + 3]),
-                            pack2(p[8 * s + 4], p[8 * s + 5]), pack2(p[8 * s + 6], p[8 * s + 7])};
+                const u32x4 pw = p_frag(p + 8 * s, p + 8 * s + 4);
                 const char *vb = Vs + (kt * 32 + 16 * s) * ROWB + v_off;
-                const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(vb));
-                const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(vb + 8 * ROWB));
-                typedef __attribute__((ext_vector_type(8))) short s16x8;
-                const s16x8 vv = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-                o = mfma32(__builtin_bit_cast(bf16x8, vv), as_bf16x8(pw), o);
+                const bf16x8 vv = v_frag<ROWB>(vb);
+                o = mfma32(vv, as_bf16x8(pw), o);
                 if (!ones_col) lsum = mfma32(as_bf16x8(ones_w), as_bf16x8(pw), lsum);  // every row = sum over this tile's keys, column = query
             }
         }
@@ -342,7 +288,7 @@ __global__ void __launch_bounds__(NW * 64, 4) k_attention_rows(AttnArgs a) {  //
             u16 *dst = a.z + (tok0 + (size_t)qglob * a.pos_stride) * a.zw + head * HDP;
 #pragma unroll
             for (int q4 = 0; q4 < HDP / 8; ++q4) {
-                u32x2 pk = {pack2(o[4 * q4] * inv_l, o[4 * q4 + 1] * inv_l), pack2(o[4 * q4 + 2] * inv_l, o[4 * q4 + 3] * inv_l)};
+                const u32x2 pk = o_pack(o, inv_l, q4);
                 store8(dst + 8 * q4 + 4 * hf, pk, a.nt);
             }
         }
@@ -443,12 +389,6 @@ __global__ void __launch_bounds__(512, 4) k_attention_stream(AttnArgs a) {
         const unsigned so = seq / (unsigned)a.inner;
         return (size_t)so * a.outer_stride + (seq - so * (unsigned)a.inner);
     };
-    // (wave-uniform by construction; the readfirstlanes make it provable for the "s" operands of the asm statements)
-    auto uni_ptr = [](const char *q) __attribute__((always_inline)) {
-        const unsigned long long v = (unsigned long long)q;
-        const unsigned lo32 = __builtin_amdgcn_readfirstlane((unsigned)v), hi32 = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-        return reinterpret_cast<const char *>(((unsigned long long)hi32 << 32) | lo32);
-    };
     // The query tile of a wave's next unit arrives by LDS-DMA as well, in a WAVE-PRIVATE 32-row image (swizzled like K): only this wave
     // reads it, so it is single-buffered and needs no barrier - the wave requests the next tile once its own reads of the current one have
     // returned.  (Asm loads into registers were tried first: hipcc copied the destination registers of the in-flight loads at the loop's
@@ -463,12 +403,14 @@ __global__ void __launch_bounds__(512, 4) k_attention_stream(AttnArgs a) {
         cst_qt[k] = 2u * ((LONG ? 0 : wave * HDP) + chunk * 8);
         if (!XL && !PACK) cst_qt[k] += pos_bytes * (unsigned)min((LONG ? 32 * wave : 0) + R, S - 1);
     }
+    auto row_base = [&](size_t tok0, int head0) __attribute__((always_inline)) {  // q of (token tok0, head head0); k, v: + cst_kv
+        return uni_ptr(reinterpret_cast<const char *>(a.qkv) + (planes ? 2 * (((size_t)head0 * a.npad + tok0) * HDP) : 2 * (tok0 * rs + (size_t)head0 * HDP)));
+    };
     // K | V rows of key chunk c of unit u -> image SET
     // (a unit's first token, head and query group are computed ONCE - when its requests are issued, one unit ahead - and carried)
     auto request_kv = [&](size_t unit_tok, int head0, int c, int SET) __attribute__((always_inline)) {
         const size_t tok0 = unit_tok + (size_t)(256 * c) * a.pos_stride;
-        const char *base = uni_ptr(reinterpret_cast<const char *>(a.qkv) +
-                                   (planes ? 2 * (((size_t)head0 * a.npad + tok0) * HDP) : 2 * (tok0 * rs + (size_t)head0 * HDP)));
+        const char *base = row_base(tok0, head0);
         const bool last = c == NC - 1;  // (uniform)
 #pragma unroll
         for (int k = 0; k < IPW; ++k) {
@@ -479,14 +421,13 @@ __global__ void __launch_bounds__(512, 4) k_attention_stream(AttnArgs a) {
             // their probabilities are exactly 0, but 0 x an uninitialised V row could still be NaN)
             const unsigned vk = XL ? cst_kv[k] + pos_bytes * (unsigned)min(row_kv[k], (last ? rows_last : 256) - 1)
                                    : (PACK ? cst_kv[k] + pos_bytes * (unsigned)min(row_kv[k], min(32, a.n_tok - (int)tok0) - 1) : cst_kv[k]);
-            asm volatile("s_mov_b32 m0, %2\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(vk), "s"(base), "s"(dst) : "memory");
+            lds_dma16(vk, base, dst);
         }
     };
     // the wave's query tile of unit u -> its private image
     auto request_q = [&](size_t unit_tok, int head0, int qg) __attribute__((always_inline)) {
         const size_t tok0 = unit_tok + (size_t)(256 * qg) * a.pos_stride;
-        const char *base = uni_ptr(reinterpret_cast<const char *>(a.qkv) +
-                                   (planes ? 2 * (((size_t)head0 * a.npad + tok0) * HDP) : 2 * (tok0 * rs + (size_t)head0 * HDP)));
+        const char *base = row_base(tok0, head0);
         const bool last = qg == QG - 1;  // (uniform)
 #pragma unroll
         for (int k = 0; k < QPW; ++k) {
@@ -494,8 +435,7 @@ __global__ void __launch_bounds__(512, 4) k_attention_stream(AttnArgs a) {
             const int R = RPI * k + lane / CPR, lim = (LONG ? (last ? qrows_last : 256) : S) - 1;
             const unsigned vq = XL ? cst_qt[k] + pos_bytes * (unsigned)max(min(32 * wave + R, lim), 0)
                                    : (PACK ? cst_qt[k] + pos_bytes * (unsigned)min(R, min(32, a.n_tok - (int)tok0) - 1) : cst_qt[k]);
-            if (QIMG >= 1024 || lane < QIMG / 16)
-                asm volatile("s_mov_b32 m0, %2\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(vq), "s"(base), "s"(dst) : "memory");
+            if (QIMG >= 1024 || lane < QIMG / 16) lds_dma16(vq, base, dst);
         }
     };
     // ones_col: the V rows a wave requested itself (waves 4 - 7: rows 64 (w - 4) .. + 63 of the image), patched once they have landed and
@@ -507,8 +447,7 @@ __global__ void __launch_bounds__(512, 4) k_attention_stream(AttnArgs a) {
         }
     };
 
-    const int gi = lane & 15, gq = gi >> 2, gp = gi & 3, grp = lane >> 4;
-    const int v_off = (4 * (grp >> 1) + gq) * ROWB + ((HDP == 32 ? (grp & 1) * 16 : 0) + 4 * gp) * 2;
+    const int v_off = v_frag_off<HDP>(lane);
     const int krow0 = LONG ? 0 : 32 * wave;  // first image row of this wave's keys
     const bool ragged = ((LONG ? rows_last : S) & 31) != 0;  // (uniform) the last key tile of the last chunk is partial
     const int last_rows = (LONG ? rows_last : S) - 32 * (nkt_last - 1);
@@ -582,16 +521,7 @@ __global__ void __launch_bounds__(512, 4) k_attention_stream(AttnArgs a) {
             }
             // softmax bound of this wave's queries (see above): decided once per unit, behind the barrier and the next stage's requests
             if (c == 0 && has_tile && a.kmax2 && !all_shifted) {
-                float qq = 0.0f;
-#pragma unroll
-                for (int s2 = 0; s2 < KS; ++s2) {
-                    const u32x4 w = __builtin_bit_cast(u32x4, qf[s2]);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const float lo = __uint_as_float(w[k] << 16), hi = __uint_as_float(w[k] & 0xffff0000u);
-                        qq = fmaf(lo, lo, fmaf(hi, hi, qq));
-                    }
-                }
+                float qq = sq_norm(qf);
                 qq += xhalf(qq);
                 const float m = sqrtf(qq * kmax2) * 1.02f;
                 shifted = __ballot(m > 60.0f) == 0;  // (wave-uniform)
@@ -654,14 +584,8 @@ __global__ void __launch_bounds__(512, 4) k_attention_stream(AttnArgs a) {
                     for (int e = 0; e < 16; ++e) p[e] = __builtin_amdgcn_exp2f(XL && !shifted ? t[e] - sub : t[e]);
 #pragma unroll
                     for (int s2 = 0; s2 < 2; ++s2) {
-                        u32x4 pw = {pack2(p[8 * s2], p[8 * s2 + 1]), pack2(p[8 * s2 + 2], p[8 * s2 + 3]),
-                                    pack2(p[8 * s2 + 4], p[8 * s2 + 5]), pack2(p[8 * s2 + 6], p[8 * s2 + 7])};
-                        const char *vb = Vs + (krow0 + kt * 32 + 16 * s2) * ROWB + v_off;
-                        const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(vb));
-                        const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(vb + 8 * ROWB));
-                        typedef __attribute__((ext_vector_type(8))) short s16x8;
-                        const s16x8 vv = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-                        o = mfma32(__builtin_bit_cast(bf16x8, vv), as_bf16x8(pw), o);
+                        const u32x4 pw = p_frag(p + 8 * s2, p + 8 * s2 + 4);
+                        o = mfma32(v_frag<ROWB>(Vs + (krow0 + kt * 32 + 16 * s2) * ROWB + v_off), as_bf16x8(pw), o);
                         if (!ones_col) lsum = mfma32(as_bf16x8(ones_w), as_bf16x8(pw), lsum);  // every row = sum over this tile's keys, column = query
                     }
                 };
@@ -682,12 +606,7 @@ __global__ void __launch_bounds__(512, 4) k_attention_stream(AttnArgs a) {
                             return as_bf16x8(*reinterpret_cast<const u32x4 *>(Ks + k_swz<HDP>(krow0 + kt * 32 + r, c + hf)));
                         };
                         auto vfrag = [&](int kt, int s2) __attribute__((always_inline)) {
-                            const char *vb = Vs + (krow0 + kt * 32 + 16 * s2) * ROWB + v_off;
-                            const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(vb));
-                            const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(vb + 8 * ROWB));
-                            typedef __attribute__((ext_vector_type(8))) short s16x8;
-                            const s16x8 vv = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-                            return __builtin_bit_cast(bf16x8, vv);
+                            return v_frag<ROWB>(Vs + (krow0 + kt * 32 + 16 * s2) * ROWB + v_off);
                         };
                         auto exp4 = [&](const f32x16 &t, int q, float (&p)[4]) __attribute__((always_inline)) {
 #pragma unroll
@@ -710,7 +629,7 @@ __global__ void __launch_bounds__(512, 4) k_attention_stream(AttnArgs a) {
                             vbc = vfrag(kt, 1);
                             tn = mfma32(k0, qf[0], zero);
                             exp4(ti, 1, pb);
-                            const u32x4 pw0 = {pack2(pa[0], pa[1]), pack2(pa[2], pa[3]), pack2(pb[0], pb[1]), pack2(pb[2], pb[3])};
+                            const u32x4 pw0 = p_frag(pa, pb);
                             __builtin_amdgcn_sched_barrier(0);
                             tn = mfma32(k1, qf[1], tn);
                             exp4(ti, 2, pa);
@@ -720,7 +639,7 @@ __global__ void __launch_bounds__(512, 4) k_attention_stream(AttnArgs a) {
                             __builtin_amdgcn_sched_barrier(0);
                             o = mfma32(va, as_bf16x8(pw0), o);
                             exp4(ti, 3, pb);
-                            pwc = u32x4{pack2(pa[0], pa[1]), pack2(pa[2], pa[3]), pack2(pb[0], pb[1]), pack2(pb[2], pb[3])};
+                            pwc = p_frag(pa, pb);
                             if (last_c && kt + 2 == nkt_last && ragged) {  // (uniform) the chunk's last tile holds clamped rows past the sequence
 #pragma unroll
                                 for (int e = 0; e < 16; ++e)
@@ -764,10 +683,7 @@ __global__ void __launch_bounds__(512, 4) k_attention_stream(AttnArgs a) {
             // O^T -> the query image, rows = queries: lane (query r, half hf) writes channels 8 q4 + 4 hf .. + 3 (8 bytes) into the 16-byte slot of
             // chunk q4; then row-wise, 16 bytes per lane
 #pragma unroll
-            for (int q4 = 0; q4 < HDP / 8; ++q4) {
-                const u32x2 pk = {pack2(o[4 * q4] * inv_l, o[4 * q4 + 1] * inv_l), pack2(o[4 * q4 + 2] * inv_l, o[4 * q4 + 3] * inv_l)};
-                *reinterpret_cast<u32x2 *>(qimg + k_swz<HDP>(r, q4) + 8 * hf) = pk;
-            }
+            for (int q4 = 0; q4 < HDP / 8; ++q4) *reinterpret_cast<u32x2 *>(qimg + k_swz<HDP>(r, q4) + 8 * hf) = o_pack(o, inv_l, q4);
             const char *zb = uni_ptr(reinterpret_cast<const char *>(a.z) + 2 * ((tok0 + (size_t)(256 * qg) * a.pos_stride) * a.zw + (size_t)head0 * HDP));
 #pragma unroll
             for (int k = 0; k < OPW; ++k) {
@@ -803,18 +719,7 @@ __global__ void __launch_bounds__(256) k_attention_tiny(AttnArgs a) {
     const size_t rs = (size_t)3 * a.HHD;
     const u16 *base = a.qkv + tok0 * rs + head * HDP;
     float q[HDP];
-    {
-        const u16 *qrow = base + (size_t)pos * a.pos_stride * rs;
-#pragma unroll
-        for (int c = 0; c < HDP / 8; ++c) {
-            const u32x4 w = *reinterpret_cast<const u32x4 *>(qrow + 8 * c);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                q[8 * c + 2 * k] = __uint_as_float(w[k] << 16);
-                q[8 * c + 2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u);
-            }
-        }
-    }
+    row_unpack<HDP>(base + (size_t)pos * a.pos_stride * rs, q);
     float sc[8];
     float mx = -INFINITY;
 #pragma unroll
@@ -828,8 +733,8 @@ __global__ void __launch_bounds__(256) k_attention_tiny(AttnArgs a) {
                 const u32x4 w = *reinterpret_cast<const u32x4 *>(krow + 8 * c);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    d = fmaf(q[8 * c + 2 * k], __uint_as_float(w[k] << 16), d);
-                    d = fmaf(q[8 * c + 2 * k + 1], __uint_as_float(w[k] & 0xffff0000u), d);
+                    d = fmaf(q[8 * c + 2 * k], bf_lo(w[k]), d);
+                    d = fmaf(q[8 * c + 2 * k + 1], bf_hi(w[k]), d);
                 }
             }
             sc[j] = d;
@@ -852,23 +757,15 @@ __global__ void __launch_bounds__(256) k_attention_tiny(AttnArgs a) {
             const u16 *vrow = base + 2 * a.HHD + (size_t)j * a.pos_stride * rs;
 #pragma unroll
             for (int c = 0; c < HDP / 8; ++c) {
-                const u32x4 w = *reinterpret_cast<const u32x4 *>(vrow + 8 * c);
+                float vf[8];
+                unpack8(*reinterpret_cast<const u32x4 *>(vrow + 8 * c), vf);
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    o[8 * c + 2 * k] = fmaf(sc[j], __uint_as_float(w[k] << 16), o[8 * c + 2 * k]);
-                    o[8 * c + 2 * k + 1] = fmaf(sc[j], __uint_as_float(w[k] & 0xffff0000u), o[8 * c + 2 * k + 1]);
-                }
+                for (int k = 0; k < 8; ++k) o[8 * c + k] = fmaf(sc[j], vf[k], o[8 * c + k]);
             }
         }
     }
     const float inv = 1.0f / sum;
-    u16 *dst = a.z + (tok0 + (size_t)pos * a.pos_stride) * a.zw + head * HDP;
-#pragma unroll
-    for (int c = 0; c < HDP / 8; ++c) {
-        u32x4 w = {pack2(o[8 * c] * inv, o[8 * c + 1] * inv), pack2(o[8 * c + 2] * inv, o[8 * c + 3] * inv),
-                   pack2(o[8 * c + 4] * inv, o[8 * c + 5] * inv), pack2(o[8 * c + 6] * inv, o[8 * c + 7] * inv)};
-        *reinterpret_cast<u32x4 *>(dst + 8 * c) = w;
-    }
+    row_pack<HDP>(a.z + (tok0 + (size_t)pos * a.pos_stride) * a.zw + head * HDP, o, inv);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -919,11 +816,11 @@ __global__ void __launch_bounds__(256) k_attention_linear(AttnArgs a) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const int c = c8 + 2 * k;
-                    const float k0 = __uint_as_float(kw[k] << 16), k1 = __uint_as_float(kw[k] & 0xffff0000u);
+                    const float k0 = bf_lo(kw[k]), k1 = bf_hi(kw[k]);
                     Ke[p][c] = (n < S && c < hd) ? __expf(k0 - kmx[c]) : 0.0f;
                     Ke[p][c + 1] = (n < S && c + 1 < hd) ? __expf(k1 - kmx[c + 1]) : 0.0f;
-                    Vs[p][c] = __uint_as_float(vw[k] << 16);
-                    Vs[p][c + 1] = __uint_as_float(vw[k] & 0xffff0000u);
+                    Vs[p][c] = bf_lo(vw[k]);
+                    Vs[p][c + 1] = bf_hi(vw[k]);
                 }
             }
             __syncthreads();
@@ -945,15 +842,7 @@ __global__ void __launch_bounds__(256) k_attention_linear(AttnArgs a) {
         for (int n = tid; n < S; n += 256) {
             const u16 *row = base + (size_t)n * a.pos_stride * rs;
             float q[HDP], o[HDP];
-#pragma unroll
-            for (int c = 0; c < VPR; ++c) {
-                const u32x4 w = *reinterpret_cast<const u32x4 *>(row + 8 * c);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    q[8 * c + 2 * k] = __uint_as_float(w[k] << 16);
-                    q[8 * c + 2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u);
-                }
-            }
+            row_unpack<HDP>(row, q);
             float m = -INFINITY, sum = 0.0f;
 #pragma unroll
             for (int c = 0; c < HDP; ++c)
@@ -971,12 +860,7 @@ __global__ void __launch_bounds__(256) k_attention_linear(AttnArgs a) {
             }
             const float sc = qscale / sum;
             u16 *dst = a.z + (tok0 + (size_t)n * a.pos_stride) * a.zw + head * HDP;
-#pragma unroll
-            for (int c = 0; c < VPR; ++c) {
-                const u32x4 w = {pack2(o[8 * c] * sc, o[8 * c + 1] * sc), pack2(o[8 * c + 2] * sc, o[8 * c + 3] * sc),
-                                 pack2(o[8 * c + 4] * sc, o[8 * c + 5] * sc), pack2(o[8 * c + 6] * sc, o[8 * c + 7] * sc)};
-                *reinterpret_cast<u32x4 *>(dst + 8 * c) = w;
-            }
+            row_pack<HDP>(dst, o, sc);
         }
         __syncthreads();  // ctx, red and kmx are rewritten by the next unit
     }

@@ -162,17 +162,11 @@ __global__ void __launch_bounds__(512, 2) k_linear2_ws(Lin2Args g) {
     const unsigned half_lanes = C::LPR / 2;
     const unsigned voff_same = lane < half_lanes ? 16u * lane : (unsigned)K + 16u * (lane - half_lanes);
     const unsigned voff_next = lane < half_lanes ? 64u * K + 16u * lane : (unsigned)K + 16u * (lane - half_lanes);
-    // (both addresses are wave-uniform by construction; the readfirstlanes make that provable where a ring-slot counter lives in a VGPR)
-    auto uni_ptr = [](const char *q) __attribute__((always_inline)) {
-        const unsigned long long v = (unsigned long long)q;
-        const unsigned lo32 = __builtin_amdgcn_readfirstlane((unsigned)v), hi32 = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-        return reinterpret_cast<const char *>(((unsigned long long)hi32 << 32) | lo32);
-    };
+    // (both addresses are wave-uniform by construction; uni_ptr and the readfirstlane make that provable where a ring-slot counter lives in a VGPR)
     auto dma_row = [&](const char *src_, unsigned dst_, unsigned voff) __attribute__((always_inline)) {
         const char *src = uni_ptr(src_);
         const unsigned dst = __builtin_amdgcn_readfirstlane(dst_);
-        if (C::LPR == 64 || lane < C::LPR)
-            asm volatile("s_mov_b32 m0, %2\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(src), "s"(dst) : "memory");
+        if (C::LPR == 64 || lane < C::LPR) lds_dma16(voff, src, dst);
     };
     // source row 8 p of chunk (m, j), its per-lane offsets; past the last block-step the requests still go out, clamped: the counted waits
     // rely on 8 per chunk-step
@@ -295,7 +289,7 @@ __global__ void __launch_bounds__(512, 2) k_linear2_ws(Lin2Args g) {
         for (int i = 0; i < 4; ++i) {
             const unsigned n = (unsigned)min((blk0 + b) * 32 + 8 * i + tr, g.N - 1);
             const unsigned voff = n * row_bytes + 4u * f0 + 16u * ch, dst = __builtin_amdgcn_readfirstlane(hbuf_lds + hb_off(b) + i * 1024);
-            asm volatile("s_mov_b32 m0, %2\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(g.h), "s"(dst) : "memory");
+            lds_dma16(voff, g.h, dst);
         }
     };
     // (LNS) statistics of block b's UPDATED row over this wave's 32 features, from the values epi_math has just computed (in registers: read back

@@ -317,12 +317,6 @@ __global__ void __launch_bounds__(RES_NTHR, 2) k_resident(ResArgs A) {
     }
     // LayerNorm (+ optional modulate) of the rows of h: 8 lanes per row (16 values each), 8 rows per wave, every row in ONE pass (64 >= NP).
     // MODE 0: h <- LN_eps(h) in place; MODE 1: a (bf16, swizzled) <- LN(h)(1+scale)+shift; MODE 2: fp32 rows into `dst` (stride RES_HS)
-    auto row8_sum = [&](float v) {  // sum over a group of 8 consecutive lanes: quad xor 1, quad xor 2, row_half_mirror
-        v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-        v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-        v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));
-        return v;
-    };
     auto layer_norm = [&](int mode, float eps, const float *shift, const float *scale, float *dst) {
         const int row = wave * 8 + (lane >> 3), l8 = lane & 7, col = l8 * 16;
         if (wave * 8 >= n_t) return;  // (wave-uniform)
@@ -345,14 +339,14 @@ __global__ void __launch_bounds__(RES_NTHR, 2) k_resident(ResArgs A) {
         float s = 0.0f;
 #pragma unroll
         for (int c4 = 0; c4 < 4; ++c4) s += (v[4 * c4] + v[4 * c4 + 1]) + (v[4 * c4 + 2] + v[4 * c4 + 3]);
-        const float mean = row8_sum(s) * (1.0f / D);
+        const float mean = oct_sum(s) * (1.0f / D);
         float q = 0.0f;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             v[e] -= mean;
             q = fmaf(v[e], v[e], q);
         }
-        const float rstd = rsqrtf(row8_sum(q) * (1.0f / D) + eps);
+        const float rstd = rsqrtf(oct_sum(q) * (1.0f / D) + eps);
         if (mode != 0) {
 #pragma unroll
             for (int c4 = 0; c4 < 4; ++c4) {

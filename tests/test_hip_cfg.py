@@ -238,6 +238,33 @@ def test_forward_argument_checks_on_device(dev):
         net(x, torch.full((2,), 0.3, device=dev), xc, m)
 
 
+def test_forward_refuses_axis_too_long_for_rows_kernel(dev):
+    """LSL_ATTN_STREAM=0 keeps the axes off the stream kernel; k_attention_rows holds K | V of a whole (sequence, head) in LDS, so at 32-wide
+    heads a temporal axis of T = 1300 (key tiles: 1312 rows, 168 000 B > 160 KiB) is refused by the pass plan (ValueError, nothing launched)
+    and T = 1200 (155 712 B) still runs.  In a child process: the library reads the variable once."""
+    import os
+    import subprocess
+    import sys
+    code = (
+        "import torch, pytest, sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+        "from test_hip_cfg import _net\n"
+        "dev = torch.device('cuda:0')\n"
+        "net, _, _ = _net(dict(depth=1, in_dim=8, hidden_size=128, num_heads=4), 2, dev)\n"
+        "def run(T):\n"
+        "    g = torch.Generator().manual_seed(0)\n"
+        "    x, xc = torch.randn(1, T, 1, 8, generator=g).to(dev), torch.randn(1, T, 1, 8, generator=g).to(dev)\n"
+        "    out = net(x, torch.full((1,), 0.3, device=dev), xc, torch.zeros(1, T, 1, dtype=torch.long, device=dev))\n"
+        "    torch.cuda.synchronize()\n"
+        "    return out\n"
+        "assert torch.isfinite(run(1200)).all()\n"
+        "with pytest.raises(ValueError, match='attention axis of 1300 positions'):\n"
+        "    run(1300)\n"
+        "assert torch.isfinite(run(1200)).all()\n"
+    ) % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.path.dirname(os.path.abspath(__file__)))
+    env = dict({k: v for k, v in os.environ.items() if k != "LSL_ATTN_STREAM"}, LSL_ATTN_STREAM="0")
+    subprocess.run([sys.executable, "-c", code], check=True, env=env, timeout=600)
+
+
 RESIDENT_CASES = {
     # name: (T, L, C, vec_in_dim, normalize, depth, method)      all with hidden 128, 4 heads of 32, mlp_ratio 2 (the pedestrian family)
     "ped_like_T20_L2": (20, 2, 32, 256, True, 6, "ODE"),          # temporal attention on MFMA (S = 20), spatial per lane (S = 2)
