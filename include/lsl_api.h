@@ -38,7 +38,8 @@ extern "C" {
  * 5: lsl_model_set_tail, lsl_model_tail, lsl_profile_kernel_name exist; no signature of version 4 changed.
  * 6: lsl_model_set_ln_fuse, lsl_model_ln_fuse exist; no signature of version 5 changed.
  * 6, later: lsl_si_loss, lsl_si_reduce, lsl_si_loss_workspace_bytes added, no signature changed (a binding that needs them finds out by
- *    looking the symbols up: a library without them is stale). */
+ *    looking the symbols up: a library without them is stale).
+ * 6, later still: lsl_geom_loss_sums, lsl_geom_loss_final added the same way. */
 #define LSL_VERSION 6
 
 typedef struct lsl_model lsl_model;
@@ -212,6 +213,20 @@ int lsl_si_loss(lsl_model *m, const lsl_io *io, const float *x1, const float *x0
  * B * ceil(per_trajectory / LSL_SI_SLAB) floats. */
 int lsl_si_reduce(const float *pred, const float *x1, const float *x0, const lsl_si_row *rows, int32_t B, uint64_t per_trajectory,
                   float *loss, void *scratch, size_t scratch_bytes, void *stream);
+
+/* Geometry losses of the decoded positions: what Loss.forward adds behind the SI term when calc_additional_losses is set
+ * (second_stage/md17.py:231-255, nba.py, pedestrian.py alike) - MaskedMSELoss, MaskedNormLoss and InterDistanceLoss of modules/losses.py.
+ * pred, target: device f32 [F, A, D] (F = B*T frames); mask: device u8 [F, A], nonzero = real entity.  Native form: 1 <= D <= 4, A <= 2048
+ * (anything else is refused with -3; the binding's Loss takes its torch path then).  sums: device f32 [F, 5], per frame
+ *      s_mse = sum_a m_a mean_d (p - t)^2,  s_norm = sum_a m_a ||p_a - t_a||,  n = sum_a m_a,
+ *      s_pair = sum_ij m_i m_j (||p_i - p_j|| - ||t_i - t_j||)^2,  n_pair = n^2
+ * with distances taken from coordinate differences; no [A, A] array exists in memory.  Masked-out entities are skipped, where the reference
+ * multiplies by the mask: the results differ only when a masked-out position is not finite.  No atomics, every sum in an order fixed by
+ * (A, D): a frame's five floats have the same bits in any batch or shard.  Nothing is allocated; a refused call enqueues nothing. */
+int lsl_geom_loss_sums(const float *pred, const float *target, const uint8_t *mask, int32_t F, int32_t A, int32_t D, float *sums, void *stream);
+/* out (device f32 [3]) = pos_loss, dist, inter_dist_loss = sum s_mse / sum n, sum s_norm / sum n, sum s_pair / sum n_pair over the F rows of sums
+ * in index order, in fp64, each rounded once (rows of several shards may be concatenated first); no real entity at all: NaN, as the reference. */
+int lsl_geom_loss_final(const float *sums, int32_t F, float *out, void *stream);
 
 /* Sampler loop (Sampler.sample_ode / sample_sde inner loops): applies n_steps affine updates to io->x
  * in place.  noise: device [n_noise, B*T*L*C] standard-normal draws, slice s belongs to step s (the

@@ -10,6 +10,9 @@ Public surface (mirrors the reference's for this path only):
   Stage1Encoder                    <- quant(Encoder(prepare_inputs(batch), entities, mask)) (frozen, before the sampler)
   best_of_k_errors, min_ade_fde    <- the K-sample test loops + _compute_errors (second_stage/pedestrian.py:178-212)
   RolloutSampler, sample_rollout   <- SIAtom14SamplingWrapper.{create_batch, sample_rollout} (modules/sampling.py:16-63)
+  Loss, geom_losses, geom_loss_sums
+                                   <- second_stage/{md17,nba,pedestrian}.Loss with calc_additional_losses: MaskedMSELoss, MaskedNormLoss
+                                      and InterDistanceLoss of the decoded positions on the device (losses.py)
   install()                        <- rebinds the reference's module-level ``Sampler`` (lightning_base.py:10); see dropin.py
 The compute lives in liblamslide_hip.so (include/lsl_api.h); build it with ``__graft_entry__.build()``.
 """
@@ -18,6 +21,7 @@ from .dropin import install, uninstall
 from .decoder import Stage1Decoder
 from .encoder import Stage1Encoder
 from .latent_si import LatentSIV3
+from .losses import Loss, geom_loss_sums, geom_losses
 from .sampling import (RolloutSampler, SecondStageSampler, best_of_k_errors, min_ade_fde, sample_rollout, sample_sharded,
                        setup_conditioning, shard_bounds)
 from .transport import (CreateTransport, ModelType, PathType, Sampler, SampleResult, Transport, WeightType, as_transport, device_randn,
@@ -25,4 +29,4 @@ from .transport import (CreateTransport, ModelType, PathType, Sampler, SampleRes
 
 __all__ = ["LatentSIV3", "CreateTransport", "Transport", "Sampler", "SampleResult", "ModelType", "PathType", "WeightType",
            "SecondStageSampler", "setup_conditioning", "sample_sharded", "shard_bounds", "min_ade_fde", "sample_rollout", "best_of_k_errors",
-           "RolloutSampler", "Stage1Decoder", "Stage1Encoder", "as_transport", "device_randn", "mix_seed", "si_reduce", "install", "uninstall", "dropin", "_lib"]
+           "RolloutSampler", "Stage1Decoder", "Stage1Encoder", "as_transport", "device_randn", "mix_seed", "si_reduce", "Loss", "geom_losses", "geom_loss_sums", "install", "uninstall", "dropin", "_lib"]

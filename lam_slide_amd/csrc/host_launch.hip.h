@@ -567,3 +567,18 @@ void launch_dense_small(float *out, const float *in, const float *W, const float
         launch_dense<PRE, POST>(out, in, W, bias, add, rows, I, O, add_stride, st, false, add_mod);
 }
 
+// the five sums of every frame (k_geomloss.hip.h): a wave per frame up to 64 entities, the whole workgroup above
+template <int D, int TEAM>
+void launch_geom_frame(float *sums, const float *pred, const float *target, const unsigned char *mask, int F, int A, hipStream_t st) {
+    constexpr int FPB = 256 / TEAM;
+    auto kern = k_geom_loss_frame<D, TEAM>;
+    if (TEAM == 256) LSL_ALLOW_LDS(kern, geom_team_bytes(LSL_GEOM_MAX_A, D));  // (above 64 KiB at D = 4)
+    hipLaunchKernelGGL(kern, dim3((unsigned)(((long long)F + FPB - 1) / FPB)), dim3(256), FPB * geom_team_bytes(A, D), st, sums, pred, target, mask, F, A);
+}
+template <int D>
+void launch_geom_frame_d(float *sums, const float *pred, const float *target, const unsigned char *mask, int F, int A, hipStream_t st) {
+    if (A <= 64)
+        launch_geom_frame<D, 64>(sums, pred, target, mask, F, A, st);
+    else
+        launch_geom_frame<D, 256>(sums, pred, target, mask, F, A, st);
+}

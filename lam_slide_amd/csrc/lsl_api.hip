@@ -2,7 +2,7 @@
 // network evaluation (latent_si_v31.py:168-188) and of the sampler loops (integrators.py:67-78,103-120)
 // on the caller's stream.  No allocation, no synchronisation, no host<->device copies.
 // One translation unit: this file = the entry points of the sampling path (model handle, forward, fused sampler + opt-in hipGraph replay,
-// noise, Runge-Kutta state arithmetic, the stochastic-interpolant objective around one evaluation, debug taps); host_common / host_launch / host_eval.hip.h = what they enqueue (host_graph.hip.h: the replay cache); decode_host.hip.h +
+// noise, Runge-Kutta state arithmetic, the stochastic-interpolant objective around one evaluation, the geometry losses of the decoded positions, debug taps); host_common / host_launch / host_eval.hip.h = what they enqueue (host_graph.hip.h: the replay cache); decode_host.hip.h +
 // stage1_api.hip.h = the frozen stage-1 encode / decode beside the path.
 #include "../../include/lsl_api.h"
 
@@ -28,6 +28,7 @@
 #include "k_small.hip.h"
 #include "k_resident.hip.h"
 #include "k_siloss.hip.h"
+#include "k_geomloss.hip.h"
 #ifdef LSL_EXPERIMENTS  // measured-and-rejected GEMM structures, built only by tools/build_experiments.sh (never in the product library)
 #include "k_gemm_pp.hip.h"        // tools/experiments/ (on the include path of tools/build_experiments.sh only)
 #include "k_gemm_drain.hip.h"
@@ -281,6 +282,33 @@ int lsl_si_loss(lsl_model *m, const lsl_io *io, const float *x1, const float *x0
     if (int rc = forward_passes(m, io, ws, plans, chunk, st)) return rc;
     float *partial = (float *)((char *)workspace + align_up(lsl_workspace_bytes(m, io->B, io->T, io->L), 256));
     return si_reduce_enqueue(io->out, x1, x0, rows, io->B, per, loss, partial, st);
+} LSL_API_CATCH
+
+// ---- geometry losses of the decoded positions (k_geomloss.hip.h) ----
+int lsl_geom_loss_sums(const float *pred, const float *target, const uint8_t *mask, int32_t F, int32_t A, int32_t D, float *sums, void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!pred || !target || !mask || !sums) return fail(-1, "null argument");
+    if (F <= 0) return fail(-3, "F must be positive");
+    if (A < 1 || A > LSL_GEOM_MAX_A) return fail(-3, "A = %d outside the native form (1..%d entities)", A, LSL_GEOM_MAX_A);
+    if (D < 1 || D > LSL_GEOM_MAX_D) return fail(-3, "D = %d outside the native form (1..%d coordinates)", D, LSL_GEOM_MAX_D);
+    hipStream_t st = (hipStream_t)stream;
+    switch (D) {
+        case 1: launch_geom_frame_d<1>(sums, pred, target, mask, F, A, st); break;
+        case 2: launch_geom_frame_d<2>(sums, pred, target, mask, F, A, st); break;
+        case 3: launch_geom_frame_d<3>(sums, pred, target, mask, F, A, st); break;
+        default: launch_geom_frame_d<4>(sums, pred, target, mask, F, A, st); break;
+    }
+    LSL_CHECK_LAUNCH("lsl_geom_loss_sums");
+    return 0;
+} LSL_API_CATCH
+
+int lsl_geom_loss_final(const float *sums, int32_t F, float *out, void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!sums || !out) return fail(-1, "null argument");
+    if (F <= 0) return fail(-3, "F must be positive");
+    hipLaunchKernelGGL(k_geom_loss_final, dim3(1), dim3(64), 0, (hipStream_t)stream, out, sums, (int)F);
+    LSL_CHECK_LAUNCH("lsl_geom_loss_final");
+    return 0;
 } LSL_API_CATCH
 
 static int sample_enqueue(lsl_model *m, const lsl_io *io, const lsl_step_ex *steps, int32_t n_steps, const float *noise, uint64_t seed,

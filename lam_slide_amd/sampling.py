@@ -137,6 +137,24 @@ class SecondStageSampler:
         return self.si.training_losses(self.forward, latents, mk, t=t, x0=x0)
 
     @torch.no_grad()
+    def validation_losses(self, latents: Tensor, pos: Tensor, attention_mask: Tensor, decode: Callable[[Tensor], Tensor],
+                          y: Optional[Tensor] = None, *, t: Optional[Tensor] = None, x0: Optional[Tensor] = None, first_index: int = 0,
+                          weight_si_loss: float = 1.0, weight_pos_loss: float = 0.0, weight_inter_dist_loss: float = 0.0) -> Dict[str, Tensor]:
+        """All of ``model_step`` with ``calc_additional_losses`` (Loss.forward, second_stage/md17.py:220-257) on the device:
+        :meth:`model_step` (one ``lsl_si_loss``), ``decode(pred [B,T,L,C]) -> positions [B,T,A,D]`` (or [B*T,A,D]; e.g. a
+        ``Stage1Decoder``), then ``geom_losses`` against ``pos`` [B,T,A,D] / ``attention_mask`` [B,T,A].  Returns the reference's dict
+        {"si_loss", "pos_loss", "inter_dist_loss", "dist", "loss"} of 0-dim tensors.  ``lam_slide_amd.Loss`` is the authority on
+        ``loss``: the three weight keywords are its constructor's with its defaults and are combined in its order, so that the five
+        numbers equal what a ``Loss`` object returns on the same draws bit for bit (tests/test_hip_geom_losses.py); with the defaults
+        ``loss`` is ``si_loss``.  Draws and ``first_index`` as in :meth:`model_step`."""
+        from .losses import geom_losses
+        step = self.model_step(latents, y, t=t, x0=x0, first_index=first_index)
+        si_loss = step["loss"].mean()
+        geo = geom_losses(decode(step["pred"]).reshape(pos.shape), pos, attention_mask)
+        loss = si_loss * weight_si_loss + weight_pos_loss * geo["pos_loss"] + weight_inter_dist_loss * geo["inter_dist_loss"]
+        return {"si_loss": si_loss, "pos_loss": geo["pos_loss"], "inter_dist_loss": geo["inter_dist_loss"], "dist": geo["dist"], "loss": loss}
+
+    @torch.no_grad()
     def sample_latents_k(self, latents: Tensor, K: int, y: Optional[Tensor] = None, inits: Optional[Tensor] = None) -> Tensor:
         """K samples per conditioning in ONE fused call.  The reference's test loops re-encode the identical batch and call
         ``sample`` K times in sequence (second_stage/pedestrian.py:193-204, nba.py:205-217, md17.py:157-166); trajectories are

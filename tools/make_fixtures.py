@@ -23,6 +23,8 @@ Fixture families:
                     what Transport.sample draws under torch.manual_seed(1234)
   f16_model_step.npz  the reference's REAL md17 Wrapper.model_step (prepare_batch, Loss.forward with calc_additional_losses, decode, the three
                     masked losses) in the F9 environment, draws fixed; F9's weights
+  f17_geom_losses.npz  the reference's MaskedMSELoss / MaskedNormLoss / InterDistanceLoss (modules/losses.py) on seeded positions and masks, in fp32
+                    and in fp64: what Loss.forward adds when calc_additional_losses is set
   f9_sample.npz     the reference's REAL LightningModule (second_stage/md17.py Wrapper built by its own __init__ from the reference YAML,
                     lightning_base.py sample / prepare_batch / setup_conditioning unchanged; tools/ref_env.py supplies the Lightning / Hydra
                     stand-ins): stage-1 inputs -> encode -> conditioning -> 5 Euler updates -> decode, with the initial noise fixed
@@ -630,6 +632,54 @@ def f16():
         **({"stage1_tables": extra} if extra else {}))
 
 
+# ------------------------------------------------------------------------------------------- F17
+F17_CASES = (
+    # name, F, A, D, share of masked-out entities, pred = target + 0.05 noise
+    ("f6_a5_d3", 6, 5, 3, 0.0, False),
+    ("f60_a13_d3", 60, 13, 3, 0.0, False),
+    ("f400_a11_d2_m20", 400, 11, 2, 0.2, False),
+    ("f40_a25_d2_m40", 40, 25, 2, 0.4, False),
+    ("f12_a57_d2_m30", 12, 57, 2, 0.3, False),
+    ("f3_a300_d3_m10", 3, 300, 3, 0.1, False),
+    ("close_f60_a13_d3", 60, 13, 3, 0.0, True),
+    ("close_f12_a57_d2_m30", 12, 57, 2, 0.3, True),
+    ("all_masked_f4_a7_d3", 4, 7, 3, 1.0, False),
+)
+
+
+def f17():
+    """The three default loss modules of Loss.forward (second_stage/md17.py:242-249) - the reference's own classes of modules/losses.py, called
+    on the layouts Loss.forward hands them - in fp32 and in fp64 on seeded positions.  Every partially masked case has frame 0 fully masked;
+    one case has no real entity at all (0 / 0 = NaN).  Above 25 entities torch.cdist takes its matmul form in fp32 (cancellation): those
+    cases are to be compared with the fp64 values only."""
+    from src.modules.losses import InterDistanceLoss, MaskedMSELoss, MaskedNormLoss
+    arrays, worst = {}, 0.0
+    for k, (name, F, A, D, share, close) in enumerate(F17_CASES):
+        g = torch.Generator().manual_seed(170 + k)
+        target = torch.randn(F, A, D, generator=g)
+        noise = torch.randn(F, A, D, generator=g)
+        pred = target + 0.05 * noise if close else noise
+        mask = torch.rand(F, A, generator=g) >= share
+        if 0.0 < share < 1.0:
+            mask[0] = False
+        out = {}
+        for tag, dt in (("ref32", torch.float32), ("ref64", torch.float64)):
+            p, t = pred.to(dt), target.to(dt)
+            out[tag] = torch.stack([MaskedMSELoss()(p.reshape(-1, D), t.reshape(-1, D), mask.reshape(-1)),
+                                    MaskedNormLoss()(p.reshape(-1, D), t.reshape(-1, D), mask.reshape(-1)),
+                                    InterDistanceLoss()(p, t, mask)])
+        if share < 1.0:
+            dev = float(((out["ref32"].double() - out["ref64"]).abs() / out["ref64"].abs()).max())
+            worst = max(worst, dev)
+            print(f"F17 {name}: pos_loss dist inter_dist_loss = {[round(float(v), 6) for v in out['ref64']]}; fp32 classes vs fp64 {dev:.2e}")
+        else:
+            assert bool(torch.isnan(out["ref32"]).all()) and bool(torch.isnan(out["ref64"]).all())
+            print(f"F17 {name}: NaN x 3 in both precisions")
+        arrays[name] = {"pred": pred, "target": target, "mask": mask, "ref32": out["ref32"], "ref64": out["ref64"]}
+    print(f"F17: worst deviation of the reference's fp32 classes from their fp64 run {worst:.2e}")
+    npz("f17_geom_losses.npz", names=np.array([c[0] for c in F17_CASES]), **arrays)
+
+
 # ------------------------------------------------------------------------------------------- F10
 F10_CASES = {
     # attention_mode="linear" (mmdit.py:50-53, 58-72; no shipped config selects it).  name: (NetShape kwargs, B, T, L, weight seed)
@@ -846,6 +896,6 @@ def f13():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["f1", "f2", "f3", "f4", "f5", "f6", "f7", "f8", "f9", "f10", "f11", "f12", "f13", "f15", "f16"]
+    which = sys.argv[1:] or ["f1", "f2", "f3", "f4", "f5", "f6", "f7", "f8", "f9", "f10", "f11", "f12", "f13", "f15", "f16", "f17"]
     for w in which:
         globals()[w]()
