@@ -39,7 +39,8 @@ extern "C" {
  * 6: lsl_model_set_ln_fuse, lsl_model_ln_fuse exist; no signature of version 5 changed.
  * 6, later: lsl_si_loss, lsl_si_reduce, lsl_si_loss_workspace_bytes added, no signature changed (a binding that needs them finds out by
  *    looking the symbols up: a library without them is stale).
- * 6, later still: lsl_geom_loss_sums, lsl_geom_loss_final added the same way. */
+ * 6, later still: lsl_geom_loss_sums, lsl_geom_loss_final added the same way.
+ * 6, later still: lsl_peptide_loss_sums, lsl_peptide_loss_final added the same way. */
 #define LSL_VERSION 6
 
 typedef struct lsl_model lsl_model;
@@ -227,6 +228,34 @@ int lsl_geom_loss_sums(const float *pred, const float *target, const uint8_t *ma
 /* out (device f32 [3]) = pos_loss, dist, inter_dist_loss = sum s_mse / sum n, sum s_norm / sum n, sum s_pair / sum n_pair over the F rows of sums
  * in index order, in fp64, each rounded once (rows of several shards may be concatenated first); no real entity at all: NaN, as the reference. */
 int lsl_geom_loss_final(const float *sums, int32_t F, float *out, void *stream);
+
+/* Frame-local and torsion losses of the decoded peptide positions: the two terms of the peptide Loss.forward (second_stage/peptide.py:293-378)
+ * that lsl_geom_loss_sums with entities = (residue, atom), A = R*14, D = 3 does not compute.  F = B*T frames of R residues, all device, row-major:
+ *   pred, target_frame  f32 [F, R, 14, 3]   decoded atom14 positions; the dataset's positions in each residue's backbone frame
+ *   atom14_mask         u8  [F, R, 14]      nonzero = real atom
+ *   tors_target         f32 [F, R, 7, 2]    (sin, cos) of pre-omega, phi, psi, chi1..4;   tors_mask u8 [F, R, 7], nonzero = counted
+ *   aatype              i64 [F, R]          residue types 0..20 (20 = unknown), as the batch holds them
+ *   restab              i8  [21, 20]        per residue type the atom14 index of atom37 slots 0, 1, 2, 4, then of the 4 x 4 chi atoms;
+ *                                           -1 = a slot the atom37 mask of the type zeroes (its position is 0).  Entries are in -1..13.
+ * sums: device f32 [F, 4], per frame
+ *      s_frame = sum_ra m_ra mean_d (local(pred)_rad - target_frame_rad)^2,   n = sum_ra m_ra,   s_tors = sum_rk w_rk l_rk,   n_tors = sum_rk w_rk
+ * local(p) = p in the residue's backbone frame: Gram-Schmidt on (C, CA, N) = atom14 slots 2, 1, 0 with eps 1e-8, x and z flipped, origin CA
+ * (modules/geometry.py:212-227, utils/rigid_utils.py:1093-1134).  Torsion k takes four atom37 positions of the residue and the one before it
+ * (zeros in front of residue 0), the frame of the first three and (sin, cos) = (z, y) / sqrt(z^2 + y^2 + 1e-8) of the fourth, negated for psi
+ * (peptide.py:170-286).  kind 0: l = 1 - cosine_similarity(pred, target) (MaskedCosineLoss; each vector over max(norm, 1e-8));
+ * kind 1: l = 1 - pred . target (MaskedCosineLossV2).  fp32 throughout.
+ * Masked-out atoms and torsions are skipped, where the reference multiplies by the mask: the results differ only when a masked-out value is
+ * not finite.  An aatype outside 0..20 makes the four sums of its frame NaN (nothing is clamped, no table row is read with it).
+ * Native form: 1 <= R <= 146 (R*14 <= 2048, the entities of lsl_geom_loss_sums); anything else is refused with -3, as is kind outside {0, 1}
+ * (the binding's PeptideLoss takes its torch path then).  No atomics, every sum in an order fixed by R: a frame's four floats have the
+ * same bits in any batch, shard or position.  Nothing is allocated; a refused call enqueues nothing. */
+int lsl_peptide_loss_sums(const float *pred, const float *target_frame, const uint8_t *atom14_mask, const float *tors_target, const uint8_t *tors_mask,
+                          const int64_t *aatype, const int8_t *restab, int32_t F, int32_t R, int32_t kind, float *sums, void *stream);
+/* out (device f32 [5]) = pos_loss, pos_frame_loss, inter_distance_loss, norm_loss, torsion_loss
+ *   = sum s_mse / sum n, sum s_frame / sum n, sum s_pair / sum n_pair, sum s_norm / sum n, sum s_tors / sum n_tors
+ * over the F rows of geom_sums [F, 5] (lsl_geom_loss_sums with A = R*14, D = 3, mask = atom14_mask) and pept_sums [F, 4], in index order, in
+ * fp64, each rounded once (rows of several shards may be concatenated first); 0 / 0 is NaN, as the reference. */
+int lsl_peptide_loss_final(const float *geom_sums, const float *pept_sums, int32_t F, float *out, void *stream);
 
 /* Sampler loop (Sampler.sample_ode / sample_sde inner loops): applies n_steps affine updates to io->x
  * in place.  noise: device [n_noise, B*T*L*C] standard-normal draws, slice s belongs to step s (the

@@ -13,6 +13,9 @@ Public surface (mirrors the reference's for this path only):
   Loss, geom_losses, geom_loss_sums
                                    <- second_stage/{md17,nba,pedestrian}.Loss with calc_additional_losses: MaskedMSELoss, MaskedNormLoss
                                       and InterDistanceLoss of the decoded positions on the device (losses.py)
+  PeptideLoss, peptide_losses, peptide_loss_sums
+                                   <- second_stage/peptide.Loss with calc_additional_losses: those three of the atom14 positions plus
+                                      the frame-local position loss and the torsion loss on the device (peptide_loss.py)
   install()                        <- rebinds the reference's module-level ``Sampler`` (lightning_base.py:10); see dropin.py
 The compute lives in liblamslide_hip.so (include/lsl_api.h); build it with ``__graft_entry__.build()``.
 """
@@ -22,6 +25,7 @@ from .decoder import Stage1Decoder
 from .encoder import Stage1Encoder
 from .latent_si import LatentSIV3
 from .losses import Loss, geom_loss_sums, geom_losses
+from .peptide_loss import PeptideLoss, peptide_loss_sums, peptide_losses
 from .sampling import (RolloutSampler, SecondStageSampler, best_of_k_errors, min_ade_fde, sample_rollout, sample_sharded,
                        setup_conditioning, shard_bounds)
 from .transport import (CreateTransport, ModelType, PathType, Sampler, SampleResult, Transport, WeightType, as_transport, device_randn,
@@ -29,4 +33,4 @@ from .transport import (CreateTransport, ModelType, PathType, Sampler, SampleRes
 
 __all__ = ["LatentSIV3", "CreateTransport", "Transport", "Sampler", "SampleResult", "ModelType", "PathType", "WeightType",
            "SecondStageSampler", "setup_conditioning", "sample_sharded", "shard_bounds", "min_ade_fde", "sample_rollout", "best_of_k_errors",
-           "RolloutSampler", "Stage1Decoder", "Stage1Encoder", "as_transport", "device_randn", "mix_seed", "si_reduce", "Loss", "geom_losses", "geom_loss_sums", "install", "uninstall", "dropin", "_lib"]
+           "RolloutSampler", "Stage1Decoder", "Stage1Encoder", "as_transport", "device_randn", "mix_seed", "si_reduce", "Loss", "geom_losses", "geom_loss_sums", "PeptideLoss", "peptide_losses", "peptide_loss_sums", "install", "uninstall", "dropin", "_lib"]

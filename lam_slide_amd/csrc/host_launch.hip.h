@@ -582,3 +582,12 @@ void launch_geom_frame_d(float *sums, const float *pred, const float *target, co
     else
         launch_geom_frame<D, 256>(sums, pred, target, mask, F, A, st);
 }
+
+// the four sums of every peptide frame (k_peptloss.hip.h): a wave per frame up to 64 atoms (R <= 4), the whole workgroup above
+template <int TEAM>
+void launch_peptide_frame(float *sums, const float *pred, const float *target_frame, const unsigned char *atom14_mask, const float *tors_target,
+                          const unsigned char *tors_mask, const long long *aatype, const signed char *restab, int F, int R, int kind, hipStream_t st) {
+    constexpr int FPB = 256 / TEAM;  // (at most 4 * pept_team_bytes(4) or pept_team_bytes(146) = 24.7 KB of LDS: below the 64 KiB default)
+    hipLaunchKernelGGL(k_peptide_loss_frame<TEAM>, dim3((unsigned)(((long long)F + FPB - 1) / FPB)), dim3(256), FPB * pept_team_bytes(R), st, sums, pred,
+                       target_frame, atom14_mask, tors_target, tors_mask, aatype, restab, F, R, kind);
+}

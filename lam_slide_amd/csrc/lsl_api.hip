@@ -2,7 +2,7 @@
 // network evaluation (latent_si_v31.py:168-188) and of the sampler loops (integrators.py:67-78,103-120)
 // on the caller's stream.  No allocation, no synchronisation, no host<->device copies.
 // One translation unit: this file = the entry points of the sampling path (model handle, forward, fused sampler + opt-in hipGraph replay,
-// noise, Runge-Kutta state arithmetic, the stochastic-interpolant objective around one evaluation, the geometry losses of the decoded positions, debug taps); host_common / host_launch / host_eval.hip.h = what they enqueue (host_graph.hip.h: the replay cache); decode_host.hip.h +
+// noise, Runge-Kutta state arithmetic, the stochastic-interpolant objective around one evaluation, the geometry losses of the decoded positions, the peptide frame and torsion losses, debug taps); host_common / host_launch / host_eval.hip.h = what they enqueue (host_graph.hip.h: the replay cache); decode_host.hip.h +
 // stage1_api.hip.h = the frozen stage-1 encode / decode beside the path.
 #include "../../include/lsl_api.h"
 
@@ -29,6 +29,7 @@
 #include "k_resident.hip.h"
 #include "k_siloss.hip.h"
 #include "k_geomloss.hip.h"
+#include "k_peptloss.hip.h"
 #ifdef LSL_EXPERIMENTS  // measured-and-rejected GEMM structures, built only by tools/build_experiments.sh (never in the product library)
 #include "k_gemm_pp.hip.h"        // tools/experiments/ (on the include path of tools/build_experiments.sh only)
 #include "k_gemm_drain.hip.h"
@@ -308,6 +309,32 @@ int lsl_geom_loss_final(const float *sums, int32_t F, float *out, void *stream) 
     if (F <= 0) return fail(-3, "F must be positive");
     hipLaunchKernelGGL(k_geom_loss_final, dim3(1), dim3(64), 0, (hipStream_t)stream, out, sums, (int)F);
     LSL_CHECK_LAUNCH("lsl_geom_loss_final");
+    return 0;
+} LSL_API_CATCH
+
+// ---- frame-local and torsion losses of the decoded peptide positions (k_peptloss.hip.h) ----
+int lsl_peptide_loss_sums(const float *pred, const float *target_frame, const uint8_t *atom14_mask, const float *tors_target, const uint8_t *tors_mask,
+                          const int64_t *aatype, const int8_t *restab, int32_t F, int32_t R, int32_t kind, float *sums, void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!pred || !target_frame || !atom14_mask || !tors_target || !tors_mask || !aatype || !restab || !sums) return fail(-1, "null argument");
+    if (F <= 0) return fail(-3, "F must be positive");
+    if (R < 1 || R > LSL_PEPT_MAX_R) return fail(-3, "R = %d outside the native form (1..%d residues)", R, LSL_PEPT_MAX_R);
+    if (kind != 0 && kind != 1) return fail(-3, "kind = %d: 0 (MaskedCosineLoss) or 1 (MaskedCosineLossV2)", kind);
+    hipStream_t st = (hipStream_t)stream;
+    if (R * 14 <= 64)
+        launch_peptide_frame<64>(sums, pred, target_frame, atom14_mask, tors_target, tors_mask, (const long long *)aatype, (const signed char *)restab, F, R, kind, st);
+    else
+        launch_peptide_frame<256>(sums, pred, target_frame, atom14_mask, tors_target, tors_mask, (const long long *)aatype, (const signed char *)restab, F, R, kind, st);
+    LSL_CHECK_LAUNCH("lsl_peptide_loss_sums");
+    return 0;
+} LSL_API_CATCH
+
+int lsl_peptide_loss_final(const float *geom_sums, const float *pept_sums, int32_t F, float *out, void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!geom_sums || !pept_sums || !out) return fail(-1, "null argument");
+    if (F <= 0) return fail(-3, "F must be positive");
+    hipLaunchKernelGGL(k_peptide_loss_final, dim3(1), dim3(64), 0, (hipStream_t)stream, out, geom_sums, pept_sums, (int)F);
+    LSL_CHECK_LAUNCH("lsl_peptide_loss_final");
     return 0;
 } LSL_API_CATCH
 

@@ -7,7 +7,7 @@
   Loss                          <- the three ``Loss`` classes, as a ``_target_`` drop-in: the device form when it applies, otherwise the
                                    given loss modules (or torch restatements of the three defaults) exactly as the reference calls them
 
-The peptide ``Loss`` (torsion and atom37 terms, second_stage/peptide.py) is not covered: it stays the reference's.
+The peptide ``Loss`` (frame-local, torsion and atom37 terms, second_stage/peptide.py) is ``PeptideLoss`` of peptide_loss.py.
 """
 from __future__ import annotations
 

@@ -94,7 +94,7 @@ def parse(dis: str):
         if cur is None or not line.startswith("\t"):
             continue
         body = line.split("//")[0].strip()
-        if not body:
+        if not body or body == "...":  # ("...": objdump's mark for the zero fill between two symbols, no instruction)
             continue
         parts = body.split(None, 1)
         ops = [o.strip() for o in parts[1].split(",")] if len(parts) > 1 else []

@@ -25,12 +25,16 @@ Fixture families:
                     masked losses) in the F9 environment, draws fixed; F9's weights
   f17_geom_losses.npz  the reference's MaskedMSELoss / MaskedNormLoss / InterDistanceLoss (modules/losses.py) on seeded positions and masks, in fp32
                     and in fp64: what Loss.forward adds when calc_additional_losses is set
+  f18_peptide_loss.npz  the reference's peptide Loss (second_stage/peptide.py): its residue tables as arrays, its five additional losses on seeded
+                    decoded positions in fp32 and fp64 with per-element torsions and frame-local positions, and its REAL peptide
+                    Wrapper.model_step at T = 8
   f9_sample.npz     the reference's REAL LightningModule (second_stage/md17.py Wrapper built by its own __init__ from the reference YAML,
                     lightning_base.py sample / prepare_batch / setup_conditioning unchanged; tools/ref_env.py supplies the Lightning / Hydra
                     stand-ins): stage-1 inputs -> encode -> conditioning -> 5 Euler updates -> decode, with the initial noise fixed
 """
 import ast
 import glob
+import importlib
 import os
 import sys
 import tempfile
@@ -678,6 +682,187 @@ def f17():
         arrays[name] = {"pred": pred, "target": target, "mask": mask, "ref32": out["ref32"], "ref64": out["ref64"]}
     print(f"F17: worst deviation of the reference's fp32 classes from their fp64 run {worst:.2e}")
     npz("f17_geom_losses.npz", names=np.array([c[0] for c in F17_CASES]), **arrays)
+
+
+# ------------------------------------------------------------------------------------------- F18
+F18_CASES = (
+    # name, F, R, pred: "mid" = target + 0.5 noise, "noise", "close" = target + 0.05 noise; every torsion masked
+    ("f1_r1", 1, 1, "mid", False),
+    ("f6_r1", 6, 1, "mid", False),
+    ("f5_r4", 5, 4, "mid", False),
+    ("noise_f40_r4", 40, 4, "noise", False),
+    ("close_f40_r4", 40, 4, "close", False),
+    ("f9_r23", 9, 23, "mid", False),
+    ("close_f3_r70", 3, 70, "close", False),
+    ("f2_r146", 2, 146, "mid", False),
+    ("tors_masked_f4_r4", 4, 4, "mid", True),
+)
+F18_KEYS = ("pos_loss", "pos_frame_loss", "inter_distance_loss", "norm_loss", "torsion_loss")
+F18C = dict(B=2, T=8, R=4)
+
+
+def f18_targets(pos, aatype):
+    """What datasets/peptide.py:60-77 stores of a trajectory, by the reference's own functions: positions in the backbone frames, torsions
+    (nan_to_num, times their mask), the torsion mask, the atom14 mask."""
+    from src.modules.geometry import atom14_to_atom37, atom14_to_frames, atom37_to_torsions
+    from src.utils.residue_constants import restype_atom14_mask
+    lead = pos.shape[:-3]
+    p, aa = pos.reshape(-1, *pos.shape[-3:]), aatype.reshape(-1, aatype.shape[-1])
+    frames = atom14_to_frames(p).unsqueeze(-1)
+    # (aatype as a numpy index and the mask the function would look up itself, handed over: numpy reads a one-element tensor index - F = R = 1 -
+    # as a scalar and drops the axes)
+    from src.utils.residue_constants import RESTYPE_ATOM37_MASK
+    atom37 = torch.from_numpy(atom14_to_atom37(p.numpy(), aa.numpy()))
+    torsions, torsions_mask = atom37_to_torsions(atom37, aa, torch.from_numpy(RESTYPE_ATOM37_MASK[aa.numpy()]))
+    torsions = torch.nan_to_num(torsions)
+    torsions = torsions * torsions_mask[..., None]
+    back = lambda x: x.reshape(*lead, *x.shape[1:])  # noqa: E731
+    return {"atom14_pos_frame": back(frames.invert_apply(p)).float(), "torsions": back(torsions).float(), "torsions_mask": back(torsions_mask).float(),
+            "atom14_mask": back(torch.from_numpy(restype_atom14_mask[aa.numpy()]).to(torch.bool))}
+
+
+def f18():
+    """The peptide Loss.forward (second_stage/peptide.py:293-378), the reference's own class.  (a) its four residue tables as arrays;
+    (b) its five additional losses - Loss built from the `loss:` block of configs/model/peptide/second-stage.yaml, and once more with
+    MaskedCosineLoss - on seeded decoded positions, in fp32 and in fp64, with its fp64 per-element torsions and frame-local positions;
+    (c) the reference's real peptide Wrapper.model_step at T = 8 (F13's first stage and seeded backbone weights, draws fixed as in F16)."""
+    import yaml
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import ref_env
+    from lam_slide_amd import dropin
+    dropin.uninstall()
+    ns = ref_env.setup()
+    pep = importlib.import_module("src.models.composites.second_stage.peptide")
+    from src.modules.geometry import atom14_to_frames, get_chi_atom_indices
+    from src.modules.losses import MaskedCosineLoss
+    from src.utils import residue_constants as rc
+    tables = {"restype_atom37_to_atom14": np.asarray(rc.RESTYPE_ATOM37_TO_ATOM14), "restype_atom37_mask": np.asarray(rc.RESTYPE_ATOM37_MASK),
+              "chi_atom_indices": np.asarray(get_chi_atom_indices()), "chi_angles_mask": np.asarray(rc.chi_angles_mask)}
+    print("F18 tables:", {k: (v.shape, str(v.dtype)) for k, v in tables.items()})
+    loss_cfg = yaml.safe_load(open(os.path.join(REF, "configs/model/peptide/second-stage.yaml")))["loss"]
+    assert loss_cfg["calc_additional_losses"] is True and loss_cfg["loss_torsion"]["_target_"].endswith("MaskedCosineLossV2")
+
+    class Si:
+        model_type = ns.transport.ModelType.DATA
+
+        def training_losses(self, model, x1, model_kwargs=None):
+            return {"pred": x1, "loss": torch.zeros(1, dtype=x1.dtype)}
+
+    class Fixed:  # what Loss.forward touches of the LightningModule; decode hands back the given positions
+        si = Si()
+
+        def __init__(self, pos):
+            self.pos = pos
+
+        def decode(self, latents, entities):
+            return {"atom14_pos": self.pos}
+
+    def five(loss, pred, b, dtype):
+        """Loss.forward UNCHANGED on one trajectory of F frames: [1, F, R, ...]"""
+        F_, R = pred.shape[:2]
+        batch = {"x1": torch.zeros(1, F_, 1, 1, dtype=dtype), "model_kwargs": {}, "entities": torch.zeros(1, F_, R, dtype=torch.long),
+                 "attention_mask": torch.ones(1, F_, R, dtype=torch.bool)}
+        for k, v in b.items():
+            batch[k] = (v.to(dtype) if v.is_floating_point() else v)[None]
+        out, _ = loss.to(dtype)(Fixed(pred.to(dtype)[None]), batch)
+        return torch.stack([out[k] for k in F18_KEYS])
+
+    arrays, worst = {}, {k: 0.0 for k in F18_KEYS}
+    for n, (name, F_, R, variant, all_masked) in enumerate(F18_CASES):
+        g = torch.Generator().manual_seed(180 + n)
+        aatype = torch.randint(0, 21, (F_, R), generator=g)
+        if R >= 21:
+            aatype[0, :21] = torch.arange(21)  # every type once, the unknown residue inside a chain
+        atom14_mask = torch.from_numpy(rc.restype_atom14_mask[aatype.numpy()]).to(torch.bool)
+        target = torch.randn(F_, R, 14, 3, generator=g) * atom14_mask[..., None]  # (absent atoms are zeros in the dataset's atom14 arrays)
+        noise = torch.randn(F_, R, 14, 3, generator=g)
+        pred = {"mid": target + 0.5 * noise, "noise": noise, "close": target + 0.05 * noise}[variant]
+        tg = f18_targets(target, aatype)
+        assert torch.equal(tg["atom14_mask"], atom14_mask)
+        own_mask = tg["torsions_mask"].clone()
+        keep = torch.rand(F_, R, 7, generator=g) >= 0.2
+        tors_mask = own_mask * keep * (0.0 if all_masked else 1.0)
+        b = {"atom14_pos": target, "atom14_pos_frame": tg["atom14_pos_frame"], "torsions": tg["torsions"], "torsions_mask": tors_mask,
+             "aatype": aatype, "atom14_mask": atom14_mask}
+        out = {}
+        for tag, dt in (("ref32", torch.float32), ("ref64", torch.float64)):
+            v2 = five(ref_env.instantiate(loss_cfg), pred, b, dt)
+            cos = five(ref_env.instantiate(dict(loss_cfg, loss_torsion={"_target_": "src.modules.losses.MaskedCosineLoss"})), pred, b, dt)
+            assert torch.equal(v2[:4], cos[:4]) and v2.dtype == dt
+            out[tag] = torch.cat([v2, cos[4:]])  # the five of the shipped YAML, then torsion_loss under MaskedCosineLoss
+        ref = ref_env.instantiate(loss_cfg).double()
+        p64 = pred.double()
+        tors64 = ref.calc_torsions(p64, aatype)
+        local64 = atom14_to_frames(p64).unsqueeze(-1).invert_apply(p64)
+        assert tors64.dtype == torch.float64 and local64.dtype == torch.float64
+        fin = torch.isfinite(out["ref64"])
+        assert bool(fin[:4].all()) and bool(fin[4:].all()) != all_masked and torch.equal(torch.isnan(out["ref32"]), torch.isnan(out["ref64"]))
+        dev = ((out["ref32"].double() - out["ref64"]).abs() / out["ref64"].abs())[:5]
+        for k, d in zip(F18_KEYS, dev):
+            worst[k] = max(worst[k], float(torch.nan_to_num(d)))
+        print(f"F18 {name}: " + " ".join(f"{k} {float(v):.6f}" for k, v in zip(F18_KEYS, out["ref64"])) + f" cos {float(out['ref64'][5]):.6f}; fp32 classes vs fp64 "
+              + " ".join(f"{float(d):.1e}" for d in dev) + f"; torsions counted {int(tors_mask.sum())} of {F_ * R * 7}")
+        arrays[name] = {"pred": pred, "target": target, "target_frame": tg["atom14_pos_frame"], "tors_target": tg["torsions"], "tors_mask": tors_mask.to(torch.bool),
+                        "own_tors_mask": own_mask.to(torch.bool), "atom14_mask": atom14_mask, "aatype": aatype.to(torch.int8), "ref32": out["ref32"],
+                        "ref64": out["ref64"], "tors64": tors64, "local64": local64}
+    print("F18b: worst deviation of the reference's fp32 classes from their fp64 run: " + " ".join(f"{k} {v:.2e}" for k, v in worst.items()))
+
+    # (c) the real Wrapper.model_step
+    F = ref_env.F13
+    B, T, R, L = F18C["B"], F18C["T"], F18C["R"], F["L"]
+    lift = torch.randn(42, F["dim_input"], generator=torch.Generator().manual_seed(50)) * 0.3  # (F13's)
+    first, first_cls = ref_env.build_peptide_first_stage(ns, lift)
+    w = ref_env.build_peptide_wrapper(ns, first, first_cls, T=T)
+    w.eval()
+    sh = latent_net.NetShape(**F["backbone"])
+    wseed = 54  # (F13's)
+    w.backbone.load_state_dict(latent_net.random_params(sh, seed=wseed))
+    f13 = {}
+    for part in [os.path.join(OUT, "f13_peptide.npz")] + sorted(glob.glob(os.path.join(OUT, "f13_peptide.part*.npz"))):
+        z = np.load(part)
+        f13.update({k: z[k] for k in z.files})
+    assert np.array_equal(f13["lift"], lift.numpy()) and int(f13["weight_seed"]) == wseed
+    s1 = first.backbone.state_dict()
+    assert all(np.array_equal(f13["stage1/" + k], v.numpy()) for k, v in s1.items() if "output_layers.aatype" not in k)  # the tests take them from F13
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from golden_inputs import peptide_frames
+    batch = peptide_frames(181, B, T, R)
+    batch.update(f18_targets(batch["atom14_pos"], batch["aatype"]))
+    g = torch.Generator().manual_seed(182)
+    x0 = torch.randn(B, T, L, 96, generator=g)
+    t0, t1 = w.si.check_interval(w.si.train_eps, w.si.sample_eps)
+    t = torch.tensor([0.37, 0.81]) * (t1 - t0) + t0
+    w.si.sample = lambda x1: (t, x0.to(x1), x1)
+    seen = {}
+    real, real_decode = w.si.training_losses, w.decode
+
+    def tap(model, x1, model_kwargs=None):
+        assert model is w
+        out = real(model=model, x1=x1, model_kwargs=model_kwargs)
+        seen.update(loss=out["loss"].clone(), pred=out["pred"].clone(), x1=x1.clone(), x_cond=model_kwargs["x_cond"].clone(), mask=model_kwargs["x_cond_mask"].clone())
+        return out
+
+    def tap_decode(latents, entities):
+        out = real_decode(latents, entities)
+        seen["decoded"] = out["atom14_pos"].clone()
+        return out
+
+    w.si.training_losses, w.decode = tap, tap_decode
+    with torch.no_grad():
+        losses, _ = w.model_step({k: v.clone() for k, v in batch.items()})
+    losses = {k: v.detach().clone() for k, v in losses.items()}
+    assert set(losses) == {"si_loss", "loss"} | set(F18_KEYS) and seen["decoded"].shape == (B, T, R, 14, 3)
+    tgt = {k: batch[k].reshape(B * T, *batch[k].shape[2:]) for k in ("atom14_pos", "atom14_pos_frame", "torsions", "torsions_mask", "aatype", "atom14_mask")}
+    dec64 = five(ref_env.instantiate(loss_cfg), seen["decoded"].reshape(B * T, R, 14, 3), tgt, torch.float64)
+    print("F18c real peptide Wrapper.model_step: " + " ".join(f"{k} {float(v):.6f}" for k, v in losses.items()) + "; the five in fp64 on the decoded positions "
+          + " ".join(f"{float(v):.6f}" for v in dec64))
+    npz("f18_peptide_loss.npz", names=np.array([c[0] for c in F18_CASES]), tables=tables, **arrays,
+        step={"atom14_pos": batch["atom14_pos"], "aatype": batch["aatype"], "entities": batch["entities"], "attention_mask": batch["attention_mask"],
+              "atom14_pos_frame": batch["atom14_pos_frame"], "torsions": batch["torsions"], "torsions_mask": batch["torsions_mask"],
+              "atom14_mask": batch["atom14_mask"], "t": t, "x0": x0, "latents": seen["x1"], "x_cond": seen["x_cond"], "mask": seen["mask"],
+              "pred": seen["pred"], "loss": seen["loss"], "decoded": seen["decoded"], "decoded_ref64": dec64,
+              "meta": np.array([B, T, R, L, F["cond_idx"][0], F["cond_idx"][1], 181])},
+        losses=losses)
 
 
 # ------------------------------------------------------------------------------------------- F10

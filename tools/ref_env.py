@@ -18,7 +18,7 @@ stand-ins that let those files import:
     src.datasets.md17              only ``dataset_cond_indices`` (a dict of 8 molecule names; the real module imports the dataset stack)
     lightning_utilities.core.rank_zero   the two names pylogger imports
 
-Used by ``tools/make_fixtures.py f9 f11 f12 f13 f16``.  Nothing here ships.
+Used by ``tools/make_fixtures.py f9 f11 f12 f13 f16 f18``.  Nothing here ships.
 """
 from __future__ import annotations
 
@@ -417,17 +417,17 @@ def build_peptide_first_stage(ns, lift, seed=51):
     return FirstStage(Backbone(dim_latent=F13["dim_latent"], encoder=enc, decoder=dec)), FirstStage
 
 
-def build_peptide_wrapper(ns, first_stage, first_stage_cls, seed=52):
+def build_peptide_wrapper(ns, first_stage, first_stage_cls, seed=52, T=None):
     """second_stage/peptide.py Wrapper, constructed by ITS OWN __init__ from the reference's own YAML block
-    (configs/model/peptide/second-stage.yaml: cond_idx [0, 1], mask_cond_mean, hidden 384, 16 heads of 24, mlp 4) with the true T = 1000;
-    depth 2 instead of 7."""
+    (configs/model/peptide/second-stage.yaml: cond_idx [0, 1], mask_cond_mean, hidden 384, 16 heads of 24, mlp 4) with the true T = 1000
+    (or the given T: F18 runs model_step at T = 8); depth 2 instead of 7."""
     import yaml
     pep = importlib.import_module("src.models.composites.second_stage.peptide")
     cfg = yaml.safe_load(open(os.path.join(REF, "configs/model/peptide/second-stage.yaml")))
     for k in ("_target_", "_recursive_", "defaults"):
         cfg.pop(k, None)
     assert cfg["cond_idx"] == F13["cond_idx"] and cfg["mask_cond_mean"] is True and cfg["backbone"]["hidden_size"] == 384
-    cfg.update(n_timesteps=F13["T"], ema=None, scheduler=None, sampling_method="ODE",
+    cfg.update(n_timesteps=F13["T"] if T is None else T, ema=None, scheduler=None, sampling_method="ODE",
                sampling_kwargs={"sampling_method": "euler", "num_steps": F13["num_steps"]})
     cfg["backbone"] = dict(cfg["backbone"], **F13["backbone"])
     key = f"f13-stage1-{id(first_stage)}"
