@@ -40,7 +40,8 @@ extern "C" {
  * 6, later: lsl_si_loss, lsl_si_reduce, lsl_si_loss_workspace_bytes added, no signature changed (a binding that needs them finds out by
  *    looking the symbols up: a library without them is stale).
  * 6, later still: lsl_geom_loss_sums, lsl_geom_loss_final added the same way.
- * 6, later still: lsl_peptide_loss_sums, lsl_peptide_loss_final added the same way. */
+ * 6, later still: lsl_peptide_loss_sums, lsl_peptide_loss_final added the same way.
+ * 6, later still: lsl_disp_error_rows, lsl_disp_error_final added the same way. */
 #define LSL_VERSION 6
 
 typedef struct lsl_model lsl_model;
@@ -256,6 +257,30 @@ int lsl_peptide_loss_sums(const float *pred, const float *target_frame, const ui
  * over the F rows of geom_sums [F, 5] (lsl_geom_loss_sums with A = R*14, D = 3, mask = atom14_mask) and pept_sums [F, 4], in index order, in
  * fp64, each rounded once (rows of several shards may be concatenated first); 0 / 0 is NaN, as the reference. */
 int lsl_peptide_loss_final(const float *geom_sums, const float *pept_sums, int32_t F, float *out, void *stream);
+
+/* Displacement errors of the decoded positions: the evaluation tail of the trajectory models.  validation_step (second_stage/md17.py:82-86,
+ * nba.py:100-104, pedestrian.py:88-92): ade = norm(true - pred, dim=-1).mean(dim=(1, 2)), fde = norm(true[:, -1] - pred[:, -1], dim=-1).mean(dim=1)
+ * over the future frames and ALL entities; test_step (nba.py:182-225, pedestrian.py:170-212): per real agent the error [K, Tf] = norm(traj -
+ * target), ADE = its mean over the frames, FDE = its last frame, each minimised on its own over the first num_runs samples.
+ *   pred    device f32 [K, B, Tp, A, D]   the decoder's output of K samples of B scenes, as it left it; frames t0p .. t0p + Tf - 1 are read
+ *   target  device f32 [B, Tt, A, D]      the batch's positions; frames t0t .. t0t + Tf - 1 are read (the full pos with t0t = cond_idx[1],
+ *                                         or the future frames alone with t0t = 0: the same call, no slice is copied)
+ *   rows    device f32 [K, B, A, 2]       per sample and agent (sum_t e_t / Tf, e_{Tf-1}),  e_t = sqrt(sum_d (pred - target)^2)
+ *   traj    device f32 [K, B, 2] or NULL  per sample (sum_a sum_t e_t / (Tf A), sum_a e_{Tf-1} / A): the two validation_step lines
+ * Native form: 1 <= D <= 4, A >= 1, Tf >= 1, 0 <= t0p, t0p + Tf <= Tp, 0 <= t0t, t0t + Tf <= Tt, K * B < 2^24 (a grid of K * B workgroups of 256 threads stays below 2^32 threads); anything else is refused with
+ * -3 (the binding's displacement_errors takes its torch path for D > 4).  Indices are 64-bit: K*B*Tp*A*D may pass 2^31.  fp32 with correctly
+ * rounded sqrt and division; no atomics; frames added in ascending order per agent, a thread's agents in ascending order, the wave by DPP,
+ * the waves in wave order - every order fixed by (A, D, Tf): the floats of a sample trajectory have the same bits in any batch or shard.
+ * Nothing is allocated, nothing is synchronised; a refused call enqueues nothing. */
+int lsl_disp_error_rows(const float *pred, const float *target, int32_t K, int32_t B, int32_t Tp, int32_t t0p, int32_t Tt, int32_t t0t, int32_t Tf,
+                        int32_t A, int32_t D, float *rows, float *traj, void *stream);
+/* agents (device f32 [B, A, 2]) = the minimum over samples k = 0 .. num_runs - 1 (ascending) of the two columns of rows [K, B, A, 2], each on
+ * its own; a NaN of any of those samples gives NaN (torch.min); quiet NaN where mask (device u8 [B, A], NULL = all agents real) is 0.
+ * totals (device f64 [5], written, not accumulated) = sum minADE, sum minFDE, n over the real agents in (b, a) order, then the sums of the two
+ * columns of traj [K, B, 2] over its first num_runs * B rows (0 when traj is NULL), in fp64 in index order: totals of several batches or
+ * shards add before the division (on_test_epoch_end, nba.py:240-245).  1 <= num_runs <= K, else -3. */
+int lsl_disp_error_final(const float *rows, const float *traj, const uint8_t *mask, int32_t K, int32_t num_runs, int32_t B, int32_t A, float *agents,
+                         double *totals, void *stream);
 
 /* Sampler loop (Sampler.sample_ode / sample_sde inner loops): applies n_steps affine updates to io->x
  * in place.  noise: device [n_noise, B*T*L*C] standard-normal draws, slice s belongs to step s (the

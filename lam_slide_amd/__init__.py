@@ -16,6 +16,9 @@ Public surface (mirrors the reference's for this path only):
   PeptideLoss, peptide_losses, peptide_loss_sums
                                    <- second_stage/peptide.Loss with calc_additional_losses: those three of the atom14 positions plus
                                       the frame-local position loss and the torsion loss on the device (peptide_loss.py)
+  displacement_errors, displacement_rows, DisplacementMeter
+                                   <- the ADE / FDE lines of validation_step, the best-of-K tail of test_step and the epoch means of
+                                      second_stage/{md17,nba,pedestrian}.py on the device (metrics.py)
   install()                        <- rebinds the reference's module-level ``Sampler`` (lightning_base.py:10); see dropin.py
 The compute lives in liblamslide_hip.so (include/lsl_api.h); build it with ``__graft_entry__.build()``.
 """
@@ -25,6 +28,7 @@ from .decoder import Stage1Decoder
 from .encoder import Stage1Encoder
 from .latent_si import LatentSIV3
 from .losses import Loss, geom_loss_sums, geom_losses
+from .metrics import DisplacementErrors, DisplacementMeter, displacement_errors, displacement_rows
 from .peptide_loss import PeptideLoss, peptide_loss_sums, peptide_losses
 from .sampling import (RolloutSampler, SecondStageSampler, best_of_k_errors, min_ade_fde, sample_rollout, sample_sharded,
                        setup_conditioning, shard_bounds)
@@ -33,4 +37,5 @@ from .transport import (CreateTransport, ModelType, PathType, Sampler, SampleRes
 
 __all__ = ["LatentSIV3", "CreateTransport", "Transport", "Sampler", "SampleResult", "ModelType", "PathType", "WeightType",
            "SecondStageSampler", "setup_conditioning", "sample_sharded", "shard_bounds", "min_ade_fde", "sample_rollout", "best_of_k_errors",
-           "RolloutSampler", "Stage1Decoder", "Stage1Encoder", "as_transport", "device_randn", "mix_seed", "si_reduce", "Loss", "geom_losses", "geom_loss_sums", "PeptideLoss", "peptide_losses", "peptide_loss_sums", "install", "uninstall", "dropin", "_lib"]
+           "RolloutSampler", "Stage1Decoder", "Stage1Encoder", "as_transport", "device_randn", "mix_seed", "si_reduce", "Loss", "geom_losses", "geom_loss_sums", "PeptideLoss", "peptide_losses", "peptide_loss_sums", "displacement_rows", "displacement_errors",
+           "DisplacementErrors", "DisplacementMeter", "install", "uninstall", "dropin", "_lib"]

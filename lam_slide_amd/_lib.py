@@ -20,13 +20,14 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 ABI_VERSION = 6  # LSL_VERSION of include/lsl_api.h this binding was written against
 RK_SCRATCH_BYTES = 8192  # LSL_RK_SCRATCH_BYTES
 GEOM_MAX_A, GEOM_MAX_D = 2048, 4  # the native form of lsl_geom_loss_sums (csrc/k_geomloss.hip.h)
+DISP_MAX_D, DISP_MAX_UNITS = 4, 16777215  # the native form of lsl_disp_error_rows (csrc/k_disperr.hip.h): coordinates, K * B
 SI_SLAB = 4096  # LSL_SI_SLAB: elements of one trajectory per partial sum of lsl_si_reduce
 
 EXPORTED = (
     "lsl_version", "lsl_build_info", "lsl_last_error", "lsl_model_create", "lsl_model_set_weights", "lsl_model_destroy",
     "lsl_model_set_chunk", "lsl_model_set_attention_mode", "lsl_model_set_tail", "lsl_model_tail", "lsl_model_set_ln_fuse", "lsl_model_ln_fuse", "lsl_profile_kernel_name", "lsl_pass_size", "lsl_sampler_path", "lsl_workspace_bytes", "lsl_forward", "lsl_sample", "lsl_sample_ex", "lsl_debug_block", "lsl_debug_taps", "lsl_debug_mods",
     "lsl_si_loss_workspace_bytes", "lsl_si_loss", "lsl_si_reduce", "lsl_geom_loss_sums", "lsl_geom_loss_final",
-    "lsl_peptide_loss_sums", "lsl_peptide_loss_final",
+    "lsl_peptide_loss_sums", "lsl_peptide_loss_final", "lsl_disp_error_rows", "lsl_disp_error_final",
     "lsl_profile_enable", "lsl_profile_read", "lsl_randn", "lsl_rk_lincomb", "lsl_rk_dense", "lsl_rk_error_ratio",
     "lsl_decoder_create", "lsl_decoder_destroy", "lsl_decode_workspace_bytes", "lsl_decode",
     "lsl_encoder_create", "lsl_encoder_destroy", "lsl_encode_workspace_bytes", "lsl_encode",
@@ -173,6 +174,8 @@ def load() -> C.CDLL:
     lib.lsl_geom_loss_final.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     lib.lsl_peptide_loss_sums.argtypes = [C.c_void_p] * 7 + [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.lsl_peptide_loss_final.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.lsl_disp_error_rows.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int32] * 9 + [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lsl_disp_error_final.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.lsl_randn.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
     lib.lsl_rk_lincomb.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.c_int32, C.c_uint64, C.c_void_p]
     lib.lsl_rk_dense.argtypes = [C.c_void_p] * 6 + [C.c_float, C.c_uint64, C.c_void_p]

@@ -591,3 +591,14 @@ void launch_peptide_frame(float *sums, const float *pred, const float *target_fr
     hipLaunchKernelGGL(k_peptide_loss_frame<TEAM>, dim3((unsigned)(((long long)F + FPB - 1) / FPB)), dim3(256), FPB * pept_team_bytes(R), st, sums, pred,
                        target_frame, atom14_mask, tors_target, tors_mask, aatype, restab, F, R, kind);
 }
+
+// per-agent and per-trajectory displacement errors (k_disperr.hip.h): a wave per sample trajectory up to 64 agents, the whole workgroup above
+template <int D>
+void launch_disp_rows(float *rows, float *traj, const float *pred, const float *target, long long units, int B, int Tp, int t0p, int Tt, int t0t,
+                      int Tf, int A, hipStream_t st) {
+    if (A <= 64)
+        hipLaunchKernelGGL((k_disp_rows<D, 64>), dim3((unsigned)((units + 3) / 4)), dim3(256), 0, st, rows, traj, pred, target, units, B, Tp, t0p, Tt,
+                           t0t, Tf, A);
+    else
+        hipLaunchKernelGGL((k_disp_rows<D, 256>), dim3((unsigned)units), dim3(256), 0, st, rows, traj, pred, target, units, B, Tp, t0p, Tt, t0t, Tf, A);
+}

@@ -2,7 +2,7 @@
 // network evaluation (latent_si_v31.py:168-188) and of the sampler loops (integrators.py:67-78,103-120)
 // on the caller's stream.  No allocation, no synchronisation, no host<->device copies.
 // One translation unit: this file = the entry points of the sampling path (model handle, forward, fused sampler + opt-in hipGraph replay,
-// noise, Runge-Kutta state arithmetic, the stochastic-interpolant objective around one evaluation, the geometry losses of the decoded positions, the peptide frame and torsion losses, debug taps); host_common / host_launch / host_eval.hip.h = what they enqueue (host_graph.hip.h: the replay cache); decode_host.hip.h +
+// noise, Runge-Kutta state arithmetic, the stochastic-interpolant objective around one evaluation, the geometry losses of the decoded positions, the peptide frame and torsion losses, the displacement errors (ADE / FDE, best-of-K), debug taps); host_common / host_launch / host_eval.hip.h = what they enqueue (host_graph.hip.h: the replay cache); decode_host.hip.h +
 // stage1_api.hip.h = the frozen stage-1 encode / decode beside the path.
 #include "../../include/lsl_api.h"
 
@@ -30,6 +30,7 @@
 #include "k_siloss.hip.h"
 #include "k_geomloss.hip.h"
 #include "k_peptloss.hip.h"
+#include "k_disperr.hip.h"
 #ifdef LSL_EXPERIMENTS  // measured-and-rejected GEMM structures, built only by tools/build_experiments.sh (never in the product library)
 #include "k_gemm_pp.hip.h"        // tools/experiments/ (on the include path of tools/build_experiments.sh only)
 #include "k_gemm_drain.hip.h"
@@ -335,6 +336,41 @@ int lsl_peptide_loss_final(const float *geom_sums, const float *pept_sums, int32
     if (F <= 0) return fail(-3, "F must be positive");
     hipLaunchKernelGGL(k_peptide_loss_final, dim3(1), dim3(64), 0, (hipStream_t)stream, out, geom_sums, pept_sums, (int)F);
     LSL_CHECK_LAUNCH("lsl_peptide_loss_final");
+    return 0;
+} LSL_API_CATCH
+
+// ---- displacement errors of the decoded positions: ADE / FDE and best-of-K (k_disperr.hip.h) ----
+int lsl_disp_error_rows(const float *pred, const float *target, int32_t K, int32_t B, int32_t Tp, int32_t t0p, int32_t Tt, int32_t t0t, int32_t Tf,
+                        int32_t A, int32_t D, float *rows, float *traj, void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!pred || !target || !rows) return fail(-1, "null argument");
+    if (K < 1 || B < 1) return fail(-3, "K = %d and B = %d must be positive", K, B);
+    if ((long long)K * B > LSL_DISP_MAX_UNITS) return fail(-3, "K * B = %lld sample trajectories: at most %lld", (long long)K * B, LSL_DISP_MAX_UNITS);
+    if (A < 1) return fail(-3, "A = %d: at least one agent", A);
+    if (D < 1 || D > LSL_DISP_MAX_D) return fail(-3, "D = %d outside the native form (1..%d coordinates)", D, LSL_DISP_MAX_D);
+    if (Tf < 1) return fail(-3, "Tf = %d: at least one future frame", Tf);
+    if (t0p < 0 || (long long)t0p + Tf > Tp) return fail(-3, "frames %d..%d outside pred's %d frames", t0p, t0p + Tf - 1, Tp);
+    if (t0t < 0 || (long long)t0t + Tf > Tt) return fail(-3, "frames %d..%d outside target's %d frames", t0t, t0t + Tf - 1, Tt);
+    hipStream_t st = (hipStream_t)stream;
+    const long long units = (long long)K * B;
+    switch (D) {
+        case 1: launch_disp_rows<1>(rows, traj, pred, target, units, B, Tp, t0p, Tt, t0t, Tf, A, st); break;
+        case 2: launch_disp_rows<2>(rows, traj, pred, target, units, B, Tp, t0p, Tt, t0t, Tf, A, st); break;
+        case 3: launch_disp_rows<3>(rows, traj, pred, target, units, B, Tp, t0p, Tt, t0t, Tf, A, st); break;
+        default: launch_disp_rows<4>(rows, traj, pred, target, units, B, Tp, t0p, Tt, t0t, Tf, A, st); break;
+    }
+    LSL_CHECK_LAUNCH("lsl_disp_error_rows");
+    return 0;
+} LSL_API_CATCH
+
+int lsl_disp_error_final(const float *rows, const float *traj, const uint8_t *mask, int32_t K, int32_t num_runs, int32_t B, int32_t A, float *agents,
+                         double *totals, void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!rows || !agents || !totals) return fail(-1, "null argument");
+    if (K < 1 || B < 1 || A < 1) return fail(-3, "K = %d, B = %d and A = %d must be positive", K, B, A);
+    if (num_runs < 1 || num_runs > K) return fail(-3, "num_runs = %d outside 1..K = %d", num_runs, K);
+    hipLaunchKernelGGL(k_disp_final, dim3(1), dim3(256), 0, (hipStream_t)stream, agents, totals, rows, traj, mask, (int)num_runs, (int)B, (int)A);
+    LSL_CHECK_LAUNCH("lsl_disp_error_final");
     return 0;
 } LSL_API_CATCH
 

@@ -155,6 +155,19 @@ class SecondStageSampler:
         return {"si_loss": si_loss, "pos_loss": geo["pos_loss"], "inter_dist_loss": geo["inter_dist_loss"], "dist": geo["dist"], "loss": loss}
 
     @torch.no_grad()
+    def validation_errors(self, latents: Tensor, pos: Tensor, decode: Callable[[Tensor], Tensor], y: Optional[Tensor] = None,
+                          init: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+        """The second half of ``validation_step`` of md17, NBA and pedestrian (second_stage/md17.py:79-86, nba.py:100-104,
+        pedestrian.py:88-92) on one sample: :meth:`sample_latents` -> ``decode(final [B,T,L,C]) -> positions [B,T,A,D]`` (or [B*T,A,D])
+        -> ``ade = norm(true - pred, dim=-1).mean(dim=(1, 2))``, ``fde = norm(true[:, -1] - pred[:, -1], dim=-1).mean(dim=1)`` over the
+        frames from ``cond_idx[1]`` on and ALL entities (no mask, as the reference), by ``displacement_rows``: ``pos`` [B,T,A,D] is
+        the batch's full positions, read in place.  Returns (ade [B], fde [B]), unscaled."""
+        from .metrics import displacement_rows
+        final = self.sample_latents(latents, y=y, init=init)
+        _, traj = displacement_rows(decode(final).reshape(pos.shape), pos, first_frame=self.cond_idx[1])
+        return traj[0, :, 0], traj[0, :, 1]
+
+    @torch.no_grad()
     def sample_latents_k(self, latents: Tensor, K: int, y: Optional[Tensor] = None, inits: Optional[Tensor] = None) -> Tensor:
         """K samples per conditioning in ONE fused call.  The reference's test loops re-encode the identical batch and call
         ``sample`` K times in sequence (second_stage/pedestrian.py:193-204, nba.py:205-217, md17.py:157-166); trajectories are
@@ -254,18 +267,25 @@ def sample_rollout(sample_positions: Callable[[Tensor], Tensor], cond_pos: Tenso
 @torch.no_grad()
 def best_of_k_errors(drv: "SecondStageSampler", latents: Tensor, target_pos: Tensor, K: int, decode: Callable[[Tensor], Tensor],
                      agent_mask: Optional[Tensor] = None, y: Optional[Tensor] = None, inits: Optional[Tensor] = None,
-                     num_runs: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+                     num_runs: Optional[int] = None, fused: bool = False) -> Tuple[Tensor, Tensor]:
     """The evaluation tail of the trajectory models on the device (second_stage/pedestrian.py:186-212, nba.py:205-225): K samples per
     scene, decoded, future frames only, one row per real agent, best-of-K ADE / FDE.  The reference runs K sequential ``sample()``
     calls (re-encoding the same batch each time) and stacks the results on the host side of the loop; here the K samples are one fused
     call (``sample_latents_k``), one decode, and the reductions of :func:`min_ade_fde`, with no host round trip in between.
 
     latents [B,T,L,C] stage-1 latents; target_pos [B, T - c1, A, D] true future positions; ``decode(latents [K*B,T,L,C]) ->
-    positions [K*B, T, A, D]``; agent_mask [B, A] bool (``attention_mask[:, -1]``) or None.  Returns (ADE, FDE) per real agent."""
+    positions [K*B, T, A, D]``; agent_mask [B, A] bool (``attention_mask[:, -1]``) or None.  Returns (ADE, FDE) per real agent.
+
+    ``fused=True``: everything after the decode is ``displacement_errors(...).real()`` (metrics.py: two HIP launches that read the
+    decoder's output in place, then the one boolean index) instead of the chain of torch operations below; same rows, same order, and
+    an agent's errors have the same bits in any batch."""
     B = latents.shape[0]
     c1 = drv.cond_idx[1]
     final = drv.sample_latents_k(latents, K, y=y, inits=inits)            # [K, B, T, L, C]
     pos = decode(final.reshape(K * B, *final.shape[2:]))                   # [K*B, T, A, D]
+    if fused:
+        from .metrics import displacement_errors
+        return displacement_errors(pos.reshape(K, B, *pos.shape[1:]), target_pos, agent_mask, first_frame=c1, num_runs=num_runs).real()
     pos = pos.reshape(K, B, *pos.shape[1:])[:, :, c1:]                     # future frames
     traj = pos.permute(1, 3, 0, 2, 4).reshape(B * pos.shape[3], K, pos.shape[2], pos.shape[4])   # "(B A) K T D"
     tgt = target_pos.permute(0, 2, 1, 3).reshape(B * target_pos.shape[2], target_pos.shape[1], target_pos.shape[3])
