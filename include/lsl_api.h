@@ -41,7 +41,8 @@ extern "C" {
  *    looking the symbols up: a library without them is stale).
  * 6, later still: lsl_geom_loss_sums, lsl_geom_loss_final added the same way.
  * 6, later still: lsl_peptide_loss_sums, lsl_peptide_loss_final added the same way.
- * 6, later still: lsl_disp_error_rows, lsl_disp_error_final added the same way. */
+ * 6, later still: lsl_disp_error_rows, lsl_disp_error_final added the same way.
+ * 6, later still: lsl_dihedral_angles, lsl_histogram, lsl_lag_products_workspace_bytes, lsl_lag_products, lsl_js_distance added the same way. */
 #define LSL_VERSION 6
 
 typedef struct lsl_model lsl_model;
@@ -281,6 +282,45 @@ int lsl_disp_error_rows(const float *pred, const float *target, int32_t K, int32
  * shards add before the division (on_test_epoch_end, nba.py:240-245).  1 <= num_runs <= K, else -3. */
 int lsl_disp_error_final(const float *rows, const float *traj, const uint8_t *mask, int32_t K, int32_t num_runs, int32_t B, int32_t A, float *agents,
                          double *totals, void *stream);
+
+/* Torsion statistics of a sampled peptide trajectory: what analyze_trajectory (eval_peptide.py:102-182) computes from the torsion features of
+ * the sampled and the MD trajectory - histograms of every torsion and of chosen pairs, their Jensen-Shannon distances, and the lagged
+ * products the decorrelation curves are made of.  Four independent calls; device pointers unless named host; nothing is allocated, nothing is
+ * synchronised, a refused call enqueues nothing.  No float atomics: counts are integers added by integer atomics (exact in any order), every
+ * float is a sum in a fixed order that does not depend on the grid, the batch or the position in the batch.
+ *
+ * lsl_dihedral_angles: angles [F, Q] f32 (radians, [-pi, pi]) of the Q atom quadruples of each of F frames pos [F, A, 3] f32,
+ *   angle = atan2((b1 . c1) |b2|, c1 . c2),  b1 = p1 - p0, b2 = p2 - p1, b3 = p3 - p2, c1 = b2 x b3, c2 = b1 x b2   (fp32, every product and
+ *   sum rounded on its own, in that order).  quads i32 [Q, 4] indexes the A atom slots of a frame - a general table, not a fixed set of
+ *   torsions; quads_host is the same table in HOST memory: it is what the range check reads (an index outside 0..A-1: -3, before any launch;
+ *   the device copy is the caller's to keep equal, an index outside the frame there gives NaN).  1 <= A <= 2044 (146 residues of 14 atoms: a
+ *   frame in LDS), 1 <= Q <= 65536, F >= 1. */
+int lsl_dihedral_angles(const float *pos, const int32_t *quads, const int32_t *quads_host, int64_t F, int32_t A, int32_t Q, float *angles,
+                        void *stream);
+/* lsl_histogram: counts i64 [S, Q, bins] += np.histogram(x[s, :, q], bins=edges)[0] of x [S, n, Q] f32, and for P > 0 counts2 i64 [S, P,
+ *   bins2, bins2] += np.histogram2d(x[s, :, pairs[p][0]], x[s, :, pairs[p][1]], bins=(edges2a, edges2b))[0].  The tables are ADDED TO: zero
+ *   them before the first call, chunks of a trajectory then accumulate exactly.  edges f64 [bins + 1], edges2a / edges2b f64 [bins2 + 1]:
+ *   ascending edge tables, np.linspace(lo, hi, bins + 1) for the range= form.  A value is binned by comparison against the fp64 table (a
+ *   multiply-and-floor estimate, then a walk against the table, as numpy corrects its own estimate): bin i holds edges[i] <= v < edges[i + 1],
+ *   the last bin is closed on the right, values outside [edges[0], edges[bins]] and NaN are dropped, a pair is dropped when either coordinate
+ *   is.  Given the same float32 values the counts equal numpy's as integers.  pairs i32 [P, 2] column indices, pairs_host the same table in
+ *   HOST memory (checked: outside 0..Q-1 is -3).  1 <= bins <= 2048, 1 <= bins2 <= 90 (bins2^2 <= 8192 LDS cells), S <= 65535, P <= 65535.
+ *   Overflow: a call adds at most n < 2^31 to a count; an int64 count overflows only after 2^63 samples in all - the caller's sum of n. */
+int lsl_histogram(const float *x, int32_t S, int32_t n, int32_t Q, const double *edges, int32_t bins, int64_t *counts, const int32_t *pairs,
+                  const int32_t *pairs_host, int32_t P, const double *edges2a, const double *edges2b, int32_t bins2, int64_t *counts2, void *stream);
+/* lsl_lag_products: ac f32 [S, C, nlag + 1], ac[s, c, k] = (sum_{t < n - k} x[s, t, c] x[s, t + k, c]) / (n - k) of x [S, n, C] f32
+ *   = statsmodels acovf(x, demean=False, adjusted=True, nlag=nlag).  A workgroup owns (series, channel, 256 lags, a segment of chunks of 448
+ *   time steps); within a chunk a lag's terms are added in t order by fp32 fused multiply-adds (the longest fp32 addition chain is m = 448),
+ *   chunks and segments in order in fp64, one division, one rounding to fp32: |error| <= (m + 8) 2^-24 for |x| <= 1.  The split is a function
+ *   of (n, nlag) alone: a series' row has the same bits alone and inside a batch.  0 <= nlag < n (else -3), nlag + 1 <= 2^21, S * C <= 65535.
+ *   workspace: lsl_lag_products_workspace_bytes(S, n, C, nlag) bytes of device memory (fp64 segment sums; 0 for a refused shape); -4 if
+ *   workspace_bytes is smaller. */
+size_t lsl_lag_products_workspace_bytes(int32_t S, int32_t n, int32_t C, int32_t nlag);
+int lsl_lag_products(const float *x, int32_t S, int32_t n, int32_t C, int32_t nlag, float *ac, void *workspace, size_t workspace_bytes, void *stream);
+/* lsl_js_distance: out f64 [rows] = scipy.spatial.distance.jensenshannon(counts_a[r], counts_b[r]) of two non-negative i64 tables [rows, bins]
+ *   (a flattened 2-D table is a row): p, q = the rows over their sums, m = (p + q) / 2, sqrt((sum rel_entr(p, m) + sum rel_entr(q, m)) / 2),
+ *   natural log, rel_entr(0, .) = 0, the bins added in index order in fp64.  A row that is all zero on either side gives NaN (0 / 0), as scipy. */
+int lsl_js_distance(const int64_t *counts_a, const int64_t *counts_b, int32_t rows, int32_t bins, double *out, void *stream);
 
 /* Sampler loop (Sampler.sample_ode / sample_sde inner loops): applies n_steps affine updates to io->x
  * in place.  noise: device [n_noise, B*T*L*C] standard-normal draws, slice s belongs to step s (the

@@ -19,6 +19,10 @@ Public surface (mirrors the reference's for this path only):
   displacement_errors, displacement_rows, DisplacementMeter
                                    <- the ADE / FDE lines of validation_step, the best-of-K tail of test_step and the epoch means of
                                       second_stage/{md17,nba,pedestrian}.py on the device (metrics.py)
+  TorsionStats, dihedral_angles, angle_histograms, js_distance, lagged_products, decorrelation
+                                   <- the torsion statistics of eval_peptide.analyze_trajectory (histograms of every torsion and of
+                                      chosen pairs, Jensen-Shannon distances to the MD reference, decorrelation curves) of the sampled
+                                      atom14 positions on the device (torsion_stats.py)
   install()                        <- rebinds the reference's module-level ``Sampler`` (lightning_base.py:10); see dropin.py
 The compute lives in liblamslide_hip.so (include/lsl_api.h); build it with ``__graft_entry__.build()``.
 """
@@ -32,10 +36,13 @@ from .metrics import DisplacementErrors, DisplacementMeter, displacement_errors,
 from .peptide_loss import PeptideLoss, peptide_loss_sums, peptide_losses
 from .sampling import (RolloutSampler, SecondStageSampler, best_of_k_errors, min_ade_fde, sample_rollout, sample_sharded,
                        setup_conditioning, shard_bounds)
+from .torsion_stats import (TorsionStats, angle_histograms, decorrelation, dihedral_angles, eval_torsion_quads, js_distance, lagged_products,
+                            summary_metrics, topology_atoms)
 from .transport import (CreateTransport, ModelType, PathType, Sampler, SampleResult, Transport, WeightType, as_transport, device_randn,
                         mix_seed, si_reduce)
 
 __all__ = ["LatentSIV3", "CreateTransport", "Transport", "Sampler", "SampleResult", "ModelType", "PathType", "WeightType",
            "SecondStageSampler", "setup_conditioning", "sample_sharded", "shard_bounds", "min_ade_fde", "sample_rollout", "best_of_k_errors",
            "RolloutSampler", "Stage1Decoder", "Stage1Encoder", "as_transport", "device_randn", "mix_seed", "si_reduce", "Loss", "geom_losses", "geom_loss_sums", "PeptideLoss", "peptide_losses", "peptide_loss_sums", "displacement_rows", "displacement_errors",
-           "DisplacementErrors", "DisplacementMeter", "install", "uninstall", "dropin", "_lib"]
+           "DisplacementErrors", "DisplacementMeter", "TorsionStats", "dihedral_angles", "angle_histograms", "js_distance", "lagged_products",
+           "decorrelation", "eval_torsion_quads", "topology_atoms", "summary_metrics", "install", "uninstall", "dropin", "_lib"]

@@ -21,6 +21,8 @@ ABI_VERSION = 6  # LSL_VERSION of include/lsl_api.h this binding was written aga
 RK_SCRATCH_BYTES = 8192  # LSL_RK_SCRATCH_BYTES
 GEOM_MAX_A, GEOM_MAX_D = 2048, 4  # the native form of lsl_geom_loss_sums (csrc/k_geomloss.hip.h)
 DISP_MAX_D, DISP_MAX_UNITS = 4, 16777215  # the native form of lsl_disp_error_rows (csrc/k_disperr.hip.h): coordinates, K * B
+TORS_MAX_A, HIST_MAX_BINS, HIST2_MAX_BINS = 2044, 2048, 90  # the native forms of lsl_dihedral_angles / lsl_histogram (csrc/k_torsstat.hip.h)
+LAG_CHUNK, LAG_MAX_LAGS, LAG_MAX_ROWS = 448, 1 << 21, 65535  # lsl_lag_products: the fp32 chain m, nlag + 1, S * C of one call
 SI_SLAB = 4096  # LSL_SI_SLAB: elements of one trajectory per partial sum of lsl_si_reduce
 
 EXPORTED = (
@@ -28,6 +30,7 @@ EXPORTED = (
     "lsl_model_set_chunk", "lsl_model_set_attention_mode", "lsl_model_set_tail", "lsl_model_tail", "lsl_model_set_ln_fuse", "lsl_model_ln_fuse", "lsl_profile_kernel_name", "lsl_pass_size", "lsl_sampler_path", "lsl_workspace_bytes", "lsl_forward", "lsl_sample", "lsl_sample_ex", "lsl_debug_block", "lsl_debug_taps", "lsl_debug_mods",
     "lsl_si_loss_workspace_bytes", "lsl_si_loss", "lsl_si_reduce", "lsl_geom_loss_sums", "lsl_geom_loss_final",
     "lsl_peptide_loss_sums", "lsl_peptide_loss_final", "lsl_disp_error_rows", "lsl_disp_error_final",
+    "lsl_dihedral_angles", "lsl_histogram", "lsl_lag_products_workspace_bytes", "lsl_lag_products", "lsl_js_distance",
     "lsl_profile_enable", "lsl_profile_read", "lsl_randn", "lsl_rk_lincomb", "lsl_rk_dense", "lsl_rk_error_ratio",
     "lsl_decoder_create", "lsl_decoder_destroy", "lsl_decode_workspace_bytes", "lsl_decode",
     "lsl_encoder_create", "lsl_encoder_destroy", "lsl_encode_workspace_bytes", "lsl_encode",
@@ -176,6 +179,13 @@ def load() -> C.CDLL:
     lib.lsl_peptide_loss_final.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     lib.lsl_disp_error_rows.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int32] * 9 + [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.lsl_disp_error_final.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lsl_dihedral_angles.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.lsl_histogram.argtypes = [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                  C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.lsl_lag_products_workspace_bytes.argtypes = [C.c_int32] * 4
+    lib.lsl_lag_products_workspace_bytes.restype = C.c_size_t
+    lib.lsl_lag_products.argtypes = [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.lsl_js_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.lsl_randn.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
     lib.lsl_rk_lincomb.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.c_int32, C.c_uint64, C.c_void_p]
     lib.lsl_rk_dense.argtypes = [C.c_void_p] * 6 + [C.c_float, C.c_uint64, C.c_void_p]

@@ -2,7 +2,7 @@
 // network evaluation (latent_si_v31.py:168-188) and of the sampler loops (integrators.py:67-78,103-120)
 // on the caller's stream.  No allocation, no synchronisation, no host<->device copies.
 // One translation unit: this file = the entry points of the sampling path (model handle, forward, fused sampler + opt-in hipGraph replay,
-// noise, Runge-Kutta state arithmetic, the stochastic-interpolant objective around one evaluation, the geometry losses of the decoded positions, the peptide frame and torsion losses, the displacement errors (ADE / FDE, best-of-K), debug taps); host_common / host_launch / host_eval.hip.h = what they enqueue (host_graph.hip.h: the replay cache); decode_host.hip.h +
+// noise, Runge-Kutta state arithmetic, the stochastic-interpolant objective around one evaluation, the geometry losses of the decoded positions, the peptide frame and torsion losses, the displacement errors (ADE / FDE, best-of-K), the torsion statistics (dihedrals, histograms, lagged products, JS distance), debug taps); host_common / host_launch / host_eval.hip.h = what they enqueue (host_graph.hip.h: the replay cache); decode_host.hip.h +
 // stage1_api.hip.h = the frozen stage-1 encode / decode beside the path.
 #include "../../include/lsl_api.h"
 
@@ -31,6 +31,7 @@
 #include "k_geomloss.hip.h"
 #include "k_peptloss.hip.h"
 #include "k_disperr.hip.h"
+#include "k_torsstat.hip.h"
 #ifdef LSL_EXPERIMENTS  // measured-and-rejected GEMM structures, built only by tools/build_experiments.sh (never in the product library)
 #include "k_gemm_pp.hip.h"        // tools/experiments/ (on the include path of tools/build_experiments.sh only)
 #include "k_gemm_drain.hip.h"
@@ -371,6 +372,95 @@ int lsl_disp_error_final(const float *rows, const float *traj, const uint8_t *ma
     if (num_runs < 1 || num_runs > K) return fail(-3, "num_runs = %d outside 1..K = %d", num_runs, K);
     hipLaunchKernelGGL(k_disp_final, dim3(1), dim3(256), 0, (hipStream_t)stream, agents, totals, rows, traj, mask, (int)num_runs, (int)B, (int)A);
     LSL_CHECK_LAUNCH("lsl_disp_error_final");
+    return 0;
+} LSL_API_CATCH
+
+// ---- torsion statistics of a sampled peptide trajectory: dihedrals, histograms, lagged products, JS distance (k_torsstat.hip.h) ----
+int lsl_dihedral_angles(const float *pos, const int32_t *quads, const int32_t *quads_host, int64_t F, int32_t A, int32_t Q, float *angles,
+                        void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!pos || !quads || !quads_host || !angles) return fail(-1, "null argument");
+    if (A < 1 || A > LSL_TORS_MAX_A) return fail(-3, "A = %d outside the native form (1..%d atoms of a frame)", A, LSL_TORS_MAX_A);
+    if (Q < 1 || Q > 65536) return fail(-3, "Q = %d outside 1..65536 quadruples", Q);
+    const int fpb = LSL_TORS_LDS_ATOMS / A;
+    if (F < 1 || (F + fpb - 1) / fpb > 0x7fffffffLL) return fail(-3, "F = %lld frames: 1 .. %lld at A = %d", (long long)F, 0x7fffffffLL * fpb, A);
+    for (int i = 0; i < 4 * Q; ++i)
+        if (quads_host[i] < 0 || quads_host[i] >= A)
+            return fail(-3, "quads[%d][%d] = %d outside the frame's atoms 0..%d", i / 4, i % 4, quads_host[i], A - 1);
+    hipLaunchKernelGGL(k_dihedral, dim3((unsigned)((F + fpb - 1) / fpb)), dim3(256), 0, (hipStream_t)stream, angles, pos, (const int *)quads,
+                       (long long)F, (int)A, (int)Q, fpb);
+    LSL_CHECK_LAUNCH("lsl_dihedral_angles");
+    return 0;
+} LSL_API_CATCH
+
+int lsl_histogram(const float *x, int32_t S, int32_t n, int32_t Q, const double *edges, int32_t bins, int64_t *counts, const int32_t *pairs,
+                  const int32_t *pairs_host, int32_t P, const double *edges2a, const double *edges2b, int32_t bins2, int64_t *counts2,
+                  void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!x || !edges || !counts) return fail(-1, "null argument");
+    if (S < 1 || S > 65535) return fail(-3, "S = %d outside 1..65535 series", S);
+    if (n < 1 || Q < 1) return fail(-3, "n = %d and Q = %d must be positive", n, Q);
+    if (bins < 1 || bins > LSL_HIST_MAX_BINS) return fail(-3, "bins = %d outside 1..%d", bins, LSL_HIST_MAX_BINS);
+    const int qt = std::min<int>(Q, LSL_HIST_CELLS / bins);
+    if ((Q + qt - 1) / qt > 65535) return fail(-3, "Q = %d columns of %d bins: at most %d", Q, bins, 65535 * qt);
+    if (P < 0 || P > 65535) return fail(-3, "P = %d outside 0..65535 pairs", P);
+    if (P > 0) {
+        if (!pairs || !pairs_host || !edges2a || !edges2b || !counts2) return fail(-1, "null argument (P > 0 needs pairs, their host copy, both edge tables and counts2)");
+        if (bins2 < 1 || bins2 > LSL_HIST2_MAX_BINS) return fail(-3, "bins2 = %d outside 1..%d", bins2, LSL_HIST2_MAX_BINS);
+        for (int i = 0; i < 2 * P; ++i)
+            if (pairs_host[i] < 0 || pairs_host[i] >= Q) return fail(-3, "pairs[%d][%d] = %d outside the columns 0..%d", i / 2, i % 2, pairs_host[i], Q - 1);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned tb = (unsigned)(((long long)n + LSL_HIST_ROWS - 1) / LSL_HIST_ROWS);
+    hipLaunchKernelGGL(k_hist1, dim3(tb, (unsigned)((Q + qt - 1) / qt), (unsigned)S), dim3(256), 0, st, (unsigned long long *)counts, x, edges, (int)n,
+                       (int)Q, (int)bins, qt);
+    LSL_CHECK_LAUNCH("lsl_histogram");
+    if (P > 0) {
+        hipLaunchKernelGGL(k_hist2, dim3(tb, (unsigned)P, (unsigned)S), dim3(256), 0, st, (unsigned long long *)counts2, x, (const int *)pairs, edges2a,
+                           edges2b, (int)n, (int)Q, (int)P, (int)bins2);
+        LSL_CHECK_LAUNCH("lsl_histogram (pairs)");
+    }
+    return 0;
+} LSL_API_CATCH
+
+static const char *lag_shape_error(int32_t S, int32_t n, int32_t C, int32_t nlag) {
+    if (S < 1 || C < 1 || (long long)S * C > 65535) return "S and C must be positive and S * C at most 65535 (series x channels of one call)";
+    if (n < 1) return "n must be positive";
+    if (nlag < 0 || nlag >= n) return "nlag outside 0..n-1 (lag k has n - k terms)";
+    if ((long long)nlag + 1 > LSL_LAG_MAX_PART) return "nlag + 1 above 2^21 lags";
+    return nullptr;
+}
+
+size_t lsl_lag_products_workspace_bytes(int32_t S, int32_t n, int32_t C, int32_t nlag) {
+    if (lag_shape_error(S, n, C, nlag)) return 0;
+    return (size_t)S * C * lag_segments(n, nlag).nseg * ((size_t)nlag + 1) * sizeof(double);
+}
+
+int lsl_lag_products(const float *x, int32_t S, int32_t n, int32_t C, int32_t nlag, float *ac, void *workspace, size_t workspace_bytes,
+                     void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!x || !ac || !workspace) return fail(-1, "null argument");
+    if (const char *why = lag_shape_error(S, n, C, nlag)) return fail(-3, "S = %d, n = %d, C = %d, nlag = %d: %s", S, n, C, nlag, why);
+    const size_t need = lsl_lag_products_workspace_bytes(S, n, C, nlag);
+    if (workspace_bytes < need) return fail(-4, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    const LagSplit sp = lag_segments(n, nlag);
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned tiles = (unsigned)((nlag + LSL_LAG_TILE) / LSL_LAG_TILE);  // ceil((nlag + 1) / tile)
+    hipLaunchKernelGGL(k_lag_partial, dim3(tiles, (unsigned)sp.nseg, (unsigned)(S * C)), dim3(LSL_LAG_TILE), 0, st, (double *)workspace, x, (int)n, (int)C,
+                       (int)nlag, sp.cps);
+    LSL_CHECK_LAUNCH("lsl_lag_products");
+    hipLaunchKernelGGL(k_lag_final, dim3((unsigned)((nlag + 256) / 256), (unsigned)(S * C)), dim3(256), 0, st, ac, (const double *)workspace, (int)n,
+                       (int)nlag, sp.nseg);
+    LSL_CHECK_LAUNCH("lsl_lag_products (final)");
+    return 0;
+} LSL_API_CATCH
+
+int lsl_js_distance(const int64_t *counts_a, const int64_t *counts_b, int32_t rows, int32_t bins, double *out, void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!counts_a || !counts_b || !out) return fail(-1, "null argument");
+    if (rows < 1 || bins < 1) return fail(-3, "rows = %d and bins = %d must be positive", rows, bins);
+    hipLaunchKernelGGL(k_js, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, out, (const long long *)counts_a, (const long long *)counts_b, (int)bins);
+    LSL_CHECK_LAUNCH("lsl_js_distance");
     return 0;
 } LSL_API_CATCH
 
