@@ -42,7 +42,8 @@ extern "C" {
  * 6, later still: lsl_geom_loss_sums, lsl_geom_loss_final added the same way.
  * 6, later still: lsl_peptide_loss_sums, lsl_peptide_loss_final added the same way.
  * 6, later still: lsl_disp_error_rows, lsl_disp_error_final added the same way.
- * 6, later still: lsl_dihedral_angles, lsl_histogram, lsl_lag_products_workspace_bytes, lsl_lag_products, lsl_js_distance added the same way. */
+ * 6, later still: lsl_dihedral_angles, lsl_histogram, lsl_lag_products_workspace_bytes, lsl_lag_products, lsl_js_distance added the same way.
+ * 6, later still: lsl_lagged_moments_workspace_bytes, lsl_lagged_moments, lsl_project, lsl_assign_centers, lsl_transition_counts added the same way. */
 #define LSL_VERSION 6
 
 typedef struct lsl_model lsl_model;
@@ -321,6 +322,43 @@ int lsl_lag_products(const float *x, int32_t S, int32_t n, int32_t C, int32_t nl
  *   (a flattened 2-D table is a row): p, q = the rows over their sums, m = (p + q) / 2, sqrt((sum rel_entr(p, m) + sum rel_entr(q, m)) / 2),
  *   natural log, rel_entr(0, .) = 0, the bins added in index order in fp64.  A row that is all zero on either side gives NaN (0 / 0), as scipy. */
 int lsl_js_distance(const int64_t *counts_a, const int64_t *counts_b, int32_t rows, int32_t bins, double *out, void *stream);
+
+/* TICA and state statistics of the peptide evaluation: the second half of analyze_trajectory (eval_peptide.py:189-288, modules/analysis.py:36-56)
+ * behind the cos / sin torsion features - the lagged second moments a TICA model is estimated from, the projection with its running ranges,
+ * the nearest-centre assignment of kmeans.transform / analysis.discretize and the sliding-window transition counts of estimate_markov_model.
+ * Four independent calls; device pointers; nothing is allocated, nothing is synchronised, a refused call enqueues nothing.  No float atomics:
+ * integer atomics for counts and for minimum / maximum only, every float a sum in a fixed order that depends on the shape alone.
+ *
+ * lsl_lagged_moments: moments f64 [S, 2 F + 3 F^2] of x [S, n, F] f32 at lag, m = n - lag: per series sx [F] = sum_{t<m} x_t, sy [F] =
+ *   sum_{t<m} x_{t+lag}, xx [F, F] = sum x_t x_t^T, yy [F, F] = sum x_{t+lag} x_{t+lag}^T, xy [F, F] = sum x_t x_{t+lag}^T, in that order, full
+ *   row-major matrices.  Products in fp64 from the fp32 values (exact), added in fp64 in ascending t within a segment of 1024 time steps
+ *   (segment g: t in [1024 g, 1024 (g + 1)) below m - a function of (n, lag) alone), segments in segment order; each of the five a direct sum
+ *   over its own window: |error| <= (1024 + segments + 2) 2^-53 sum_t |x_a x_b|.  xx and yy are bit-symmetric; a series has the same bits
+ *   alone and inside a batch.  1 <= F <= 128, n >= 2, 1 <= lag < n, S <= 65535 (else -3).  workspace: lsl_lagged_moments_workspace_bytes(S, n,
+ *   F, lag) bytes of device memory (the fp64 segment sums: S * segments * (2 F + 3 F^2) * 8; 0 for a refused shape); -4 if smaller. */
+size_t lsl_lagged_moments_workspace_bytes(int32_t S, int32_t n, int32_t F, int32_t lag);
+int lsl_lagged_moments(const float *x, int32_t S, int32_t n, int32_t F, int32_t lag, double *moments, void *workspace, size_t workspace_bytes,
+                       void *stream);
+/* lsl_project: y f32 [n, d], y[t, j] = fp32(sum_f (x[t, f] - mean[f]) W[f, j]) of x [n, F] f32, mean f64 [F], W f64 [F, d]: the subtraction and
+ *   the fused chain over f ascending in fp64, one rounding to fp32.  lim (or NULL): f32 [2, d], in and out: lim[0, j] = min(lim[0, j], min_t
+ *   y[t, j]), lim[1, j] = max(lim[1, j], max_t y[t, j]), NaN values of y ignored - by integer atomics on an order-preserving key of the float
+ *   (the table holds keys while the call runs), so the result has no order dependence; start it at (+inf, -inf); lim itself must hold no NaN.
+ *   Two calls with one table give the joint ranges of two trajectories (eval_peptide.py:203-207) with no read-back.  1 <= F <= 128,
+ *   1 <= d <= 16, n >= 1. */
+int lsl_project(const float *x, int32_t n, int32_t F, const double *mean, const double *W, int32_t d, float *y, float *lim, void *stream);
+/* lsl_assign_centers: labels i32 [n], labels[t] = argmin_c sum_j (y[t, j] - centers[c, j])^2 of y [n, d] f32 and centers [k, d] f32
+ *   (kmeans.transform): differences and the fused sum over j ascending in fp64, ties to the lowest index as np.argmin; a row that holds a NaN
+ *   gets -1.  map (or NULL) i32 [k]: the label is map[argmin] (msm.metastable_assignments[...]), -1 when that is outside 0..nstates-1.
+ *   state_counts (or NULL) i64 [nstates] += the rows of each label in 0..nstates-1 (added to: chunks accumulate; the occupancies as exact
+ *   integers).  The centres stay in LDS: k <= 1024, d <= 64, k * d <= 8192; nstates 1..1024 when map or state_counts is given (ignored
+ *   otherwise). */
+int lsl_assign_centers(const float *y, int32_t n, int32_t d, const float *centers, int32_t k, const int32_t *map, int32_t nstates, int32_t *labels,
+                       int64_t *state_counts, void *stream);
+/* lsl_transition_counts: counts i64 [S, nstates, nstates] += #{t < n - lag : dtraj[s, t] = i, dtraj[s, t + lag] = j} of dtraj i32 [S, n]: the
+ *   sliding-window count matrix of estimate_markov_model(dtraj, lag).  A pair with either label outside 0..nstates-1 (the -1 of
+ *   lsl_assign_centers) is skipped.  The table is ADDED TO.  lag >= n adds nothing and returns 0.  lag >= 1, 1 <= nstates <= 128 (int32 counts
+ *   of a workgroup in LDS), S <= 65535. */
+int lsl_transition_counts(const int32_t *dtraj, int32_t S, int32_t n, int32_t lag, int32_t nstates, int64_t *counts, void *stream);
 
 /* Sampler loop (Sampler.sample_ode / sample_sde inner loops): applies n_steps affine updates to io->x
  * in place.  noise: device [n_noise, B*T*L*C] standard-normal draws, slice s belongs to step s (the

@@ -23,6 +23,10 @@ Public surface (mirrors the reference's for this path only):
                                    <- the torsion statistics of eval_peptide.analyze_trajectory (histograms of every torsion and of
                                       chosen pairs, Jensen-Shannon distances to the MD reference, decorrelation curves) of the sampled
                                       atom14 positions on the device (torsion_stats.py)
+  TicaModel, tica_jsd, lagged_moments, tica_covariances, assign_centers, transition_counts, metastable_jsd, ...
+                                   <- the TICA and Markov-state half of analyze_trajectory (eval_peptide.py:189-288): the lagged second
+                                      moments and the projection of a TICA model, TICA-0 / TICA-0,1 on the joint range, nearest-centre
+                                      labels, state occupancies and transition counts on the device (tica.py)
   install()                        <- rebinds the reference's module-level ``Sampler`` (lightning_base.py:10); see dropin.py
 The compute lives in liblamslide_hip.so (include/lsl_api.h); build it with ``__graft_entry__.build()``.
 """
@@ -36,6 +40,9 @@ from .metrics import DisplacementErrors, DisplacementMeter, displacement_errors,
 from .peptide_loss import PeptideLoss, peptide_loss_sums, peptide_losses
 from .sampling import (RolloutSampler, SecondStageSampler, best_of_k_errors, min_ade_fde, sample_rollout, sample_sharded,
                        setup_conditioning, shard_bounds)
+from . import tica
+from .tica import (TicaHistograms, TicaModel, assign_centers, cossin_features, lagged_moments, linspace_edges, metastable_jsd, solve_tica,
+                   tica_autocovariance, tica_covariances, tica_dimension, tica_histograms, tica_jsd, transition_counts)
 from .torsion_stats import (TorsionStats, angle_histograms, decorrelation, dihedral_angles, eval_torsion_quads, js_distance, lagged_products,
                             summary_metrics, topology_atoms)
 from .transport import (CreateTransport, ModelType, PathType, Sampler, SampleResult, Transport, WeightType, as_transport, device_randn,
@@ -45,4 +52,6 @@ __all__ = ["LatentSIV3", "CreateTransport", "Transport", "Sampler", "SampleResul
            "SecondStageSampler", "setup_conditioning", "sample_sharded", "shard_bounds", "min_ade_fde", "sample_rollout", "best_of_k_errors",
            "RolloutSampler", "Stage1Decoder", "Stage1Encoder", "as_transport", "device_randn", "mix_seed", "si_reduce", "Loss", "geom_losses", "geom_loss_sums", "PeptideLoss", "peptide_losses", "peptide_loss_sums", "displacement_rows", "displacement_errors",
            "DisplacementErrors", "DisplacementMeter", "TorsionStats", "dihedral_angles", "angle_histograms", "js_distance", "lagged_products",
-           "decorrelation", "eval_torsion_quads", "topology_atoms", "summary_metrics", "install", "uninstall", "dropin", "_lib"]
+           "decorrelation", "eval_torsion_quads", "topology_atoms", "summary_metrics", "tica", "TicaModel", "TicaHistograms", "cossin_features",
+           "lagged_moments", "tica_covariances", "solve_tica", "tica_dimension", "linspace_edges", "tica_histograms", "tica_jsd", "assign_centers",
+           "transition_counts", "metastable_jsd", "tica_autocovariance", "install", "uninstall", "dropin", "_lib"]

@@ -23,6 +23,10 @@ GEOM_MAX_A, GEOM_MAX_D = 2048, 4  # the native form of lsl_geom_loss_sums (csrc/
 DISP_MAX_D, DISP_MAX_UNITS = 4, 16777215  # the native form of lsl_disp_error_rows (csrc/k_disperr.hip.h): coordinates, K * B
 TORS_MAX_A, HIST_MAX_BINS, HIST2_MAX_BINS = 2044, 2048, 90  # the native forms of lsl_dihedral_angles / lsl_histogram (csrc/k_torsstat.hip.h)
 LAG_CHUNK, LAG_MAX_LAGS, LAG_MAX_ROWS = 448, 1 << 21, 65535  # lsl_lag_products: the fp32 chain m, nlag + 1, S * C of one call
+MOM_SEG = 1024  # lsl_lagged_moments (csrc/k_tica.hip.h): segment g holds the time steps [g * MOM_SEG, (g + 1) * MOM_SEG) below n - lag
+MOM_CHAIN = MOM_SEG  # the longest fp64 addition chain inside a segment
+MOM_MAX_F, PROJ_MAX_D = 128, 16  # the native forms of lsl_lagged_moments / lsl_project: features, output columns
+ASG_MAX_K, ASG_MAX_D, ASG_CELLS, ASG_MAX_STATES, TR_MAX_STATES = 1024, 64, 8192, 1024, 128  # lsl_assign_centers, lsl_transition_counts
 SI_SLAB = 4096  # LSL_SI_SLAB: elements of one trajectory per partial sum of lsl_si_reduce
 
 EXPORTED = (
@@ -31,10 +35,16 @@ EXPORTED = (
     "lsl_si_loss_workspace_bytes", "lsl_si_loss", "lsl_si_reduce", "lsl_geom_loss_sums", "lsl_geom_loss_final",
     "lsl_peptide_loss_sums", "lsl_peptide_loss_final", "lsl_disp_error_rows", "lsl_disp_error_final",
     "lsl_dihedral_angles", "lsl_histogram", "lsl_lag_products_workspace_bytes", "lsl_lag_products", "lsl_js_distance",
+    "lsl_lagged_moments_workspace_bytes", "lsl_lagged_moments", "lsl_project", "lsl_assign_centers", "lsl_transition_counts",
     "lsl_profile_enable", "lsl_profile_read", "lsl_randn", "lsl_rk_lincomb", "lsl_rk_dense", "lsl_rk_error_ratio",
     "lsl_decoder_create", "lsl_decoder_destroy", "lsl_decode_workspace_bytes", "lsl_decode",
     "lsl_encoder_create", "lsl_encoder_destroy", "lsl_encode_workspace_bytes", "lsl_encode",
 )
+
+
+def mom_segments(n: int, lag: int) -> int:
+    """The segment rule of lsl_lagged_moments: the number of segments of a series of n steps at this lag."""
+    return -(-(int(n) - int(lag)) // MOM_SEG)
 
 
 class ModelDesc(C.Structure):
@@ -186,6 +196,12 @@ def load() -> C.CDLL:
     lib.lsl_lag_products_workspace_bytes.restype = C.c_size_t
     lib.lsl_lag_products.argtypes = [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.lsl_js_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.lsl_lagged_moments_workspace_bytes.argtypes = [C.c_int32] * 4
+    lib.lsl_lagged_moments_workspace_bytes.restype = C.c_size_t
+    lib.lsl_lagged_moments.argtypes = [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.lsl_project.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lsl_assign_centers.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lsl_transition_counts.argtypes = [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p]
     lib.lsl_randn.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
     lib.lsl_rk_lincomb.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.c_int32, C.c_uint64, C.c_void_p]
     lib.lsl_rk_dense.argtypes = [C.c_void_p] * 6 + [C.c_float, C.c_uint64, C.c_void_p]

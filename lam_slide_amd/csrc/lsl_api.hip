@@ -2,7 +2,7 @@
 // network evaluation (latent_si_v31.py:168-188) and of the sampler loops (integrators.py:67-78,103-120)
 // on the caller's stream.  No allocation, no synchronisation, no host<->device copies.
 // One translation unit: this file = the entry points of the sampling path (model handle, forward, fused sampler + opt-in hipGraph replay,
-// noise, Runge-Kutta state arithmetic, the stochastic-interpolant objective around one evaluation, the geometry losses of the decoded positions, the peptide frame and torsion losses, the displacement errors (ADE / FDE, best-of-K), the torsion statistics (dihedrals, histograms, lagged products, JS distance), debug taps); host_common / host_launch / host_eval.hip.h = what they enqueue (host_graph.hip.h: the replay cache); decode_host.hip.h +
+// noise, Runge-Kutta state arithmetic, the stochastic-interpolant objective around one evaluation, the geometry losses of the decoded positions, the peptide frame and torsion losses, the displacement errors (ADE / FDE, best-of-K), the torsion statistics (dihedrals, histograms, lagged products, JS distance), the TICA and state statistics (lagged second moments, projection, nearest centre, transition counts), debug taps); host_common / host_launch / host_eval.hip.h = what they enqueue (host_graph.hip.h: the replay cache); decode_host.hip.h +
 // stage1_api.hip.h = the frozen stage-1 encode / decode beside the path.
 #include "../../include/lsl_api.h"
 
@@ -32,6 +32,7 @@
 #include "k_peptloss.hip.h"
 #include "k_disperr.hip.h"
 #include "k_torsstat.hip.h"
+#include "k_tica.hip.h"
 #ifdef LSL_EXPERIMENTS  // measured-and-rejected GEMM structures, built only by tools/build_experiments.sh (never in the product library)
 #include "k_gemm_pp.hip.h"        // tools/experiments/ (on the include path of tools/build_experiments.sh only)
 #include "k_gemm_drain.hip.h"
@@ -461,6 +462,95 @@ int lsl_js_distance(const int64_t *counts_a, const int64_t *counts_b, int32_t ro
     if (rows < 1 || bins < 1) return fail(-3, "rows = %d and bins = %d must be positive", rows, bins);
     hipLaunchKernelGGL(k_js, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, out, (const long long *)counts_a, (const long long *)counts_b, (int)bins);
     LSL_CHECK_LAUNCH("lsl_js_distance");
+    return 0;
+} LSL_API_CATCH
+
+// ---- TICA and state statistics of the peptide evaluation: lagged second moments, projection, nearest centre, transition counts (k_tica.hip.h) ----
+static const char *moments_shape_error(int32_t S, int32_t n, int32_t F, int32_t lag) {
+    if (S < 1 || S > 65535) return "S outside 1..65535 series";
+    if (F < 1 || F > LSL_MOM_MAX_F) return "F outside the native form (1..128 features)";
+    if (n < 2) return "n must be at least 2";
+    if (lag < 1 || lag >= n) return "lag outside 1..n-1 (the window has n - lag rows)";
+    return nullptr;
+}
+
+size_t lsl_lagged_moments_workspace_bytes(int32_t S, int32_t n, int32_t F, int32_t lag) {
+    if (moments_shape_error(S, n, F, lag)) return 0;
+    return (size_t)S * mom_segments(n, lag) * mom_entries(F) * sizeof(double);
+}
+
+int lsl_lagged_moments(const float *x, int32_t S, int32_t n, int32_t F, int32_t lag, double *moments, void *workspace, size_t workspace_bytes,
+                       void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!x || !moments || !workspace) return fail(-1, "null argument");
+    if (const char *why = moments_shape_error(S, n, F, lag)) return fail(-3, "S = %d, n = %d, F = %d, lag = %d: %s", S, n, F, lag, why);
+    const size_t need = lsl_lagged_moments_workspace_bytes(S, n, F, lag);
+    if (workspace_bytes < need) return fail(-4, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    hipStream_t st = (hipStream_t)stream;
+    const int nseg = mom_segments(n, lag), T = mom_block(F), nb = (F + T - 1) / T;
+    const dim3 grid((unsigned)nseg, (unsigned)((nb * nb + 255) / 256), (unsigned)S);
+    if (T == 2)
+        hipLaunchKernelGGL(k_moments_partial<2>, grid, dim3(256), 0, st, (double *)workspace, x, (int)n, (int)F, (int)lag);
+    else
+        hipLaunchKernelGGL(k_moments_partial<4>, grid, dim3(256), 0, st, (double *)workspace, x, (int)n, (int)F, (int)lag);
+    LSL_CHECK_LAUNCH("lsl_lagged_moments");
+    const long long E = (long long)mom_entries(F);
+    hipLaunchKernelGGL(k_moments_final, dim3((unsigned)((E + 255) / 256), (unsigned)S), dim3(256), 0, st, moments, (const double *)workspace, E, nseg);
+    LSL_CHECK_LAUNCH("lsl_lagged_moments (final)");
+    return 0;
+} LSL_API_CATCH
+
+int lsl_project(const float *x, int32_t n, int32_t F, const double *mean, const double *W, int32_t d, float *y, float *lim, void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!x || !mean || !W || !y) return fail(-1, "null argument");
+    if (n < 1) return fail(-3, "n = %d must be positive", n);
+    if (F < 1 || F > LSL_MOM_MAX_F) return fail(-3, "F = %d outside the native form (1..%d features)", F, LSL_MOM_MAX_F);
+    if (d < 1 || d > LSL_PROJ_MAX_D) return fail(-3, "d = %d outside the native form (1..%d output columns)", d, LSL_PROJ_MAX_D);
+    hipStream_t st = (hipStream_t)stream;
+    if (lim) {
+        hipLaunchKernelGGL(k_lim_keys, dim3(1), dim3(64), 0, st, lim, 2 * (int)d);
+        LSL_CHECK_LAUNCH("lsl_project (limits to keys)");
+    }
+    hipLaunchKernelGGL(k_project, dim3((unsigned)(((long long)n + LSL_PROJ_ROWS - 1) / LSL_PROJ_ROWS)), dim3(256), 0, st, y, x, mean, W, (unsigned *)lim,
+                       (int)n, (int)F, (int)d);
+    LSL_CHECK_LAUNCH("lsl_project");
+    if (lim) {
+        hipLaunchKernelGGL(k_lim_floats, dim3(1), dim3(64), 0, st, lim, 2 * (int)d);
+        LSL_CHECK_LAUNCH("lsl_project (keys to limits)");
+    }
+    return 0;
+} LSL_API_CATCH
+
+int lsl_assign_centers(const float *y, int32_t n, int32_t d, const float *centers, int32_t k, const int32_t *map, int32_t nstates, int32_t *labels,
+                       int64_t *state_counts, void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!y || !centers || !labels) return fail(-1, "null argument");
+    if (n < 1) return fail(-3, "n = %d must be positive", n);
+    if (d < 1 || d > LSL_ASG_MAX_D) return fail(-3, "d = %d outside the native form (1..%d coordinates)", d, LSL_ASG_MAX_D);
+    if (k < 1 || k > LSL_ASG_MAX_K || (long long)k * d > LSL_ASG_CELLS)
+        return fail(-3, "k = %d centres of d = %d outside the native form (1..%d centres, k * d <= %d: the centres stay in LDS)", k, d, LSL_ASG_MAX_K, LSL_ASG_CELLS);
+    if ((map || state_counts) && (nstates < 1 || nstates > LSL_ASG_MAX_STATES))
+        return fail(-3, "nstates = %d outside 1..%d (a map or a count table needs the number of states)", nstates, LSL_ASG_MAX_STATES);
+    const int ra = std::min<int>(256, LSL_ASG_TILE / d);
+    hipLaunchKernelGGL(k_assign, dim3((unsigned)(((long long)n + ra - 1) / ra)), dim3(256), 0, (hipStream_t)stream, (int *)labels,
+                       (unsigned long long *)state_counts, y, centers, (const int *)map, (int)n, (int)d, (int)k, (int)nstates, ra);
+    LSL_CHECK_LAUNCH("lsl_assign_centers");
+    return 0;
+} LSL_API_CATCH
+
+int lsl_transition_counts(const int32_t *dtraj, int32_t S, int32_t n, int32_t lag, int32_t nstates, int64_t *counts, void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!dtraj || !counts) return fail(-1, "null argument");
+    if (S < 1 || S > 65535) return fail(-3, "S = %d outside 1..65535 series", S);
+    if (n < 1) return fail(-3, "n = %d must be positive", n);
+    if (lag < 1) return fail(-3, "lag = %d must be positive", lag);
+    if (nstates < 1 || nstates > LSL_TR_MAX_STATES)
+        return fail(-3, "nstates = %d outside the native form (1..%d: the counts of a workgroup stay in LDS)", nstates, LSL_TR_MAX_STATES);
+    if (lag >= n) return 0;  // (no pair: nothing to add)
+    const unsigned tb = (unsigned)(((long long)n - lag + LSL_TR_ROWS - 1) / LSL_TR_ROWS);
+    hipLaunchKernelGGL(k_transitions, dim3(tb, (unsigned)S), dim3(256), 0, (hipStream_t)stream, (unsigned long long *)counts, (const int *)dtraj, (int)n,
+                       (int)lag, (int)nstates);
+    LSL_CHECK_LAUNCH("lsl_transition_counts");
     return 0;
 } LSL_API_CATCH
 

@@ -1,0 +1,409 @@
+"""The second half of the peptide evaluation's tail: TICA and the state statistics of a sampled trajectory, on the device.
+
+  cossin_features     <- pyemma's ``add_*_torsions(cossin=True)`` columns of a table of torsion angles: cos q0, sin q0, cos q1, ...
+  lagged_moments      <- the five sums a TICA estimate is made of: sum x_t, sum x_{t+lag}, sum x_t x_t^T, sum x_{t+lag} x_{t+lag}^T,
+                         sum x_t x_{t+lag}^T over t < n - lag, float64
+  tica_covariances    <- the reversible estimator's mean, C0 and C_lag from them (float64, on the device)
+  TicaModel           <- ``pyemma.coordinates.tica(ref, lag=1000, kinetic_map=True)`` (modules/analysis.py:36-39): ``fit`` (moments on the
+                         device, the F x F eigenproblem ``solve_tica`` in numpy on the host), ``from_arrays`` for a model pyemma fitted,
+                         ``transform`` (the projection, with the running minimum / maximum of every column)
+  linspace_edges      <- ``np.linspace(lo, hi, bins + 1)``'s bits from device scalars: the joint range feeds the histograms with no read-back
+  tica_jsd            <- ``out["JSD"]["TICA-0"]`` / ``["TICA-0,1"]`` (eval_peptide.py:199-219); ``tica_histograms`` returns what it is made of
+  assign_centers      <- ``kmeans.transform(y)[:, 0]`` and ``analysis.discretize`` (through ``msm.metastable_assignments``), with the
+                         state occupancies as exact integer counts
+  transition_counts   <- the sliding-window count matrix of ``pyemma.msm.estimate_markov_model(dtraj, lag)``
+  metastable_jsd      <- the "MSMS" entry of ``calc_summary_metrics``
+  tica_autocovariance <- ``acovf(tica[:, 0], adjusted=True, demean=False, nlag=)``
+
+The device form is liblamslide_hip.so (``lsl_lagged_moments`` / ``lsl_project`` / ``lsl_assign_centers`` / ``lsl_transition_counts``,
+csrc/k_tica.hip.h; the histograms and distances are ``lsl_histogram`` / ``lsl_js_distance`` of ``torsion_stats``).  The dispatch rule is
+``torsion_stats.fused_applies``: float32 tensors (labels: int32) on the GPU, nothing requires grad, a native shape; anything else takes a
+numpy / torch float64 restatement with the same outputs.  ``last_path[name]`` tells which of the two ("fused" / "torch") ran last.
+
+Not here: k-means fitting (pyemma's seeded k-means++ cannot be reproduced: the centres come from the caller), the reversible
+maximum-likelihood MSM estimate and PCCA (they take the count matrix ``transition_counts`` returns), plots.  The estimator is fixed as
+mathematics below and checked against numpy / scipy; parity with a live pyemma was not checked - a model pyemma fitted enters through
+``TicaModel.from_arrays``."""
+from __future__ import annotations
+
+from typing import Dict, NamedTuple, Optional, Tuple
+
+import numpy as np
+import torch
+from torch import Tensor
+
+from . import _lib
+from . import torsion_stats as _ts
+from .torsion_stats import fused_applies, js_distance, lagged_products
+
+last_path: Dict[str, str] = {}
+_PAIR01 = np.array([[0, 1]], dtype=np.int32)
+_pair01_on: dict = {}
+
+
+def _stream(dev) -> int:
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+# ---- features ----
+def cossin_features(angles: Tensor) -> Tensor:
+    """angles [..., n, Q] -> [..., n, 2 Q]: columns cos q0, sin q0, cos q1, sin q1, ... (pyemma's ``cossin=True`` order)."""
+    if angles.dim() < 1:
+        raise ValueError(f"expected angles [..., Q], got {tuple(angles.shape)}")
+    return torch.stack([torch.cos(angles), torch.sin(angles)], dim=-1).reshape(*angles.shape[:-1], 2 * angles.shape[-1])
+
+
+# ---- a. lagged second moments ----
+def _moments_torch(v: Tensor, lag: int):
+    v = v.double()
+    m = v.shape[1] - lag
+    a, b = v[:, :m], v[:, lag:]
+    at, bt = a.transpose(1, 2), b.transpose(1, 2)
+    return a.sum(dim=1), b.sum(dim=1), at @ a, bt @ b, at @ b
+
+
+def lagged_moments(x: Tensor, lag: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """x [n, F] or [S, n, F], 1 <= lag < n -> (sx, sy, xx, yy, xy), float64 [(S,) F] x 2 and [(S,) F, F] x 3, the sums over t < m = n - lag
+    of x_t, x_{t+lag}, x_t x_t^T, x_{t+lag} x_{t+lag}^T, x_t x_{t+lag}^T.  The device form multiplies in float64 (exact for float32
+    values) and adds in ascending t within segments of ``_lib.MOM_SEG`` steps, the segments in order: every entry within
+    ``(MOM_CHAIN + segments + 2) * 2^-53 * sum |x_a x_b|`` of the exact sum, xx and yy bit-symmetric, a series' bits the same alone and
+    in a batch."""
+    if x.dim() not in (2, 3):
+        raise ValueError(f"expected x [n, F] or [S, n, F], got {tuple(x.shape)}")
+    v = x if x.dim() == 3 else x[None]
+    S, n, F = (int(d) for d in v.shape)
+    lag = int(lag)
+    if min(S, F) < 1 or n < 2:
+        raise ValueError(f"x {tuple(x.shape)}: at least one series, one feature and two steps")
+    if not 1 <= lag < n:
+        raise ValueError(f"lag = {lag} outside 1..n-1 = {n - 1}: the window has n - lag rows")
+    if fused_applies(v) and F <= _lib.MOM_MAX_F and S <= 65535:
+        lib, dev = _lib.load(), v.device
+        vc = v.detach().contiguous()
+        with torch.cuda.device(dev):
+            need = lib.lsl_lagged_moments_workspace_bytes(S, n, F, lag)
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            out = torch.empty(S, 2 * F + 3 * F * F, dtype=torch.float64, device=dev)
+            _lib.check(lib.lsl_lagged_moments(vc.data_ptr(), S, n, F, lag, out.data_ptr(), ws.data_ptr(), need, _stream(dev)))
+        mats = out[:, 2 * F:].reshape(S, 3, F, F)
+        res = (out[:, :F], out[:, F:2 * F], mats[:, 0], mats[:, 1], mats[:, 2])
+        last_path["lagged_moments"] = "fused"
+    else:
+        res = _moments_torch(v.detach(), lag)
+        last_path["lagged_moments"] = "torch"
+    return res if x.dim() == 3 else tuple(r[0] for r in res)
+
+
+def tica_covariances(x: Tensor, lag: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """x [n, F] or [S, n, F] -> (mean [(S,) F], C0 [(S,) F, F], C_lag [(S,) F, F]), float64 on x's device: the reversible estimator
+    ``mean = (sx + sy) / 2m``, ``C0 = (xx + yy) / 2m - mean mean^T``, ``C_lag = (xy + xy^T) / 2m - mean mean^T``, m = n - lag, no Bessel
+    correction.  Both matrices are bit-symmetric."""
+    sx, sy, xx, yy, xy = lagged_moments(x, lag)
+    last_path["tica_covariances"] = last_path["lagged_moments"]
+    two_m = 2.0 * (int(x.shape[-2]) - int(lag))
+    mean = (sx + sy) / two_m
+    mm = mean[..., :, None] * mean[..., None, :]
+    return mean, (xx + yy) / two_m - mm, (xy + xy.transpose(-1, -2)) / two_m - mm
+
+
+# ---- the model ----
+def solve_tica(C0, Ct, epsilon: float = 1e-6) -> Tuple[np.ndarray, np.ndarray]:
+    """The generalised symmetric eigenproblem ``Ct r = lambda C0 r`` in numpy float64 -> (eigenvalues [r] descending, R [F, r] with
+    ``R^T C0 R = I``): the symmetric eigendecomposition of C0, eigenvalues <= ``epsilon`` dropped, ``L = V diag(s^-1/2)``, the symmetric
+    eigendecomposition of ``L^T Ct L``, ``R = L U``; each column's sign set so that its entry of largest magnitude is positive."""
+    C0, Ct = np.asarray(C0, dtype=np.float64), np.asarray(Ct, dtype=np.float64)
+    if C0.ndim != 2 or C0.shape[0] != C0.shape[1] or Ct.shape != C0.shape:
+        raise ValueError(f"expected two square matrices of one shape, got {C0.shape} and {Ct.shape}")
+    s, V = np.linalg.eigh(C0)
+    keep = s > epsilon
+    if not keep.any():
+        raise ValueError(f"no eigenvalue of C0 above epsilon = {epsilon}")
+    L = V[:, keep] / np.sqrt(s[keep])
+    M = L.T @ Ct @ L
+    lam, U = np.linalg.eigh((M + M.T) / 2)
+    order = np.argsort(-lam, kind="stable")
+    lam, R = lam[order], L @ U[:, order]
+    top = np.abs(R).argmax(axis=0)
+    R = R * np.where(R[top, np.arange(R.shape[1])] < 0, -1.0, 1.0)
+    return lam, R
+
+
+def tica_dimension(eigenvalues, var_cutoff: float = 0.95) -> int:
+    """``searchsorted(cumsum(lambda^2) / sum(lambda^2), var_cutoff) + 1``: the leading components that hold ``var_cutoff`` of the kinetic
+    variance."""
+    lam2 = np.asarray(eigenvalues, dtype=np.float64) ** 2
+    return min(int(np.searchsorted(np.cumsum(lam2) / lam2.sum(), var_cutoff)) + 1, lam2.size)
+
+
+class TicaModel:
+    """``mean`` [F], ``eigenvectors`` R [F, r], ``eigenvalues`` [r] (numpy float64, on the host), ``dim``, ``kinetic_map``, ``lag``;
+    ``W`` [F, dim] = R[:, :dim], times diag(eigenvalues[:dim]) under the kinetic map.  ``transform`` uploads mean and W once per device."""
+
+    def __init__(self, mean, eigenvectors, eigenvalues, dim: int, kinetic_map: bool = True, lag: Optional[int] = None) -> None:
+        self.mean = np.ascontiguousarray(mean, dtype=np.float64).reshape(-1)
+        self.eigenvectors = np.ascontiguousarray(eigenvectors, dtype=np.float64)
+        self.eigenvalues = np.ascontiguousarray(eigenvalues, dtype=np.float64).reshape(-1)
+        F = self.mean.size
+        if self.eigenvectors.ndim != 2 or self.eigenvectors.shape[0] != F or self.eigenvectors.shape[1] != self.eigenvalues.size:
+            raise ValueError(f"mean [{F}], eigenvectors {self.eigenvectors.shape} and eigenvalues [{self.eigenvalues.size}] do not fit: [F], [F, r], [r]")
+        self.dim, self.kinetic_map, self.lag = int(dim), bool(kinetic_map), lag
+        if not 1 <= self.dim <= self.eigenvalues.size:
+            raise ValueError(f"dim = {dim} outside 1..{self.eigenvalues.size}")
+        W = self.eigenvectors[:, :self.dim]
+        self.W = np.ascontiguousarray(W * self.eigenvalues[:self.dim] if self.kinetic_map else W)
+        self._on: dict = {}
+
+    @classmethod
+    def fit(cls, x: Tensor, lag: int = 1000, epsilon: float = 1e-6, var_cutoff: float = 0.95, kinetic_map: bool = True) -> "TicaModel":
+        """x [n, F] (the MD reference's features).  The moments and covariances on x's device, one copy of C0 and C_lag to the host,
+        ``solve_tica`` there; ``dim`` from ``var_cutoff`` (``tica_dimension``)."""
+        if x.dim() != 2:
+            raise ValueError(f"expected x [n, F], got {tuple(x.shape)}")
+        mean, C0, Ct = tica_covariances(x, lag)
+        last_path["fit"] = last_path["tica_covariances"]
+        host = torch.stack([C0, Ct]).cpu().numpy()
+        lam, R = solve_tica(host[0], host[1], epsilon)
+        return cls(mean.cpu().numpy(), R, lam, tica_dimension(lam, var_cutoff), kinetic_map, int(lag))
+
+    @classmethod
+    def from_arrays(cls, mean, eigenvectors, eigenvalues, dim: Optional[int] = None, kinetic_map: bool = True) -> "TicaModel":
+        """A stored model - pyemma's ``tica.mean``, ``tica.eigenvectors``, ``tica.eigenvalues`` and ``tica.dimension()``; ``dim`` None
+        keeps every column of ``eigenvectors``."""
+        ev = np.asarray(eigenvectors)
+        return cls(mean, ev, eigenvalues, ev.shape[1] if dim is None else dim, kinetic_map)
+
+    def _tensors(self, dev) -> Tuple[Tensor, Tensor]:
+        if dev not in self._on:
+            self._on[dev] = (torch.from_numpy(self.mean).to(dev), torch.from_numpy(self.W).to(dev))
+        return self._on[dev]
+
+    def transform(self, x: Tensor, lim: Optional[Tensor] = None) -> Tensor:
+        """x [n, F] or [S, n, F] -> y float32 [(S,) n, dim], ``y[t, j] = float32(sum_f (x[t, f] - mean[f]) W[f, j])`` (subtraction and sum in
+        float64, one rounding).  ``lim`` float32 [2, dim] on x's device is updated in place: row 0 the minimum of itself and every y[:, j],
+        row 1 the maximum, NaN values of y ignored - start it at (+inf, -inf)."""
+        F, d = self.mean.size, self.dim
+        if x.dim() not in (2, 3) or x.shape[-1] != F:
+            raise ValueError(f"expected x [n, {F}] or [S, n, {F}], got {tuple(x.shape)}")
+        if x.numel() == 0:
+            raise ValueError(f"empty x {tuple(x.shape)}")
+        if lim is not None and (tuple(lim.shape) != (2, d) or lim.dtype != torch.float32 or lim.device != x.device or not lim.is_contiguous()):
+            raise ValueError(f"lim must be a contiguous float32 [2, {d}] on {x.device}")
+        mean, W = self._tensors(x.device)
+        rows = x.numel() // F
+        if fused_applies(x) and F <= _lib.MOM_MAX_F and d <= _lib.PROJ_MAX_D and rows < 2 ** 31:
+            xc, dev = x.detach().contiguous(), x.device
+            with torch.cuda.device(dev):
+                y = torch.empty(*x.shape[:-1], d, dtype=torch.float32, device=dev)
+                _lib.check(_lib.load().lsl_project(xc.data_ptr(), rows, F, mean.data_ptr(), W.data_ptr(), d, y.data_ptr(),
+                                                   None if lim is None else lim.data_ptr(), _stream(dev)))
+            last_path["transform"] = "fused"
+            return y
+        y = ((x.detach().double() - mean) @ W).float()
+        if lim is not None:
+            flat, nan = y.reshape(-1, d), torch.isnan(y.reshape(-1, d))
+            inf = torch.full((), float("inf"), dtype=torch.float32, device=y.device)
+            lim[0].copy_(torch.minimum(lim[0], torch.where(nan, inf, flat).amin(dim=0)))
+            lim[1].copy_(torch.maximum(lim[1], torch.where(nan, -inf, flat).amax(dim=0)))
+        last_path["transform"] = "torch"
+        return y
+
+
+# ---- histograms on the joint range ----
+def linspace_edges(lo, hi, bins: int) -> Tensor:
+    """float64 [bins + 1] on ``lo``'s device with ``np.linspace(lo, hi, bins + 1)``'s bits, from scalars that may live on the device (no
+    synchronisation): ``i * step`` then ``+ lo`` as two roundings, ``step = (hi - lo) / bins``, the last edge set to ``hi``; ``lo == hi``
+    is widened to (lo - 0.5, hi + 0.5) first, as ``np.histogram`` does with such a range."""
+    bins = int(bins)
+    if bins < 1:
+        raise ValueError(f"bins = {bins} must be positive")
+    lo = torch.as_tensor(lo).detach().double().reshape(())
+    hi = torch.as_tensor(hi).detach().double().reshape(()).to(lo.device)
+    same = lo == hi
+    lo, hi = torch.where(same, lo - 0.5, lo), torch.where(same, hi + 0.5, hi)
+    step = (hi - lo) / torch.full((), bins, dtype=torch.float64, device=lo.device)  # (a tensor divisor: a true division, not a reciprocal)
+    e = torch.arange(bins + 1, dtype=torch.float64, device=lo.device) * step
+    e = e + lo
+    e[bins] = hi
+    return e
+
+
+class TicaHistograms(NamedTuple):
+    """What ``tica_jsd`` is made of: the projections (float32 [n, dim]), the joint ranges ``lim`` (float32 [2, dim]), the edge tables
+    (float64: ``edges`` of TICA-0 at ``bins``, ``edges2a`` / ``edges2b`` of TICA-0 / TICA-1 at ``bins2``; None when dim == 1), the counts
+    (int64 [bins]) and the joint counts (int64 [bins2, bins2] or None) of the reference and of the sampled trajectory."""
+    y_ref: Tensor
+    y_traj: Tensor
+    lim: Tensor
+    edges: Tensor
+    edges2a: Optional[Tensor]
+    edges2b: Optional[Tensor]
+    ref_counts: Tensor
+    traj_counts: Tensor
+    ref_counts2: Optional[Tensor]
+    traj_counts2: Optional[Tensor]
+
+
+def _counts(y: Tensor, edges: Tensor, ea: Optional[Tensor], eb: Optional[Tensor]) -> Tuple[Tensor, Optional[Tensor], str]:
+    """np.histogram of y[:, 0] on ``edges`` and np.histogram2d of (y[:, 0], y[:, 1]) on (ea, eb), on y's device."""
+    two = ea is not None
+    x = y[:, :2 if two else 1].contiguous()[None]
+    n, Q, bins, bins2 = int(x.shape[1]), int(x.shape[2]), edges.numel() - 1, (ea.numel() - 1) if two else 0
+    dev = y.device
+    counts = torch.zeros(1, Q, bins, dtype=torch.int64, device=dev)
+    counts2 = torch.zeros(1, 1, bins2, bins2, dtype=torch.int64, device=dev) if two else None
+    if fused_applies(x) and edges.is_cuda and bins <= _lib.HIST_MAX_BINS and bins2 <= _lib.HIST2_MAX_BINS and n < 2 ** 31:
+        if two and dev not in _pair01_on:
+            _pair01_on[dev] = torch.from_numpy(_PAIR01).to(dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().lsl_histogram(x.data_ptr(), 1, n, Q, edges.data_ptr(), bins, counts.data_ptr(),
+                                                 _pair01_on[dev].data_ptr() if two else None, _PAIR01.ctypes.data if two else None, 1 if two else 0,
+                                                 ea.data_ptr() if two else None, eb.data_ptr() if two else None, bins2,
+                                                 counts2.data_ptr() if two else None, _stream(dev)))
+        path = "fused"
+    else:
+        host = lambda t: None if t is None else t.cpu().numpy()  # noqa: E731
+        c, c2 = _ts._hist_numpy(x, host(edges), _PAIR01 if two else None, host(ea), host(eb))
+        counts += torch.from_numpy(c).to(dev)
+        if two:
+            counts2 += torch.from_numpy(c2).to(dev)
+        path = "torch"
+    return counts[0, 0], counts2[0, 0] if two else None, path
+
+
+def tica_histograms(model: TicaModel, ref_feats: Tensor, traj_feats: Tensor, bins: int = 100, bins2: int = 50) -> TicaHistograms:
+    """Project the MD reference's and the sampled trajectory's features [n, F] with ``model``, take the joint minimum / maximum of
+    TICA-0 and TICA-1 (eval_peptide.py:203-207), build ``np.linspace``'s edge tables from them on the device and count: the 100-bin
+    histogram of TICA-0 and the 50 x 50 histogram of (TICA-0, TICA-1) of each side.  Nothing is read back."""
+    if ref_feats.dim() != 2 or traj_feats.dim() != 2:
+        raise ValueError(f"expected two feature tables [n, F], got {tuple(ref_feats.shape)} and {tuple(traj_feats.shape)}")
+    if traj_feats.device != ref_feats.device:
+        raise ValueError(f"ref_feats on {ref_feats.device}, traj_feats on {traj_feats.device}")
+    d, dev = model.dim, ref_feats.device
+    lim = torch.empty(2, d, dtype=torch.float32, device=dev)
+    lim[0], lim[1] = float("inf"), float("-inf")
+    y_ref = model.transform(ref_feats, lim)
+    paths = {last_path["transform"]}
+    y_traj = model.transform(traj_feats, lim)
+    paths.add(last_path["transform"])
+    edges = linspace_edges(lim[0, 0], lim[1, 0], bins)
+    ea = eb = None
+    if d >= 2:
+        ea, eb = linspace_edges(lim[0, 0], lim[1, 0], bins2), linspace_edges(lim[0, 1], lim[1, 1], bins2)
+    rc, rc2, p1 = _counts(y_ref, edges, ea, eb)
+    tc, tc2, p2 = _counts(y_traj, edges, ea, eb)
+    paths.update((p1, p2))
+    last_path["tica_histograms"] = "fused" if paths == {"fused"} else "torch"
+    return TicaHistograms(y_ref, y_traj, lim, edges, ea, eb, rc, tc, rc2, tc2)
+
+
+def tica_jsd(model: TicaModel, ref_feats: Tensor, traj_feats: Tensor, bins: int = 100, bins2: int = 50) -> Dict[str, float]:
+    """{"TICA-0": jensenshannon of the two histograms of the first component on their joint range, "TICA-0,1": of the two joint
+    histograms of the first two} - the two entries eval_peptide.py:199-219 adds to ``out["JSD"]``; merge the dict into
+    ``TorsionStats.jsd(...)``'s and ``summary_metrics`` averages the keys.  With ``model.dim == 1`` only "TICA-0"."""
+    h = tica_histograms(model, ref_feats, traj_feats, bins, bins2)
+    d = [js_distance(h.ref_counts, h.traj_counts)]
+    if h.ref_counts2 is not None:
+        d.append(js_distance(h.ref_counts2.reshape(-1), h.traj_counts2.reshape(-1)))
+    out = dict(zip(("TICA-0", "TICA-0,1"), torch.stack(d).tolist()))  # (the one read)
+    last_path["tica_jsd"] = "fused" if last_path["tica_histograms"] == "fused" and _ts.last_path["js_distance"] == "fused" else "torch"
+    return out
+
+
+# ---- nearest centre ----
+def _assign_torch(y: Tensor, c: Tensor) -> Tensor:
+    out = []
+    c64 = c.double()
+    for r0 in range(0, y.shape[0], 4096):
+        v = y[r0:r0 + 4096].double()
+        idx = ((v[:, None, :] - c64[None]) ** 2).sum(dim=-1).argmin(dim=1)
+        out.append(torch.where(torch.isnan(v).any(dim=1), torch.full_like(idx, -1), idx))
+    return torch.cat(out)
+
+
+def assign_centers(y: Tensor, centers, state_map=None, nstates: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+    """y [n, d], centers [k, d] -> (labels int32 [n], state_counts int64 [nstates]): ``labels[t] = argmin_c sum_j (y[t, j] -
+    centers[c, j])^2`` (float64, ties to the lowest index: ``kmeans.transform``), through ``state_map`` [k] when given
+    (``msm.metastable_assignments[...]``: ``analysis.discretize``; a mapped value outside 0..nstates-1 gives -1); a row that holds a NaN
+    gets -1 and is not counted.  ``state_counts[i]`` = the rows with label i: the occupancies as exact integers.  ``nstates`` defaults to
+    k without a map and to ``max(state_map) + 1`` with one (a device map is read back for that: pass ``nstates`` to avoid it)."""
+    if y.dim() != 2 or y.shape[0] < 1 or y.shape[1] < 1:
+        raise ValueError(f"expected y [n, d], got {tuple(y.shape)}")
+    dev = y.device
+    c = (centers.detach() if torch.is_tensor(centers) else torch.as_tensor(np.asarray(centers))).to(device=dev, dtype=y.dtype)
+    if c.dim() != 2 or c.shape[1] != y.shape[1] or c.shape[0] < 1:
+        raise ValueError(f"centers must be [k, {y.shape[1]}], got {tuple(c.shape)}")
+    n, d, k = int(y.shape[0]), int(y.shape[1]), int(c.shape[0])
+    smap = None
+    if state_map is not None:
+        smap = (state_map.detach() if torch.is_tensor(state_map) else torch.as_tensor(np.asarray(state_map))).to(device=dev, dtype=torch.int32).contiguous()
+        if tuple(smap.shape) != (k,):
+            raise ValueError(f"state_map must be [{k}], got {tuple(smap.shape)}")
+    if nstates is None:
+        nstates = k if smap is None else int(smap.max()) + 1
+    nstates = int(nstates)
+    if nstates < 1:
+        raise ValueError(f"nstates = {nstates} must be positive")
+    counts = torch.zeros(nstates, dtype=torch.int64, device=dev)
+    if (fused_applies(y, c) and d <= _lib.ASG_MAX_D and k <= _lib.ASG_MAX_K and k * d <= _lib.ASG_CELLS and nstates <= _lib.ASG_MAX_STATES
+            and n < 2 ** 31):
+        yc, cc = y.detach().contiguous(), c.contiguous()
+        with torch.cuda.device(dev):
+            labels = torch.empty(n, dtype=torch.int32, device=dev)
+            _lib.check(_lib.load().lsl_assign_centers(yc.data_ptr(), n, d, cc.data_ptr(), k, None if smap is None else smap.data_ptr(), nstates,
+                                                      labels.data_ptr(), counts.data_ptr(), _stream(dev)))
+        last_path["assign_centers"] = "fused"
+        return labels, counts
+    idx = _assign_torch(y.detach(), c)
+    if smap is not None:
+        mapped = smap.long()[idx.clamp_min(0)]
+        idx = torch.where((idx >= 0) & (mapped >= 0) & (mapped < nstates), mapped, torch.full_like(idx, -1))
+    ok = (idx >= 0) & (idx < nstates)
+    counts += torch.bincount(idx[ok], minlength=nstates)[:nstates]
+    last_path["assign_centers"] = "torch"
+    return idx.to(torch.int32), counts
+
+
+# ---- transition counts ----
+def transition_counts(dtraj: Tensor, lag: int, nstates: int) -> Tensor:
+    """dtraj [n] or [S, n] (integer labels) -> int64 [(S,) nstates, nstates]: ``C[i, j] = #{t < n - lag : d_t = i, d_{t+lag} = j}``, the
+    sliding-window count matrix ``estimate_markov_model(dtraj, lag)`` estimates from.  A pair with either label outside 0..nstates-1
+    (the -1 of ``assign_centers``) is skipped; ``lag >= n`` gives zeros."""
+    if dtraj.dim() not in (1, 2) or dtraj.dtype.is_floating_point or dtraj.dtype == torch.bool:
+        raise ValueError(f"expected integer labels [n] or [S, n], got {dtraj.dtype} {tuple(dtraj.shape)}")
+    v = dtraj.detach() if dtraj.dim() == 2 else dtraj.detach()[None]
+    S, n = int(v.shape[0]), int(v.shape[1])
+    lag, ns = int(lag), int(nstates)
+    if lag < 1 or ns < 1 or S < 1 or n < 1:
+        raise ValueError(f"lag = {lag}, nstates = {ns}, dtraj {tuple(dtraj.shape)}: all must be positive")
+    dev = v.device
+    counts = torch.zeros(S, ns, ns, dtype=torch.int64, device=dev)
+    if v.is_cuda and v.dtype in (torch.int32, torch.int64) and ns <= _lib.TR_MAX_STATES and S <= 65535:
+        vc = v.to(torch.int32).contiguous()
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().lsl_transition_counts(vc.data_ptr(), S, n, lag, ns, counts.data_ptr(), _stream(dev)))
+        last_path["transition_counts"] = "fused"
+    else:
+        if lag < n:
+            a, b = v[:, :n - lag].long(), v[:, lag:].long()
+            ok = (a >= 0) & (a < ns) & (b >= 0) & (b < ns)
+            for s in range(S):
+                counts[s] += torch.bincount((a[s] * ns + b[s])[ok[s]], minlength=ns * ns).reshape(ns, ns)
+        last_path["transition_counts"] = "torch"
+    return counts if dtraj.dim() == 2 else counts[0]
+
+
+def metastable_jsd(ref_counts: Tensor, traj_counts: Tensor) -> Tensor:
+    """``jensenshannon(ref_metastable_probs, traj_metastable_probs)`` from the two occupancy count tables [nstates]: the "MSMS" entry of
+    ``calc_summary_metrics`` (eval_peptide.py:393-406).  float64, 0-dim."""
+    d = js_distance(ref_counts, traj_counts.to(ref_counts.device))
+    last_path["metastable_jsd"] = _ts.last_path["js_distance"]
+    return d
+
+
+def tica_autocovariance(y: Tensor, nlag: int) -> Tensor:
+    """y [n, dim] -> [nlag + 1]: ``acovf(y[:, 0], adjusted=True, demean=False, nlag=nlag)`` - ``lagged_products`` of the first column."""
+    if y.dim() != 2 or y.shape[1] < 1:
+        raise ValueError(f"expected y [n, dim], got {tuple(y.shape)}")
+    out = lagged_products(y[:, :1].contiguous(), nlag)[0]
+    last_path["tica_autocovariance"] = _ts.last_path["lagged_products"]
+    return out

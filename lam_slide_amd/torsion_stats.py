@@ -15,8 +15,8 @@ The device form is liblamslide_hip.so (``lsl_dihedral_angles`` / ``lsl_histogram
 csrc/k_torsstat.hip.h): counts are integers (exact, equal to numpy's on the same float32 values), every float is a sum in a fixed order
 (the same bits in any batch).  Each primitive runs it when its tensors are float32 (counts: integers) on the GPU, nothing requires grad
 and the shape is native; otherwise a numpy / torch restatement runs, with the same outputs and the same NaN conventions.
-``last_path[name]`` tells which of the two ("fused" / "torch") the last call of a primitive took.  The TICA projection itself (a pyemma
-model fitted on MD: one small matmul) stays the caller's.
+``last_path[name]`` tells which of the two ("fused" / "torch") the last call of a primitive took.  The TICA model, its projection and
+the state statistics behind it are ``lam_slide_amd.tica``.
 """
 from __future__ import annotations
 
@@ -430,8 +430,8 @@ class TorsionStats:
     def summary_metrics(jsd_dicts: Sequence[Mapping[str, float]]) -> Dict[str, float]:
         """BB / SC / ALL of ``calc_summary_metrics`` (eval_peptide.py:378-404) over the ``jsd`` dicts of several peptides: the mean distance
         of the keys holding "PHI" or "PSI" (not the "a|b" joint ones), of the keys holding "CHI", and of all three kinds without the
-        joint ones; "TICA-0" / "TICA-0,1" the means of those keys when every dict has them (the caller adds them: the projection is
-        pyemma's).  An empty group gives NaN, like the mean of an empty list."""
+        joint ones; "TICA-0" / "TICA-0,1" the means of those keys when every dict has them (``tica.tica_jsd`` returns them: merge its
+        dict into ``jsd``'s).  An empty group gives NaN, like the mean of an empty list."""
         bb, sc, al = [], [], []
         for d in jsd_dicts:
             bb += [v for k, v in d.items() if ("PHI" in k or "PSI" in k) and "|" not in k]
