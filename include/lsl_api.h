@@ -468,7 +468,17 @@ typedef struct lsl_decoder lsl_decoder;
 int lsl_decoder_create(const lsl_decoder_desc *desc, const lsl_decoder_weights *w, lsl_decoder **out);
 void lsl_decoder_destroy(lsl_decoder *d);
 size_t lsl_decode_workspace_bytes(const lsl_decoder *d, int32_t frames, int32_t L, int32_t A);
-/* z: device [frames, L, C] latents; entities: device [frames, A] int64; out: device [frames, A, out_dim]. */
+/* z: device [frames, L, C] latents; entities: device [frames, A] int64; out: device [frames, A, out_dim].
+ * Limits (lsl_decoder_create / lsl_decode return -3 outside them):
+ *   - in_dim, dim_latent, dim_query, dim_emb, heads_latent * dim_head_latent and heads_cross * dim_head_cross are multiples of 4
+ *     (16-byte row loads); dim_head_latent and dim_head_cross are 1..64; out_dim is free.
+ *   - One attention call keeps the keys and values of a (frame, head) in 64 KiB of LDS, in a head tile of 16 / 32 / 64 floats for
+ *     dim_head <= 16 / <= 32 / <= 64: (2 * keys * tile + keys) * 4 <= 65536, i.e. at most 496 / 252 / 127 keys.  A self block has L keys
+ *     (dim_head_latent), a cross block A keys and the output block L * max(num_split, 1) keys (dim_head_cross).  The query axis is free.
+ *   - The shape is checked block by block as the launches are enqueued: a refused call has written nothing to `out` (only the last launch
+ *     does), but the stages before the refused block have been enqueued on `stream` and have overwritten the workspace.
+ *   - An entity index outside 0..n_entities-1 reads the nearest row of the table (negative: row 0, too large: the last row); the
+ *     reference's nn.Embedding raises instead, so a caller that wants that error checks the indices itself. */
 int lsl_decode(lsl_decoder *d, const float *z, const int64_t *entities, int32_t frames, int32_t L, int32_t A, float *out,
                void *workspace, size_t workspace_bytes, void *stream);
 
@@ -498,7 +508,14 @@ int lsl_encoder_create(const lsl_encoder_desc *desc, const lsl_encoder_weights *
 void lsl_encoder_destroy(lsl_encoder *e);
 size_t lsl_encode_workspace_bytes(const lsl_encoder *e, int32_t frames, int32_t A);
 /* x: device [frames, A, dim_input]; entities: device [frames, A] int64; mask: device [frames, A] bytes, non-zero = real entity,
- * or NULL (all real); out: device [frames, num_latents, dim_latent]. */
+ * or NULL (all real: the same bits as a mask of ones); out: device [frames, num_latents, dim_latent].
+ * Limits, as for lsl_decode: dim_input, dim_emb, dim_latent and both heads * dim_head are multiples of 4, dim_head is 1..64; a cross
+ * block has A keys (head tile of dim_head_cross: A <= 496 / 252 / 127), a self block num_latents keys (tile of dim_head_latent); -3
+ * beyond that, with nothing written to `out` and the earlier stages enqueued; entity indices are clamped to the table.
+ * A masked-out entity never reaches the latents, whatever x holds there (finite).  A frame whose mask is all zero has no softmax: its
+ * latents are NaN (softmax over a row of -inf, as in tests' oracle; what F.scaled_dot_product_attention of the reference returns for
+ * such a row has differed between PyTorch versions, NaN or zeros, so do not pass an empty frame), and the other frames of the call
+ * are unaffected. */
 int lsl_encode(lsl_encoder *e, const float *x, const int64_t *entities, const unsigned char *mask, int32_t frames, int32_t A, float *out,
                void *workspace, size_t workspace_bytes, void *stream);
 

@@ -8,7 +8,7 @@ BASELINE.json (decoded coordinates within 1e-3) is 4-25x looser than any of them
   * one block update with bf16 MFMA operands against the reference's own intermediates: measured 3-4e-3 of the UPDATE, bar 1e-2
   * one network evaluation: measured 0.3-1.4e-4, bars 4-6e-4
   * samplers end to end: final latents measured 0.4-2.4e-4, bars 6e-4..1e-3; decoded coordinates measured 2.6-5.9e-5, bars 1.5-3e-4
-  * fp32 stage-1 encode / decode: measured 2.4-3.8e-7, bar 2e-6
+  * fp32 stage-1 encode / decode: measured 2.4-3.8e-7, bar 2e-6 (every head tile, key limit and remainder path: test_hip_stage1.py)
   * integer / indexing behaviour (sharding, chunking, batch independence, K-folding, graph replay): bit-exact
 """
 import ctypes as C
