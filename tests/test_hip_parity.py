@@ -9,6 +9,9 @@ BASELINE.json (decoded coordinates within 1e-3) is 4-25x looser than any of them
   * one network evaluation: measured 0.3-1.4e-4, bars 4-6e-4
   * samplers end to end: final latents measured 0.4-2.4e-4, bars 6e-4..1e-3; decoded coordinates measured 2.6-5.9e-5, bars 1.5-3e-4
   * fp32 stage-1 encode / decode: measured 2.4-3.8e-7, bar 2e-6 (every head tile, key limit and remainder path: test_hip_stage1.py)
+  * attention kernels per row against an fp64 softmax of the tapped bf16 q | k | v (test_hip_attention.py, attention_cases.py): per element
+    2^-6 A for the MFMA forms (A = p |v|; three bf16 roundings of 2^-8 A each, bar four), 2^-8 |o| + (S + head_dim + 16) 2^-23 A for
+    k_attention_tiny and, with A_lin, for k_attention_linear: derived, not measured (profiles/attention_rowwise_parity.txt)
   * integer / indexing behaviour (sharding, chunking, batch independence, K-folding, graph replay): bit-exact
 """
 import ctypes as C
