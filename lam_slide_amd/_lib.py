@@ -10,7 +10,10 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
+from collections import OrderedDict
 from typing import Optional
+
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liblamslide_hip.so")
@@ -21,7 +24,7 @@ ABI_VERSION = 6  # LSL_VERSION of include/lsl_api.h this binding was written aga
 RK_SCRATCH_BYTES = 8192  # LSL_RK_SCRATCH_BYTES
 GEOM_MAX_A, GEOM_MAX_D = 2048, 4  # the native form of lsl_geom_loss_sums (csrc/k_geomloss.hip.h)
 DISP_MAX_D, DISP_MAX_UNITS = 4, 16777215  # the native form of lsl_disp_error_rows (csrc/k_disperr.hip.h): coordinates, K * B
-TORS_MAX_A, HIST_MAX_BINS, HIST2_MAX_BINS = 2044, 2048, 90  # the native forms of lsl_dihedral_angles / lsl_histogram (csrc/k_torsstat.hip.h)
+TORS_MAX_A, TORS_MAX_Q, HIST_MAX_BINS, HIST2_MAX_BINS = 2044, 65536, 2048, 90  # the native forms of lsl_dihedral_angles / lsl_histogram (csrc/k_torsstat.hip.h)
 LAG_CHUNK, LAG_MAX_LAGS, LAG_MAX_ROWS = 448, 1 << 21, 65535  # lsl_lag_products: the fp32 chain m, nlag + 1, S * C of one call
 MOM_SEG = 1024  # lsl_lagged_moments (csrc/k_tica.hip.h): segment g holds the time steps [g * MOM_SEG, (g + 1) * MOM_SEG) below n - lag
 MOM_CHAIN = MOM_SEG  # the longest fp64 addition chain inside a segment
@@ -234,12 +237,49 @@ def last_error() -> str:
     return load().lsl_last_error().decode()
 
 
-def check(rc: int, shape_error=RuntimeError):
+def check(rc: int):
     if rc == 0:
         return
     msg = last_error()
-    if rc in (-20, -21):
-        raise ValueError(msg)
-    if rc == -3:
+    if rc in (-3, -20, -21):
         raise ValueError(msg)
     raise RuntimeError(f"lamslide_hip error {rc}: {msg}")
+
+
+def call(dev, name: str, *args) -> None:
+    """Run the compute entry point ``name`` of the library on ``dev``: inside that device's context, on its current stream (every such
+    entry point takes the stream last), the return code through :func:`check`.  Handle calls without a stream (create, destroy, ``set_*``,
+    ``*_workspace_bytes``) stay ``check(load().f(...))``."""
+    fn = getattr(load(), name)
+    with torch.cuda.device(dev):
+        check(fn(*args, torch.cuda.current_stream(dev).cuda_stream))
+
+
+def device_form(*tensors, dtype=torch.float32, same_device: bool = True) -> bool:
+    """The dispatch rule of every device form: all tensors on one GPU, all of ``dtype`` (the torch paths promote as the reference does),
+    none requiring grad under grad mode (a library result carries no grad_fn).  The callers add their own shape or module clause.
+    ``same_device=False`` leaves the comparison of the devices to a caller whose argument check raises the reference's "Expected all
+    tensors to be on the same device" instead."""
+    dev, grad = tensors[0].device, torch.is_grad_enabled()
+    return all(t.is_cuda and t.dtype == dtype and (t.device == dev or not same_device) and not (grad and t.requires_grad) for t in tensors)
+
+
+class Scratch:
+    """The scratch buffers of one owner object (a model, a stage-1 handle): one uint8 buffer per (device, current stream), so two calls
+    of the owner in flight on different streams never share scratch (calls on ONE stream are ordered by the stream).  A buffer is replaced
+    when a call needs more; the ``keep`` most recently used are kept."""
+
+    def __init__(self, keep: int = 4):
+        self.keep = keep
+        self.buffers: "OrderedDict[tuple, torch.Tensor]" = OrderedDict()
+
+    def get(self, device, need: int) -> "torch.Tensor":
+        device = torch.device(device)
+        key = (device, torch.cuda.current_stream(device).cuda_stream)
+        ws = self.buffers.get(key)
+        if ws is None or ws.numel() < need:
+            ws = self.buffers[key] = torch.empty(need, dtype=torch.uint8, device=device)
+        self.buffers.move_to_end(key)
+        while len(self.buffers) > self.keep:
+            self.buffers.popitem(last=False)
+        return ws

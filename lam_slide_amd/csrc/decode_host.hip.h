@@ -1,4 +1,6 @@
-// Host side of lsl_decode / lsl_encode: the launch sequences of the frozen stage-1 decode and encode (kernels in k_decode.hip.h).
+// Host side of lsl_decode / lsl_encode: the handles, what their two create calls check and build alike (stage1_check, stage1_make), the
+// scratch layout of a call (stage1_carve, sized by dec_carve / enc_carve) and the launch helpers of the frozen stage-1 decode and encode
+// (kernels in k_decode.hip.h; the entry points themselves in stage1_api.hip.h).
 #pragma once
 #include "k_decode.hip.h"
 
@@ -22,12 +24,10 @@ struct DecWs {
 
 inline size_t dec_align(size_t n) { return (n + 63) & ~(size_t)63; }
 
-// every buffer in floats; returns the total in bytes
-size_t dec_carve(const lsl_decoder_desc &d, int frames, int L, int A, char *base, DecWs *ws) {
-    const int split = d.num_split > 1 ? d.num_split : 1;
-    const size_t nl = (size_t)frames * L, na = (size_t)frames * A, nmax = std::max(nl * split, na);
-    const int inner_l = d.heads_latent * d.dim_head_latent, inner_c = d.heads_cross * d.dim_head_cross;
-    const int dmax = std::max(std::max(d.dim_latent, d.dim_query), std::max(d.in_dim, d.dim_emb));
+// The scratch of one call, shared by decode and encode: every size in floats, the buffers in this order, each aligned to 64 bytes; returns
+// the total in bytes (base == nullptr: the size alone).  `rows` x `dmax` / `imax` hold a LayerNorm output, q | k | v, the attention output
+// and the feed-forward hidden layer of the longer of the two token sets.
+size_t stage1_carve(size_t lat, size_t q, size_t rows, int dmax, int inner_l, int inner_c, size_t ext, char *base, DecWs *ws) {
     const int imax = std::max(3 * inner_l, 2 * inner_c);
     size_t off = 0;
     auto take = [&](size_t floats) {
@@ -36,17 +36,61 @@ size_t dec_carve(const lsl_decoder_desc &d, int frames, int L, int A, char *base
         return p;
     };
     DecWs w;
-    w.lat = take(nl * d.dim_latent);
-    w.q = take(na * d.dim_query);
-    w.xn = take(nmax * dmax);
-    w.cn = take(nmax * dmax);
-    w.qb = take(nmax * imax);
-    w.kvb = take(nmax * imax);
-    w.att = take(nmax * std::max(inner_l, inner_c));
-    w.hid = take(nmax * dmax);
-    w.ext = split > 1 ? take(nl * split * d.dim_latent) : nullptr;
+    w.lat = take(lat);
+    w.q = take(q);
+    w.xn = take(rows * dmax);
+    w.cn = take(rows * dmax);
+    w.qb = take(rows * imax);
+    w.kvb = take(rows * imax);
+    w.att = take(rows * std::max(inner_l, inner_c));
+    w.hid = take(rows * dmax);
+    w.ext = ext ? take(ext) : nullptr;
     if (ws) *ws = w;
     return off;
+}
+
+size_t dec_carve(const lsl_decoder_desc &d, int frames, int L, int A, char *base, DecWs *ws) {
+    const int split = d.num_split > 1 ? d.num_split : 1;
+    const size_t nl = (size_t)frames * L, na = (size_t)frames * A;
+    const int dmax = std::max(std::max(d.dim_latent, d.dim_query), std::max(d.in_dim, d.dim_emb));
+    return stage1_carve(nl * d.dim_latent, na * d.dim_query, std::max(nl * split, na), dmax, d.heads_latent * d.dim_head_latent,
+                        d.heads_cross * d.dim_head_cross, split > 1 ? nl * split * d.dim_latent : 0, base, ws);
+}
+
+// latents [frames * N, dim_latent]; ws->q is the context [frames * A, dim_ctx]
+size_t enc_carve(const lsl_encoder_desc &d, int frames, int A, char *base, DecWs *ws) {
+    const size_t nl = (size_t)frames * d.num_latents, na = (size_t)frames * A;
+    const int dim_ctx = d.dim_input + d.dim_emb;
+    return stage1_carve(nl * d.dim_latent, na * dim_ctx, std::max(nl, na), std::max(dim_ctx, d.dim_latent), d.heads_latent * d.dim_head_latent,
+                        d.heads_cross * d.dim_head_cross, 0, base, ws);
+}
+
+// What lsl_decoder_create and lsl_encoder_create check alike (`what` is "decoder" / "encoder", `dims` the widths beside the two
+// attention widths, `rest` whether their own fields are in range) ...
+template <class Desc>
+int stage1_check(const char *what, const Desc &d, std::initializer_list<int> dims, bool rest) {
+    bool ragged = (d.heads_latent * d.dim_head_latent) % 4 || (d.heads_cross * d.dim_head_cross) % 4;
+    for (int w : dims) ragged |= w % 4 != 0;
+    if (ragged) return fail(-3, "%s widths must be multiples of 4", what);
+    if (d.dim_head_latent > 64 || d.dim_head_cross > 64 || d.dim_head_latent < 1 || d.dim_head_cross < 1) return fail(-3, "%s dim_head must be 1..64", what);
+    if (d.act != 1 && d.act != 2) return fail(-3, "%s activation must be 1 (erf GELU) or 2 (tanh GELU)", what);
+    if (d.num_block_attn < 0 || d.num_block_cross < 0 || !rest) return fail(-3, "bad %s description", what);
+    return 0;
+}
+
+// ... and the handle they make: the description, the pointers, and its own copy of the two block vectors.
+template <class Handle, class Desc, class Weights>
+int stage1_make(const Desc &d, const Weights &w, Handle **out) {
+    Handle *h = new (std::nothrow) Handle();
+    if (!h) return fail(-5, "out of host memory");
+    h->d = d;
+    h->w = w;
+    if (d.num_block_attn) h->self_blocks.assign(w.self_blocks, w.self_blocks + d.num_block_attn);
+    if (d.num_block_cross) h->cross_blocks.assign(w.cross_blocks, w.cross_blocks + d.num_block_cross);
+    h->w.self_blocks = h->self_blocks.data();
+    h->w.cross_blocks = h->cross_blocks.data();
+    *out = h;
+    return 0;
 }
 
 void dec_ln(float *out, const float *in, const float *w, const float *b, int rows, int D, hipStream_t st) {
@@ -111,34 +155,6 @@ int dec_block(const lsl_dec_block &b, float *x, int Sx, int dim, const float *ct
     dec_dense(act, ws.hid, ws.xn, b.ff_w1, b.ff_b1, nullptr, nx, dim, dim, st);
     dec_dense(0, x, ws.hid, b.ff_w2, b.ff_b2, x, nx, dim, dim, st);
     return 0;
-}
-
-// encoder scratch: the same buffers as the decoder's, sized for latents [frames*N, dim_latent] and context [frames*A, dim_ctx]
-size_t enc_carve(const lsl_encoder_desc &d, int frames, int A, char *base, DecWs *ws, float **ctx) {
-    const size_t nl = (size_t)frames * d.num_latents, na = (size_t)frames * A, nmax = std::max(nl, na);
-    const int dim_ctx = d.dim_input + d.dim_emb;
-    const int inner_l = d.heads_latent * d.dim_head_latent, inner_c = d.heads_cross * d.dim_head_cross;
-    const int dmax = std::max(dim_ctx, d.dim_latent), imax = std::max(3 * inner_l, 2 * inner_c);
-    size_t off = 0;
-    auto take = [&](size_t floats) {
-        float *p = base ? reinterpret_cast<float *>(base + off) : nullptr;
-        off += dec_align(floats * sizeof(float));
-        return p;
-    };
-    DecWs w;
-    w.lat = take(nl * d.dim_latent);
-    w.q = nullptr;
-    float *c = take(na * dim_ctx);
-    w.xn = take(nmax * dmax);
-    w.cn = take(nmax * dmax);
-    w.qb = take(nmax * imax);
-    w.kvb = take(nmax * imax);
-    w.att = take(nmax * std::max(inner_l, inner_c));
-    w.hid = take(nmax * dmax);
-    w.ext = nullptr;
-    if (ws) *ws = w;
-    if (ctx) *ctx = c;
-    return off;
 }
 
 }  // namespace

@@ -30,6 +30,7 @@
 #include "common.hip.h"
 
 #define LSL_TORS_MAX_A 2044        // 146 residues of 14 atoms: a frame in LDS (the GEOM_MAX_A entities of lsl_geom_loss_sums hold 2048)
+#define LSL_TORS_MAX_Q 65536       // quadruples of one call of lsl_dihedral_angles
 #define LSL_TORS_LDS_ATOMS 2048    // atoms of the frames one workgroup of k_dihedral stages
 #define LSL_HIST_MAX_BINS 2048     // 1-D: the fp64 edge table (16 KiB) beside LSL_HIST_CELLS int32 counts (32 KiB) in LDS
 #define LSL_HIST_CELLS 8192        // int32 counts a workgroup holds: qt * bins (1-D), bins2 * bins2 (2-D: bins2 <= 90)
@@ -37,6 +38,7 @@
 #define LSL_HIST_ROWS 1024        // rows of x per workgroup: an LDS count stays <= 1024
 #define LSL_LAG_TILE 256           // lags per workgroup (one thread each)
 #define LSL_LAG_CHUNK 448          // time steps per LDS chunk = the longest fp32 addition chain m
+#define LSL_LAG_MAX_ROWS 65535     // S * C of one call of lsl_lag_products: (series, channel) rows are a grid dimension
 #define LSL_LAG_MAX_PART (1 << 21) // fp64 partials per (series, channel): segments * (nlag + 1) stays at or below this (16 MiB)
 
 // ---- a. dihedral angles ----

@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <vector>
 
 #include <atomic>
@@ -382,7 +383,7 @@ int lsl_dihedral_angles(const float *pos, const int32_t *quads, const int32_t *q
     DeviceGuard dev_guard_((hipStream_t)stream);
     if (!pos || !quads || !quads_host || !angles) return fail(-1, "null argument");
     if (A < 1 || A > LSL_TORS_MAX_A) return fail(-3, "A = %d outside the native form (1..%d atoms of a frame)", A, LSL_TORS_MAX_A);
-    if (Q < 1 || Q > 65536) return fail(-3, "Q = %d outside 1..65536 quadruples", Q);
+    if (Q < 1 || Q > LSL_TORS_MAX_Q) return fail(-3, "Q = %d outside 1..%d quadruples", Q, LSL_TORS_MAX_Q);
     const int fpb = LSL_TORS_LDS_ATOMS / A;
     if (F < 1 || (F + fpb - 1) / fpb > 0x7fffffffLL) return fail(-3, "F = %lld frames: 1 .. %lld at A = %d", (long long)F, 0x7fffffffLL * fpb, A);
     for (int i = 0; i < 4 * Q; ++i)
@@ -425,7 +426,7 @@ int lsl_histogram(const float *x, int32_t S, int32_t n, int32_t Q, const double 
 } LSL_API_CATCH
 
 static const char *lag_shape_error(int32_t S, int32_t n, int32_t C, int32_t nlag) {
-    if (S < 1 || C < 1 || (long long)S * C > 65535) return "S and C must be positive and S * C at most 65535 (series x channels of one call)";
+    if (S < 1 || C < 1 || (long long)S * C > LSL_LAG_MAX_ROWS) return "S and C must be positive and S * C at most 65535 (series x channels of one call)";
     if (n < 1) return "n must be positive";
     if (nlag < 0 || nlag >= n) return "nlag outside 0..n-1 (lag k has n - k terms)";
     if ((long long)nlag + 1 > LSL_LAG_MAX_PART) return "nlag + 1 above 2^21 lags";

@@ -5,23 +5,10 @@
 int lsl_decoder_create(const lsl_decoder_desc *desc, const lsl_decoder_weights *w, lsl_decoder **out) try {
     if (!desc || !w || !out) return fail(-1, "null decoder argument");
     const lsl_decoder_desc &d = *desc;
-    if (d.in_dim % 4 || d.dim_latent % 4 || d.dim_query % 4 || d.dim_emb % 4 || (d.heads_latent * d.dim_head_latent) % 4 ||
-        (d.heads_cross * d.dim_head_cross) % 4)
-        return fail(-3, "decoder widths must be multiples of 4");
-    if (d.dim_head_latent > 64 || d.dim_head_cross > 64 || d.dim_head_latent < 1 || d.dim_head_cross < 1) return fail(-3, "decoder dim_head must be 1..64");
-    if (d.act != 1 && d.act != 2) return fail(-3, "decoder activation must be 1 (erf GELU) or 2 (tanh GELU)");
-    if (d.num_block_attn < 0 || d.num_block_cross < 0 || d.out_dim < 1 || d.n_entities < 1 || d.num_split < 0) return fail(-3, "bad decoder description");
+    const bool rest = d.out_dim >= 1 && d.n_entities >= 1 && d.num_split >= 0;
+    if (int rc = stage1_check("decoder", d, {d.in_dim, d.dim_latent, d.dim_query, d.dim_emb}, rest)) return rc;
     if (d.num_split > 1 && (!w->ext_w || !w->ext_b)) return fail(-2, "decoder with num_split > 1 needs the extender weights");
-    lsl_decoder *dec = new (std::nothrow) lsl_decoder();
-    if (!dec) return fail(-5, "out of host memory");
-    dec->d = d;
-    dec->w = *w;
-    if (d.num_block_attn) dec->self_blocks.assign(w->self_blocks, w->self_blocks + d.num_block_attn);
-    if (d.num_block_cross) dec->cross_blocks.assign(w->cross_blocks, w->cross_blocks + d.num_block_cross);
-    dec->w.self_blocks = dec->self_blocks.data();
-    dec->w.cross_blocks = dec->cross_blocks.data();
-    *out = dec;
-    return 0;
+    return stage1_make(d, *w, out);
 } LSL_API_CATCH
 
 void lsl_decoder_destroy(lsl_decoder *d) { delete d; }
@@ -71,28 +58,15 @@ int lsl_decode(lsl_decoder *dec, const float *z, const int64_t *entities, int32_
 int lsl_encoder_create(const lsl_encoder_desc *desc, const lsl_encoder_weights *w, lsl_encoder **out) try {
     if (!desc || !w || !out) return fail(-1, "null encoder argument");
     const lsl_encoder_desc &d = *desc;
-    if (d.dim_input % 4 || d.dim_emb % 4 || d.dim_latent % 4 || (d.heads_latent * d.dim_head_latent) % 4 || (d.heads_cross * d.dim_head_cross) % 4)
-        return fail(-3, "encoder widths must be multiples of 4");
-    if (d.dim_head_latent > 64 || d.dim_head_cross > 64 || d.dim_head_latent < 1 || d.dim_head_cross < 1) return fail(-3, "encoder dim_head must be 1..64");
-    if (d.act != 1 && d.act != 2) return fail(-3, "encoder activation must be 1 (erf GELU) or 2 (tanh GELU)");
-    if (d.num_block_attn < 0 || d.num_block_cross < 0 || d.num_latents < 1 || d.n_entities < 1) return fail(-3, "bad encoder description");
-    lsl_encoder *enc = new (std::nothrow) lsl_encoder();
-    if (!enc) return fail(-5, "out of host memory");
-    enc->d = d;
-    enc->w = *w;
-    if (d.num_block_cross) enc->cross_blocks.assign(w->cross_blocks, w->cross_blocks + d.num_block_cross);
-    if (d.num_block_attn) enc->self_blocks.assign(w->self_blocks, w->self_blocks + d.num_block_attn);
-    enc->w.cross_blocks = enc->cross_blocks.data();
-    enc->w.self_blocks = enc->self_blocks.data();
-    *out = enc;
-    return 0;
+    if (int rc = stage1_check("encoder", d, {d.dim_input, d.dim_emb, d.dim_latent}, d.num_latents >= 1 && d.n_entities >= 1)) return rc;
+    return stage1_make(d, *w, out);
 } LSL_API_CATCH
 
 void lsl_encoder_destroy(lsl_encoder *e) { delete e; }
 
 size_t lsl_encode_workspace_bytes(const lsl_encoder *e, int32_t frames, int32_t A) {
     if (!e || frames <= 0 || A <= 0) return 0;
-    return enc_carve(e->d, frames, A, nullptr, nullptr, nullptr);
+    return enc_carve(e->d, frames, A, nullptr, nullptr);
 }
 
 // quant(Encoder.forward(x, entities, mask))   (encoder.py:96-103, lightning_base.py:37-40)
@@ -103,11 +77,11 @@ int lsl_encode(lsl_encoder *enc, const float *x, const int64_t *entities, const 
     if (frames <= 0 || A <= 0) return fail(-3, "encode: empty input");
     const lsl_encoder_desc &d = enc->d;
     const lsl_encoder_weights &w = enc->w;
-    if (workspace_bytes < enc_carve(d, frames, A, nullptr, nullptr, nullptr) || !workspace) return fail(-4, "encode workspace too small");
+    if (workspace_bytes < enc_carve(d, frames, A, nullptr, nullptr) || !workspace) return fail(-4, "encode workspace too small");
     hipStream_t st = (hipStream_t)stream;
     DecWs ws;
-    float *ctx;
-    enc_carve(d, frames, A, (char *)workspace, &ws, &ctx);
+    enc_carve(d, frames, A, (char *)workspace, &ws);
+    float *ctx = ws.q;
     const int N = d.num_latents, nl = frames * N, na = frames * A, dim_ctx = d.dim_input + d.dim_emb;
     // prepare_inputs of EncoderBase: context = mlp(cat(x, entity_embedding(entities))), latents = the learned array per frame
     hipLaunchKernelGGL(k_enc_context, dim3((na + 3) / 4), dim3(256), 0, st, ws.xn, x, w.table, entities, na, d.dim_input, d.dim_emb, d.n_entities);

@@ -28,7 +28,74 @@ def renorm_table(table: Tensor, max_norm: Optional[float]) -> Tensor:
     return torch.where(norms > max_norm, table * (max_norm / (norms + 1e-7)), table)
 
 
-class Stage1Decoder:
+class _Stage1:
+    """What Stage1Decoder and Stage1Encoder share: the float32 weights ``_sd`` (and ``qk_norm``), their device copies behind the native
+    handle, and the scratch of a call - one buffer per (device, stream), so two calls of one object on two streams never write the same
+    LayerNorm, q/k/v and attention buffers.  A subclass names the library's ``_create`` / ``_destroy`` symbols and builds the
+    description and the weight struct in ``_describe(dev)``."""
+    _create = _destroy = ""
+
+    def _init_handle(self, device) -> None:
+        self._handle = C.c_void_p()
+        self._dev_tensors: List[Tensor] = []
+        self._scratch = _lib.Scratch()
+        if device is not None:
+            self.to(device)
+
+    def _p(self, key: str, dev) -> Optional[int]:
+        if key not in self._sd:
+            return None
+        t = self._sd[key].to(dev).contiguous()
+        self._dev_tensors.append(t)
+        return t.data_ptr()
+
+    def _block(self, prefix: str, dev, cross: bool) -> "_lib.DecBlock":
+        g = lambda name: self._p(f"{prefix}.{name}", dev)  # noqa: E731
+        return _lib.DecBlock(
+            ln_w=g("attn.norm.weight"), ln_b=g("attn.norm.bias"),
+            lnc_w=g("attn.norm_context.weight") if cross else None, lnc_b=g("attn.norm_context.bias") if cross else None,
+            w_q=g("attn.fn.to_q.weight") if cross else g("attn.fn.to_qkv.weight"), w_kv=g("attn.fn.to_kv.weight") if cross else None,
+            w_out=g("attn.fn.to_out.weight"), b_out=g("attn.fn.to_out.bias"),
+            q_scale=g("attn.fn.norm.query_norm.scale") if self.qk_norm else None, k_scale=g("attn.fn.norm.key_norm.scale") if self.qk_norm else None,
+            ff_ln_w=g("ff.norm.weight"), ff_ln_b=g("ff.norm.bias"), ff_w1=g("ff.fn.net.0.0.weight"), ff_b1=g("ff.fn.net.0.0.bias"),
+            ff_w2=g("ff.fn.net.1.weight"), ff_b2=g("ff.fn.net.1.bias"))
+
+    def _blocks(self, prefix: str, n: int, dev, cross: bool):
+        return (_lib.DecBlock * max(n, 1))(*[self._block(f"{prefix}.{i}", dev, cross) for i in range(n)])
+
+    def _destroy_handle(self) -> None:
+        if self._handle:
+            getattr(_lib.load(), self._destroy)(self._handle)
+            self._handle = C.c_void_p()
+
+    def to(self, device):
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError(f"{type(self).__name__} runs on the MI355X only (no CPU path)")
+        self._destroy_handle()
+        self._dev_tensors = []
+        desc, w = self._describe(dev)
+        _lib.check(getattr(_lib.load(), self._create)(C.byref(desc), C.byref(w), C.byref(self._handle)))
+        self.device = dev
+        return self
+
+    def __del__(self):
+        try:
+            self._destroy_handle()
+        except Exception:
+            pass
+
+    def _on(self, x: Tensor, method: str) -> None:
+        """The handle on x's device, before a call."""
+        if not x.is_cuda:
+            raise RuntimeError(f"{type(self).__name__}.{method} needs CUDA/HIP tensors (no CPU path)")
+        if not self._handle or self.device != x.device:
+            self.to(x.device)
+
+
+class Stage1Decoder(_Stage1):
+    _create, _destroy = "lsl_decoder_create", "lsl_decoder_destroy"
+
     def __init__(self, state_dict: Dict[str, Tensor], *, num_head_latent: int, dim_head_latent: int, num_head_cross: int,
                  dim_head_cross: int, act: str = "gelu_erf", output: str = "pos", max_norm: Optional[float] = 1.0,
                  device: Optional[torch.device] = None):
@@ -66,85 +133,37 @@ class Stage1Decoder:
             self._sd["decoder.extender.rows"] = w.reshape(self.dim_latent, n, self.dim_latent).permute(1, 0, 2).reshape(n * self.dim_latent, self.dim_latent).contiguous()
             self._sd["decoder.extender.rows_bias"] = b.reshape(self.dim_latent, n).t().reshape(-1).contiguous()
         self._sd["decoder.entity_embedding.embedding.weight"] = renorm_table(self._sd["decoder.entity_embedding.embedding.weight"], max_norm)
-        self._handle = C.c_void_p()
-        self._dev_tensors: List[Tensor] = []
-        self._ws: Optional[Tensor] = None
-        if device is not None:
-            self.to(device)
+        self._init_handle(device)
 
-    # -- packing ---------------------------------------------------------------------------------------------
-    def _p(self, key: str, dev) -> Optional[int]:
-        if key not in self._sd:
-            return None
-        t = self._sd[key].to(dev).contiguous()
-        self._dev_tensors.append(t)
-        return t.data_ptr()
-
-    def _block(self, prefix: str, dev, cross: bool) -> "_lib.DecBlock":
-        g = lambda name: self._p(f"{prefix}.{name}", dev)  # noqa: E731
-        return _lib.DecBlock(
-            ln_w=g("attn.norm.weight"), ln_b=g("attn.norm.bias"),
-            lnc_w=g("attn.norm_context.weight") if cross else None, lnc_b=g("attn.norm_context.bias") if cross else None,
-            w_q=g("attn.fn.to_q.weight") if cross else g("attn.fn.to_qkv.weight"), w_kv=g("attn.fn.to_kv.weight") if cross else None,
-            w_out=g("attn.fn.to_out.weight"), b_out=g("attn.fn.to_out.bias"),
-            q_scale=g("attn.fn.norm.query_norm.scale") if self.qk_norm else None, k_scale=g("attn.fn.norm.key_norm.scale") if self.qk_norm else None,
-            ff_ln_w=g("ff.norm.weight"), ff_ln_b=g("ff.norm.bias"), ff_w1=g("ff.fn.net.0.0.weight"), ff_b1=g("ff.fn.net.0.0.bias"),
-            ff_w2=g("ff.fn.net.1.weight"), ff_b2=g("ff.fn.net.1.bias"))
-
-    def to(self, device) -> "Stage1Decoder":
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("Stage1Decoder runs on the MI355X only (no CPU path)")
-        lib = _lib.load()
-        if self._handle:
-            lib.lsl_decoder_destroy(self._handle)
-            self._handle = C.c_void_p()
-        self._dev_tensors = []
-        selfs = (_lib.DecBlock * max(self.num_block_attn, 1))(*[self._block(f"decoder.self_attn_blocks.{i}", dev, False) for i in range(self.num_block_attn)])
-        cross = (_lib.DecBlock * max(self.num_block_cross, 1))(*[self._block(f"decoder.cross_attn_blocks.{i}", dev, True) for i in range(self.num_block_cross)])
+    def _describe(self, dev):
         w = _lib.DecoderWeights(
             pq_w=self._p("post_quant.1.weight", dev), pq_b=self._p("post_quant.1.bias", dev),
             table=self._p("decoder.entity_embedding.embedding.weight", dev),
             qm_w=self._p("decoder.query_mlp.1.weight", dev), qm_b=self._p("decoder.query_mlp.1.bias", dev),
-            self_blocks=selfs, cross_blocks=cross, out_block=self._block("decoder.output_block", dev, True),
+            self_blocks=self._blocks("decoder.self_attn_blocks", self.num_block_attn, dev, False),
+            cross_blocks=self._blocks("decoder.cross_attn_blocks", self.num_block_cross, dev, True), out_block=self._block("decoder.output_block", dev, True),
             ext_w=self._p("decoder.extender.rows", dev), ext_b=self._p("decoder.extender.rows_bias", dev),
             head_w1=self._p(f"decoder.output_layers.{self.output}.0.weight", dev), head_b1=self._p(f"decoder.output_layers.{self.output}.0.bias", dev),
             head_w2=self._p(f"decoder.output_layers.{self.output}.2.weight", dev), head_b2=self._p(f"decoder.output_layers.{self.output}.2.bias", dev))
         desc = _lib.DecoderDesc(self.in_dim, self.dim_latent, self.dim_query, self.dim_emb, self.n_entities, self.heads_latent, self.dim_head_latent,
                                 self.heads_cross, self.dim_head_cross, self.num_block_attn, self.num_block_cross, _ACT[self.act], self.out_dim, self.num_split)
-        _lib.check(lib.lsl_decoder_create(C.byref(desc), C.byref(w), C.byref(self._handle)))
-        self.device = dev
-        return self
-
-    def __del__(self):
-        try:
-            if self._handle:
-                _lib.load().lsl_decoder_destroy(self._handle)
-        except Exception:
-            pass
+        return desc, w
 
     # -- decode ----------------------------------------------------------------------------------------------
     @torch.no_grad()
     def decode(self, latents: Tensor, entities: Tensor) -> Tensor:
         """latents [F, L, C] fp32, entities [F, A] integer -> [F, A, out_dim] (the reference returns ``{"pos": ...}``;
         this is the tensor of the one head selected by ``output``)."""
-        if not latents.is_cuda:
-            raise RuntimeError("Stage1Decoder.decode needs CUDA/HIP tensors (no CPU path)")
-        if not self._handle or self.device != latents.device:
-            self.to(latents.device)
+        self._on(latents, "decode")
         if latents.dim() != 3 or latents.shape[-1] != self.in_dim or entities.dim() != 2 or entities.shape[0] != latents.shape[0]:
             raise ValueError("expected latents [F, L, C] and entities [F, A]")
-        lib = _lib.load()
         F_, L, _ = latents.shape
         A = entities.shape[1]
         z = latents.contiguous().float()
         ent = entities.contiguous().to(torch.int64)
-        need = lib.lsl_decode_workspace_bytes(self._handle, F_, L, A)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != z.device:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=z.device)
+        ws = self._scratch.get(z.device, _lib.load().lsl_decode_workspace_bytes(self._handle, F_, L, A))
         out = torch.empty(F_, A, self.out_dim, dtype=torch.float32, device=z.device)
-        _lib.check(lib.lsl_decode(self._handle, z.data_ptr(), ent.data_ptr(), F_, L, A, out.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
-                                  torch.cuda.current_stream(z.device).cuda_stream))
+        _lib.call(z.device, "lsl_decode", self._handle, z.data_ptr(), ent.data_ptr(), F_, L, A, out.data_ptr(), ws.data_ptr(), ws.numel())
         return out
 
     __call__ = decode

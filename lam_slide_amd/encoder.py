@@ -5,17 +5,18 @@
 """
 from __future__ import annotations
 
-import ctypes as C
-from typing import Dict, List, Optional
+from typing import Dict, Optional
 
 import torch
 from torch import Tensor
 
 from . import _lib
-from .decoder import _ACT, renorm_table
+from .decoder import _ACT, _Stage1, renorm_table
 
 
-class Stage1Encoder:
+class Stage1Encoder(_Stage1):
+    _create, _destroy = "lsl_encoder_create", "lsl_encoder_destroy"
+
     def __init__(self, state_dict: Dict[str, Tensor], *, num_head_cross: int, dim_head_cross: int, num_head_latent: int,
                  dim_head_latent: int, act: str = "gelu_erf", max_norm: Optional[float] = 1.0, device: Optional[torch.device] = None):
         if act not in _ACT:
@@ -40,82 +41,36 @@ class Stage1Encoder:
         self.act = act
         self._sd = {k: v.detach().to(torch.float32) for k, v in sd.items() if k.startswith(("quant.", "encoder."))}
         self._sd["encoder.entity_embedding.embedding.weight"] = renorm_table(self._sd["encoder.entity_embedding.embedding.weight"], max_norm)
-        self._handle = C.c_void_p()
-        self._dev_tensors: List[Tensor] = []
-        self._ws: Optional[Tensor] = None
-        if device is not None:
-            self.to(device)
+        self._init_handle(device)
 
-    def _p(self, key: str, dev) -> Optional[int]:
-        if key not in self._sd:
-            return None
-        t = self._sd[key].to(dev).contiguous()
-        self._dev_tensors.append(t)
-        return t.data_ptr()
-
-    def _block(self, prefix: str, dev, cross: bool) -> "_lib.DecBlock":
-        g = lambda name: self._p(f"{prefix}.{name}", dev)  # noqa: E731
-        return _lib.DecBlock(
-            ln_w=g("attn.norm.weight"), ln_b=g("attn.norm.bias"),
-            lnc_w=g("attn.norm_context.weight") if cross else None, lnc_b=g("attn.norm_context.bias") if cross else None,
-            w_q=g("attn.fn.to_q.weight") if cross else g("attn.fn.to_qkv.weight"), w_kv=g("attn.fn.to_kv.weight") if cross else None,
-            w_out=g("attn.fn.to_out.weight"), b_out=g("attn.fn.to_out.bias"),
-            q_scale=g("attn.fn.norm.query_norm.scale") if self.qk_norm else None, k_scale=g("attn.fn.norm.key_norm.scale") if self.qk_norm else None,
-            ff_ln_w=g("ff.norm.weight"), ff_ln_b=g("ff.norm.bias"), ff_w1=g("ff.fn.net.0.0.weight"), ff_b1=g("ff.fn.net.0.0.bias"),
-            ff_w2=g("ff.fn.net.1.weight"), ff_b2=g("ff.fn.net.1.bias"))
-
-    def to(self, device) -> "Stage1Encoder":
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("Stage1Encoder runs on the MI355X only (no CPU path)")
-        lib = _lib.load()
-        if self._handle:
-            lib.lsl_encoder_destroy(self._handle)
-            self._handle = C.c_void_p()
-        self._dev_tensors = []
-        cross = (_lib.DecBlock * max(self.num_block_cross, 1))(*[self._block(f"encoder.cross_attn_blocks.{i}", dev, True) for i in range(self.num_block_cross)])
-        selfs = (_lib.DecBlock * max(self.num_block_attn, 1))(*[self._block(f"encoder.blocks_attn.{i}", dev, False) for i in range(self.num_block_attn)])
+    def _describe(self, dev):
         w = _lib.EncoderWeights(
             table=self._p("encoder.entity_embedding.embedding.weight", dev),
             mlp_w1=self._p("encoder.mlp.0.weight", dev), mlp_b1=self._p("encoder.mlp.0.bias", dev),
             mlp_w2=self._p("encoder.mlp.2.weight", dev), mlp_b2=self._p("encoder.mlp.2.bias", dev),
-            latents=self._p("encoder.latents", dev), cross_blocks=cross, self_blocks=selfs,
+            latents=self._p("encoder.latents", dev), cross_blocks=self._blocks("encoder.cross_attn_blocks", self.num_block_cross, dev, True),
+            self_blocks=self._blocks("encoder.blocks_attn", self.num_block_attn, dev, False),
             quant_w=self._p("quant.0.weight", dev), quant_b=self._p("quant.0.bias", dev))
         desc = _lib.EncoderDesc(self.dim_input, self.dim_emb, self.n_entities, self.dim_latent, self.num_latents, self.heads_cross,
                                 self.dim_head_cross, self.heads_latent, self.dim_head_latent, self.num_block_cross, self.num_block_attn, _ACT[self.act])
-        _lib.check(lib.lsl_encoder_create(C.byref(desc), C.byref(w), C.byref(self._handle)))
-        self.device = dev
-        return self
-
-    def __del__(self):
-        try:
-            if self._handle:
-                _lib.load().lsl_encoder_destroy(self._handle)
-        except Exception:
-            pass
+        return desc, w
 
     @torch.no_grad()
     def encode(self, x: Tensor, entities: Tensor, mask: Optional[Tensor] = None) -> Tensor:
         """x [F, A, dim_input] fp32, entities [F, A] integer, mask [F, A] bool (True = real entity) -> latents [F, num_latents, dim_latent]."""
-        if not x.is_cuda:
-            raise RuntimeError("Stage1Encoder.encode needs CUDA/HIP tensors (no CPU path)")
-        if not self._handle or self.device != x.device:
-            self.to(x.device)
+        self._on(x, "encode")
         if x.dim() != 3 or x.shape[-1] != self.dim_input or tuple(entities.shape) != tuple(x.shape[:2]):
             raise ValueError("expected x [F, A, dim_input] and entities [F, A]")
         if mask is not None and tuple(mask.shape) != tuple(x.shape[:2]):
             raise ValueError("expected mask [F, A]")
-        lib = _lib.load()
         F_, A, _ = x.shape
         xx = x.contiguous().float()
         ent = entities.contiguous().to(torch.int64)
         mk = mask.contiguous().to(torch.uint8) if mask is not None else None
-        need = lib.lsl_encode_workspace_bytes(self._handle, F_, A)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != xx.device:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=xx.device)
+        ws = self._scratch.get(xx.device, _lib.load().lsl_encode_workspace_bytes(self._handle, F_, A))
         out = torch.empty(F_, self.num_latents, self.dim_latent, dtype=torch.float32, device=xx.device)
-        _lib.check(lib.lsl_encode(self._handle, xx.data_ptr(), ent.data_ptr(), mk.data_ptr() if mk is not None else None, F_, A, out.data_ptr(),
-                                  self._ws.data_ptr(), self._ws.numel(), torch.cuda.current_stream(xx.device).cuda_stream))
+        _lib.call(xx.device, "lsl_encode", self._handle, xx.data_ptr(), ent.data_ptr(), mk.data_ptr() if mk is not None else None, F_, A,
+                  out.data_ptr(), ws.data_ptr(), ws.numel())
         return out
 
     __call__ = encode

@@ -124,7 +124,7 @@ class LatentSIV3(nn.Module):
         self._packed: Optional[PackedWeights] = None
         self._packed_key = None
         self._handle = C.c_void_p()
-        self._workspaces: "OrderedDict[tuple, Tensor]" = OrderedDict()
+        self._scratch = _lib.Scratch(keep=4)
         self._pinned: "OrderedDict[tuple, Tensor]" = OrderedDict()
         self._chunk = 0
         self._tail = None  # None: the library's default (LSL_TAIL); True / False: set_tail
@@ -221,20 +221,9 @@ class LatentSIV3(nn.Module):
             _lib.load().lsl_model_set_chunk(self._handle, self._chunk)
 
     def workspace(self, B: int, T: int, L: int, device, need: Optional[int] = None) -> Tensor:
-        """Scratch of one call.  One buffer per (device, stream): two sampling calls of one model in flight on different streams
-        never share scratch (calls on ONE stream are ordered by the stream).  At most 4 buffers are kept.  ``need``: the bytes of a call
-        that wants more than a forward (``lsl_si_loss_workspace_bytes``)."""
-        device = torch.device(device)
-        need = max(_lib.load().lsl_workspace_bytes(self._handle, B, T, L), need or 0)
-        key = (device, torch.cuda.current_stream(device).cuda_stream)
-        ws = self._workspaces.get(key)
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(need, dtype=torch.uint8, device=device)
-            self._workspaces[key] = ws
-        self._workspaces.move_to_end(key)
-        while len(self._workspaces) > 4:
-            self._workspaces.popitem(last=False)
-        return ws
+        """Scratch of one call (``_lib.Scratch``: one buffer per (device, stream), at most 4 kept).  ``need``: the bytes of a call that
+        wants more than a forward (``lsl_si_loss_workspace_bytes``)."""
+        return self._scratch.get(device, max(_lib.load().lsl_workspace_bytes(self._handle, B, T, L), need or 0))
 
     @staticmethod
     def graph_replay_enabled(tokens: Optional[int] = None) -> bool:
@@ -312,7 +301,6 @@ class LatentSIV3(nn.Module):
     @torch.no_grad()
     def forward(self, x: Tensor, t: Tensor, x_cond: Tensor, x_cond_mask: Tensor, y: Tensor = None) -> Tensor:
         self._require_gpu(x)
-        lib = _lib.load()
         if x.dim() != 4:
             raise ValueError(f"x must be [B, T, L, C], got {tuple(x.shape)}")
         if t.device != x.device:
@@ -324,14 +312,12 @@ class LatentSIV3(nn.Module):
         if tuple(tt.shape) != (B,):
             raise ValueError(f"t must have shape ({B},) (or be a scalar), got {tuple(t.shape)}")
         tt = tt.contiguous()
-        with torch.cuda.device(x.device):
-            self.ensure_packed(x.device)
-            xin = x.detach().float().contiguous()
-            out = torch.empty_like(xin)
-            io, keep = self.make_io(xin, x_cond, x_cond_mask, y, tt, out)
-            ws = self.workspace(io.B, io.T, io.L, x.device)
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-            _lib.check(lib.lsl_forward(self._handle, C.byref(io), ws.data_ptr(), ws.numel(), stream))
+        self.ensure_packed(x.device)
+        xin = x.detach().float().contiguous()
+        out = torch.empty_like(xin)
+        io, keep = self.make_io(xin, x_cond, x_cond_mask, y, tt, out)
+        ws = self.workspace(io.B, io.T, io.L, x.device)
+        _lib.call(x.device, "lsl_forward", self._handle, C.byref(io), ws.data_ptr(), ws.numel())
         self.last_path = "hip"
         del keep
         return out.to(x.dtype)

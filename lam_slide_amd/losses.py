@@ -52,11 +52,8 @@ def geom_loss_sums(pred: Tensor, target: Tensor, mask: Tensor) -> Tensor:
     F_, A, D = p.shape
     if F_ == 0:
         raise ValueError("no frames")
-    dev = p.device
-    with torch.cuda.device(dev):
-        sums = torch.empty(F_, 5, dtype=torch.float32, device=dev)
-        _lib.check(_lib.load().lsl_geom_loss_sums(p.data_ptr(), t.data_ptr(), m.data_ptr(), F_, A, D, sums.data_ptr(),
-                                                  torch.cuda.current_stream(dev).cuda_stream))
+    sums = torch.empty(F_, 5, dtype=torch.float32, device=p.device)
+    _lib.call(p.device, "lsl_geom_loss_sums", p.data_ptr(), t.data_ptr(), m.data_ptr(), F_, A, D, sums.data_ptr())
     return sums
 
 
@@ -77,10 +74,8 @@ def geom_losses(pred: Optional[Tensor] = None, target: Optional[Tensor] = None, 
     if sums.dim() != 2 or sums.shape[1] != 5 or sums.shape[0] == 0 or sums.dtype != torch.float32:
         raise ValueError(f"sums must be float32 [F, 5] with F > 0, got {sums.dtype} {tuple(sums.shape)}")
     sums = sums.contiguous()
-    dev = sums.device
-    with torch.cuda.device(dev):
-        out = torch.empty(3, dtype=torch.float32, device=dev)
-        _lib.check(_lib.load().lsl_geom_loss_final(sums.data_ptr(), sums.shape[0], out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+    out = torch.empty(3, dtype=torch.float32, device=sums.device)
+    _lib.call(sums.device, "lsl_geom_loss_final", sums.data_ptr(), sums.shape[0], out.data_ptr())
     return {"pos_loss": out[0], "dist": out[1], "inter_dist_loss": out[2]}
 
 
@@ -139,11 +134,8 @@ class Loss(nn.Module):
         return all(_is_default(getattr(self, attr), name) for attr, (name, _) in _DEFAULTS.items())
 
     def fused_applies(self, pred_pos: Tensor, target_pos: Tensor) -> bool:
-        if not (pred_pos.is_cuda and target_pos.is_cuda and pred_pos.dim() >= 2):
-            return False
-        if pred_pos.dtype != torch.float32 or target_pos.dtype != torch.float32:  # (the torch path promotes as the reference does)
-            return False
-        if torch.is_grad_enabled() and (pred_pos.requires_grad or target_pos.requires_grad):
+        # (tensors on two GPUs stay on this path: ``_frames`` raises the reference-style device error)
+        if not _lib.device_form(pred_pos, target_pos, same_device=False) or pred_pos.dim() < 2:
             return False
         return native_shape(int(pred_pos.shape[-2]), int(pred_pos.shape[-1])) and self.default_modules()
 

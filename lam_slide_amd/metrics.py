@@ -31,14 +31,8 @@ def native_shape(D: int) -> bool:
 
 
 def fused_applies(pred: Tensor, target: Tensor) -> bool:
-    """The dispatch rule (as ``Loss.fused_applies``): float32 on the GPU, nothing requires grad, a native shape."""
-    if not (pred.is_cuda and target.is_cuda and target.device == pred.device):
-        return False
-    if pred.dtype != torch.float32 or target.dtype != torch.float32:  # (the torch path promotes as the reference does)
-        return False
-    if torch.is_grad_enabled() and (pred.requires_grad or target.requires_grad):
-        return False
-    return native_shape(int(pred.shape[-1]))
+    """The dispatch rule (``_lib.device_form``: float32 on one GPU, nothing requires grad) and a native shape."""
+    return _lib.device_form(pred, target) and native_shape(int(pred.shape[-1]))
 
 
 def _layout(pred: Tensor, target: Tensor, first_frame: int) -> Tuple[Tensor, int, int]:
@@ -78,11 +72,10 @@ def displacement_rows(pred: Tensor, target: Tensor, *, first_frame: int = 0) -> 
     K, B, T, A, D = pred.shape
     p, t = pred.detach().contiguous(), target.detach().contiguous()
     dev = p.device
-    with torch.cuda.device(dev):
-        rows = torch.empty(K, B, A, 2, dtype=torch.float32, device=dev)
-        traj = torch.empty(K, B, 2, dtype=torch.float32, device=dev)
-        _lib.check(_lib.load().lsl_disp_error_rows(p.data_ptr(), t.data_ptr(), K, B, T, int(first_frame), t.shape[1], t0t, Tf, A, D, rows.data_ptr(),
-                                                   traj.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+    rows = torch.empty(K, B, A, 2, dtype=torch.float32, device=dev)
+    traj = torch.empty(K, B, 2, dtype=torch.float32, device=dev)
+    _lib.call(dev, "lsl_disp_error_rows", p.data_ptr(), t.data_ptr(), K, B, T, int(first_frame), t.shape[1], t0t, Tf, A, D, rows.data_ptr(),
+              traj.data_ptr())
     return rows, traj
 
 
@@ -134,11 +127,10 @@ def displacement_errors(pred: Tensor, target: Tensor, agent_mask: Optional[Tenso
     if fused_applies(pred5, target):
         dev = rows.device
         m8 = None if keep is None else keep.contiguous().view(torch.uint8)
-        with torch.cuda.device(dev):
-            agents = torch.empty(B, A, 2, dtype=torch.float32, device=dev)
-            totals = torch.empty(5, dtype=torch.float64, device=dev)
-            _lib.check(_lib.load().lsl_disp_error_final(rows.data_ptr(), traj.data_ptr(), None if m8 is None else m8.data_ptr(), K, R, B, A,
-                                                        agents.data_ptr(), totals.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        agents = torch.empty(B, A, 2, dtype=torch.float32, device=dev)
+        totals = torch.empty(5, dtype=torch.float64, device=dev)
+        _lib.call(dev, "lsl_disp_error_final", rows.data_ptr(), traj.data_ptr(), None if m8 is None else m8.data_ptr(), K, R, B, A,
+                  agents.data_ptr(), totals.data_ptr())
         path = "fused"
     else:
         agents = rows[:R].min(dim=0).values  # (torch.min keeps a NaN)

@@ -217,10 +217,9 @@ def peptide_loss_sums(pred: Tensor, target_frame: Tensor, atom14_mask: Tensor, t
         raise ValueError("no frames")
     dev = p.device
     restab = residue_tables_on(residue_tables, dev)
-    with torch.cuda.device(dev):
-        sums = torch.empty(F_, 4, dtype=torch.float32, device=dev)
-        _lib.check(_lib.load().lsl_peptide_loss_sums(p.data_ptr(), tf.data_ptr(), am.data_ptr(), tt.data_ptr(), tm.data_ptr(), aa.data_ptr(),
-                                                     restab.data_ptr(), F_, R, int(kind), sums.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+    sums = torch.empty(F_, 4, dtype=torch.float32, device=dev)
+    _lib.call(dev, "lsl_peptide_loss_sums", p.data_ptr(), tf.data_ptr(), am.data_ptr(), tt.data_ptr(), tm.data_ptr(), aa.data_ptr(), restab.data_ptr(),
+              F_, R, int(kind), sums.data_ptr())
     return sums
 
 
@@ -262,11 +261,8 @@ def peptide_losses(pred: Optional[Tensor] = None, target: Optional[Tensor] = Non
     if not ok or geom.dtype != torch.float32 or pept.dtype != torch.float32 or geom.device != pept.device:
         raise ValueError(f"sums must be float32 ([F, 5], [F, 4]) with F > 0 on one device, got {geom.dtype} {tuple(geom.shape)} and {pept.dtype} {tuple(pept.shape)}")
     geom, pept = geom.contiguous(), pept.contiguous()
-    dev = geom.device
-    with torch.cuda.device(dev):
-        out = torch.empty(5, dtype=torch.float32, device=dev)
-        _lib.check(_lib.load().lsl_peptide_loss_final(geom.data_ptr(), pept.data_ptr(), geom.shape[0], out.data_ptr(),
-                                                      torch.cuda.current_stream(dev).cuda_stream))
+    out = torch.empty(5, dtype=torch.float32, device=geom.device)
+    _lib.call(geom.device, "lsl_peptide_loss_final", geom.data_ptr(), pept.data_ptr(), geom.shape[0], out.data_ptr())
     return {k: out[i] for i, k in enumerate(LOSS_KEYS)}
 
 
@@ -328,12 +324,9 @@ class PeptideLoss(nn.Module):
         return kind if kind is not None and _is_default(self.loss_torsion, type(self.loss_torsion).__name__) else None
 
     def fused_applies(self, pred_pos: Tensor, *float_targets: Tensor) -> bool:
-        tensors = (pred_pos,) + float_targets
-        if not all(x.is_cuda and x.dtype == torch.float32 for x in tensors):  # (the torch path promotes as the reference does)
-            return False
-        if torch.is_grad_enabled() and any(x.requires_grad for x in tensors):
-            return False
-        return native_shape(pred_pos.shape) and self.torsion_kind() is not None
+        # (tensors on two GPUs stay on this path: ``_peptide_frames`` raises the reference-style device error)
+        return (_lib.device_form(pred_pos, *float_targets, same_device=False) and native_shape(pred_pos.shape)
+                and self.torsion_kind() is not None)
 
     def _call(self, attr: str, *args: Tensor, **kwargs: Tensor) -> Tensor:
         module = getattr(self, attr)

@@ -41,10 +41,6 @@ _PAIR01 = np.array([[0, 1]], dtype=np.int32)
 _pair01_on: dict = {}
 
 
-def _stream(dev) -> int:
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 # ---- features ----
 def cossin_features(angles: Tensor) -> Tensor:
     """angles [..., n, Q] -> [..., n, 2 Q]: columns cos q0, sin q0, cos q1, sin q1, ... (pyemma's ``cossin=True`` order)."""
@@ -78,13 +74,12 @@ def lagged_moments(x: Tensor, lag: int) -> Tuple[Tensor, Tensor, Tensor, Tensor,
     if not 1 <= lag < n:
         raise ValueError(f"lag = {lag} outside 1..n-1 = {n - 1}: the window has n - lag rows")
     if fused_applies(v) and F <= _lib.MOM_MAX_F and S <= 65535:
-        lib, dev = _lib.load(), v.device
+        dev = v.device
         vc = v.detach().contiguous()
-        with torch.cuda.device(dev):
-            need = lib.lsl_lagged_moments_workspace_bytes(S, n, F, lag)
-            ws = torch.empty(need, dtype=torch.uint8, device=dev)
-            out = torch.empty(S, 2 * F + 3 * F * F, dtype=torch.float64, device=dev)
-            _lib.check(lib.lsl_lagged_moments(vc.data_ptr(), S, n, F, lag, out.data_ptr(), ws.data_ptr(), need, _stream(dev)))
+        need = _lib.load().lsl_lagged_moments_workspace_bytes(S, n, F, lag)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        out = torch.empty(S, 2 * F + 3 * F * F, dtype=torch.float64, device=dev)
+        _lib.call(dev, "lsl_lagged_moments", vc.data_ptr(), S, n, F, lag, out.data_ptr(), ws.data_ptr(), need)
         mats = out[:, 2 * F:].reshape(S, 3, F, F)
         res = (out[:, :F], out[:, F:2 * F], mats[:, 0], mats[:, 1], mats[:, 2])
         last_path["lagged_moments"] = "fused"
@@ -192,10 +187,8 @@ class TicaModel:
         rows = x.numel() // F
         if fused_applies(x) and F <= _lib.MOM_MAX_F and d <= _lib.PROJ_MAX_D and rows < 2 ** 31:
             xc, dev = x.detach().contiguous(), x.device
-            with torch.cuda.device(dev):
-                y = torch.empty(*x.shape[:-1], d, dtype=torch.float32, device=dev)
-                _lib.check(_lib.load().lsl_project(xc.data_ptr(), rows, F, mean.data_ptr(), W.data_ptr(), d, y.data_ptr(),
-                                                   None if lim is None else lim.data_ptr(), _stream(dev)))
+            y = torch.empty(*x.shape[:-1], d, dtype=torch.float32, device=dev)
+            _lib.call(dev, "lsl_project", xc.data_ptr(), rows, F, mean.data_ptr(), W.data_ptr(), d, y.data_ptr(), None if lim is None else lim.data_ptr())
             last_path["transform"] = "fused"
             return y
         y = ((x.detach().double() - mean) @ W).float()
@@ -254,11 +247,9 @@ def _counts(y: Tensor, edges: Tensor, ea: Optional[Tensor], eb: Optional[Tensor]
     if fused_applies(x) and edges.is_cuda and bins <= _lib.HIST_MAX_BINS and bins2 <= _lib.HIST2_MAX_BINS and n < 2 ** 31:
         if two and dev not in _pair01_on:
             _pair01_on[dev] = torch.from_numpy(_PAIR01).to(dev)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().lsl_histogram(x.data_ptr(), 1, n, Q, edges.data_ptr(), bins, counts.data_ptr(),
-                                                 _pair01_on[dev].data_ptr() if two else None, _PAIR01.ctypes.data if two else None, 1 if two else 0,
-                                                 ea.data_ptr() if two else None, eb.data_ptr() if two else None, bins2,
-                                                 counts2.data_ptr() if two else None, _stream(dev)))
+        _lib.call(dev, "lsl_histogram", x.data_ptr(), 1, n, Q, edges.data_ptr(), bins, counts.data_ptr(),
+                  _pair01_on[dev].data_ptr() if two else None, _PAIR01.ctypes.data if two else None, 1 if two else 0,
+                  ea.data_ptr() if two else None, eb.data_ptr() if two else None, bins2, counts2.data_ptr() if two else None)
         path = "fused"
     else:
         host = lambda t: None if t is None else t.cpu().numpy()  # noqa: E731
@@ -347,10 +338,9 @@ def assign_centers(y: Tensor, centers, state_map=None, nstates: Optional[int] = 
     if (fused_applies(y, c) and d <= _lib.ASG_MAX_D and k <= _lib.ASG_MAX_K and k * d <= _lib.ASG_CELLS and nstates <= _lib.ASG_MAX_STATES
             and n < 2 ** 31):
         yc, cc = y.detach().contiguous(), c.contiguous()
-        with torch.cuda.device(dev):
-            labels = torch.empty(n, dtype=torch.int32, device=dev)
-            _lib.check(_lib.load().lsl_assign_centers(yc.data_ptr(), n, d, cc.data_ptr(), k, None if smap is None else smap.data_ptr(), nstates,
-                                                      labels.data_ptr(), counts.data_ptr(), _stream(dev)))
+        labels = torch.empty(n, dtype=torch.int32, device=dev)
+        _lib.call(dev, "lsl_assign_centers", yc.data_ptr(), n, d, cc.data_ptr(), k, None if smap is None else smap.data_ptr(), nstates,
+                  labels.data_ptr(), counts.data_ptr())
         last_path["assign_centers"] = "fused"
         return labels, counts
     idx = _assign_torch(y.detach(), c)
@@ -379,8 +369,7 @@ def transition_counts(dtraj: Tensor, lag: int, nstates: int) -> Tensor:
     counts = torch.zeros(S, ns, ns, dtype=torch.int64, device=dev)
     if v.is_cuda and v.dtype in (torch.int32, torch.int64) and ns <= _lib.TR_MAX_STATES and S <= 65535:
         vc = v.to(torch.int32).contiguous()
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().lsl_transition_counts(vc.data_ptr(), S, n, lag, ns, counts.data_ptr(), _stream(dev)))
+        _lib.call(dev, "lsl_transition_counts", vc.data_ptr(), S, n, lag, ns, counts.data_ptr())
         last_path["transition_counts"] = "fused"
     else:
         if lag < n:

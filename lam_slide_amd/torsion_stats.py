@@ -92,14 +92,8 @@ def eval_torsion_quads(aatype, tables=None, sidechains: bool = True) -> Tuple[np
 
 # ---- dispatch ----
 def fused_applies(*tensors: Tensor, dtype: torch.dtype = torch.float32) -> bool:
-    """The dispatch rule (as ``metrics.fused_applies``): every tensor of ``dtype`` on the same GPU, nothing requires grad."""
-    dev = tensors[0].device
-    for t in tensors:
-        if not t.is_cuda or t.device != dev or t.dtype != dtype:
-            return False
-        if torch.is_grad_enabled() and t.requires_grad:
-            return False
-    return True
+    """The dispatch rule: every tensor of ``dtype`` on the same GPU, nothing requires grad; each function adds its own limits."""
+    return _lib.device_form(*tensors, dtype=dtype)
 
 
 def _index_table(table, width: int, name: str) -> np.ndarray:
@@ -121,10 +115,6 @@ def _edges(lo_hi, bins: int, name: str = "range") -> np.ndarray:
     return np.linspace(lo, hi, int(bins) + 1)  # (float64: the edge table np.histogram builds for range=)
 
 
-def _stream(dev) -> int:
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 # ---- a. dihedral angles ----
 def _dihedral_torch(pos: Tensor, quads: Tensor) -> Tensor:
     p = pos[..., quads, :]  # [..., Q, 4, 3]
@@ -136,11 +126,8 @@ def _dihedral_torch(pos: Tensor, quads: Tensor) -> Tensor:
 def _dihedral_fused(pos: Tensor, quads_host: np.ndarray, quads_dev: Tensor) -> Tensor:
     A, Q = int(pos.shape[-2]), int(quads_host.shape[0])
     p = pos.detach().contiguous()
-    dev = p.device
-    with torch.cuda.device(dev):
-        out = torch.empty(*p.shape[:-2], Q, dtype=torch.float32, device=dev)
-        _lib.check(_lib.load().lsl_dihedral_angles(p.data_ptr(), quads_dev.data_ptr(), quads_host.ctypes.data, p.numel() // (A * 3), A, Q,
-                                                   out.data_ptr(), _stream(dev)))
+    out = torch.empty(*p.shape[:-2], Q, dtype=torch.float32, device=p.device)
+    _lib.call(p.device, "lsl_dihedral_angles", p.data_ptr(), quads_dev.data_ptr(), quads_host.ctypes.data, p.numel() // (A * 3), A, Q, out.data_ptr())
     return out
 
 
@@ -155,7 +142,7 @@ def dihedral_angles(pos: Tensor, quads) -> Tensor:
     A = int(pos.shape[-2])
     if qh.min() < 0 or qh.max() >= A:
         raise ValueError(f"quads holds an index outside the frame's atoms 0..{A - 1}")
-    if fused_applies(pos) and 1 <= A <= _lib.TORS_MAX_A and qh.shape[0] <= 65536 and pos.numel() > 0:
+    if fused_applies(pos) and 1 <= A <= _lib.TORS_MAX_A and qh.shape[0] <= _lib.TORS_MAX_Q and pos.numel() > 0:
         last_path["dihedral_angles"] = "fused"
         return _dihedral_fused(pos, qh, torch.from_numpy(qh).to(pos.device))
     last_path["dihedral_angles"] = "torch"
@@ -194,11 +181,9 @@ def _hist_add(x: Tensor, edges, pairs, ea, eb, counts: Tensor, counts2: Optional
         else:
             on = cache[key]
         xc = x.detach().contiguous()
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().lsl_histogram(xc.data_ptr(), S, n, Q, on["edges"].data_ptr(), bins, counts.data_ptr(),
-                                                 on["pairs"].data_ptr() if P else None, pairs.ctypes.data if P else None, P,
-                                                 on["ea"].data_ptr() if P else None, on["eb"].data_ptr() if P else None, bins2,
-                                                 counts2.data_ptr() if P else None, _stream(dev)))
+        _lib.call(dev, "lsl_histogram", xc.data_ptr(), S, n, Q, on["edges"].data_ptr(), bins, counts.data_ptr(),
+                  on["pairs"].data_ptr() if P else None, pairs.ctypes.data if P else None, P,
+                  on["ea"].data_ptr() if P else None, on["eb"].data_ptr() if P else None, bins2, counts2.data_ptr() if P else None)
         return "fused"
     c, c2 = _hist_numpy(x, edges, pairs, ea, eb)
     counts += torch.from_numpy(c).to(counts.device)
@@ -264,9 +249,8 @@ def js_distance(counts_a: Tensor, counts_b: Tensor) -> Tensor:
             and counts_a.numel() > 0 and counts_a.numel() // counts_a.shape[-1] < 2 ** 31):
         a, b = counts_a.to(torch.int64).contiguous(), counts_b.to(torch.int64).contiguous()
         dev, bins = a.device, int(a.shape[-1])
-        with torch.cuda.device(dev):
-            out = torch.empty(a.shape[:-1], dtype=torch.float64, device=dev)
-            _lib.check(_lib.load().lsl_js_distance(a.data_ptr(), b.data_ptr(), a.numel() // bins, bins, out.data_ptr(), _stream(dev)))
+        out = torch.empty(a.shape[:-1], dtype=torch.float64, device=dev)
+        _lib.call(dev, "lsl_js_distance", a.data_ptr(), b.data_ptr(), a.numel() // bins, bins, out.data_ptr())
         last_path["js_distance"] = "fused"
         return out
     last_path["js_distance"] = "torch"
@@ -297,23 +281,17 @@ def lagged_products(x: Tensor, nlag: int) -> Tensor:
     if not 0 <= nlag < n:
         raise ValueError(f"nlag = {nlag} outside 0..n-1 = {n - 1}: lag k has n - k terms")
     if fused_applies(v) and nlag + 1 <= _lib.LAG_MAX_LAGS and S <= _lib.LAG_MAX_ROWS:
-        lib, dev = _lib.load(), v.device
-        per_channel = lib.lsl_lag_products_workspace_bytes(S, n, 1, nlag)
+        dev = v.device
+        per_channel = _lib.load().lsl_lag_products_workspace_bytes(S, n, 1, nlag)
         step = max(1, min(C, LAG_WORKSPACE_BYTES // per_channel, _lib.LAG_MAX_ROWS // S))
-        with torch.cuda.device(dev):
-            ws = torch.empty(per_channel * step, dtype=torch.uint8, device=dev)
-            if step >= C:
-                vc = v.detach().contiguous()
-                out = torch.empty(S, C, nlag + 1, dtype=torch.float32, device=dev)
-                _lib.check(lib.lsl_lag_products(vc.data_ptr(), S, n, C, nlag, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
-            else:  # (a channel's bits do not depend on the channels beside it)
-                parts = []
-                for c0 in np.arange(0, C, step):
-                    vc = v.detach()[:, :, c0:c0 + step].contiguous()
-                    part = torch.empty(S, vc.shape[2], nlag + 1, dtype=torch.float32, device=dev)
-                    _lib.check(lib.lsl_lag_products(vc.data_ptr(), S, n, vc.shape[2], nlag, part.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
-                    parts.append(part)
-                out = torch.cat(parts, dim=1)
+        ws = torch.empty(per_channel * step, dtype=torch.uint8, device=dev)
+        parts = []
+        for c0 in np.arange(0, C, step):  # (a channel's bits do not depend on the channels beside it)
+            vc = v.detach()[:, :, c0:c0 + step].contiguous()
+            part = torch.empty(S, vc.shape[2], nlag + 1, dtype=torch.float32, device=dev)
+            _lib.call(dev, "lsl_lag_products", vc.data_ptr(), S, n, vc.shape[2], nlag, part.data_ptr(), ws.data_ptr(), ws.numel())
+            parts.append(part)
+        out = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
         last_path["lagged_products"] = "fused"
     else:
         out = _lag_torch(v.detach(), nlag)
@@ -388,7 +366,7 @@ class TorsionStats:
             self.counts2 = None if self.pairs is None else torch.zeros(self.pairs.shape[0], self.bins2, self.bins2, dtype=torch.int64, device=dev)
         elif self.counts.device != dev:
             raise RuntimeError(f"TorsionStats holds counts on {self.counts.device}, pos is on {dev}")
-        if fused_applies(pos) and A <= _lib.TORS_MAX_A and Q <= 65536:
+        if fused_applies(pos) and A <= _lib.TORS_MAX_A and Q <= _lib.TORS_MAX_Q:
             if ("quads", dev) not in self._on:
                 self._on[("quads", dev)] = torch.from_numpy(self.quads).to(dev)
             angles = _dihedral_fused(pos, self.quads, self._on[("quads", dev)])

@@ -258,7 +258,6 @@ class Transport:
         for name in ("x_cond", "x_cond_mask"):
             if name not in model_kwargs:
                 raise TypeError(f"missing model kwarg {name!r}")
-        lib = _lib.load()
         dev = x1.device
         B = x1.shape[0]
         if tuple(x0.shape) != tuple(x1.shape) or tuple(t.shape) != (B,):
@@ -266,19 +265,16 @@ class Transport:
         for name, ten in (("t", t), ("x0", x0)):
             if ten.device != dev:
                 raise RuntimeError(f"Expected all tensors to be on the same device, but {name} is on {ten.device} and x1 is on {dev}")
-        with torch.cuda.device(dev):
-            net.ensure_packed(dev)
-            x1 = x1.detach()
-            x0 = x0.detach().float().contiguous()
-            tt = t.detach().float().contiguous()
-            xt, pred = torch.empty_like(x1), torch.empty_like(x1)
-            loss = torch.empty(B, dtype=torch.float32, device=dev)
-            table = rows.contiguous().to(dev)
-            io, keep = net.make_io(xt, model_kwargs["x_cond"], model_kwargs["x_cond_mask"], model_kwargs.get("y"), tt, pred)
-            ws = net.workspace(io.B, io.T, io.L, dev, need=lib.lsl_si_loss_workspace_bytes(net._handle, io.B, io.T, io.L))
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(lib.lsl_si_loss(net._handle, C.byref(io), x1.data_ptr(), x0.data_ptr(), table.data_ptr(), loss.data_ptr(), ws.data_ptr(),
-                                       ws.numel(), stream))
+        net.ensure_packed(dev)
+        x1 = x1.detach()
+        x0 = x0.detach().float().contiguous()
+        tt = t.detach().float().contiguous()
+        xt, pred = torch.empty_like(x1), torch.empty_like(x1)
+        loss = torch.empty(B, dtype=torch.float32, device=dev)
+        table = rows.contiguous().to(dev)
+        io, keep = net.make_io(xt, model_kwargs["x_cond"], model_kwargs["x_cond_mask"], model_kwargs.get("y"), tt, pred)
+        ws = net.workspace(io.B, io.T, io.L, dev, need=_lib.load().lsl_si_loss_workspace_bytes(net._handle, io.B, io.T, io.L))
+        _lib.call(dev, "lsl_si_loss", net._handle, C.byref(io), x1.data_ptr(), x0.data_ptr(), table.data_ptr(), loss.data_ptr(), ws.data_ptr(), ws.numel())
         net.last_path = "hip"
         del keep
         return {"pred": pred, "loss": loss, "xt": xt}
@@ -309,12 +305,11 @@ def si_reduce(pred: Tensor, x1: Tensor, x0: Tensor, rows: Tensor) -> Tensor:
     if tuple(rows.shape) != (B, 6):
         raise ValueError(f"rows must be [{B}, 6], got {tuple(rows.shape)}")
     dev = pred.device
-    with torch.cuda.device(dev):
-        table = rows.float().contiguous().to(dev)
-        loss = torch.empty(B, dtype=torch.float32, device=dev)
-        scratch = torch.empty(B * ((per + _lib.SI_SLAB - 1) // _lib.SI_SLAB), dtype=torch.float32, device=dev)
-        _lib.check(_lib.load().lsl_si_reduce(pred.data_ptr(), x1.data_ptr(), x0.data_ptr(), table.data_ptr(), B, per, loss.data_ptr(),
-                                             scratch.data_ptr(), scratch.numel() * 4, torch.cuda.current_stream(dev).cuda_stream))
+    table = rows.float().contiguous().to(dev)
+    loss = torch.empty(B, dtype=torch.float32, device=dev)
+    scratch = torch.empty(B * ((per + _lib.SI_SLAB - 1) // _lib.SI_SLAB), dtype=torch.float32, device=dev)
+    _lib.call(dev, "lsl_si_reduce", pred.data_ptr(), x1.data_ptr(), x0.data_ptr(), table.data_ptr(), B, per, loss.data_ptr(), scratch.data_ptr(),
+              scratch.numel() * 4)
     return loss
 
 
@@ -383,10 +378,8 @@ def device_randn(shape, device, seed: int, elem_offset: int = 0) -> Tensor:
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("device_randn draws on the GPU (HIP kernel); there is no CPU fallback")
-    with torch.cuda.device(device):
-        out = torch.empty(tuple(shape), dtype=torch.float32, device=device)
-        _lib.check(_lib.load().lsl_randn(out.data_ptr(), out.numel(), int(seed) & _MASK64, int(elem_offset),
-                                         torch.cuda.current_stream(device).cuda_stream))
+    out = torch.empty(tuple(shape), dtype=torch.float32, device=device)
+    _lib.call(device, "lsl_randn", out.data_ptr(), out.numel(), int(seed) & _MASK64, int(elem_offset))
     return out
 
 
@@ -476,7 +469,7 @@ class _RkOps:
     def __init__(self, like: Tensor):
         self.hip = like.is_cuda and like.dtype == torch.float32
         if self.hip:
-            self.lib = _lib.load()
+            _lib.load()  # (LibraryMissing is raised here, where Sampler._vel catches it)
             self.dev = like.device
             self.scratch = torch.empty(_lib.RK_SCRATCH_BYTES // 4, dtype=torch.float32, device=like.device)
             self.ratio = torch.empty(1, dtype=torch.float32, device=like.device)
@@ -487,9 +480,6 @@ class _RkOps:
         cs = (C.c_float * len(xs))(*[float(c) for c, _ in terms])
         return xs, ptrs, cs
 
-    def _stream(self):
-        return torch.cuda.current_stream(self.dev).cuda_stream
-
     def lincomb(self, terms) -> Tensor:
         if not self.hip:
             rnd = _f32 if terms[0][1].dtype == torch.float32 else float  # (the kernels take fp32 coefficients)
@@ -499,8 +489,7 @@ class _RkOps:
             return acc
         xs, ptrs, cs = self._pack(terms)
         out = torch.empty_like(xs[0])
-        with torch.cuda.device(self.dev):
-            _lib.check(self.lib.lsl_rk_lincomb(out.data_ptr(), ptrs, cs, len(xs), out.numel(), self._stream()))
+        _lib.call(self.dev, "lsl_rk_lincomb", out.data_ptr(), ptrs, cs, len(xs), out.numel())
         return out
 
     def error_ratio(self, y0: Tensor, y1: Tensor, terms, atol: float, rtol: float) -> float:
@@ -509,9 +498,8 @@ class _RkOps:
             return _rms(self.lincomb(terms) / (atol + rtol * torch.maximum(y0.abs(), y1.abs())))
         xs, ptrs, cs = self._pack(terms)
         y0, y1 = y0.contiguous(), y1.contiguous()
-        with torch.cuda.device(self.dev):
-            _lib.check(self.lib.lsl_rk_error_ratio(self.ratio.data_ptr(), y0.data_ptr(), y1.data_ptr(), ptrs, cs, len(xs), float(atol), float(rtol),
-                                                   y0.numel(), self.scratch.data_ptr(), self._stream()))
+        _lib.call(self.dev, "lsl_rk_error_ratio", self.ratio.data_ptr(), y0.data_ptr(), y1.data_ptr(), ptrs, cs, len(xs), float(atol), float(rtol),
+                  y0.numel(), self.scratch.data_ptr())
         return float(self.ratio.item())
 
     def poly4(self, a: Tensor, b: Tensor, c: Tensor, d: Tensor, e: Tensor, x: float) -> Tensor:
@@ -519,9 +507,7 @@ class _RkOps:
             xf = _f32(x) if e.dtype == torch.float32 else float(x)
             return e + xf * (d + xf * (c + xf * (b + xf * a)))
         out = torch.empty_like(e)
-        with torch.cuda.device(self.dev):
-            _lib.check(self.lib.lsl_rk_dense(out.data_ptr(), a.data_ptr(), b.data_ptr(), c.data_ptr(), d.data_ptr(), e.data_ptr(), float(x), out.numel(),
-                                             self._stream()))
+        _lib.call(self.dev, "lsl_rk_dense", out.data_ptr(), a.data_ptr(), b.data_ptr(), c.data_ptr(), d.data_ptr(), e.data_ptr(), float(x), out.numel())
         return out
 
 
@@ -763,41 +749,39 @@ class Sampler:
         needs_device_noise = noise is None and any(s[3] != 0.0 for s in table)
         call_seed = self.next_call_seed(draw=needs_device_noise)
         self.last_seed = call_seed if needs_device_noise else None
-        with torch.cuda.device(dev):
-            net.ensure_packed(dev)
-            # the state is updated in place by the library: always a private copy (persistent buffers only for calls the library may replay as a hipGraph, see staged())
-            replay = net.graph_replay_enabled(tokens=int(init.shape[0]) * int(init.shape[1]) * int(init.shape[2]))
-            x = net.staged("state", init, torch.float32, dev, fresh=True, persistent=replay)
-            xc = net.staged("x_cond", model_kwargs["x_cond"], torch.float32, dev, persistent=replay)
-            xm = net.staged("x_cond_mask", model_kwargs["x_cond_mask"], torch.int64, dev, persistent=replay)
-            yv = model_kwargs.get("y")
-            if yv is not None:
-                yv = net.staged("y", yv, torch.float32, dev, persistent=replay)
-            io, keep = net.make_io(x, xc, xm, yv)
-            ws = net.workspace(io.B, io.T, io.L, dev)
+        net.ensure_packed(dev)
+        # the state is updated in place by the library: always a private copy (persistent buffers only for calls the library may replay as a hipGraph, see staged())
+        replay = net.graph_replay_enabled(tokens=int(init.shape[0]) * int(init.shape[1]) * int(init.shape[2]))
+        x = net.staged("state", init, torch.float32, dev, fresh=True, persistent=replay)
+        xc = net.staged("x_cond", model_kwargs["x_cond"], torch.float32, dev, persistent=replay)
+        xm = net.staged("x_cond_mask", model_kwargs["x_cond_mask"], torch.int64, dev, persistent=replay)
+        yv = model_kwargs.get("y")
+        if yv is not None:
+            yv = net.staged("y", yv, torch.float32, dev, persistent=replay)
+        io, keep = net.make_io(x, xc, xm, yv)
+        ws = net.workspace(io.B, io.T, io.L, dev)
+        if records is None:
+            arr = (_lib.Step * len(steps))(*[_lib.Step(*s) for s in steps])
+        else:
+            arr = (_lib.StepEx * len(records))(*[_lib.StepEx(*r) for r in records])
+        trace = None
+        if self.keep_trajectory:
+            trace = torch.empty((len(steps),) + tuple(x.shape), dtype=torch.float32, device=dev)
+        nz = None
+        if noise is not None:  # slice s belongs to step s, like the reference's one draw per EM / Heun step
+            nz = noise.detach().float().contiguous().to(dev)
             if records is None:
-                arr = (_lib.Step * len(steps))(*[_lib.Step(*s) for s in steps])
+                need = max([i + 1 for i, s in enumerate(steps) if s[3] != 0.0], default=0)
             else:
-                arr = (_lib.StepEx * len(records))(*[_lib.StepEx(*r) for r in records])
-            trace = None
-            if self.keep_trajectory:
-                trace = torch.empty((len(steps),) + tuple(x.shape), dtype=torch.float32, device=dev)
-            nz = None
-            if noise is not None:  # slice s belongs to step s, like the reference's one draw per EM / Heun step
-                nz = noise.detach().float().contiguous().to(dev)
-                if records is None:
-                    need = max([i + 1 for i, s in enumerate(steps) if s[3] != 0.0], default=0)
-                else:
-                    need = max([r[6] + 1 for r in records if r[3] != 0.0], default=0)
-                if nz.shape[0] < need or tuple(nz.shape[1:]) != tuple(x.shape):
-                    raise ValueError(f"noise must be [>={need}, {tuple(x.shape)}], got {tuple(nz.shape)}")
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            head = (net._handle, C.byref(io), arr, len(arr), nz.data_ptr() if nz is not None else None,
-                    nz.shape[0] if nz is not None else 0, call_seed, self.elem_offset, trace.data_ptr() if trace is not None else None)
-            if records is None:
-                _lib.check(lib.lsl_sample(*head, ws.data_ptr(), ws.numel(), stream))
-            else:  # (the library checks every record's trace slice against the slices the buffer really has)
-                _lib.check(lib.lsl_sample_ex(*head, trace.shape[0] if trace is not None else 0, ws.data_ptr(), ws.numel(), stream))
+                need = max([r[6] + 1 for r in records if r[3] != 0.0], default=0)
+            if nz.shape[0] < need or tuple(nz.shape[1:]) != tuple(x.shape):
+                raise ValueError(f"noise must be [>={need}, {tuple(x.shape)}], got {tuple(nz.shape)}")
+        head = (net._handle, C.byref(io), arr, len(arr), nz.data_ptr() if nz is not None else None,
+                nz.shape[0] if nz is not None else 0, call_seed, self.elem_offset, trace.data_ptr() if trace is not None else None)
+        if records is None:
+            _lib.call(dev, "lsl_sample", *head, ws.data_ptr(), ws.numel())
+        else:  # (the library checks every record's trace slice against the slices the buffer really has)
+            _lib.call(dev, "lsl_sample_ex", *head, trace.shape[0] if trace is not None else 0, ws.data_ptr(), ws.numel())
         net.last_path = "hip"
         self.last_path = "fused"
         # (extended records always run the general kernels: the trajectory-resident kernel implements the plain affine step only)
@@ -823,8 +807,7 @@ class Sampler:
         tf = float(t.flatten()[0])
         vx, vm = tr.velocity_coeffs(tf)
         v = None
-        needs_grad = torch.is_grad_enabled() and (x.requires_grad or out.requires_grad)  # (the library result carries no grad_fn)
-        if x.is_cuda and x.dtype == torch.float32 and out.dtype == torch.float32 and out.shape == x.shape and not needs_grad:
+        if _lib.device_form(x, out) and out.shape == x.shape:
             # one library launch instead of three element-wise kernels; the same two rounded products and their rounded sum
             ops = self._rk_ops.get(x.device)
             if ops is None:

@@ -59,6 +59,11 @@ ENCODER_CASES = (
 )
 ENCODER_MULTI = {"md17": (2, 300), "w32": (3, 65), "w64": (2, 127), "w32_noqk": (3, 65)}
 
+# lsl_decode_workspace_bytes / lsl_encode_workspace_bytes of every case, in the order of the case tables, recorded from the library as it
+# was before dec_carve and enc_carve were put on one carve function: callers size their scratch by these, the carve must keep them
+DECODE_WORKSPACE_BYTES = (4736, 2810880, 2097664, 4416, 832768, 1083200, 990656, 668608, 512, 4544, 2152448, 832768)
+ENCODE_WORKSPACE_BYTES = (1106944, 4042752, 912000, 2053632, 1276224, 912000)
+
 Model = namedtuple("Model", "sd shape ctor")  # state dict, oracle.harness shape, keyword arguments of Stage1Decoder / Stage1Encoder
 DecoderCase = namedtuple("DecoderCase", "z entities want ref_err")
 EncoderCase = namedtuple("EncoderCase", "x entities mask want want_nomask ref_err ref_err_nomask")

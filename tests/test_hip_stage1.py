@@ -14,7 +14,8 @@ Measured on MI355X (profiles/stage1_parity.txt); in brackets the fp32 oracle's o
   * encode, every class, with and without the mask: 1.7-2.5e-7 [1.6-2.5e-7]
   every other bar is 2e-6.
 
-Everything else is bit-exact: frame subsets, a reused handle, mask forms, masked-out inputs, views and index types, clamped indices.
+Everything else is bit-exact: frame subsets, a reused handle, calls on side streams (each with a scratch buffer of its own), mask forms,
+masked-out inputs, views and index types, clamped indices.
 A key count beyond the tile is refused by `_lib.check` as every shape refusal of the library is (code -3, ValueError) with a message
 that names the LDS tile."""
 import ctypes as C
@@ -164,6 +165,41 @@ def test_encode_handle_reused_across_shapes_matches_fresh_handles(dev):
     for F, A in ((2, 252), (1, 1), (3, 65), (2, 252)):
         x, ent, mask = (t.to(dev) for t in sc.encoder_inputs("w32", F, A))
         assert torch.equal(enc.encode(x, ent, mask), encoder("w32", dev, fresh=True).encode(x, ent, mask)), (F, A)
+
+
+def test_scratch_is_per_stream_for_the_stage1_objects_and_the_model(dev):
+    """One decoder / encoder called on the default stream and on two side streams: the same bits three times, a scratch buffer of its
+    own per stream (two calls in flight on two streams never write the same LayerNorm, q/k/v and attention buffers), and the buffer of a
+    stream reused by the next call on it.  ``LatentSIV3.workspace`` keeps its buffers the same way.  (The race of a shared buffer is
+    not staged here: only who owns which buffer.)"""
+    from lam_slide_amd import LatentSIV3
+    dec, enc = decoder("tiny", dev, fresh=True), encoder("w32", dev, fresh=True)
+    z, ent = (t.to(dev) for t in sc.decoder_inputs("tiny", 5, 3, 2))
+    x, ent_e, mask = (t.to(dev) for t in sc.encoder_inputs("w32", 3, 65))
+    side = [torch.cuda.Stream(dev), torch.cuda.Stream(dev)]
+    torch.cuda.synchronize()  # the inputs are there before any side stream reads them
+
+    def on(stream, run):
+        with torch.cuda.stream(stream):
+            out = run()
+        stream.synchronize()
+        return out
+
+    for obj, run in ((dec, lambda: dec.decode(z, ent)), (enc, lambda: enc.encode(x, ent_e, mask))):
+        buf = lambda stream: obj._scratch.buffers[dev, stream.cuda_stream]  # noqa: E731
+        first = on(torch.cuda.current_stream(dev), run)
+        main = buf(torch.cuda.current_stream(dev))
+        assert torch.equal(on(side[0], run), first) and torch.equal(on(side[1], run), first)
+        a, b = buf(side[0]), buf(side[1])
+        assert len({main.data_ptr(), a.data_ptr(), b.data_ptr()}) == 3 and min(main.numel(), a.numel(), b.numel()) > 0
+        assert torch.equal(on(side[0], run), first)
+        assert buf(side[0]) is a and buf(side[1]) is b and len(obj._scratch.buffers) == 3
+    net = LatentSIV3(depth=1, in_dim=8, hidden_size=64, num_heads=4)
+    net.ensure_packed(dev)
+    ws = lambda: net.workspace(2, 3, 5, dev)  # noqa: E731
+    main, a, b = ws(), on(side[0], ws), on(side[1], ws)
+    assert len({main.data_ptr(), a.data_ptr(), b.data_ptr()}) == 3 and min(main.numel(), a.numel(), b.numel()) > 0
+    assert on(side[0], ws) is a and on(side[1], ws) is b and ws() is main
 
 
 # ---------------------------------------------------------------------------------------------------------- boundaries

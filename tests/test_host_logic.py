@@ -32,6 +32,39 @@ def test_library_builds_and_exports_header_symbols():
     assert defined == declared, defined ^ declared
 
 
+def test_every_limit_the_binding_mirrors_equals_its_macro():
+    """The limits the dispatch rules read (_lib.py) are copies of ``#define`` s of the header and the kernel headers: each equals the
+    integer value of its macro's expression (``(1 << 21)``, ``16777215LL``, ``(LSL_GEOM_MAX_A / 14)``), so a limit changed in a header
+    alone cannot send a shape the kernel refuses down the device path."""
+    import glob
+    from lam_slide_amd import _lib, peptide_loss
+    defines = {}
+    for path in [os.path.join(ROOT, "include", "lsl_api.h")] + sorted(glob.glob(os.path.join(_lib.SRC_DIR, "*.hip.h"))):
+        for name, expr in re.findall(r"^#define (LSL_\w+)[ \t]+([^\n]*?)[ \t]*(?://[^\n]*|/\*[^\n]*)?$", open(path).read(), re.M):
+            defines[name] = expr
+
+    def macro(name):
+        expr = re.sub(r"LSL_\w+", lambda m: str(macro(m.group(0))), defines[name])
+        expr = re.sub(r"(\d)L+\b", r"\1", expr).replace("/", "//")
+        assert re.fullmatch(r"[\d\s()<>*/+-]+", expr), (name, expr)
+        return eval(expr)  # (digits, brackets and integer operators only)
+
+    mirrors = {"RK_SCRATCH_BYTES": "LSL_RK_SCRATCH_BYTES", "SI_SLAB": "LSL_SI_SLAB", "GEOM_MAX_A": "LSL_GEOM_MAX_A", "GEOM_MAX_D": "LSL_GEOM_MAX_D",
+               "DISP_MAX_D": "LSL_DISP_MAX_D", "DISP_MAX_UNITS": "LSL_DISP_MAX_UNITS", "TORS_MAX_A": "LSL_TORS_MAX_A", "TORS_MAX_Q": "LSL_TORS_MAX_Q",
+               "HIST_MAX_BINS": "LSL_HIST_MAX_BINS", "HIST2_MAX_BINS": "LSL_HIST2_MAX_BINS", "LAG_CHUNK": "LSL_LAG_CHUNK",
+               "LAG_MAX_LAGS": "LSL_LAG_MAX_PART", "LAG_MAX_ROWS": "LSL_LAG_MAX_ROWS", "MOM_SEG": "LSL_MOM_SEG", "MOM_CHAIN": "LSL_MOM_SEG",
+               "MOM_MAX_F": "LSL_MOM_MAX_F", "PROJ_MAX_D": "LSL_PROJ_MAX_D", "ASG_MAX_K": "LSL_ASG_MAX_K", "ASG_MAX_D": "LSL_ASG_MAX_D",
+               "ASG_CELLS": "LSL_ASG_CELLS", "ASG_MAX_STATES": "LSL_ASG_MAX_STATES", "TR_MAX_STATES": "LSL_TR_MAX_STATES"}
+    # every upper-case integer of the binding is in the table, except the ABI version (checked above) and the two step flags
+    ints = {k for k, v in vars(_lib).items() if k.isupper() and type(v) is int}
+    assert ints - {"ABI_VERSION", "STEP_NO_NETWORK", "STEP_SAVE"} == set(mirrors), ints ^ set(mirrors)
+    for attr, name in mirrors.items():
+        assert getattr(_lib, attr) == macro(name), (attr, name, getattr(_lib, attr), macro(name))
+    assert (_lib.LAG_MAX_LAGS, _lib.DISP_MAX_UNITS, _lib.TORS_MAX_Q, _lib.LAG_MAX_ROWS) == (1 << 21, 16777215, 65536, 65535)
+    assert peptide_loss.MAX_R == macro("LSL_PEPT_MAX_R") == 146
+    assert (_lib.STEP_NO_NETWORK, _lib.STEP_SAVE) == (macro("LSL_STEP_NO_NETWORK"), macro("LSL_STEP_SAVE"))
+
+
 def test_model_create_validation_without_gpu():
     from lam_slide_amd import _lib
     lib = _lib.load()

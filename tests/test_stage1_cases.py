@@ -4,7 +4,12 @@ with it: the bar there (2e-6, or 5x this distance where that is larger) rests on
 
 The distance follows the BLAS the fp32 oracle runs on (its summation order).  Seen so far: 0.3e-7 .. 6.5e-7 everywhere except
 md17-1x496x5, where it was 4.4e-7 with one BLAS and 8.8e-7, the worst figure of the table, with another.  A failure of the 1e-6
-assertion at that case on a new host is therefore first a statement about that host's fp32 GEMM, not about the case table."""
+assertion at that case on a new host is therefore first a statement about that host's fp32 GEMM, not about the case table.
+
+Also here, because it needs no device: the scratch size the library reports for every case (``lsl_decode_workspace_bytes`` /
+``lsl_encode_workspace_bytes``) against the recorded table of stage1_cases.py."""
+import ctypes as C
+
 import pytest
 import torch
 
@@ -73,3 +78,39 @@ def test_oracle_gives_nan_for_a_fully_masked_frame_only():
         z, z_dead = enc("w32", x, entities, mask), enc("w32", x, entities, dead)
         assert torch.isnan(z_dead[0]).all() and torch.isfinite(z_dead[1:]).all()
         assert torch.equal(z_dead[1:], z[1:])
+
+
+def test_workspace_bytes_of_every_case_are_the_recorded_ones():
+    """The create calls only copy the description and the pointers and the size calls only add: handles made through ctypes from the
+    description of each model class, with placeholder weight pointers, need no device."""
+    from lam_slide_amd import _lib
+    from lam_slide_amd.decoder import _ACT
+    lib = _lib.load()
+    blocks = lambda n: (_lib.DecBlock * max(n, 1))()  # noqa: E731
+
+    def decoder(name):
+        r, h = sc.DECODER_MODELS[name], C.c_void_p()
+        desc = _lib.DecoderDesc(r.in_dim, r.dim_latent, r.dim_query, r.dim_emb, sc.N_ENTITIES, *r.latent, *r.cross, r.n_self, r.n_cross, _ACT[r.act],
+                                r.out_dim, r.num_split)
+        w = _lib.DecoderWeights(self_blocks=blocks(r.n_self), cross_blocks=blocks(r.n_cross), ext_w=64, ext_b=64)
+        _lib.check(lib.lsl_decoder_create(C.byref(desc), C.byref(w), C.byref(h)))
+        return h
+
+    def encoder(name):
+        r, h = sc.ENCODER_MODELS[name], C.c_void_p()
+        desc = _lib.EncoderDesc(r.dim_input, r.dim_emb, sc.N_ENTITIES, r.dim_latent, r.num_latents, *r.cross, *r.latent, r.n_cross, r.n_self, _ACT[r.act])
+        w = _lib.EncoderWeights(self_blocks=blocks(r.n_self), cross_blocks=blocks(r.n_cross))
+        _lib.check(lib.lsl_encoder_create(C.byref(desc), C.byref(w), C.byref(h)))
+        return h
+
+    assert len(sc.DECODE_WORKSPACE_BYTES) == len(sc.DECODER_CASES) == 12 and len(sc.ENCODE_WORKSPACE_BYTES) == len(sc.ENCODER_CASES) == 6
+    for (name, F, L, A), want in zip(sc.DECODER_CASES, sc.DECODE_WORKSPACE_BYTES):
+        h = decoder(name)
+        assert lib.lsl_decode_workspace_bytes(h, F, L, A) == want, (name, F, L, A)
+        assert lib.lsl_decode_workspace_bytes(h, 0, L, A) == 0 and lib.lsl_decode_workspace_bytes(None, F, L, A) == 0
+        lib.lsl_decoder_destroy(h)
+    for (name, F, A), want in zip(sc.ENCODER_CASES, sc.ENCODE_WORKSPACE_BYTES):
+        h = encoder(name)
+        assert lib.lsl_encode_workspace_bytes(h, F, A) == want, (name, F, A)
+        assert lib.lsl_encode_workspace_bytes(h, F, 0) == 0 and lib.lsl_encode_workspace_bytes(None, F, A) == 0
+        lib.lsl_encoder_destroy(h)
