@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The TICA and Markov-state half of the peptide evaluation on one MI355X, on seeded synthetic features: fit a TICA model on the "MD"
 features (lagged second moments on the device, the F x F eigenproblem on the host) -> project both trajectories and take the joint ranges
--> TICA-0 / TICA-0,1 Jensen-Shannon distances -> nearest-centre labels through a microstate -> state map -> state occupancies and their
+-> TICA-0 / TICA-0,1 Jensen-Shannon distances -> 100 k-means microstates of the projected reference -> nearest-centre labels through a microstate -> state map -> state occupancies and their
 distance -> the transition count matrix of the sampled trajectory.  Nothing is read back before the distances.
 
 Mirrors eval_peptide.py:189-288 without pyemma: the features would be ``cossin_features(TorsionStats.update(frames))`` of the sampled
@@ -21,7 +21,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from lam_slide_amd import TicaModel, assign_centers, metastable_jsd, summary_metrics, tica, tica_autocovariance, tica_jsd, transition_counts  # noqa: E402
+from lam_slide_amd import TicaModel, assign_centers, fit_microstates, metastable_jsd, summary_metrics, tica, tica_autocovariance, tica_jsd, transition_counts  # noqa: E402
 
 
 def features(n, F, seed, mix_seed=1):
@@ -49,7 +49,7 @@ def main():
     model = TicaModel.fit(ref, lag=args.lag)                       # pyemma.coordinates.tica(ref, lag=, kinetic_map=True)
     jsd = tica_jsd(model, ref, traj)                               # {"TICA-0", "TICA-0,1"}: merge into TorsionStats.jsd(...)'s dict
     y_ref, y_traj = model.transform(ref), model.transform(traj)
-    centers = y_ref[:: args.n_ref // 100][:100].contiguous()      # stands for the k-means centres (fitting them is the caller's)
+    centers = fit_microstates(y_ref, k=100, max_iter=100, seed=137)  # analysis.get_kmeans: k-means++ and Lloyd iterations on the device
     state_map = np.arange(100) % 10                                # stands for msm.metastable_assignments
     _, ref_counts = assign_centers(y_ref, centers, state_map=state_map, nstates=10)
     labels, traj_counts = assign_centers(y_traj, centers, state_map=state_map, nstates=10)

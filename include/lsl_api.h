@@ -43,7 +43,8 @@ extern "C" {
  * 6, later still: lsl_peptide_loss_sums, lsl_peptide_loss_final added the same way.
  * 6, later still: lsl_disp_error_rows, lsl_disp_error_final added the same way.
  * 6, later still: lsl_dihedral_angles, lsl_histogram, lsl_lag_products_workspace_bytes, lsl_lag_products, lsl_js_distance added the same way.
- * 6, later still: lsl_lagged_moments_workspace_bytes, lsl_lagged_moments, lsl_project, lsl_assign_centers, lsl_transition_counts added the same way. */
+ * 6, later still: lsl_lagged_moments_workspace_bytes, lsl_lagged_moments, lsl_project, lsl_assign_centers, lsl_transition_counts added the same way.
+ * 6, later still: lsl_kmeans_workspace_bytes, lsl_kmeans_step, lsl_kmeans_nearest_rows added the same way. */
 #define LSL_VERSION 6
 
 typedef struct lsl_model lsl_model;
@@ -359,6 +360,35 @@ int lsl_assign_centers(const float *y, int32_t n, int32_t d, const float *center
  *   lsl_assign_centers) is skipped.  The table is ADDED TO.  lag >= n adds nothing and returns 0.  lag >= 1, 1 <= nstates <= 128 (int32 counts
  *   of a workgroup in LDS), S <= 65535. */
 int lsl_transition_counts(const int32_t *dtraj, int32_t S, int32_t n, int32_t lag, int32_t nstates, int64_t *counts, void *stream);
+
+/* k-means fitting: S independent Lloyd problems y [S, n, d] f32 -> centers [S, k, d] f32 - the microstates of the peptide evaluation
+ * (modules/analysis.py:42-44: S = 1, n ~ 10^6, k = 100) and the post_process branch of the NBA / pedestrian test_step (second_stage/nba.py:202-203,
+ * 228-238: one problem per agent over its K final frames, k = num_runs).  Device pointers; nothing is allocated, nothing is synchronised, a
+ * refused call enqueues nothing.  No float atomics (integer ones for the changed-label count only).  The seeding is the caller's: centers holds
+ * the initial centres.  The algorithm is fixed here as mathematics; parity with pyemma's or torch_kmeans' own streams is not claimed.
+ *
+ * lsl_kmeans_step: one Lloyd iteration of every series whose done[s] is 0 (update != 0), or the final assignment of every series (update == 0).
+ *   assign   labels[s, t] = the lowest c that minimises sum_j (y[s, t, j] - centers[s, c, j])^2 - the arithmetic of lsl_assign_centers (fp64
+ *            differences, the fused sum over j ascending, strict <); a row that holds a NaN gets -1 and takes no part in sums, counts or inertia.
+ *            labels i32 [S, n] is in and out: the previous labels are compared with the new ones (fill it with -2 before the first step).
+ *   update   sum[c, j] over the rows labelled c in fp64: rows ascending in t within a segment of 2048 rows (segment g: t in [2048 g, 2048 (g + 1)),
+ *            a function of n alone), segments in segment order; centers[s, c, j] = fp32(sum / count), one fp64 division and one rounding; an
+ *            empty cluster keeps its centre bit for bit.  counts i64 [S, k]: the members of this assignment, exact.
+ *   state    f64 [S, 4] = (iterations done, J, J of the iteration before, sum (new - old)^2 of the centres); J = the fp64 sum of the winning
+ *            squared distances of this assignment, against the centres before the update, in an order fixed by (n, d, k).  Start it at zeros.
+ *   done     i32 [S]: set after an iteration when no label changed, or rel_tol > 0 and |J_prev - J| <= rel_tol J_prev from the second iteration
+ *            on, or center_tol > 0 and the shift <= center_tol^2.  A later call with update != 0 touches no buffer of such a series, so
+ *            max_iter calls are enqueued with no host synchronisation.  update == 0 ignores done, leaves centers alone and writes labels, counts
+ *            and state[s, 1] = J of the final centres.
+ *   A series has the same bits alone, inside any batch and wherever it stands in it.  k <= 1024, d <= 64, k * d <= 8192 (the centres stay in
+ *   LDS), n >= 1, 1 <= S <= 65535, tolerances >= 0 (else -3).  workspace: lsl_kmeans_workspace_bytes(S, n, d, k) bytes = S * segments *
+ *   (8 (k d + 1) + 4 (k + 1)), segments = ceil(n / 2048); 0 for a refused shape; -4 if smaller.
+ * lsl_kmeans_nearest_rows: rows i32 [S, k], rows[s, c] = the lowest t that minimises sum_j (y[s, t, j] - centers[s, c, j])^2 (same arithmetic);
+ *   rows that hold a NaN are skipped; -1 when the series has no finite row.  The sample nearest each centre: what post_process selects. */
+size_t lsl_kmeans_workspace_bytes(int32_t S, int32_t n, int32_t d, int32_t k);
+int lsl_kmeans_step(const float *y, int32_t S, int32_t n, int32_t d, float *centers, int32_t k, int32_t *labels, int64_t *counts, double *state,
+                    int32_t *done, int32_t update, double rel_tol, double center_tol, void *workspace, size_t workspace_bytes, void *stream);
+int lsl_kmeans_nearest_rows(const float *y, int32_t S, int32_t n, int32_t d, const float *centers, int32_t k, int32_t *rows, void *stream);
 
 /* Sampler loop (Sampler.sample_ode / sample_sde inner loops): applies n_steps affine updates to io->x
  * in place.  noise: device [n_noise, B*T*L*C] standard-normal draws, slice s belongs to step s (the

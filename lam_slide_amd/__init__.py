@@ -27,6 +27,9 @@ Public surface (mirrors the reference's for this path only):
                                    <- the TICA and Markov-state half of analyze_trajectory (eval_peptide.py:189-288): the lagged second
                                       moments and the projection of a TICA model, TICA-0 / TICA-0,1 on the joint range, nearest-centre
                                       labels, state occupancies and transition counts on the device (tica.py)
+  kmeans_fit, nearest_rows, KMeansResult, fit_microstates
+                                   <- k-means fitting on the device (kmeans.py): ``analysis.get_kmeans`` of the peptide evaluation and the
+                                      ``post_process`` branch of the NBA / pedestrian test_step (``displacement_errors(post_process=True)``)
   install()                        <- rebinds the reference's module-level ``Sampler`` (lightning_base.py:10); see dropin.py
 The compute lives in liblamslide_hip.so (include/lsl_api.h); build it with ``__graft_entry__.build()``.
 """
@@ -40,8 +43,9 @@ from .metrics import DisplacementErrors, DisplacementMeter, displacement_errors,
 from .peptide_loss import PeptideLoss, peptide_loss_sums, peptide_losses
 from .sampling import (RolloutSampler, SecondStageSampler, best_of_k_errors, min_ade_fde, sample_rollout, sample_sharded,
                        setup_conditioning, shard_bounds)
-from . import tica
-from .tica import (TicaHistograms, TicaModel, assign_centers, cossin_features, lagged_moments, linspace_edges, metastable_jsd, solve_tica,
+from . import kmeans, tica
+from .kmeans import KMeansResult, kmeans_fit, nearest_rows
+from .tica import (TicaHistograms, TicaModel, assign_centers, cossin_features, fit_microstates, lagged_moments, linspace_edges, metastable_jsd, solve_tica,
                    tica_autocovariance, tica_covariances, tica_dimension, tica_histograms, tica_jsd, transition_counts)
 from .torsion_stats import (TorsionStats, angle_histograms, decorrelation, dihedral_angles, eval_torsion_quads, js_distance, lagged_products,
                             summary_metrics, topology_atoms)
@@ -54,4 +58,4 @@ __all__ = ["LatentSIV3", "CreateTransport", "Transport", "Sampler", "SampleResul
            "DisplacementErrors", "DisplacementMeter", "TorsionStats", "dihedral_angles", "angle_histograms", "js_distance", "lagged_products",
            "decorrelation", "eval_torsion_quads", "topology_atoms", "summary_metrics", "tica", "TicaModel", "TicaHistograms", "cossin_features",
            "lagged_moments", "tica_covariances", "solve_tica", "tica_dimension", "linspace_edges", "tica_histograms", "tica_jsd", "assign_centers",
-           "transition_counts", "metastable_jsd", "tica_autocovariance", "install", "uninstall", "dropin", "_lib"]
+           "transition_counts", "metastable_jsd", "tica_autocovariance", "kmeans", "kmeans_fit", "nearest_rows", "KMeansResult", "fit_microstates", "install", "uninstall", "dropin", "_lib"]

@@ -34,6 +34,7 @@
 #include "k_disperr.hip.h"
 #include "k_torsstat.hip.h"
 #include "k_tica.hip.h"
+#include "k_kmeans.hip.h"
 #ifdef LSL_EXPERIMENTS  // measured-and-rejected GEMM structures, built only by tools/build_experiments.sh (never in the product library)
 #include "k_gemm_pp.hip.h"        // tools/experiments/ (on the include path of tools/build_experiments.sh only)
 #include "k_gemm_drain.hip.h"
@@ -552,6 +553,64 @@ int lsl_transition_counts(const int32_t *dtraj, int32_t S, int32_t n, int32_t la
     hipLaunchKernelGGL(k_transitions, dim3(tb, (unsigned)S), dim3(256), 0, (hipStream_t)stream, (unsigned long long *)counts, (const int *)dtraj, (int)n,
                        (int)lag, (int)nstates);
     LSL_CHECK_LAUNCH("lsl_transition_counts");
+    return 0;
+} LSL_API_CATCH
+
+// ---- k-means fitting: one Lloyd step of S independent problems, the reverse lookup of post_process (k_kmeans.hip.h) ----
+static const char *kmeans_shape_error(int32_t S, int32_t n, int32_t d, int32_t k) {
+    if (S < 1 || S > 65535) return "S outside 1..65535 series";
+    if (n < 1) return "n must be positive";
+    if (d < 1 || d > LSL_KM_MAX_D) return "d outside the native form (1..64 coordinates)";
+    if (k < 1 || k > LSL_KM_MAX_K || (long long)k * d > LSL_KM_CELLS) return "k outside the native form (1..1024 centres, k * d <= 8192: the centres stay in LDS)";
+    return nullptr;
+}
+
+size_t lsl_kmeans_workspace_bytes(int32_t S, int32_t n, int32_t d, int32_t k) {
+    if (kmeans_shape_error(S, n, d, k)) return 0;
+    const size_t units = (size_t)S * km_segments(n);
+    return units * ((size_t)k * d + 1) * sizeof(double) + units * ((size_t)k + 1) * sizeof(int32_t);
+}
+
+int lsl_kmeans_step(const float *y, int32_t S, int32_t n, int32_t d, float *centers, int32_t k, int32_t *labels, int64_t *counts, double *state,
+                    int32_t *done, int32_t update, double rel_tol, double center_tol, void *workspace, size_t workspace_bytes, void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!y || !centers || !labels || !counts || !state || !done || !workspace) return fail(-1, "null argument");
+    if (const char *why = kmeans_shape_error(S, n, d, k)) return fail(-3, "S = %d, n = %d, d = %d, k = %d: %s", S, n, d, k, why);
+    if (!(rel_tol >= 0.0) || !(center_tol >= 0.0)) return fail(-3, "rel_tol = %g and center_tol = %g must not be negative (0 switches a rule off)", rel_tol, center_tol);
+    const size_t need = lsl_kmeans_workspace_bytes(S, n, d, k);
+    if (workspace_bytes < need) return fail(-4, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    hipStream_t st = (hipStream_t)stream;
+    const int nseg = km_segments(n), G = km_group(n, d, k), per = 256 / G;
+    const size_t units = (size_t)S * nseg;
+    double *wsum = (double *)workspace, *winert = wsum + units * k * d;
+    int *wcnt = (int *)(winert + units), *wchg = wcnt + units * k;
+    const dim3 grid = (G == 256) ? dim3((unsigned)nseg, (unsigned)S) : dim3((unsigned)((S + per - 1) / per));
+    const int q = (k * d + G - 1) / G;  // items (c, j) per thread, at most LSL_KM_MAX_Q: the next power of two is compiled
+#define LSL_KM_LAUNCH(NQ) launch_kmeans_step<NQ>(grid, st, y, centers, (int *)labels, (const int *)done, wsum, winert, wcnt, wchg, (int)S, (int)n, (int)d, (int)k, nseg, G, (int)update)
+    if (q <= 1) LSL_KM_LAUNCH(1);
+    else if (q <= 2) LSL_KM_LAUNCH(2);
+    else if (q <= 4) LSL_KM_LAUNCH(4);
+    else if (q <= 8) LSL_KM_LAUNCH(8);
+    else if (q <= 16) LSL_KM_LAUNCH(16);
+    else LSL_KM_LAUNCH(32);
+#undef LSL_KM_LAUNCH
+    LSL_CHECK_LAUNCH("lsl_kmeans_step");
+    hipLaunchKernelGGL(k_kmeans_final, dim3((unsigned)S), dim3(256), 0, st, centers, (long long *)counts, state, (int *)done, (const double *)wsum,
+                       (const double *)winert, (const int *)wcnt, (const int *)wchg, (int)d, (int)k, nseg, (int)update, rel_tol, center_tol);
+    LSL_CHECK_LAUNCH("lsl_kmeans_step (final)");
+    return 0;
+} LSL_API_CATCH
+
+int lsl_kmeans_nearest_rows(const float *y, int32_t S, int32_t n, int32_t d, const float *centers, int32_t k, int32_t *rows, void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!y || !centers || !rows) return fail(-1, "null argument");
+    if (const char *why = kmeans_shape_error(S, n, d, k)) return fail(-3, "S = %d, n = %d, d = %d, k = %d: %s", S, n, d, k, why);
+    const int P = n <= 64 ? 1 : 64;
+    const long long items = (long long)S * k;
+    if ((items * P + 255) / 256 > 2147483647LL) return fail(-3, "S = %d series of k = %d centres: more than 2^31 - 1 workgroups; split the batch", S, k);
+    hipLaunchKernelGGL(k_nearest_rows, dim3((unsigned)((items * P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (int *)rows, y, centers, items, (int)n,
+                       (int)d, (int)k, P);
+    LSL_CHECK_LAUNCH("lsl_kmeans_nearest_rows");
     return 0;
 } LSL_API_CATCH
 

@@ -6,8 +6,12 @@
   displacement_errors   <- ``test_step`` of NBA / pedestrian (nba.py:182-225, pedestrian.py:170-212): best-of-``num_runs`` ADE / FDE of the
                            real agents (``attention_mask[:, -1]``), the two minima taken independently; md17's ``test_step``
                            (md17.py:157-169) is the mean of ``traj_ade`` / ``traj_fde`` over its K = 5 samples
-  DisplacementMeter     <- ``on_test_epoch_end`` (nba.py:240-245) and the ``MeanMetric`` s of ``validation_step``: the epoch means,
+  DisplacementMeter     <- ``on_test_epoch_end`` (nba.py:240-251) and the ``MeanMetric`` s of ``validation_step``: the epoch means,
                            accumulated on the device in float64
+  displacement_errors(post_process=True)
+                        <- the ``post_process`` branch of ``test_step`` (nba.py:202-203, 228-238; pedestrian.py:191, 217): k-means with
+                           ``num_runs`` centres over the K final predicted frames of every agent (``kmeans.kmeans_fit``), the sample
+                           nearest each centre (``kmeans.nearest_rows``), ``ades_post`` / ``fdes_post`` from the selection
 
 The device form is two launches of liblamslide_hip.so (``lsl_disp_error_rows`` / ``lsl_disp_error_final``, csrc/k_disperr.hip.h): the
 decoder's output [K, B, T, A, D] and the batch's positions [B, T, A, D] are read in place (no permute, no slice, no boolean index, no
@@ -83,12 +87,16 @@ class DisplacementErrors:
     """What :func:`displacement_errors` returns.  ``ade`` / ``fde`` [B, A]: best-of-``num_runs``, NaN where the agent is masked out;
     ``traj_ade`` / ``traj_fde`` [K, B]: the unmasked per-sample means of ``validation_step``; ``totals`` float64 [5] = (sum of ``ade``,
     sum of ``fde``, number of real agents, sum of ``traj_ade[:num_runs]``, sum of ``traj_fde[:num_runs]``): totals of several batches
-    or shards add before the division (:class:`DisplacementMeter`).  ``path`` is "fused" (two HIP launches) or "torch"."""
+    or shards add before the division (:class:`DisplacementMeter`).  ``path`` is "fused" (two HIP launches) or "torch".  With
+    ``post_process=True`` also ``ade_post`` / ``fde_post`` [B, A] (the minima over the samples nearest the ``num_runs`` k-means centres
+    of the agent's final frames; NaN where masked), ``totals_post`` float64 [2] (their sums over the real agents), ``post_rows`` int32
+    [B, A, num_runs] (the selected samples) and ``post_fit`` (the :class:`~lam_slide_amd.kmeans.KMeansResult`); None otherwise."""
 
     def __init__(self, ade: Tensor, fde: Tensor, traj_ade: Tensor, traj_fde: Tensor, totals: Tensor, agent_mask: Optional[Tensor], num_runs: int,
                  path: str) -> None:
         self.ade, self.fde, self.traj_ade, self.traj_fde, self.totals = ade, fde, traj_ade, traj_fde, totals
         self.agent_mask, self.num_runs, self.path = agent_mask, num_runs, path
+        self.ade_post = self.fde_post = self.totals_post = self.post_rows = self.post_fit = None
 
     @property
     def n_trajectories(self) -> int:
@@ -103,14 +111,53 @@ class DisplacementErrors:
         keep = self.agent_mask.reshape(-1)
         return self.ade.reshape(-1)[keep], self.fde.reshape(-1)[keep]
 
+    def real_post(self) -> Tuple[Tensor, Tensor]:
+        """(``ade_post``, ``fde_post``) of the real agents, in the order of :meth:`real`."""
+        if self.ade_post is None:
+            raise ValueError("no post_process results: call displacement_errors(..., post_process=True)")
+        if self.agent_mask is None:
+            return self.ade_post.reshape(-1), self.fde_post.reshape(-1)
+        keep = self.agent_mask.reshape(-1)
+        return self.ade_post.reshape(-1)[keep], self.fde_post.reshape(-1)[keep]
+
+
+def post_process_errors(rows: Tensor, finals: Tensor, num_runs: int, keep: Optional[Tensor] = None, post_kmeans: Optional[dict] = None,
+                        centers: Optional[Tensor] = None):
+    """The ``post_process`` selection (nba.py:228-238) from the per-sample rows.  rows [K, B, A, 2] (ADE, FDE of every sample and agent),
+    finals [K, B, A, D] (the final predicted frame) -> (post [B, A, 2], totals_post float64 [2], sel int32 [B, A, num_runs], fit):
+    ``kmeans_fit`` with ``num_runs`` centres over the K final frames of every agent (``post_kmeans``: its keyword arguments; or
+    ``centers`` [B A, num_runs, D] fitted elsewhere, then ``fit`` is None), the sample nearest each centre, and the minimum of ADE and of
+    FDE, each on its own, over the selected samples.  A gather and a ``min``: no synchronisation.  NaN for a masked agent."""
+    from . import kmeans
+    K, B, A, D = finals.shape
+    yk = finals.detach().permute(1, 2, 0, 3).reshape(B * A, K, D).contiguous()
+    fit = None
+    if centers is None:
+        fit = kmeans.kmeans_fit(yk, int(num_runs), **(post_kmeans or {}))
+        centers = fit.centers
+    sel = kmeans.nearest_rows(yk, centers.to(yk.dtype))  # [B A, R]
+    per_agent = rows.permute(1, 2, 0, 3).reshape(B * A, K, 2)
+    picked = torch.gather(per_agent, 1, sel.clamp_min(0).long()[:, :, None].expand(-1, -1, 2))  # [B A, R, 2]
+    nan = torch.full((), float("nan"), dtype=rows.dtype, device=rows.device)
+    picked = torch.where((sel >= 0)[:, :, None], picked, nan)
+    post = picked.min(dim=1).values.reshape(B, A, 2)  # (torch.min keeps a NaN)
+    if keep is not None:
+        post = torch.where(keep[..., None], post, nan)
+        kept = torch.where(keep[..., None], post, torch.zeros((), dtype=post.dtype, device=post.device))
+    else:
+        kept = post
+    return post, kept.double().sum(dim=(0, 1)), sel.reshape(B, A, -1), fit
+
 
 @torch.no_grad()
 def displacement_errors(pred: Tensor, target: Tensor, agent_mask: Optional[Tensor] = None, *, first_frame: int = 0,
-                        num_runs: Optional[int] = None) -> DisplacementErrors:
+                        num_runs: Optional[int] = None, post_process: bool = False, post_kmeans: Optional[dict] = None) -> DisplacementErrors:
     """Best-of-``num_runs`` ADE / FDE per agent (the minima over the first ``num_runs`` of the K samples, each on its own; default all
     K), the per-sample trajectory means, and the float64 sums of both.  pred / target / first_frame as :func:`displacement_rows`;
     agent_mask [B, A] (``attention_mask[:, -1]``; nonzero = real agent) or None for all.  A NaN in any of the ``num_runs`` samples of
-    an agent makes that agent's minimum NaN, like ``torch.min``."""
+    an agent makes that agent's minimum NaN, like ``torch.min``.  ``post_process=True`` adds the reference's ``post_process`` branch
+    (:func:`post_process_errors` over all K samples, ``post_kmeans`` = keyword arguments of ``kmeans_fit``: pass a ``seed`` for a
+    repeatable seeding); the default leaves every other member as it is."""
     pred5, t0t, Tf = _layout(pred, target, first_frame)
     K, B, T, A, D = pred5.shape
     R = K if num_runs is None else int(num_runs)
@@ -139,7 +186,11 @@ def displacement_errors(pred: Tensor, target: Tensor, agent_mask: Optional[Tenso
         kept = torch.where(real[..., None], agents, torch.zeros((), dtype=agents.dtype, device=agents.device)).double()
         totals = torch.cat((kept.sum(dim=(0, 1)), real.sum().double()[None], traj[:R].double().sum(dim=(0, 1))))
         path = "torch"
-    return DisplacementErrors(agents[..., 0], agents[..., 1], traj[..., 0], traj[..., 1], totals, keep, R, path)
+    res = DisplacementErrors(agents[..., 0], agents[..., 1], traj[..., 0], traj[..., 1], totals, keep, R, path)
+    if post_process:
+        post, res.totals_post, res.post_rows, res.post_fit = post_process_errors(rows, pred5[:, :, T - 1], R, keep, post_kmeans)
+        res.ade_post, res.fde_post = post[..., 0], post[..., 1]
+    return res
 
 
 class DisplacementMeter:
@@ -149,7 +200,9 @@ class DisplacementMeter:
 
     ``compute()`` -> {"ade", "fde"}: scale x the mean best-of-K ADE / FDE over all real agents of all batches (``on_test_epoch_end``);
     {"traj_ade", "traj_fde"}: scale x the mean over all trajectories of all batches of the unmasked means (the ``MeanMetric`` s of
-    ``validation_step``; md17's ``test_step``).  Python floats; an empty meter gives NaN, like the mean of an empty tensor."""
+    ``validation_step``; md17's ``test_step``); {"ade_post", "fde_post"}: scale x the means of the ``post_process`` errors over the real
+    agents of the batches that carried them - present only when an update carried them.  Python floats; an empty meter gives NaN, like
+    the mean of an empty tensor."""
 
     def __init__(self, scale: float = 1.0) -> None:
         self.scale = float(scale)
@@ -157,18 +210,29 @@ class DisplacementMeter:
 
     def reset(self) -> None:
         self.sums: Optional[Tensor] = None
+        self.sums_post: Optional[Tensor] = None  # (sum of ade_post, sum of fde_post, real agents) of the updates that carried them
         self.n_trajectories = 0
 
     def update(self, result: DisplacementErrors) -> None:
         totals = result.totals.detach().to(torch.float64)
         self.sums = totals.clone() if self.sums is None else self.sums + totals.to(self.sums.device)
         self.n_trajectories += result.n_trajectories
+        if getattr(result, "totals_post", None) is not None:
+            post = torch.cat((result.totals_post.detach().to(torch.float64), totals[2:3].to(result.totals_post.device)))
+            self.sums_post = post if self.sums_post is None else self.sums_post + post.to(self.sums_post.device)
 
     def compute(self) -> Dict[str, float]:
         nan = float("nan")
         if self.sums is None:
             return {"ade": nan, "fde": nan, "traj_ade": nan, "traj_fde": nan}
-        s = self.sums.tolist()  # the one synchronisation
+        if self.sums_post is None:
+            s = self.sums.tolist()  # the one synchronisation
+        else:
+            s = torch.cat((self.sums, self.sums_post.to(self.sums.device))).tolist()
         n, nt = s[2], float(self.n_trajectories)
-        return {"ade": self.scale * s[0] / n if n else nan, "fde": self.scale * s[1] / n if n else nan,
-                "traj_ade": self.scale * s[3] / nt if nt else nan, "traj_fde": self.scale * s[4] / nt if nt else nan}
+        out = {"ade": self.scale * s[0] / n if n else nan, "fde": self.scale * s[1] / n if n else nan,
+               "traj_ade": self.scale * s[3] / nt if nt else nan, "traj_fde": self.scale * s[4] / nt if nt else nan}
+        if self.sums_post is not None:
+            out["ade_post"] = self.scale * s[5] / s[7] if s[7] else nan
+            out["fde_post"] = self.scale * s[6] / s[7] if s[7] else nan
+        return out

@@ -267,7 +267,8 @@ def sample_rollout(sample_positions: Callable[[Tensor], Tensor], cond_pos: Tenso
 @torch.no_grad()
 def best_of_k_errors(drv: "SecondStageSampler", latents: Tensor, target_pos: Tensor, K: int, decode: Callable[[Tensor], Tensor],
                      agent_mask: Optional[Tensor] = None, y: Optional[Tensor] = None, inits: Optional[Tensor] = None,
-                     num_runs: Optional[int] = None, fused: bool = False) -> Tuple[Tensor, Tensor]:
+                     num_runs: Optional[int] = None, fused: bool = False, post_process: bool = False,
+                     post_kmeans: Optional[dict] = None) -> Tuple[Tensor, ...]:
     """The evaluation tail of the trajectory models on the device (second_stage/pedestrian.py:186-212, nba.py:205-225): K samples per
     scene, decoded, future frames only, one row per real agent, best-of-K ADE / FDE.  The reference runs K sequential ``sample()``
     calls (re-encoding the same batch each time) and stacks the results on the host side of the loop; here the K samples are one fused
@@ -278,14 +279,20 @@ def best_of_k_errors(drv: "SecondStageSampler", latents: Tensor, target_pos: Ten
 
     ``fused=True``: everything after the decode is ``displacement_errors(...).real()`` (metrics.py: two HIP launches that read the
     decoder's output in place, then the one boolean index) instead of the chain of torch operations below; same rows, same order, and
-    an agent's errors have the same bits in any batch."""
+    an agent's errors have the same bits in any batch.  ``post_process=True`` (with ``fused=True``) adds the reference's ``post_process``
+    branch (nba.py:228-238, ``displacement_errors(post_process=True, post_kmeans=...)``): the result is the 4-tuple (ADE, FDE, ADE_post,
+    FDE_post) per real agent."""
+    if post_process and not fused:
+        raise ValueError("post_process=True runs through displacement_errors: pass fused=True")
     B = latents.shape[0]
     c1 = drv.cond_idx[1]
     final = drv.sample_latents_k(latents, K, y=y, inits=inits)            # [K, B, T, L, C]
     pos = decode(final.reshape(K * B, *final.shape[2:]))                   # [K*B, T, A, D]
     if fused:
         from .metrics import displacement_errors
-        return displacement_errors(pos.reshape(K, B, *pos.shape[1:]), target_pos, agent_mask, first_frame=c1, num_runs=num_runs).real()
+        res = displacement_errors(pos.reshape(K, B, *pos.shape[1:]), target_pos, agent_mask, first_frame=c1, num_runs=num_runs,
+                                  post_process=post_process, post_kmeans=post_kmeans)
+        return res.real() + res.real_post() if post_process else res.real()
     pos = pos.reshape(K, B, *pos.shape[1:])[:, :, c1:]                     # future frames
     traj = pos.permute(1, 3, 0, 2, 4).reshape(B * pos.shape[3], K, pos.shape[2], pos.shape[4])   # "(B A) K T D"
     tgt = target_pos.permute(0, 2, 1, 3).reshape(B * target_pos.shape[2], target_pos.shape[1], target_pos.shape[3])

@@ -20,8 +20,11 @@ csrc/k_tica.hip.h; the histograms and distances are ``lsl_histogram`` / ``lsl_js
 ``torsion_stats.fused_applies``: float32 tensors (labels: int32) on the GPU, nothing requires grad, a native shape; anything else takes a
 numpy / torch float64 restatement with the same outputs.  ``last_path[name]`` tells which of the two ("fused" / "torch") ran last.
 
-Not here: k-means fitting (pyemma's seeded k-means++ cannot be reproduced: the centres come from the caller), the reversible
-maximum-likelihood MSM estimate and PCCA (they take the count matrix ``transition_counts`` returns), plots.  The estimator is fixed as
+  fit_microstates     <- ``analysis.get_kmeans`` (``cluster_kmeans(k=100, max_iter=100, fixed_seed=137)``, modules/analysis.py:42-44):
+                         ``kmeans.kmeans_fit`` of the projected reference, centres ready for ``assign_centers`` (pyemma's own seeded
+                         k-means++ stream is not reproduced: centres pyemma fitted enter ``assign_centers`` directly)
+
+Not here: the reversible maximum-likelihood MSM estimate and PCCA (they take the count matrix ``transition_counts`` returns), plots.  The estimator is fixed as
 mathematics below and checked against numpy / scipy; parity with a live pyemma was not checked - a model pyemma fitted enters through
 ``TicaModel.from_arrays``."""
 from __future__ import annotations
@@ -351,6 +354,18 @@ def assign_centers(y: Tensor, centers, state_map=None, nstates: Optional[int] = 
     counts += torch.bincount(idx[ok], minlength=nstates)[:nstates]
     last_path["assign_centers"] = "torch"
     return idx.to(torch.int32), counts
+
+
+def fit_microstates(y_ref: Tensor, k: int = 100, max_iter: int = 100, seed: Optional[int] = 137, **kw) -> Tensor:
+    """y_ref [n, d] (the projected MD reference) -> centres float32 [k, d] for :func:`assign_centers`: ``kmeans.kmeans_fit(y_ref, k,
+    max_iter=, seed=, **kw)`` - k-means++ seeding from ``seed`` and Lloyd iterations on y_ref's device, nothing read back.  The
+    counterpart of ``analysis.get_kmeans``; pyemma's random stream and its restart policy are not reproduced."""
+    from . import kmeans
+    if y_ref.dim() != 2:
+        raise ValueError(f"expected y_ref [n, d], got {tuple(y_ref.shape)}")
+    fit = kmeans.kmeans_fit(y_ref, k, max_iter=max_iter, seed=seed, **kw)
+    last_path["fit_microstates"] = fit.path
+    return fit.centers
 
 
 # ---- transition counts ----

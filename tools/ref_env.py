@@ -11,7 +11,8 @@ stand-ins that let those files import:
     omegaconf.DictConfig           = AttrDict (dict with attribute access)
     torchmetrics.MeanMetric        an nn.Module that is never updated here
     torchdiffeq.odeint             fixed-grid Euler with the package's published semantics (grid == t, states stacked; method == "euler")
-    torch_kmeans.KMeans            a name only (second_stage/pedestrian.py imports it; used only with post_process=True, which no config sets)
+    torch_kmeans.KMeans            a name only (second_stage/pedestrian.py imports it; used only with post_process=True, which no config sets;
+                                   the branch itself is lam_slide_amd.metrics.displacement_errors(post_process=True))
     src.datasets.pedestrian        only ``dataset_cond_indices`` (the five scene names; the real module imports the dataset stack)
     src.utils (package shell)      real ``pylogger`` / ``tensor_utils`` are imported from the reference, ``__init__`` is not executed;
                                    ``src.utils.utils.load_class`` is the reference's four lines of importlib (checkpoint plumbing)
@@ -152,7 +153,7 @@ def setup():
 
         class KMeans:  # (second_stage/pedestrian.py:8; instantiated only under post_process=True)
             def __init__(self, *a, **k):
-                raise RuntimeError("torch_kmeans is not available in the build container (post_process=True is not covered)")
+                raise RuntimeError("torch_kmeans is not available in the build container (post_process=True: use lam_slide_amd.metrics.displacement_errors(post_process=True))")
 
         mod("torch_kmeans", KMeans=KMeans)
         mod("src.datasets.pedestrian", dataset_cond_indices={"zara1": 0, "zara2": 1, "univ": 2, "hotel": 3, "eth": 4})  # (datasets/pedestrian.py:14-20)
