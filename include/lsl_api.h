@@ -44,7 +44,8 @@ extern "C" {
  * 6, later still: lsl_disp_error_rows, lsl_disp_error_final added the same way.
  * 6, later still: lsl_dihedral_angles, lsl_histogram, lsl_lag_products_workspace_bytes, lsl_lag_products, lsl_js_distance added the same way.
  * 6, later still: lsl_lagged_moments_workspace_bytes, lsl_lagged_moments, lsl_project, lsl_assign_centers, lsl_transition_counts added the same way.
- * 6, later still: lsl_kmeans_workspace_bytes, lsl_kmeans_step, lsl_kmeans_nearest_rows added the same way. */
+ * 6, later still: lsl_kmeans_workspace_bytes, lsl_kmeans_step, lsl_kmeans_nearest_rows added the same way.
+ * 6, later still: lsl_debug_block_ex added the same way. */
 #define LSL_VERSION 6
 
 typedef struct lsl_model lsl_model;
@@ -429,6 +430,14 @@ int lsl_rk_error_ratio(float *ratio, const float *y0, const float *y1, const flo
 int lsl_debug_block(lsl_model *m, int32_t block_index /* 0..2*depth-1 */, const float *h_in, float *h_out,
                     const float *mods /* [B, (6*depth+2)*D] */, int32_t B, int32_t T, int32_t L,
                     void *workspace, size_t workspace_bytes, void *stream);
+/* lsl_debug_block with two more arguments (lsl_debug_block is this call with a_out = NULL, mod_rows = B: same plan, same kernels, same bits):
+ *   a_out    NULL, or bf16 [B*T*L][hidden]: linear1's operand, LayerNorm + modulate of h_in as the LayerNorm kernel left it.  Copied right
+ *            behind the LayerNorm launch, which every debug plan runs (tail and ln_fuse handles skip it in network evaluations only): on a
+ *            tail handle k_tail overwrites that buffer with the next sub-block's operand, so a copy after the block would hand out that one.
+ *   mod_rows B: `mods` holds a row per trajectory; 1: one row [(6*depth+2)*D] shared by every trajectory - the kernels run their shared-row
+ *            forms (modulation stride 0: one row in k_linear2_ws's gate table), as a sampler's evaluations do.  Anything else: -3. */
+int lsl_debug_block_ex(lsl_model *m, int32_t block_index, const float *h_in, float *h_out, void *a_out, const float *mods, int32_t mod_rows,
+                       int32_t B, int32_t T, int32_t L, void *workspace, size_t workspace_bytes, void *stream);
 /* The same sub-block up to and including attention (LayerNorm + modulate, linear1 with its epilogue, attention), then the two
  * intermediate buffers as the kernels leave them:
  *   qkv_out bf16 [B*T*L][3 * H * head_dim_pad]  q (after QK-norm and RoPE, times head_dim^-1/2 * log2 e) | k (after QK-norm and RoPE) | v,

@@ -240,8 +240,10 @@ AttnArgs attention_args(const lsl_model *m, const Workspace &ws, const PassPlan 
     return aa;
 }
 
-// one ParallelMLPAttentionV2 sub-block on ws.h (in place): LN+modulate -> linear1 -> attention -> linear2; which kernels: the plan
-int run_block(lsl_model *m, const Workspace &ws, const PassPlan &p, int bi, const float *mods, hipStream_t st) {
+// one ParallelMLPAttentionV2 sub-block on ws.h (in place): LN+modulate -> linear1 -> attention -> linear2; which kernels: the plan.
+// a_tap (lsl_debug_block_ex; debug plans only, where the LayerNorm launch always runs): receives ws.a, linear1's operand, right behind the
+// LayerNorm launch - on a tail handle k_tail overwrites ws.a with the NEXT sub-block's operand (TailArgs::a_next aliases A)
+int run_block(lsl_model *m, const Workspace &ws, const PassPlan &p, int bi, const float *mods, hipStream_t st, void *a_tap = nullptr) {
     const lsl_model_desc &d = m->d;
     const lsl_block_weights &bw = m->blocks[bi];
     const int D = d.hidden, n = p.n, tpt = p.T * p.L, mod_stride = p.mod_stride, temporal = bi & 1;
@@ -255,6 +257,7 @@ int run_block(lsl_model *m, const Workspace &ws, const PassPlan &p, int bi, cons
         m->prof.begin(3, st);
         DISPATCH_D(D, launch_ln_mod_t, ws.a, ws.h, mbase, mbase + D, mod_stride, n, tpt, st);
         m->prof.end(3, st);
+        if (a_tap) hipMemcpyAsync(a_tap, ws.a, (size_t)n * D * 2, hipMemcpyDeviceToDevice, st);
     }
     m->prof.begin(0, st);
     if (p.lin1_ts) {

@@ -231,10 +231,10 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) k_linear1_ts(Lin1Args g) {
             a[4 * q4] = b.x; a[4 * q4 + 1] = b.y; a[4 * q4 + 2] = b.z; a[4 * q4 + 3] = b.w;
         }
     };
-    // Vector-memory bookkeeping.  A fused step issues, in this order: [the 4 stores of a finished slab: every other step] and the 4 DMA
+    // Vector-memory bookkeeping.  A fused step issues, in this order: [the 4 stores of a finished slab: every other step] and the PPW DMA
     // instructions of the block two ahead, all inside its MFMA chain.  At the head of a step the block to compute must have landed: it
     // was requested two steps ago, and everything the wave issued after that request is younger: the previous step's stores (if it
-    // flushed a slab) and its 4 DMA instructions.  So s_waitcnt vmcnt(8) (previous step flushed) or vmcnt(4) leaves exactly those in
+    // flushed a slab) and its PPW DMA instructions.  So s_waitcnt vmcnt(4 + PPW) (previous step flushed) or vmcnt(PPW) leaves exactly those in
     // flight: no head waits for the acknowledgement of a store issued less than a step ago.  Extra younger operations only make a
     // counted wait conservative, never wrong.  Then the workgroup barrier: every wave's pieces have landed and every wave has left the
     // previous block, whose slot is free for the block two ahead.
@@ -244,7 +244,10 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) k_linear1_ts(Lin1Args g) {
             if (decltype(flushed_c)::value) wait_vmcnt<PPW>();
             else wait_vmcnt<0>();
         } else {
-            if (decltype(flushed_c)::value) wait_vmcnt<2 * PPW>();
+            // (the slab's 4 stores + the PPW requests of the block one ahead.  Not 2 PPW: that is the same 8 at 8 waves, but 16 at 4 waves
+            // (PPW = 8), which left 4 of the awaited block's 8 rows unconfirmed - now and then a wave read a ring slot before its rows had
+            // landed: a wrong 32-feature block over a 128-token tile, found by tests/test_hip_gemm.py at 10 240 tokens)
+            if (decltype(flushed_c)::value) wait_vmcnt<PPW + 4>();
             else wait_vmcnt<PPW>();
         }
         __builtin_amdgcn_s_barrier();

@@ -794,22 +794,28 @@ int lsl_rk_error_ratio(float *ratio, const float *y0, const float *y1, const flo
     return 0;
 } LSL_API_CATCH
 
-int lsl_debug_block(lsl_model *m, int32_t bi, const float *h_in, float *h_out, const float *mods, int32_t B, int32_t T, int32_t L,
-                    void *workspace, size_t workspace_bytes, void *stream) try {
+int lsl_debug_block_ex(lsl_model *m, int32_t bi, const float *h_in, float *h_out, void *a_out, const float *mods, int32_t mod_rows, int32_t B,
+                       int32_t T, int32_t L, void *workspace, size_t workspace_bytes, void *stream) try {
     DeviceGuard dev_guard_((hipStream_t)stream);
-    if (int rc = check_debug(m, bi, true, B, T, L, workspace, workspace_bytes)) return rc;
+    const bool args_ok = mod_rows == 1 || mod_rows == B;  // a row per trajectory, or one row shared by all of them (mod_stride 0)
+    if (int rc = check_debug(m, bi, args_ok, B, T, L, workspace, workspace_bytes)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const Workspace ws = carve(m, (char *)workspace, B, T, L);
     PassPlan plan;
-    if (int rc = plan_pass(m, ws, B, T, L, m->MODW, PlanMode::debug_block, bi, plan)) return rc;
+    if (int rc = plan_pass(m, ws, B, T, L, mod_rows == 1 ? 0 : m->MODW, PlanMode::debug_block, bi, plan)) return rc;
     run_tables(m, ws, T, L, st);
     const size_t bytes = (size_t)B * T * L * m->d.hidden * 4;
     // (on the workspace's residual stream, like an evaluation: its rows are padded to whole tiles)
     hipMemcpyAsync(ws.h, h_in, bytes, hipMemcpyDeviceToDevice, st);
-    if (int rc = run_block(m, ws, plan, bi, mods, st)) return rc;
+    if (int rc = run_block(m, ws, plan, bi, mods, st, a_out)) return rc;
     hipMemcpyAsync(h_out, ws.h, bytes, hipMemcpyDeviceToDevice, st);
     return 0;
 } LSL_API_CATCH
+
+int lsl_debug_block(lsl_model *m, int32_t bi, const float *h_in, float *h_out, const float *mods, int32_t B, int32_t T, int32_t L,
+                    void *workspace, size_t workspace_bytes, void *stream) {
+    return lsl_debug_block_ex(m, bi, h_in, h_out, nullptr, mods, B, B, T, L, workspace, workspace_bytes, stream);
+}
 
 int lsl_debug_taps(lsl_model *m, int32_t bi, const float *h_in, const float *mods, int32_t B, int32_t T, int32_t L, void *qkv_out,
                    void *z_out, void *workspace, size_t workspace_bytes, void *stream) try {

@@ -12,6 +12,10 @@ BASELINE.json (decoded coordinates within 1e-3) is 4-25x looser than any of them
   * attention kernels per row against an fp64 softmax of the tapped bf16 q | k | v (test_hip_attention.py, attention_cases.py): per element
     2^-6 A for the MFMA forms (A = p |v|; three bf16 roundings of 2^-8 A each, bar four), 2^-8 |o| + (S + head_dim + 16) 2^-23 A for
     k_attention_tiny and, with A_lin, for k_attention_linear: derived, not measured (profiles/attention_rowwise_parity.txt)
+  * LayerNorm + modulate, linear1, linear2 and k_tail per element against fp64 references built from the tapped bf16 operands
+    (test_hip_gemm.py, gemm_cases.py): one rounding to bf16 (half a unit in the last place) + (K + 2) 2^-24 sum |w x| of accumulation for
+    a, q, k, v, GELU(mlp); |gate| (K2 + 3) 2^-24 sum |w z| + 2^-23 |h| for the residual update: derived, not measured
+    (profiles/gemm_rowwise_parity.txt)
   * integer / indexing behaviour (sharding, chunking, batch independence, K-folding, graph replay): bit-exact
 """
 import ctypes as C
