@@ -45,7 +45,8 @@ extern "C" {
  * 6, later still: lsl_dihedral_angles, lsl_histogram, lsl_lag_products_workspace_bytes, lsl_lag_products, lsl_js_distance added the same way.
  * 6, later still: lsl_lagged_moments_workspace_bytes, lsl_lagged_moments, lsl_project, lsl_assign_centers, lsl_transition_counts added the same way.
  * 6, later still: lsl_kmeans_workspace_bytes, lsl_kmeans_step, lsl_kmeans_nearest_rows added the same way.
- * 6, later still: lsl_debug_block_ex added the same way. */
+ * 6, later still: lsl_debug_block_ex added the same way.
+ * 6, later still: lsl_decode_heads, lsl_class_loss_sums, lsl_class_loss_final added the same way. */
 #define LSL_VERSION 6
 
 typedef struct lsl_model lsl_model;
@@ -261,6 +262,28 @@ int lsl_peptide_loss_sums(const float *pred, const float *target_frame, const ui
  * over the F rows of geom_sums [F, 5] (lsl_geom_loss_sums with A = R*14, D = 3, mask = atom14_mask) and pept_sums [F, 4], in index order, in
  * fp64, each rounded once (rows of several shards may be concatenated first); 0 / 0 is NaN, as the reference. */
 int lsl_peptide_loss_final(const float *geom_sums, const float *pept_sums, int32_t F, float *out, void *stream);
+
+/* Class losses of the first-stage decoder heads: the cross-entropy terms of the first-stage Loss classes - MaskedCrossEntropyLoss on the atom
+ * types (modules/losses.py:62-72, first_stage/md17.py:176-178) and nn.CrossEntropyLoss on team / group / aatype (first_stage/nba.py:266-267,
+ * peptide.py:443).  logits: device f32 [F, A, K]; target: device i64 [F, A]; mask: device u8 [F, A], nonzero = counted, or NULL;
+ * 0 <= label_smoothing < 1.  Per row, in fp32 (torch's definition):
+ *      lse = max_k l_k + log sum_k exp(l_k - max),  nll = lse - l_y,  smooth = lse - mean_k l_k,  loss = (1 - eps) nll + eps smooth
+ * sums: device f32 [F, 2], per frame
+ *      s_ce = sum of loss over the counted rows: mask nonzero (or mask NULL) and target != -100
+ *      n    = with a mask the rows whose mask is nonzero (MaskedCrossEntropyLoss divides by mask.sum(); an ignored row adds 0 above),
+ *             with NULL the rows whose target != -100 (nn.CrossEntropyLoss takes the mean over the non-ignored rows)
+ * Masked-out rows are skipped, where the reference multiplies by the mask: the results differ only when a masked-out logit is not finite.
+ * A counted row whose target is < 0 (and not -100) or >= K makes both sums of its frame NaN and touches nothing else (nothing is clamped, no
+ * logit is read with it); torch raises there.
+ * confusion: device i64 [K, K] or NULL, zeroed by the caller: every counted row with a target in range and no NaN logit adds one to cell
+ * [target, argmax], the argmax being the lowest index among equal maxima.  Integer atomics only (exact in any order): several calls accumulate.
+ * Native form: 1 <= K <= LSL_CLS_MAX_K, A >= 1; anything else is refused with -3.  No float atomics, every sum in an order fixed by (A, K):
+ * a frame's two floats have the same bits in any batch, shard or position.  Nothing is allocated; a refused call enqueues nothing. */
+int lsl_class_loss_sums(const float *logits, const int64_t *target, const uint8_t *mask, int32_t F, int32_t A, int32_t K, float label_smoothing,
+                        float *sums, int64_t *confusion, void *stream);
+/* out (device f32 [1]) = sum s_ce / sum n over the F rows of sums in index order, in fp64, rounded once (rows of several shards may be
+ * concatenated first); 0 / 0 is NaN, as the reference. */
+int lsl_class_loss_final(const float *sums, int32_t F, float *out, void *stream);
 
 /* Displacement errors of the decoded positions: the evaluation tail of the trajectory models.  validation_step (second_stage/md17.py:82-86,
  * nba.py:100-104, pedestrian.py:88-92): ade = norm(true - pred, dim=-1).mean(dim=(1, 2)), fde = norm(true[:, -1] - pred[:, -1], dim=-1).mean(dim=1)
@@ -520,6 +543,21 @@ size_t lsl_decode_workspace_bytes(const lsl_decoder *d, int32_t frames, int32_t 
  *     reference's nn.Embedding raises instead, so a caller that wants that error checks the indices itself. */
 int lsl_decode(lsl_decoder *d, const float *z, const int64_t *entities, int32_t frames, int32_t L, int32_t A, float *out,
                void *workspace, size_t workspace_bytes, void *stream);
+
+#define LSL_DECODE_MAX_HEADS 8
+typedef struct lsl_decoder_head {    /* decoder.output_layers.<name>: Linear(dim_query, dim_query), act, Linear(dim_query, out_dim) */
+    const float *w1, *b1;            /* decoder.output_layers.<name>.0 [dim_query, dim_query]             */
+    const float *w2, *b2;            /* decoder.output_layers.<name>.2 [out_dim, dim_query]               */
+    int32_t out_dim;
+} lsl_decoder_head;
+/* Decoder.forward returns every head of output_layers from one trunk (decoder.py:97-102): the trunk of lsl_decode once (post_quant ..
+ * output_block), then heads[0..n_heads-1] on the same rows.  heads, outs: HOST arrays; outs[h]: device f32 [frames, A, heads[h].out_dim].
+ * 1 <= n_heads <= LSL_DECODE_MAX_HEADS; the head the handle was created with is not evaluated unless it is listed.  Head h has the same
+ * bits as lsl_decode on a handle created with that head's weights (the same launches in the same order), plain Decoder and
+ * DecoderQuerySplitter alike.  Workspace: lsl_decode_workspace_bytes, unchanged (the hidden buffer is reused head after head on the
+ * stream).  The limits and the refusal behaviour of lsl_decode apply unchanged: a refused call has written to no outs[h]. */
+int lsl_decode_heads(lsl_decoder *d, const lsl_decoder_head *heads, int32_t n_heads, const float *z, const int64_t *entities,
+                     int32_t frames, int32_t L, int32_t A, float *const *outs, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Frozen stage-1 encode, the step before setup_conditioning: stands in for

@@ -30,6 +30,11 @@ Public surface (mirrors the reference's for this path only):
   kmeans_fit, nearest_rows, KMeansResult, fit_microstates
                                    <- k-means fitting on the device (kmeans.py): ``analysis.get_kmeans`` of the peptide evaluation and the
                                       ``post_process`` branch of the NBA / pedestrian test_step (``displacement_errors(post_process=True)``)
+  Stage1Autoencoder, class_losses, class_loss_sums, ClassMeter, first_stage.{MD17Loss, PedestrianLoss, NBALoss, PeptideLoss}
+                                   <- first-stage validation (first_stage/{md17,pedestrian,nba,peptide}.py model_step / validation_step):
+                                      encode -> decode with every output head from one trunk (``Stage1Decoder.decode_heads``), the four
+                                      first-stage ``Loss`` classes with their cross-entropy terms and the accuracy / precision / recall
+                                      counts on the device (first_stage.py)
   install()                        <- rebinds the reference's module-level ``Sampler`` (lightning_base.py:10); see dropin.py
 The compute lives in liblamslide_hip.so (include/lsl_api.h); build it with ``__graft_entry__.build()``.
 """
@@ -37,6 +42,8 @@ from . import _lib, dropin
 from .dropin import install, uninstall
 from .decoder import Stage1Decoder
 from .encoder import Stage1Encoder
+from . import first_stage
+from .first_stage import ClassMeter, Stage1Autoencoder, class_loss_sums, class_losses
 from .latent_si import LatentSIV3
 from .losses import Loss, geom_loss_sums, geom_losses
 from .metrics import DisplacementErrors, DisplacementMeter, displacement_errors, displacement_rows
@@ -58,4 +65,5 @@ __all__ = ["LatentSIV3", "CreateTransport", "Transport", "Sampler", "SampleResul
            "DisplacementErrors", "DisplacementMeter", "TorsionStats", "dihedral_angles", "angle_histograms", "js_distance", "lagged_products",
            "decorrelation", "eval_torsion_quads", "topology_atoms", "summary_metrics", "tica", "TicaModel", "TicaHistograms", "cossin_features",
            "lagged_moments", "tica_covariances", "solve_tica", "tica_dimension", "linspace_edges", "tica_histograms", "tica_jsd", "assign_centers",
-           "transition_counts", "metastable_jsd", "tica_autocovariance", "kmeans", "kmeans_fit", "nearest_rows", "KMeansResult", "fit_microstates", "install", "uninstall", "dropin", "_lib"]
+           "transition_counts", "metastable_jsd", "tica_autocovariance", "kmeans", "kmeans_fit", "nearest_rows", "KMeansResult", "fit_microstates", "install", "uninstall", "dropin", "_lib",
+           "first_stage", "Stage1Autoencoder", "ClassMeter", "class_losses", "class_loss_sums"]

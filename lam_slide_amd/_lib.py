@@ -43,6 +43,7 @@ EXPORTED = (
     "lsl_profile_enable", "lsl_profile_read", "lsl_randn", "lsl_rk_lincomb", "lsl_rk_dense", "lsl_rk_error_ratio",
     "lsl_decoder_create", "lsl_decoder_destroy", "lsl_decode_workspace_bytes", "lsl_decode",
     "lsl_encoder_create", "lsl_encoder_destroy", "lsl_encode_workspace_bytes", "lsl_encode",
+    "lsl_decode_heads", "lsl_class_loss_sums", "lsl_class_loss_final",
 )
 
 
@@ -85,6 +86,10 @@ class DecoderWeights(C.Structure):  # lsl_decoder_weights
     _fields_ = [("pq_w", C.c_void_p), ("pq_b", C.c_void_p), ("table", C.c_void_p), ("qm_w", C.c_void_p), ("qm_b", C.c_void_p),
                 ("self_blocks", C.POINTER(DecBlock)), ("cross_blocks", C.POINTER(DecBlock)), ("out_block", DecBlock),
                 ("ext_w", C.c_void_p), ("ext_b", C.c_void_p), ("head_w1", C.c_void_p), ("head_b1", C.c_void_p), ("head_w2", C.c_void_p), ("head_b2", C.c_void_p)]
+
+
+class DecoderHead(C.Structure):  # lsl_decoder_head
+    _fields_ = [("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p), ("out_dim", C.c_int32)]
 
 
 class EncoderDesc(C.Structure):  # lsl_encoder_desc
@@ -227,6 +232,11 @@ def load() -> C.CDLL:
     lib.lsl_decode_workspace_bytes.restype = C.c_size_t
     lib.lsl_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
                                C.c_void_p]
+    lib.lsl_decode_heads.argtypes = [C.c_void_p, C.POINTER(DecoderHead), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                     C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.lsl_class_loss_sums.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]
+    lib.lsl_class_loss_final.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     lib.lsl_encoder_create.argtypes = [C.POINTER(EncoderDesc), C.POINTER(EncoderWeights), C.POINTER(C.c_void_p)]
     lib.lsl_encoder_destroy.argtypes = [C.c_void_p]
     lib.lsl_encoder_destroy.restype = None

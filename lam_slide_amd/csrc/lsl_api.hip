@@ -3,7 +3,7 @@
 // on the caller's stream.  No allocation, no synchronisation, no host<->device copies.
 // One translation unit: this file = the entry points of the sampling path (model handle, forward, fused sampler + opt-in hipGraph replay,
 // noise, Runge-Kutta state arithmetic, the stochastic-interpolant objective around one evaluation, the geometry losses of the decoded positions, the peptide frame and torsion losses, the displacement errors (ADE / FDE, best-of-K), the torsion statistics (dihedrals, histograms, lagged products, JS distance), the TICA and state statistics (lagged second moments, projection, nearest centre, transition counts), debug taps); host_common / host_launch / host_eval.hip.h = what they enqueue (host_graph.hip.h: the replay cache); decode_host.hip.h +
-// stage1_api.hip.h = the frozen stage-1 encode / decode beside the path.
+// stage1_api.hip.h = the frozen stage-1 encode / decode beside the path (every decoder head from one trunk) and the class losses of those heads.
 #include "../../include/lsl_api.h"
 
 #include <hip/hip_runtime.h>
@@ -35,6 +35,7 @@
 #include "k_torsstat.hip.h"
 #include "k_tica.hip.h"
 #include "k_kmeans.hip.h"
+#include "k_classloss.hip.h"
 #ifdef LSL_EXPERIMENTS  // measured-and-rejected GEMM structures, built only by tools/build_experiments.sh (never in the product library)
 #include "k_gemm_pp.hip.h"        // tools/experiments/ (on the include path of tools/build_experiments.sh only)
 #include "k_gemm_drain.hip.h"

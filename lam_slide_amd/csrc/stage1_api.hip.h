@@ -1,5 +1,5 @@
-// Host side, part 4 of 4: C entry points of the frozen stage-1 decoder / encoder (decode_host.hip.h holds their launch helpers).  Inside
-// the extern "C" block of lsl_api.hip.
+// Host side, part 4 of 4: C entry points of the frozen stage-1 decoder / encoder (decode_host.hip.h holds their launch helpers) and of the
+// class losses of the decoder heads (k_classloss.hip.h).  Inside the extern "C" block of lsl_api.hip.
 #pragma once
 
 int lsl_decoder_create(const lsl_decoder_desc *desc, const lsl_decoder_weights *w, lsl_decoder **out) try {
@@ -18,18 +18,11 @@ size_t lsl_decode_workspace_bytes(const lsl_decoder *d, int32_t frames, int32_t 
     return dec_carve(d->d, frames, L, A, nullptr, nullptr);
 }
 
-// Decoder.forward (decoder.py:88-102) after post_quant (lightning_base.py:28-31,42-44)
-int lsl_decode(lsl_decoder *dec, const float *z, const int64_t *entities, int32_t frames, int32_t L, int32_t A, float *out, void *workspace,
-               size_t workspace_bytes, void *stream) try {
-    DeviceGuard dev_guard_((hipStream_t)stream);
-    if (!dec || !z || !entities || !out) return fail(-1, "null decode argument");
-    if (frames <= 0 || L <= 0 || A <= 0) return fail(-3, "decode: empty input");
+// Decoder.forward (decoder.py:88-102) after post_quant (lightning_base.py:28-31,42-44), up to the output block: leaves its rows
+// [frames * A, dim_query] in ws.q.  Arguments already checked; -3 from a block whose keys exceed the LDS tile (nothing of a head is enqueued then).
+static int decode_trunk(lsl_decoder *dec, const float *z, const int64_t *entities, int frames, int L, int A, const DecWs &ws, hipStream_t st) {
     const lsl_decoder_desc &d = dec->d;
     const lsl_decoder_weights &w = dec->w;
-    if (workspace_bytes < dec_carve(d, frames, L, A, nullptr, nullptr) || !workspace) return fail(-4, "decode workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    DecWs ws;
-    dec_carve(d, frames, L, A, (char *)workspace, &ws);
     const int nl = frames * L, na = frames * A;
     // post_quant: LayerNorm(C, elementwise_affine=False) then Linear(C, dim_latent)
     dec_ln(ws.xn, z, nullptr, nullptr, nl, d.in_dim, st);
@@ -48,10 +41,71 @@ int lsl_decode(lsl_decoder *dec, const float *z, const int64_t *entities, int32_
         ctx = ws.ext;
         Lc = L * d.num_split;
     }
-    if (int rc = dec_block(w.out_block, ws.q, A, d.dim_query, ctx, Lc, d.dim_latent, d.heads_cross, d.dim_head_cross, d.act, frames, ws, st)) return rc;
-    dec_dense(d.act, ws.hid, ws.q, w.head_w1, w.head_b1, nullptr, na, d.dim_query, d.dim_query, st);
-    dec_dense(0, out, ws.hid, w.head_w2, w.head_b2, nullptr, na, d.dim_query, d.out_dim, st);
-    LSL_CHECK_LAUNCH("lsl_decode");
+    return dec_block(w.out_block, ws.q, A, d.dim_query, ctx, Lc, d.dim_latent, d.heads_cross, d.dim_head_cross, d.act, frames, ws, st);
+}
+
+// output_layers.<name> on the trunk's rows: Linear(dim_query, dim_query), act, Linear(dim_query, out_dim).  ws.hid is rewritten head after
+// head: the stream orders a head's second launch before the next head's first.
+static void decode_head(const lsl_decoder_desc &d, const lsl_decoder_head &h, float *out, int na, const DecWs &ws, hipStream_t st) {
+    dec_dense(d.act, ws.hid, ws.q, h.w1, h.b1, nullptr, na, d.dim_query, d.dim_query, st);
+    dec_dense(0, out, ws.hid, h.w2, h.b2, nullptr, na, d.dim_query, h.out_dim, st);
+}
+
+// lsl_decode = the one-head case (the handle's own head); lsl_decode_heads = the caller's heads on one trunk
+static int decode_call(lsl_decoder *dec, const lsl_decoder_head *heads, int n_heads, const float *z, const int64_t *entities, int frames, int L, int A,
+                       float *const *outs, void *workspace, size_t workspace_bytes, hipStream_t st, const char *name) {
+    if (frames <= 0 || L <= 0 || A <= 0) return fail(-3, "decode: empty input");
+    const lsl_decoder_desc &d = dec->d;
+    if (workspace_bytes < dec_carve(d, frames, L, A, nullptr, nullptr) || !workspace) return fail(-4, "decode workspace too small");
+    DecWs ws;
+    dec_carve(d, frames, L, A, (char *)workspace, &ws);
+    if (int rc = decode_trunk(dec, z, entities, frames, L, A, ws, st)) return rc;
+    for (int h = 0; h < n_heads; ++h) decode_head(d, heads[h], outs[h], frames * A, ws, st);
+    LSL_CHECK_LAUNCH(name);
+    return 0;
+}
+
+int lsl_decode(lsl_decoder *dec, const float *z, const int64_t *entities, int32_t frames, int32_t L, int32_t A, float *out, void *workspace,
+               size_t workspace_bytes, void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!dec || !z || !entities || !out) return fail(-1, "null decode argument");
+    const lsl_decoder_head own{dec->w.head_w1, dec->w.head_b1, dec->w.head_w2, dec->w.head_b2, dec->d.out_dim};
+    return decode_call(dec, &own, 1, z, entities, frames, L, A, &out, workspace, workspace_bytes, (hipStream_t)stream, "lsl_decode");
+} LSL_API_CATCH
+
+int lsl_decode_heads(lsl_decoder *dec, const lsl_decoder_head *heads, int32_t n_heads, const float *z, const int64_t *entities, int32_t frames,
+                     int32_t L, int32_t A, float *const *outs, void *workspace, size_t workspace_bytes, void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!dec || !heads || !z || !entities || !outs) return fail(-1, "null decode argument");
+    if (n_heads < 1 || n_heads > LSL_DECODE_MAX_HEADS) return fail(-3, "decode: n_heads = %d outside 1..%d", n_heads, LSL_DECODE_MAX_HEADS);
+    for (int h = 0; h < n_heads; ++h) {
+        if (!heads[h].w1 || !heads[h].b1 || !heads[h].w2 || !heads[h].b2 || !outs[h]) return fail(-1, "null decode argument (head %d)", h);
+        if (heads[h].out_dim < 1) return fail(-3, "decode: head %d has out_dim = %d", h, heads[h].out_dim);
+    }
+    return decode_call(dec, heads, n_heads, z, entities, frames, L, A, outs, workspace, workspace_bytes, (hipStream_t)stream, "lsl_decode_heads");
+} LSL_API_CATCH
+
+// ---- class losses of the decoder heads (k_classloss.hip.h) ----
+int lsl_class_loss_sums(const float *logits, const int64_t *target, const uint8_t *mask, int32_t F, int32_t A, int32_t K, float label_smoothing,
+                        float *sums, int64_t *confusion, void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!logits || !target || !sums) return fail(-1, "null argument");
+    if (F <= 0) return fail(-3, "F must be positive");
+    if (A < 1) return fail(-3, "A = %d: at least one row per frame", A);
+    if (K < 1 || K > LSL_CLS_MAX_K) return fail(-3, "K = %d outside the native form (1..%d classes)", K, LSL_CLS_MAX_K);
+    if (!(label_smoothing >= 0.0f && label_smoothing < 1.0f)) return fail(-3, "label_smoothing = %g outside [0, 1)", (double)label_smoothing);
+    hipLaunchKernelGGL(k_class_loss_frame, dim3((unsigned)F), dim3(64), class_tile_bytes(K), (hipStream_t)stream, sums, (unsigned long long *)confusion, logits,
+                       (const long long *)target, mask, (int)A, (int)K, label_smoothing);
+    LSL_CHECK_LAUNCH("lsl_class_loss_sums");
+    return 0;
+} LSL_API_CATCH
+
+int lsl_class_loss_final(const float *sums, int32_t F, float *out, void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!sums || !out) return fail(-1, "null argument");
+    if (F <= 0) return fail(-3, "F must be positive");
+    hipLaunchKernelGGL(k_class_loss_final, dim3(1), dim3(64), 0, (hipStream_t)stream, out, sums, (int)F);
+    LSL_CHECK_LAUNCH("lsl_class_loss_final");
     return 0;
 } LSL_API_CATCH
 

@@ -9,7 +9,7 @@ constructor arguments that cannot be read off the weight shapes carry the refere
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Sequence
 
 import torch
 from torch import Tensor
@@ -17,6 +17,7 @@ from torch import Tensor
 from . import _lib
 
 _ACT = {"gelu_erf": 1, "gelu": 1, "gelu_tanh": 2}
+MAX_HEADS = 8  # LSL_DECODE_MAX_HEADS: the heads of one lsl_decode_heads call
 
 
 def renorm_table(table: Tensor, max_norm: Optional[float]) -> Tensor:
@@ -39,6 +40,7 @@ class _Stage1:
         self._handle = C.c_void_p()
         self._dev_tensors: List[Tensor] = []
         self._scratch = _lib.Scratch()
+        self._head_ptrs = None
         if device is not None:
             self.to(device)
 
@@ -74,6 +76,7 @@ class _Stage1:
             raise RuntimeError(f"{type(self).__name__} runs on the MI355X only (no CPU path)")
         self._destroy_handle()
         self._dev_tensors = []
+        self._head_ptrs = None  # (Stage1Decoder.decode_heads: the device copies of every head, made on first use)
         desc, w = self._describe(dev)
         _lib.check(getattr(_lib.load(), self._create)(C.byref(desc), C.byref(w), C.byref(self._handle)))
         self.device = dev
@@ -122,6 +125,11 @@ class Stage1Decoder(_Stage1):
         if self.num_block_attn and sd["decoder.self_attn_blocks.0.attn.fn.to_qkv.weight"].shape[0] != 3 * self.heads_latent * self.dim_head_latent:
             raise ValueError("num_head_latent * dim_head_latent does not match decoder.self_attn_blocks.0.attn.fn.to_qkv.weight")
         self.act, self.output, self.max_norm = act, output, max_norm
+        # every head of decoder.output_layers in the state dict's (= the ModuleDict's) order: name -> out_dim (decode_heads)
+        self.heads: Dict[str, int] = {}
+        for k in sd:
+            if k.startswith("decoder.output_layers.") and k.endswith(".2.weight"):
+                self.heads[k[len("decoder.output_layers."):-len(".2.weight")]] = int(sd[k].shape[0])
         self._sd = {k: v.detach().to(torch.float32) for k, v in sd.items() if k.startswith(("post_quant.", "decoder."))}
         # DecoderQuerySplitter (decoder.py:384-388): Conv1d(D, D*N, 1) then "B (D N) L -> B (L N) D"; as a Linear whose rows are
         # reordered from channel d*N + n to n*D + d, the output of one latent IS its N context tokens back to back
@@ -167,3 +175,32 @@ class Stage1Decoder(_Stage1):
         return out
 
     __call__ = decode
+
+    @torch.no_grad()
+    def decode_heads(self, latents: Tensor, entities: Tensor, outputs: Optional[Sequence[str]] = None) -> Dict[str, Tensor]:
+        """What the reference's ``Decoder.forward`` returns (decoder.py:97-102): ``{name: [F, A, out_dim]}`` for every head of
+        ``decoder.output_layers`` in the state dict's order, or for the named ``outputs`` in the order given - the trunk once and the heads
+        on its rows, one ``lsl_decode_heads`` call.  Each tensor has the bits of ``Stage1Decoder(output=name).decode``."""
+        self._on(latents, "decode_heads")
+        if latents.dim() != 3 or latents.shape[-1] != self.in_dim or entities.dim() != 2 or entities.shape[0] != latents.shape[0]:
+            raise ValueError("expected latents [F, L, C] and entities [F, A]")
+        names = list(self.heads) if outputs is None else list(outputs)
+        for n in names:
+            if n not in self.heads:
+                raise KeyError(f"decoder.output_layers.{n}")
+        if not 1 <= len(names) <= MAX_HEADS or len(set(names)) != len(names):
+            raise ValueError(f"expected 1..{MAX_HEADS} distinct heads, got {names}")
+        F_, L, _ = latents.shape
+        A = entities.shape[1]
+        z = latents.contiguous().float()
+        ent = entities.contiguous().to(torch.int64)
+        dev = z.device
+        if self._head_ptrs is None:
+            self._head_ptrs = {n: tuple(self._p(f"decoder.output_layers.{n}.{i}.{wb}", dev) for i, wb in ((0, "weight"), (0, "bias"), (2, "weight"), (2, "bias")))
+                               for n in self.heads}
+        heads = (_lib.DecoderHead * len(names))(*[_lib.DecoderHead(*self._head_ptrs[n], self.heads[n]) for n in names])
+        outs = {n: torch.empty(F_, A, self.heads[n], dtype=torch.float32, device=dev) for n in names}
+        ptrs = (C.c_void_p * len(names))(*[outs[n].data_ptr() for n in names])
+        ws = self._scratch.get(dev, _lib.load().lsl_decode_workspace_bytes(self._handle, F_, L, A))
+        _lib.call(dev, "lsl_decode_heads", self._handle, heads, len(names), z.data_ptr(), ent.data_ptr(), F_, L, A, ptrs, ws.data_ptr(), ws.numel())
+        return outs

@@ -28,6 +28,9 @@ Fixture families:
   f18_peptide_loss.npz  the reference's peptide Loss (second_stage/peptide.py): its residue tables as arrays, its five additional losses on seeded
                     decoded positions in fp32 and fp64 with per-element torsions and frame-local positions, and its REAL peptide
                     Wrapper.model_step at T = 8
+  f19_first_stage.npz  the reference's REAL first-stage Wrappers (first_stage/{md17,nba,peptide}.py: Backbone with its prepare_inputs, Loss,
+                    FirstStageLightningBase.model_step) on seeded weights: state dict, batch, prepare_inputs output, latents, every head, the
+                    loss dict in fp32 and of a .double() rerun; and MaskedCrossEntropyLoss / nn.CrossEntropyLoss on seeded logits in both
   f9_sample.npz     the reference's REAL LightningModule (second_stage/md17.py Wrapper built by its own __init__ from the reference YAML,
                     lightning_base.py sample / prepare_batch / setup_conditioning unchanged; tools/ref_env.py supplies the Lightning / Hydra
                     stand-ins): stage-1 inputs -> encode -> conditioning -> 5 Euler updates -> decode, with the initial noise fixed
@@ -863,6 +866,86 @@ def f18():
               "pred": seen["pred"], "loss": seen["loss"], "decoded": seen["decoded"], "decoded_ref64": dec64,
               "meta": np.array([B, T, R, L, F["cond_idx"][0], F["cond_idx"][1], 181])},
         losses=losses)
+
+
+# ------------------------------------------------------------------------------------------- F19
+# pure cross-entropy cases: name -> (F, A, K, logit scale, label smoothing, masked?, ignored targets?)
+F19_CE = {"k10_masked": (6, 9, 10, 1.0, 0.0, True, False), "k10_masked_smooth": (6, 9, 10, 30.0, 0.1, True, False),
+          "k21_masked_ignored": (4, 65, 21, 80.0, 0.1, True, True), "k3_plain": (5, 11, 3, 1.0, 0.0, False, False),
+          "k2_plain_ignored": (5, 11, 2, 30.0, 0.0, False, True), "k128_plain": (3, 70, 128, 80.0, 0.0, False, False),
+          "k65_masked": (3, 130, 65, 1.0, 0.0, True, False)}
+
+
+def f19():
+    """The first-stage model_step of the reference's own classes (see the list above).  Stores arrays only."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import ref_env
+    from lam_slide_amd import dropin
+    from src.modules.losses import MaskedCrossEntropyLoss
+    dropin.uninstall()
+    ns = ref_env.setup()
+    arrays = {}
+    for name in ("md17", "nba", "peptide"):
+        w, cfg = ref_env.build_first_stage_wrapper(ns, name)
+        batch = ref_env.f19_batch(name)
+        if name == "peptide":
+            batch.update(f18_targets(batch["atom14_pos"], batch["aatype"]))
+        runs = {}
+        for tag, dt in (("ref32", torch.float32), ("ref64", torch.float64)):
+            m = w.to(dt)
+            b = {k: (v.to(dt) if v.is_floating_point() else v).clone() for k, v in batch.items()}
+            with torch.no_grad():
+                x = m.backbone.prepare_inputs(b)
+                z = m.encode(b)
+                losses, preds = m.model_step(b)
+            assert all(v.dtype == dt for v in losses.values()) and all(torch.equal(preds[h], m.decode(z, b["entities"])[h]) for h in preds)
+            runs[tag] = dict(x=x, z=z, losses=losses, preds=preds)
+        w.float()
+        # (what Stage1Encoder / Stage1Decoder read; the embeddings behind prepare_inputs are not stored: its output is)
+        sd = {k: v.detach().clone() for k, v in w.backbone.state_dict().items() if k.startswith(("encoder.", "decoder.", "quant.", "post_quant."))}
+        r32, r64 = runs["ref32"], runs["ref64"]
+        dev = {k: abs(float(r32["losses"][k]) - float(r64["losses"][k])) / max(abs(float(r64["losses"][k])), 1e-30) for k in r64["losses"]}
+        print(f"F19 {name}: " + " ".join(f"{k} {float(v):.6f}" for k, v in r64["losses"].items()) + "; fp32 classes vs fp64 "
+              + " ".join(f"{k} {v:.1e}" for k, v in dev.items()))
+        dcfg, ecfg = cfg["backbone"]["decoder"], cfg["backbone"]["encoder"]
+        meta = {"enc_heads": np.array([ecfg["num_head_cross"], ecfg["dim_head_cross"], ecfg["num_head_latent"], ecfg["dim_head_latent"]]),
+                "dec_heads": np.array([dcfg["num_head_cross"], dcfg["dim_head_cross"], dcfg["num_head_latent"], dcfg["dim_head_latent"]]),
+                "scale": np.float64(ref_env.F19[name]["scale"]), "heads": np.array(list(r32["preds"]))}
+        arrays[name + ".p"] = sd
+        arrays[name + ".batch"] = batch
+        arrays[name + ".meta"] = meta
+        arrays[name + ".x"] = r32["x"]
+        arrays[name + ".x64"] = r64["x"]
+        arrays[name + ".z"] = r32["z"]
+        arrays[name + ".z64"] = r64["z"]
+        arrays[name + ".preds"] = r32["preds"]
+        arrays[name + ".preds64"] = r64["preds"]
+        arrays[name + ".loss32"] = r32["losses"]
+        arrays[name + ".loss64"] = r64["losses"]
+        arrays[name + ".weights"] = {k: np.float64(v) for k, v in cfg["loss"].items() if k.endswith("_weight")}
+    worst = 0.0
+    for n, (cname, F_, A, K, scale, eps, masked, ignored) in enumerate([(k,) + v for k, v in F19_CE.items()]):
+        g = torch.Generator().manual_seed(1900 + n)
+        logits = torch.randn(F_, A, K, generator=g) * scale
+        target = torch.randint(0, K, (F_, A), generator=g)
+        mask = (torch.rand(F_, A, generator=g) >= 0.25) if masked else None
+        if ignored:
+            target[torch.rand(F_, A, generator=g) < 0.2] = -100
+        out = {}
+        for tag, dt in (("ref32", torch.float32), ("ref64", torch.float64)):
+            lf, tf = logits.to(dt).reshape(-1, K), target.reshape(-1)
+            if masked:
+                out[tag] = MaskedCrossEntropyLoss(label_smoothing=eps)(logits=lf, target=tf, mask=mask.reshape(-1))
+            else:
+                out[tag] = torch.nn.CrossEntropyLoss(label_smoothing=eps)(lf, tf)
+            assert out[tag].dtype == dt
+        d = abs(float(out["ref32"]) - float(out["ref64"])) / abs(float(out["ref64"]))
+        worst = max(worst, d)
+        print(f"F19 ce {cname}: {float(out['ref64']):.8f}; fp32 class vs fp64 {d:.1e}")
+        arrays["ce." + cname] = {"logits": logits, "target": target, "eps": np.float64(eps), "ref32": out["ref32"], "ref64": out["ref64"],
+                                 **({"mask": mask} if masked else {})}
+    print(f"F19 ce: worst deviation of the reference's fp32 classes from their fp64 run {worst:.2e}")
+    npz("f19_first_stage.npz", ce_names=np.array(list(F19_CE)), **arrays)
 
 
 # ------------------------------------------------------------------------------------------- F10

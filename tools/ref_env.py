@@ -19,7 +19,7 @@ stand-ins that let those files import:
     src.datasets.md17              only ``dataset_cond_indices`` (a dict of 8 molecule names; the real module imports the dataset stack)
     lightning_utilities.core.rank_zero   the two names pylogger imports
 
-Used by ``tools/make_fixtures.py f9 f11 f12 f13 f16 f18``.  Nothing here ships.
+Used by ``tools/make_fixtures.py f9 f11 f12 f13 f16 f18 f19``.  Nothing here ships.
 """
 from __future__ import annotations
 
@@ -139,7 +139,14 @@ def setup():
             def forward(self, *a, **k):
                 return None
 
-        mod("torchmetrics", MeanMetric=MeanMetric)
+        class _Metric(nn.Module):  # (first_stage/nba.py:90-111, peptide.py:134-152 construct these; F19 never updates them)
+            def __init__(self, *a, **k):
+                super().__init__()
+
+            def clone(self, prefix=None):
+                return self
+
+        mod("torchmetrics", MeanMetric=MeanMetric, AUROC=_Metric, Accuracy=_Metric, Precision=_Metric, Recall=_Metric, MetricCollection=_Metric)
 
         def odeint(f, y0, t, method=None, atol=None, rtol=None, **kw):
             assert method == "euler", "the stand-in knows the fixed-grid Euler only"
@@ -465,3 +472,86 @@ class randn_like_sequence:
 
     def __exit__(self, *exc):
         torch.randn_like = self._orig
+
+
+# ---- F19: the reference's real first-stage Wrappers (first_stage/{md17,nba,peptide}.py): Backbone with its real prepare_inputs, Loss, model_step ----
+
+F19 = {"md17": dict(frames=6, A=9, n_atom_types=10, num_latents=8, n_entities=32, scale=2.5, seed=191),
+       "nba": dict(frames=5, A=11, num_latents=8, n_entities=32, scale=1.7, seed=192),
+       "peptide": dict(frames=3, R=4, n_entities=32, scale=1.3, seed=193)}
+
+
+def _resolve(node, root):
+    """The ``${a.b.c}`` interpolations of the reference's YAML on plain dicts (whole-string references only, which is all these files use)."""
+    if isinstance(node, dict):
+        return {k: _resolve(v, root) for k, v in node.items()}
+    if isinstance(node, list):
+        return [_resolve(v, root) for v in node]
+    if isinstance(node, str) and node.startswith("${") and node.endswith("}"):
+        cur = root
+        for part in node[2:-1].split("."):
+            cur = cur[part]
+        return _resolve(cur, root)
+    return node
+
+
+def build_first_stage_wrapper(ns, name):
+    """first_stage/<name>.py Wrapper, constructed by ITS OWN __init__ from the reference's own YAML (configs/model/<name>/first-stage.yaml:
+    its ``backbone`` and ``loss`` blocks unchanged but for the F19 sizes), eval mode, seeded weights.  The peptide Loss reads
+    preds["atom14_pos"] as [B, R, 14, 3] (first_stage/peptide.py:421-426) while DecoderQuerySplitter returns [B, R, 42]: the Backbone used
+    here adds the rearrange of the reference's own commented-out decode (peptide.py:82-86) and nothing else."""
+    import yaml
+    c = F19[name]
+    module = importlib.import_module(f"src.models.composites.first_stage.{name}")
+    cfg = yaml.safe_load(open(os.path.join(REF, f"configs/model/{name}/first-stage.yaml")))
+    root = {"model": cfg, "num_entities": c["n_entities"], "n_atom_types": c.get("n_atom_types"), "shift": 0.0, "scale": c["scale"],
+            "trainer": {"max_epochs": 1}}
+    if "num_latents" in c:
+        cfg["backbone"]["encoder"]["num_latents"] = c["num_latents"]
+    cfg = {k: _resolve(cfg[k], root) for k in ("backbone", "loss", "optimizer")}  # (the blocks the Wrapper instantiates; the rest is trainer plumbing)
+    backbone_cfg = cfg["backbone"]
+    if name == "peptide":
+        class Backbone(module.Backbone):
+            def decode(self, z, entities):
+                preds = super().decode(z=z, entities=entities)
+                preds["atom14_pos"] = preds["atom14_pos"].reshape(*preds["atom14_pos"].shape[:-1], 14, 3)  # "B R (A D) -> B R A D", A = 14
+                return preds
+
+        mod_name = "_lsl_f19_peptide"
+        sys.modules.setdefault(mod_name, types.ModuleType(mod_name)).Backbone = Backbone
+        backbone_cfg = dict(backbone_cfg, _target_=f"{mod_name}.Backbone")
+    torch.manual_seed(c["seed"])
+    w = module.Wrapper(backbone=AttrDict(backbone_cfg), optimizer=AttrDict(cfg["optimizer"]), loss=AttrDict(cfg["loss"]), scheduler=None,
+                       compile=False, shift=0.0, scale=c["scale"], ema=None)
+    with torch.no_grad():  # some rows of the entity table above unit norm (the max_norm path), non-trivial QK-norm scales
+        g = torch.Generator().manual_seed(c["seed"] + 1000)
+        for n, p in w.backbone.named_parameters():
+            if n.endswith("_norm.scale"):
+                p.copy_(1.0 + 0.2 * torch.randn(p.shape, generator=g))
+        for n, p in list(w.backbone.named_parameters()) + list(w.backbone.named_buffers()):
+            if n.endswith("entity_embedding.embedding.weight") or n == "embed_entity.embedding.weight" or n == "embedding_entity.embedding.weight":
+                p.mul_(torch.linspace(0.5, 1.8, p.shape[0])[:, None])
+    w.eval()
+    return w, cfg
+
+
+def f19_batch(name):
+    c = F19[name]
+    g = torch.Generator().manual_seed(c["seed"] + 1)
+    F_ = c["frames"]
+    if name == "peptide":
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+        from golden_inputs import peptide_frames
+        b = peptide_frames(c["seed"] + 1, 1, F_, c["R"])
+        return {k: v[0].clone() for k, v in b.items()}
+    A = c["A"]
+    ent = torch.stack([torch.randperm(c["n_entities"], generator=g)[:A] for _ in range(F_)])
+    am = torch.ones(F_, A, dtype=torch.bool)
+    if name == "md17":
+        am[1, 7:] = False  # padded atoms
+        am[4, 5:] = False
+        return {"pos": torch.randn(F_, A, 3, generator=g), "atom": torch.randint(0, c["n_atom_types"], (F_, A), generator=g), "entities": ent,
+                "attention_mask": am}
+    am[2, 10:] = False
+    return {"pos": torch.randn(F_, A, 2, generator=g), "team": torch.randint(0, 3, (F_, A), generator=g), "group": torch.randint(0, 2, (F_, A), generator=g),
+            "entities": ent, "attention_mask": am}
