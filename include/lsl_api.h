@@ -46,7 +46,8 @@ extern "C" {
  * 6, later still: lsl_lagged_moments_workspace_bytes, lsl_lagged_moments, lsl_project, lsl_assign_centers, lsl_transition_counts added the same way.
  * 6, later still: lsl_kmeans_workspace_bytes, lsl_kmeans_step, lsl_kmeans_nearest_rows added the same way.
  * 6, later still: lsl_debug_block_ex added the same way.
- * 6, later still: lsl_decode_heads, lsl_class_loss_sums, lsl_class_loss_final added the same way. */
+ * 6, later still: lsl_decode_heads, lsl_class_loss_sums, lsl_class_loss_final added the same way.
+ * 6, later still: lsl_pair_distances, lsl_ca_frame_stats, lsl_histogram_columns, lsl_js_distance_density added the same way. */
 #define LSL_VERSION 6
 
 typedef struct lsl_model lsl_model;
@@ -347,6 +348,51 @@ int lsl_lag_products(const float *x, int32_t S, int32_t n, int32_t C, int32_t nl
  *   (a flattened 2-D table is a row): p, q = the rows over their sums, m = (p + q) / 2, sqrt((sum rel_entr(p, m) + sum rel_entr(q, m)) / 2),
  *   natural log, rel_entr(0, .) = 0, the bins added in index order in fp64.  A row that is all zero on either side gives NaN (0 / 0), as scipy. */
 int lsl_js_distance(const int64_t *counts_a, const int64_t *counts_b, int32_t rows, int32_t bins, double *out, void *stream);
+
+/* Structure statistics of a sampled peptide trajectory: what SIAtom14SampleCallback logs per validation epoch through traj_analysis
+ * (utils/traj_utils.py:63-103, utils/backbone_utils.py, utils/tica_utils.py:12-39) - pair distances, the radius of gyration, the clash /
+ * bond-break validity and the contact counts of the selected (C-alpha) atoms, histograms with one edge table per column and the
+ * Jensen-Shannon distance of density histograms.  Four independent calls; device pointers unless named host; nothing is allocated, nothing
+ * is synchronised, a refused call enqueues nothing.  No float atomics: counts are integers added by integer atomics (exact in any order),
+ * every float is a sum in a fixed order that depends on the shape alone - a frame has the same bits alone and inside any batch.
+ *
+ * lsl_pair_distances: dist [F, P] f32 of the P atom pairs of each of F frames pos [F, A, 3] f32,
+ *   dist[f, p] = sqrtf((dx dx + dy dy) + dz dz),  d = pos[f, pairs[p][0]] - pos[f, pairs[p][1]]   (fp32, every operation rounded on its own, in
+ *   that order: np.linalg.norm(.., axis=-1) on float32).  pairs i32 [P, 2] indexes the A atom slots of a frame - a general table; pairs_host
+ *   is the same table in HOST memory: it is what the range check reads (an index outside 0..A-1: -3, before any launch; the device copy is
+ *   the caller's to keep equal, an index outside the frame there gives NaN and reads nothing).  1 <= A <= 2044 (a frame in LDS),
+ *   1 <= P <= 65536, F >= 1. */
+int lsl_pair_distances(const float *pos, const int32_t *pairs, const int32_t *pairs_host, int64_t F, int32_t A, int32_t P, float *dist,
+                       void *stream);
+/* lsl_ca_frame_stats: statistics of the R selected atoms sel i32 [R] (sel_host: the same table in HOST memory, range-checked: outside 0..A-1
+ *   is -3; a device entry outside the frame stages NaN and reads nothing) of each of F frames pos [F, A, 3] f32; d_ij below is the fp32
+ *   distance of lsl_pair_distances between selected atoms i and j.  Each output may be NULL.
+ *   rg       f32 [F] = sqrt(mean_i |x_i - mean_j x_j|^2): fp64 from the fp32 coordinates, atoms in sel order (three coordinate sums over R,
+ *            one division each; then the sum over i of (dx dx + dy dy) + dz dz, one division by R, one square root), rounded to fp32 once:
+ *            mdtraj.compute_rg with unit masses.
+ *   flags    i32 [F]: bit 0 if some i < j has d_ij < clash_thr, bit 1 if some d_{i,i+1} > break_thr; NaN compares false on both, as numpy
+ *            (compute_validity: a frame is valid when flags is 0).
+ *   tally    i64 [4] += (frames, frames with bit 0, frames with bit 1, frames with neither).
+ *   contacts i64 [R, R] += for i < j only the number of frames with d_ij < contact_thr (compute_contact_matrix times the frames); cells
+ *            with i >= j are untouched.
+ *   tally and contacts are ADDED TO: zero them before the first call, chunks of a trajectory then accumulate exactly.  1 <= R <= 146,
+ *   A >= 1, F >= 1. */
+int lsl_ca_frame_stats(const float *pos, const int32_t *sel, const int32_t *sel_host, int64_t F, int32_t A, int32_t R, float clash_thr,
+                       float break_thr, float contact_thr, float *rg, int32_t *flags, int64_t *tally, int64_t *contacts, void *stream);
+/* lsl_histogram_columns: counts i64 [Q, bins] += np.histogram(x[:, q], bins=edges[q])[0] of x [n, Q] f32 with edges f64 [Q, bins + 1], one
+ *   ascending table per column (compute_js_distance's np.linspace(ref_col.min(), ref_col.max(), .)).  Binning as lsl_histogram, against the
+ *   column's own table: bin i holds edges[q][i] <= v < edges[q][i + 1], the last bin is closed on the right, values outside the table and
+ *   NaN are dropped; given the same float32 values the counts equal numpy's as integers.  The table is ADDED TO.  1 <= bins <= 2048,
+ *   n >= 1, Q >= 1 (at most 65535 column tiles of floor(4096 / (bins + 1)) columns). */
+int lsl_histogram_columns(const float *x, int32_t n, int32_t Q, const double *edges, int32_t bins, int64_t *counts, void *stream);
+/* lsl_js_distance_density: out f64 [rows] = scipy.spatial.distance.jensenshannon(h_a[r], h_b[r]) of the density histograms
+ *   h[i] = (counts[r, i] / measure[r, i]) / N + pseudo, N the row's total count (exact, int64): numpy's density=True, n / db / n.sum(), plus
+ *   discretize_features' pseudo-count.  counts_a, counts_b i64 [rows, bins]; measure f64 [rows, bins] the cell sizes - np.diff(edges) for
+ *   a 1-D row, the flattened outer product of the two np.diff s for a 2-D table.  Then as lsl_js_distance: both rows over their sums (the
+ *   sums added in bin order in fp64), m = (p + q) / 2, sqrt((sum rel_entr(p, m) + sum rel_entr(q, m)) / 2), the terms added in bin order
+ *   in fp64.  A row with N = 0 on either side (0 / 0) or a zero cell size gives NaN, as the same arithmetic in numpy. */
+int lsl_js_distance_density(const int64_t *counts_a, const int64_t *counts_b, const double *measure, int32_t rows, int32_t bins, double pseudo,
+                            double *out, void *stream);
 
 /* TICA and state statistics of the peptide evaluation: the second half of analyze_trajectory (eval_peptide.py:189-288, modules/analysis.py:36-56)
  * behind the cos / sin torsion features - the lagged second moments a TICA model is estimated from, the projection with its running ranges,

@@ -30,6 +30,10 @@ Public surface (mirrors the reference's for this path only):
   kmeans_fit, nearest_rows, KMeansResult, fit_microstates
                                    <- k-means fitting on the device (kmeans.py): ``analysis.get_kmeans`` of the peptide evaluation and the
                                       ``post_process`` branch of the NBA / pedestrian test_step (``displacement_errors(post_process=True)``)
+  traj_analysis, StructureTables, pair_distances, ca_frame_stats, tica_features, density_js, joint_density_js, ...
+                                   <- the structure statistics SIAtom14SampleCallback logs per validation epoch (utils/traj_utils.py
+                                      traj_analysis: ramachandran_js, pwd_js, rg_js, tic_js, tic2d_js, val_ca, rmse_contact) of the sampled
+                                      atom14 positions on the device (structure_stats.py)
   Stage1Autoencoder, class_losses, class_loss_sums, ClassMeter, first_stage.{MD17Loss, PedestrianLoss, NBALoss, PeptideLoss}
                                    <- first-stage validation (first_stage/{md17,pedestrian,nba,peptide}.py model_step / validation_step):
                                       encode -> decode with every output head from one trunk (``Stage1Decoder.decode_heads``), the four
@@ -56,6 +60,10 @@ from .tica import (TicaHistograms, TicaModel, assign_centers, cossin_features, f
                    tica_autocovariance, tica_covariances, tica_dimension, tica_histograms, tica_jsd, transition_counts)
 from .torsion_stats import (TorsionStats, angle_histograms, decorrelation, dihedral_angles, eval_torsion_quads, js_distance, lagged_products,
                             summary_metrics, topology_atoms)
+from . import structure_stats
+from .structure_stats import (CaFrameStats, StructureTables, backbone_torsion_quads, ca_atoms, ca_frame_stats, ca_pair_table, column_edges, density_js,
+                              histogram_columns, joint_density_js, js_distance_density, pair_distances, tica_atom_selection, tica_features,
+                              traj_analysis, triu_pairs)
 from .transport import (CreateTransport, ModelType, PathType, Sampler, SampleResult, Transport, WeightType, as_transport, device_randn,
                         mix_seed, si_reduce)
 
@@ -66,4 +74,7 @@ __all__ = ["LatentSIV3", "CreateTransport", "Transport", "Sampler", "SampleResul
            "decorrelation", "eval_torsion_quads", "topology_atoms", "summary_metrics", "tica", "TicaModel", "TicaHistograms", "cossin_features",
            "lagged_moments", "tica_covariances", "solve_tica", "tica_dimension", "linspace_edges", "tica_histograms", "tica_jsd", "assign_centers",
            "transition_counts", "metastable_jsd", "tica_autocovariance", "kmeans", "kmeans_fit", "nearest_rows", "KMeansResult", "fit_microstates", "install", "uninstall", "dropin", "_lib",
+           "structure_stats", "traj_analysis", "StructureTables", "CaFrameStats", "pair_distances", "ca_frame_stats", "tica_features", "column_edges",
+           "histogram_columns", "js_distance_density", "density_js", "joint_density_js", "ca_atoms", "ca_pair_table", "backbone_torsion_quads",
+           "tica_atom_selection", "triu_pairs",
            "first_stage", "Stage1Autoencoder", "ClassMeter", "class_losses", "class_loss_sums"]

@@ -38,6 +38,7 @@ EXPORTED = (
     "lsl_si_loss_workspace_bytes", "lsl_si_loss", "lsl_si_reduce", "lsl_geom_loss_sums", "lsl_geom_loss_final",
     "lsl_peptide_loss_sums", "lsl_peptide_loss_final", "lsl_disp_error_rows", "lsl_disp_error_final",
     "lsl_dihedral_angles", "lsl_histogram", "lsl_lag_products_workspace_bytes", "lsl_lag_products", "lsl_js_distance",
+    "lsl_pair_distances", "lsl_ca_frame_stats", "lsl_histogram_columns", "lsl_js_distance_density",
     "lsl_lagged_moments_workspace_bytes", "lsl_lagged_moments", "lsl_project", "lsl_assign_centers", "lsl_transition_counts",
     "lsl_kmeans_workspace_bytes", "lsl_kmeans_step", "lsl_kmeans_nearest_rows",
     "lsl_profile_enable", "lsl_profile_read", "lsl_randn", "lsl_rk_lincomb", "lsl_rk_dense", "lsl_rk_error_ratio",
@@ -207,6 +208,10 @@ def load() -> C.CDLL:
     lib.lsl_lag_products_workspace_bytes.restype = C.c_size_t
     lib.lsl_lag_products.argtypes = [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.lsl_js_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.lsl_pair_distances.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.lsl_ca_frame_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float] + [C.c_void_p] * 5
+    lib.lsl_histogram_columns.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.lsl_js_distance_density.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]
     lib.lsl_lagged_moments_workspace_bytes.argtypes = [C.c_int32] * 4
     lib.lsl_lagged_moments_workspace_bytes.restype = C.c_size_t
     lib.lsl_lagged_moments.argtypes = [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]

@@ -33,6 +33,7 @@
 #include "k_peptloss.hip.h"
 #include "k_disperr.hip.h"
 #include "k_torsstat.hip.h"
+#include "k_structstat.hip.h"
 #include "k_tica.hip.h"
 #include "k_kmeans.hip.h"
 #include "k_classloss.hip.h"
@@ -465,6 +466,66 @@ int lsl_js_distance(const int64_t *counts_a, const int64_t *counts_b, int32_t ro
     if (rows < 1 || bins < 1) return fail(-3, "rows = %d and bins = %d must be positive", rows, bins);
     hipLaunchKernelGGL(k_js, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, out, (const long long *)counts_a, (const long long *)counts_b, (int)bins);
     LSL_CHECK_LAUNCH("lsl_js_distance");
+    return 0;
+} LSL_API_CATCH
+
+// ---- structure statistics of a sampled peptide trajectory: pair distances, per-frame statistics, column histograms, density JS (k_structstat.hip.h) ----
+int lsl_pair_distances(const float *pos, const int32_t *pairs, const int32_t *pairs_host, int64_t F, int32_t A, int32_t P, float *dist,
+                       void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!pos || !pairs || !pairs_host || !dist) return fail(-1, "null argument");
+    if (A < 1 || A > LSL_TORS_MAX_A) return fail(-3, "A = %d outside the native form (1..%d atoms of a frame)", A, LSL_TORS_MAX_A);
+    if (P < 1 || P > LSL_PAIR_MAX_P) return fail(-3, "P = %d outside 1..%d pairs", P, LSL_PAIR_MAX_P);
+    const int fpb = LSL_TORS_LDS_ATOMS / A;
+    if (F < 1 || (F + fpb - 1) / fpb > 0x7fffffffLL) return fail(-3, "F = %lld frames: 1 .. %lld at A = %d", (long long)F, 0x7fffffffLL * fpb, A);
+    for (int i = 0; i < 2 * P; ++i)
+        if (pairs_host[i] < 0 || pairs_host[i] >= A)
+            return fail(-3, "pairs[%d][%d] = %d outside the frame's atoms 0..%d", i / 2, i % 2, pairs_host[i], A - 1);
+    hipLaunchKernelGGL(k_pair_dist, dim3((unsigned)((F + fpb - 1) / fpb)), dim3(256), 0, (hipStream_t)stream, dist, pos, (const int *)pairs,
+                       (long long)F, (int)A, (int)P, fpb);
+    LSL_CHECK_LAUNCH("lsl_pair_distances");
+    return 0;
+} LSL_API_CATCH
+
+int lsl_ca_frame_stats(const float *pos, const int32_t *sel, const int32_t *sel_host, int64_t F, int32_t A, int32_t R, float clash_thr,
+                       float break_thr, float contact_thr, float *rg, int32_t *flags, int64_t *tally, int64_t *contacts, void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!pos || !sel || !sel_host) return fail(-1, "null argument");
+    if (A < 1) return fail(-3, "A = %d must be positive", A);
+    if (R < 1 || R > LSL_CA_MAX_R) return fail(-3, "R = %d outside 1..%d selected atoms", R, LSL_CA_MAX_R);
+    const int tf = std::min<int>(LSL_CA_TILE, LSL_CA_LDS_ATOMS / R);
+    if (F < 1 || (F + tf - 1) / tf > 0x7fffffffLL) return fail(-3, "F = %lld frames: 1 .. %lld at R = %d", (long long)F, 0x7fffffffLL * tf, R);
+    for (int i = 0; i < R; ++i)
+        if (sel_host[i] < 0 || sel_host[i] >= A) return fail(-3, "sel[%d] = %d outside the frame's atoms 0..%d", i, sel_host[i], A - 1);
+    if (!rg && !flags && !tally && !contacts) return 0;  // (nothing asked for)
+    hipLaunchKernelGGL(k_ca_stats, dim3((unsigned)((F + tf - 1) / tf)), dim3(256), 0, (hipStream_t)stream, rg, (int *)flags, (unsigned long long *)tally,
+                       (unsigned long long *)contacts, pos, (const int *)sel, (long long)F, (int)A, (int)R, tf, clash_thr, break_thr, contact_thr);
+    LSL_CHECK_LAUNCH("lsl_ca_frame_stats");
+    return 0;
+} LSL_API_CATCH
+
+int lsl_histogram_columns(const float *x, int32_t n, int32_t Q, const double *edges, int32_t bins, int64_t *counts, void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!x || !edges || !counts) return fail(-1, "null argument");
+    if (n < 1 || Q < 1) return fail(-3, "n = %d and Q = %d must be positive", n, Q);
+    if (bins < 1 || bins > LSL_HIST_MAX_BINS) return fail(-3, "bins = %d outside 1..%d", bins, LSL_HIST_MAX_BINS);
+    const int qt = std::min<int>(Q, LSL_HCOL_CELLS / (bins + 1));
+    if ((Q + qt - 1) / qt > 65535) return fail(-3, "Q = %d columns of %d bins: at most %d", Q, bins, 65535 * qt);
+    const unsigned tb = (unsigned)(((long long)n + LSL_HIST_ROWS - 1) / LSL_HIST_ROWS);
+    hipLaunchKernelGGL(k_hist_cols, dim3(tb, (unsigned)((Q + qt - 1) / qt)), dim3(256), 0, (hipStream_t)stream, (unsigned long long *)counts, x, edges,
+                       (int)n, (int)Q, (int)bins, qt);
+    LSL_CHECK_LAUNCH("lsl_histogram_columns");
+    return 0;
+} LSL_API_CATCH
+
+int lsl_js_distance_density(const int64_t *counts_a, const int64_t *counts_b, const double *measure, int32_t rows, int32_t bins, double pseudo,
+                            double *out, void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!counts_a || !counts_b || !measure || !out) return fail(-1, "null argument");
+    if (rows < 1 || bins < 1) return fail(-3, "rows = %d and bins = %d must be positive", rows, bins);
+    hipLaunchKernelGGL(k_js_density, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, out, (const long long *)counts_a,
+                       (const long long *)counts_b, measure, (int)bins, pseudo);
+    LSL_CHECK_LAUNCH("lsl_js_distance_density");
     return 0;
 } LSL_API_CATCH
 
