@@ -47,7 +47,8 @@ extern "C" {
  * 6, later still: lsl_kmeans_workspace_bytes, lsl_kmeans_step, lsl_kmeans_nearest_rows added the same way.
  * 6, later still: lsl_debug_block_ex added the same way.
  * 6, later still: lsl_decode_heads, lsl_class_loss_sums, lsl_class_loss_final added the same way.
- * 6, later still: lsl_pair_distances, lsl_ca_frame_stats, lsl_histogram_columns, lsl_js_distance_density added the same way. */
+ * 6, later still: lsl_pair_distances, lsl_ca_frame_stats, lsl_histogram_columns, lsl_js_distance_density added the same way.
+ * 6, later still: lsl_debug_mods_ex, lsl_debug_mods_steps, lsl_debug_embed, lsl_debug_head added the same way. */
 #define LSL_VERSION 6
 
 typedef struct lsl_model lsl_model;
@@ -517,6 +518,39 @@ int lsl_debug_taps(lsl_model *m, int32_t block_index, const float *h_in, const f
                    void *qkv_out, void *z_out, void *workspace, size_t workspace_bytes, void *stream);
 int lsl_debug_mods(lsl_model *m, const float *t, const float *y, int32_t B, float *vec_out, float *mods_out,
                    void *workspace, size_t workspace_bytes, void *stream);
+/* The fp32 frame of an evaluation on caller buffers - the conditioning chain, the two embeddings, the output head - through the launch
+ * helpers an evaluation uses (one dispatch rule).  Every `*_out` below may be NULL unless said otherwise.
+ *
+ * lsl_debug_mods with more arguments (lsl_debug_mods is this call with t_scalar = 0 and the four taps NULL: same kernels, same bits):
+ *   t          device [B], or NULL: every row takes t_scalar - with B = 1 the sampler's single-row route (the wave-per-output kernel whatever
+ *              the width); NULL requires y == NULL (the route has no class vector), else -3
+ *   tfeat_out  [B, 256] the sinusoidal features, hid_out [B, hidden] the first layer's SiLU output: the fp32 operands the next layer read
+ *   yhid_out, yemb_out  [B, hidden] the two layers of vec_in(y); only with y
+ * vec_out [B, hidden] and mods_out [B, (6*depth+2)*hidden] are required. */
+int lsl_debug_mods_ex(lsl_model *m, const float *t, float t_scalar, const float *y, int32_t B, float *vec_out, float *mods_out, float *tfeat_out,
+                      float *hid_out, float *yhid_out, float *yemb_out, void *workspace, size_t workspace_bytes, void *stream);
+/* The modulation tables of `count` sampler records at once, as lsl_sample_ex computes them for a group of records of a model without class
+ * conditioning: times HOST [count]; mods_out [count, (6*depth+2)*hidden] (required), vec_out [count, hidden].  Row s has the bits of
+ * lsl_debug_mods_ex(t = NULL, t_scalar = times[s], B = 1).  count above the group size of the model, or a class-conditioned model: -3.
+ * workspace: lsl_workspace_bytes(m, 1, 1, 1). */
+int lsl_debug_mods_steps(lsl_model *m, const float *times, int32_t count, float *mods_out, float *vec_out, void *workspace, size_t workspace_bytes,
+                         void *stream);
+/* The two embeddings of a pass of B trajectories (an evaluation with one shared modulation row): cond_emb = cond_to_emb(x_cond) + biases +
+ * mask_emb[mask] (once per sample), then h = x_in(x) + cond_emb with what the handle attaches to it.
+ *   cond_emb_out [n, hidden]; h_out [n, hidden] in front of the normalize LayerNorm; hn_out [n, hidden] behind it (equal to h_out on models
+ *   without normalize); stats_out float2 [n] = (rstd, -mean rstd) of every row of h, eps 1e-6: ln_fuse handles whose embedding leaves them
+ *   (no normalize, in_dim <= 32, hidden 256 / 512, a pass the fused linear1 takes), -3 elsewhere.  n = B*T*L.
+ * workspace: lsl_workspace_bytes(m, B, T, L). */
+int lsl_debug_embed(lsl_model *m, const float *x, const float *x_cond, const int64_t *mask, int32_t B, int32_t T, int32_t L, float *cond_emb_out,
+                    float *h_out, float *hn_out, void *stats_out, void *workspace, size_t workspace_bytes, void *stream);
+/* The output head on the caller's residual rows h [n, hidden] with mods as in lsl_debug_block_ex (mod_rows 1 or B; the final shift | scale
+ * of every row is read).  rec == NULL: out [n, in_dim] = the network output.  Else one record of lsl_sample_ex applied to x [n, in_dim] in
+ * place: x <- ax x + am m + aw w + as saved, with w = noise [n, in_dim] or, when noise is NULL, the device stream at (seed, step
+ * rec->noise_index, element elem_offset + e); trace and save_out [n, in_dim] receive the new state (rec->trace_index and LSL_STEP_SAVE are
+ * not consulted: the pointers say it); saved is required when as != 0.  No workspace. */
+int lsl_debug_head(lsl_model *m, const float *h, const float *mods, int32_t mod_rows, float *x, float *out, const lsl_step_ex *rec, const float *noise,
+                   uint64_t seed, uint64_t elem_offset, float *trace, const float *saved, float *save_out, int32_t B, int32_t T, int32_t L,
+                   void *stream);
 
 /* Measurement hooks (bench.py roofline leg): bracket every launch of one kernel class with HIP events on
  * the stream it is launched on.  kernel: 0 linear1 GEMM, 1 linear2 GEMM, 2 attention, 3 LayerNorm+modulate,

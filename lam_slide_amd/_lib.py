@@ -35,6 +35,7 @@ SI_SLAB = 4096  # LSL_SI_SLAB: elements of one trajectory per partial sum of lsl
 EXPORTED = (
     "lsl_version", "lsl_build_info", "lsl_last_error", "lsl_model_create", "lsl_model_set_weights", "lsl_model_destroy",
     "lsl_model_set_chunk", "lsl_model_set_attention_mode", "lsl_model_set_tail", "lsl_model_tail", "lsl_model_set_ln_fuse", "lsl_model_ln_fuse", "lsl_profile_kernel_name", "lsl_pass_size", "lsl_sampler_path", "lsl_workspace_bytes", "lsl_forward", "lsl_sample", "lsl_sample_ex", "lsl_debug_block", "lsl_debug_block_ex", "lsl_debug_taps", "lsl_debug_mods",
+    "lsl_debug_mods_ex", "lsl_debug_mods_steps", "lsl_debug_embed", "lsl_debug_head",
     "lsl_si_loss_workspace_bytes", "lsl_si_loss", "lsl_si_reduce", "lsl_geom_loss_sums", "lsl_geom_loss_final",
     "lsl_peptide_loss_sums", "lsl_peptide_loss_final", "lsl_disp_error_rows", "lsl_disp_error_final",
     "lsl_dihedral_angles", "lsl_histogram", "lsl_lag_products_workspace_bytes", "lsl_lag_products", "lsl_js_distance",
@@ -190,6 +191,12 @@ def load() -> C.CDLL:
                                    C.c_void_p, C.c_size_t, C.c_void_p]
     lib.lsl_debug_mods.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                    C.c_void_p]
+    lib.lsl_debug_mods_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.lsl_debug_mods_steps.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.lsl_debug_embed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [
+        C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.lsl_debug_head.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(StepEx), C.c_void_p, C.c_uint64,
+                                   C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
     lib.lsl_si_loss_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
     lib.lsl_si_loss_workspace_bytes.restype = C.c_size_t
     lib.lsl_si_loss.argtypes = [C.c_void_p, C.POINTER(IO), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]

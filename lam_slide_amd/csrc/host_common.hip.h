@@ -42,7 +42,7 @@ struct Profiler {
     void end(int k, hipStream_t st) {
         if (k == kernel && used < cap) hipEventRecord(ev[2 * used++ + 1], st);
     }
-    char name[96] = "";  // what the profiled class launched (lsl_profile_kernel_name)
+    char name[192] = "";  // what the profiled class launched (lsl_profile_kernel_name); classes 5 and 6 name every kernel of their chain
     void label(int k, const char *fmt, ...) {
         if (k != kernel) return;
         va_list ap;

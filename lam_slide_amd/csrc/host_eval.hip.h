@@ -14,9 +14,12 @@ int run_mods(lsl_model *m, const Workspace &ws, const float *t_dev, float t_scal
     m->prof.begin(6, st);
     hipLaunchKernelGGL(k_time_features, dim3((rows * 128 + 255) / 256), dim3(256), 0, st, ws.tfeat, t_dev, t_scalar, w.time_freqs, rows);
     const bool single = !t_dev && !yemb;  // shared scalar time, no class vector: one row whatever the batch
-    launch_dense<false, true>(ws.hid, ws.tfeat, w.time_w1, w.time_b1, nullptr, rows, 256, D, 0, st, single);
-    launch_dense<false, false>(vec_out, ws.hid, w.time_w2, w.time_b2, yemb, rows, D, D, D, st, single);
-    launch_dense<true, false>(mods_out, vec_out, w.mod_w, w.mod_b, nullptr, rows, D, m->MODW, 0, st, single);
+    char k1[32], k2[32], k3[32];  // (the label of class 6: what each launch_dense chose)
+    const bool lab = m->prof.kernel == 6;
+    launch_dense<false, true>(ws.hid, ws.tfeat, w.time_w1, w.time_b1, nullptr, rows, 256, D, 0, st, single, 0, lab ? k1 : nullptr);
+    launch_dense<false, false>(vec_out, ws.hid, w.time_w2, w.time_b2, yemb, rows, D, D, D, st, single, 0, lab ? k2 : nullptr);
+    launch_dense<true, false>(mods_out, vec_out, w.mod_w, w.mod_b, nullptr, rows, D, m->MODW, 0, st, single, 0, lab ? k3 : nullptr);
+    if (lab) m->prof.label(6, "k_time_features > %s > %s > %s", k1, k2, k3);
     m->prof.end(6, st);
     LSL_CHECK_LAUNCH("modulation");
     return 0;
@@ -40,17 +43,22 @@ int run_mods_steps(lsl_model *m, const Workspace &ws, const float *times, int co
     hipLaunchKernelGGL((k_dense_rows<false, false>), dim3((D + 3) / 4, gy), dim3(256), 0, st, ws.vec_all, ws.hid_all, w.time_w2, w.time_b2, nullptr, count, D, D, D, 0);
     // (the wide last layer: a workgroup's four weight rows are its HBM traffic, re-read once per row range - 16 rows per workgroup)
     hipLaunchKernelGGL((k_dense_rows<true, false>), dim3((m->MODW + 3) / 4, (unsigned)((count + 15) / 16)), dim3(256), 0, st, ws.mods_all, ws.vec_all, w.mod_w, w.mod_b, nullptr, count, D, m->MODW, 0, 0);
+    m->prof.label(6, "k_time_features_steps > k_dense_rows<0, 1> > k_dense_rows<0, 0> > k_dense_rows<1, 0> (row ranges of 8, 8, 16)");
     m->prof.end(6, st);
     LSL_CHECK_LAUNCH("modulation (group of records)");
     return 0;
 }
 
 // vec_in(y) (mmdit.py:118-126), constant over a sample
-int run_yemb(lsl_model *m, const Workspace &ws, const float *y, int rows, hipStream_t st) {
+int run_yemb(lsl_model *m, const Workspace &ws, const float *y, int rows, hipStream_t st, float *yhid_tap = nullptr) {
     const lsl_weights &w = m->w;
     const int D = m->d.hidden, V = m->d.vec_in_dim;
-    launch_dense<false, true>(ws.hid, y, w.vec_w1, w.vec_b1, nullptr, rows, V, D, 0, st);
-    launch_dense<false, false>(ws.yemb, ws.hid, w.vec_w2, w.vec_b2, nullptr, rows, D, D, 0, st);
+    char k1[32], k2[32];
+    const bool lab = m->prof.kernel == 6;  // (not timed with class 6 - once per sample; lsl_debug_mods_ex reports the label in front of run_mods')
+    launch_dense<false, true>(ws.hid, y, w.vec_w1, w.vec_b1, nullptr, rows, V, D, 0, st, false, 0, lab ? k1 : nullptr);
+    if (yhid_tap) hipMemcpyAsync(yhid_tap, ws.hid, (size_t)rows * D * 4, hipMemcpyDeviceToDevice, st);  // (run_mods reuses ws.hid)
+    launch_dense<false, false>(ws.yemb, ws.hid, w.vec_w2, w.vec_b2, nullptr, rows, D, D, 0, st, false, 0, lab ? k2 : nullptr);
+    if (lab) m->prof.label(6, "%s > %s", k1, k2);
     LSL_CHECK_LAUNCH("vec_in");
     return 0;
 }
@@ -318,6 +326,37 @@ struct EvalArgs {
     const float *mods_ready = nullptr;  // this record's row of the group table (run_mods_steps), or nullptr
 };
 
+// The state embedding of an evaluation: ws.h = x_in(x) + ws.cond_emb, with what the pass plan attaches to it (ln_fuse handles: the rows'
+// statistics for the first sub-block's linear1; normalize models: the in-place LayerNorm).  h_tap (lsl_debug_embed): ws.h in front of the LayerNorm.
+int run_embed(lsl_model *m, const Workspace &ws, const PassPlan &p, const float *x, hipStream_t st, float *h_tap = nullptr) {
+    const lsl_model_desc &d = m->d;
+    const int D = d.hidden, n = p.n;
+    m->prof.begin(5, st);
+    // ln_fuse handles: the embedding leaves the rows' statistics, so that the FIRST sub-block's LayerNorm runs inside its linear1 too
+    launch_embed<1>(ws.h, x, m->w.x_in_w, nullptr, nullptr, nullptr, nullptr, ws.cond_emb, n, d.in_dim, D, st, p.emb_stats ? ws.lnparts : nullptr, p.npad,
+                    &m->prof);
+    if (p.emb_stats) hipLaunchKernelGGL(k_ln_finalize, dim3((n + 255) / 256), dim3(256), 0, st, ws.lnstat, ws.lnparts, D / 256, p.npad, n, 256.0f);
+    if (h_tap) hipMemcpyAsync(h_tap, ws.h, (size_t)n * D * 4, hipMemcpyDeviceToDevice, st);
+    if (d.normalize) { DISPATCH_D(D, launch_ln_inplace_t, ws.h, n, 1e-5f, st); }
+    m->prof.end(5, st);
+    LSL_CHECK_LAUNCH("embed");
+    return 0;
+}
+
+// The output head on the rows h [n, D] with the final modulation rows fm = (shift | scale): e.out <- the network output, or the record's
+// update of e.x fused into it
+int run_head(lsl_model *m, const float *h, const float *fm, int mod_stride, int n, int tpt, const EvalArgs &e, hipStream_t st) {
+    const int D = m->d.hidden;
+    const lsl_step_ex r = e.rec ? *e.rec : lsl_step_ex{};
+    m->prof.begin(4, st);
+    DISPATCH_D(D, launch_head_t, e.x, e.out, h, fm, fm + D, mod_stride, m->w.out_w, m->w.out_b, n, m->d.in_dim, tpt, e.rec ? 1 : 0,
+               r.ax, r.am, r.aw, e.noise, (unsigned long long)e.seed, (unsigned)r.noise_index, (unsigned long long)e.elem_off, e.trace, r.as,
+               e.saved, e.save_out, st, &m->prof);
+    m->prof.end(4, st);
+    LSL_CHECK_LAUNCH("head");
+    return 0;
+}
+
 // One evaluation for a pass: embeds x, runs the sub-blocks and the head (write the network output, or fuse the record's update into it)
 int run_eval(lsl_model *m, const Workspace &ws, const PassPlan &p, const EvalArgs &e, hipStream_t st) {
     const lsl_model_desc &d = m->d;
@@ -330,30 +369,18 @@ int run_eval(lsl_model *m, const Workspace &ws, const PassPlan &p, const EvalArg
     if (e.mods_ready && shared) mods = e.mods_ready;
     else rc = run_mods(m, ws, e.t, r.t, e.have_y ? ws.yemb : nullptr, shared ? 1 : p.bc, ws.vec, ws.mods, st);
     if (rc) return rc;
-    m->prof.begin(5, st);
-    // ln_fuse handles: the embedding leaves the rows' statistics, so that the FIRST sub-block's LayerNorm runs inside its linear1 too
-    launch_embed<1>(ws.h, e.x, m->w.x_in_w, nullptr, nullptr, nullptr, nullptr, ws.cond_emb, n, d.in_dim, D, st, p.emb_stats ? ws.lnparts : nullptr, p.npad);
-    if (p.emb_stats) hipLaunchKernelGGL(k_ln_finalize, dim3((n + 255) / 256), dim3(256), 0, st, ws.lnstat, ws.lnparts, D / 256, p.npad, n, 256.0f);
-    if (d.normalize) { DISPATCH_D(D, launch_ln_inplace_t, ws.h, n, 1e-5f, st); }
-    m->prof.end(5, st);
-    LSL_CHECK_LAUNCH("embed");
+    if ((rc = run_embed(m, ws, p, e.x, st))) return rc;
     for (int bi = 0; bi < 2 * d.depth; ++bi)
         if ((rc = run_block(m, ws, p, bi, mods, st))) return rc;
     const float *fm = mods + (size_t)d.depth * 6 * D;  // adaLN: shift, scale
-    m->prof.begin(4, st);
-    DISPATCH_D(D, launch_head_t, e.x, e.out, ws.h, fm, fm + D, p.mod_stride, m->w.out_w, m->w.out_b, n, d.in_dim, p.T * p.L, e.rec ? 1 : 0,
-               r.ax, r.am, r.aw, e.noise, (unsigned long long)e.seed, (unsigned)r.noise_index, (unsigned long long)e.elem_off, e.trace, r.as,
-               e.saved, e.save_out, st);
-    m->prof.end(4, st);
-    LSL_CHECK_LAUNCH("head");
-    return 0;
+    return run_head(m, ws.h, fm, p.mod_stride, n, p.T * p.L, e, st);
 }
 
 int prepare_pass(lsl_model *m, const Workspace &ws, const float *x_cond, const int64_t *mask, const float *y, int bc, int T,
                  int L, hipStream_t st) {
     const lsl_model_desc &d = m->d;
     const int n = bc * T * L;
-    launch_embed<0>(ws.cond_emb, x_cond, m->w.cond_w, m->w.cond_b, m->w.x_in_b, m->w.mask_emb, mask, nullptr, n, d.in_dim, d.hidden, st);
+    launch_embed<0>(ws.cond_emb, x_cond, m->w.cond_w, m->w.cond_b, m->w.x_in_b, m->w.mask_emb, mask, nullptr, n, d.in_dim, d.hidden, st, nullptr, 0, &m->prof);
     LSL_CHECK_LAUNCH("cond_embed");
     if (y) return run_yemb(m, ws, y, bc, st);
     return 0;

@@ -69,13 +69,14 @@ template <int NE, int VEC>
 void launch_head_mfma(float *x, float *out, const float *h, const float *shift, const float *scale, int stride, const float *Wo,
                       const float *bo, int n, int C, int tpt, int do_step, float ax, float am, float aw, const float *noise,
                       unsigned long long seed, unsigned step, unsigned long long eo, float *trace, float as, const float *saved, float *save_out,
-                      hipStream_t st) {
+                      hipStream_t st, Profiler *pr = nullptr) {
     auto kern = k_head_step_mfma<NE, VEC>;
     const size_t lds = head_mfma_lds_bytes<NE>(C <= 32);
     LSL_ALLOW_LDS(kern, head_mfma_lds_bytes<NE>(false));
     // two workgroups per CU where the LDS image allows it (any hidden size with <= 32 channels): one workgroup's LayerNorm / weight-load latencies under the other's MFMAs
     static const int per_cu = tune_int("LSL_HEAD_PER_CU", 2);
     const int wgs = device_cus() * (per_cu >= 2 && 2 * lds <= LDS_BUDGET ? 2 : 1);
+    if (pr) pr->label(4, "k_head_step_mfma<%d, %d> (%s, %d per CU)", NE, VEC, C <= 32 ? "one slab" : "cycled slabs", wgs / device_cus());
     hipLaunchKernelGGL(kern, dim3(std::min((n + HEAD_TOK - 1) / HEAD_TOK, wgs)), dim3(256), lds, st, x, out, h, shift, scale, stride,
                        Wo, bo, n, C, tpt, do_step, ax, am, aw, noise, seed, step, eo, trace, as, saved, save_out);
 }
@@ -84,9 +85,9 @@ template <int NE, int VEC>
 void launch_head_t(float *x, float *out, const float *h, const float *shift, const float *scale, int stride, const float *Wo,
                    const float *bo, int n, int C, int tpt, int do_step, float ax, float am, float aw, const float *noise,
                    unsigned long long seed, unsigned step, unsigned long long eo, float *trace, float as, const float *saved, float *save_out,
-                   hipStream_t st) {
+                   hipStream_t st, Profiler *pr = nullptr) {
     if (launch_head_experiment<NE, VEC>(x, out, h, shift, scale, stride, Wo, bo, n, C, tpt, do_step, ax, am, aw, noise, seed, step, eo, trace, as, saved, save_out, st)) return;
-    launch_head_mfma<NE, VEC>(x, out, h, shift, scale, stride, Wo, bo, n, C, tpt, do_step, ax, am, aw, noise, seed, step, eo, trace, as, saved, save_out, st);
+    launch_head_mfma<NE, VEC>(x, out, h, shift, scale, stride, Wo, bo, n, C, tpt, do_step, ax, am, aw, noise, seed, step, eo, trace, as, saved, save_out, st, pr);
 }
 
 #define DISPATCH_D(D, FN, ...)                          \
@@ -105,11 +106,13 @@ void launch_head_t(float *x, float *out, const float *h, const float *shift, con
 bool embed_stats_ok(int C, int D) { return C <= 32 && D % 256 == 0 && D <= 512; }
 template <int MODE>
 int launch_embed(float *out, const float *in, const float *W, const float *b, const float *b2, const float *me,
-                 const int64_t *mask, const float *base, int n, int C, int D, hipStream_t st, float2 *stats = nullptr, int npad = 0) {
+                 const int64_t *mask, const float *base, int n, int C, int D, hipStream_t st, float2 *stats = nullptr, int npad = 0,
+                 Profiler *pr = nullptr) {  // (pr: the launch leaves its label under profile class 5)
     if (C > 32 && C % 8 == 0 && C <= 128 && D % 32 == 0) {  // wide inputs: fp32 MFMA form (k_embed_mfma)
         const int tpw = 3, ngrp = (D / 32 + tpw - 1) / tpw;
         const long units = (long)((n + 31) / 32) * ngrp;
         const dim3 g((unsigned)((units + 3) / 4));
+        if (pr) pr->label(5, "k_embed_mfma<%d, %d> (32-token tiles)", MODE, C / 8);
         switch (C / 8) {
 #define LSL_EMB_CASE(CK) case CK: hipLaunchKernelGGL((k_embed_mfma<MODE, CK>), g, dim3(256), 0, st, out, in, W, b, b2, me, mask, base, n, C, D, tpw); return 0;
             LSL_EMB_CASE(5) LSL_EMB_CASE(6) LSL_EMB_CASE(7) LSL_EMB_CASE(8) LSL_EMB_CASE(9) LSL_EMB_CASE(10) LSL_EMB_CASE(11) LSL_EMB_CASE(12)
@@ -126,9 +129,13 @@ int launch_embed(float *out, const float *in, const float *W, const float *b, co
     if (w_lds)
         while (tok > 16 && (n + tok - 1) / tok < 2 * device_cus()) tok /= 2;
     const dim3 grid(std::min((n + tok - 1) / tok, 2 * device_cus())), blk(256);
+    const bool with_stats = stats && MODE == 1 && C <= 32 && embed_stats_ok(C, D);
+    if (pr)
+        pr->label(5, "k_embed<%d, %d, %d%s> (%d-token tiles%s)", C <= 32 ? 32 : C <= 64 ? 64 : C <= 96 ? 96 : 128, MODE, C <= 32 ? 4 : C <= 96 ? 2 : 1,
+                  with_stats ? ", true" : "", tok, w_lds ? ", weights through LDS" : (C & 3) ? ", scalar weight loads" : "");
     if (C <= 32) {
         const size_t lds = w_lds ? embed_w_lds_bytes<32, 4>(D) : 0;
-        if (stats && MODE == 1 && embed_stats_ok(C, D)) {
+        if (with_stats) {
             auto kern = k_embed<32, 1, 4, true>;
             LSL_ALLOW_LDS(kern, (embed_w_lds_bytes<32, 4>(512)));
             hipLaunchKernelGGL(kern, grid, blk, lds, st, out, in, W, b, b2, me, mask, base, n, C, D, w_lds ? 1 : 0, tok, stats, npad);
@@ -536,22 +543,32 @@ void launch_attention_t(const AttnPlan &p, const AttnArgs &a, hipStream_t st) {
 
 template <bool PRE, bool POST>
 void launch_dense(float *out, const float *in, const float *W, const float *bias, const float *add, int rows, int I, int O,
-                  int add_stride, hipStream_t st, bool single = false, int add_mod = 0) {
+                  int add_stride, hipStream_t st, bool single = false, int add_mod = 0, char *name = nullptr) {
+    // (name: 32 bytes or NULL - receives the kernel the branch taken below launches, for the label of profile class 6)
+    auto named = [&](const char *kernel, int kq) {
+        if (name && kq) snprintf(name, 32, "%s<%d, %d, %d>", kernel, (int)PRE, (int)POST, kq);
+        else if (name) snprintf(name, 32, "%s<%d, %d>", kernel, (int)PRE, (int)POST);
+    };
     // The choice must not depend on the BATCH: the two kernels sum k in different orders, and a trajectory's result has to be the
     // same bits whatever batch it is sampled in (K-sample batching, sharding, pass size).  `single` marks the calls that have one
     // row by construction (the sampler's shared time without class conditioning: one conditioning vector for any batch); they
     // take the wave-per-output kernel (a coalesced GEMV, 8x faster at one row than the 64-row tile kernel).
-    if (single && rows == 1 && I <= 512)
+    if (single && rows == 1 && I <= 512) {
+        named("k_dense_rows", 0);
         hipLaunchKernelGGL((k_dense_rows<PRE, POST>), dim3((O + 3) / 4), dim3(256), 0, st, out, in, W, bias, add, rows, I, O, add_stride, add_mod);
-    else if ((I == 128 || I == 256) && tune_int("LSL_DENSE_MFMA", 1)) {  // many rows, usual widths: the fp32 matrix pipe (k_dense_mfma)
+    } else if ((I == 128 || I == 256) && tune_int("LSL_DENSE_MFMA", 1)) {  // many rows, usual widths: the fp32 matrix pipe (k_dense_mfma)
         const dim3 grid((O + 31) / 32, (rows + 31) / 32);
+        named("k_dense_mfma", I / 4);
         if (I == 128) hipLaunchKernelGGL((k_dense_mfma<PRE, POST, 32>), grid, dim3(256), 0, st, out, in, W, bias, add, rows, I, O, add_stride, add_mod);
         else hipLaunchKernelGGL((k_dense_mfma<PRE, POST, 64>), grid, dim3(256), 0, st, out, in, W, bias, add, rows, I, O, add_stride, add_mod);
-    } else if (I % 4 == 0)
+    } else if (I % 4 == 0) {
+        named("k_dense_tiled", 0);
         hipLaunchKernelGGL((k_dense_tiled<PRE, POST>), dim3((O + 63) / 64, (rows + 63) / 64), dim3(256), 0, st, out, in, W, bias, add, rows,
                            I, O, add_stride, add_mod);
-    else
+    } else {
+        named("k_dense_rows", 0);
         hipLaunchKernelGGL((k_dense_rows<PRE, POST>), dim3((O + 3) / 4), dim3(256), 0, st, out, in, W, bias, add, rows, I, O, add_stride, add_mod);
+    }
 }
 
 // the short GEMM chains in front of the trajectory-resident kernel (k_dense_mfma: latency-optimised; one kernel for any row count)

@@ -270,9 +270,11 @@ __global__ void __launch_bounds__(256) k_embed(float *out, const float *in, cons
     const int n_tiles = (N + tok - 1) / tok;  // tok <= EMB_TOK tokens per tile (small launches: smaller tiles, so that every CU gets work)
     const int DQ = D / ND, groups = DQ >= 256 ? 1 : 256 / DQ;
     // persistent workgroups: a thread's weight rows are fetched once and stay in registers while it walks the token tiles
-    for (int dq = threadIdx.x % (DQ < 256 ? DQ : 256); dq < DQ; dq += 256) {
+    // (DQ > 256: the columns in trips of 256.  Every thread makes every trip, because the loop holds the workgroup's barriers and the
+    // cooperative staging of xs; a thread whose column lies beyond DQ in the last trip only stages)
+    for (int dq = threadIdx.x % (DQ < 256 ? DQ : 256), trip = 0; trip < (DQ + 255) / 256; dq += 256, ++trip) {
         const int tg = DQ >= 256 ? 0 : threadIdx.x / DQ, d = ND * dq;
-        const bool active = tg < groups;  // (threads beyond groups * DQ only help with the staging)
+        const bool active = tg < groups && dq < DQ;  // (threads beyond groups * DQ, or beyond DQ in the last trip, only help with the staging)
         float w[ND][CMAX];
         if (w_lds) {
             // C == CMAX: a thread's ND weight rows are ND * C * 4 contiguous bytes.  Fetched by the lanes directly, every load instruction

@@ -903,16 +903,102 @@ int lsl_debug_taps(lsl_model *m, int32_t bi, const float *h_in, const float *mod
     return 0;
 } LSL_API_CATCH
 
-int lsl_debug_mods(lsl_model *m, const float *t, const float *y, int32_t B, float *vec_out, float *mods_out, void *workspace,
-                   size_t workspace_bytes, void *stream) try {
+int lsl_debug_mods_ex(lsl_model *m, const float *t, float t_scalar, const float *y, int32_t B, float *vec_out, float *mods_out, float *tfeat_out,
+                      float *hid_out, float *yhid_out, float *yemb_out, void *workspace, size_t workspace_bytes, void *stream) try {
     DeviceGuard dev_guard_((hipStream_t)stream);
-    if (int rc = check_debug(m, 0, true, B, 1, 1, workspace, workspace_bytes)) return rc;  // (no sub-block: index 0 always exists)
+    // (t == NULL: the scalar time for every row - with one row the sampler's `single` route, which has no class vector)
+    const bool args_ok = m && B > 0 && vec_out && mods_out && (t || !y) && (!y || m->d.vec_in_dim > 0) && ((!yhid_out && !yemb_out) || y);
+    if (int rc = check_debug(m, 0, args_ok, B, 1, 1, workspace, workspace_bytes)) return rc;  // (no sub-block: index 0 always exists)
     hipStream_t st = (hipStream_t)stream;
     const Workspace ws = carve(m, (char *)workspace, B, 1, 1);
+    const size_t D = m->d.hidden;
+    char ylabel[sizeof(m->prof.name)] = "";
     if (y) {
-        if (int rc = run_yemb(m, ws, y, B, st)) return rc;
+        if (int rc = run_yemb(m, ws, y, B, st, yhid_out)) return rc;
+        if (yemb_out) hipMemcpyAsync(yemb_out, ws.yemb, (size_t)B * D * 4, hipMemcpyDeviceToDevice, st);
+        if (m->prof.kernel == 6) snprintf(ylabel, sizeof(ylabel), "%s", m->prof.name);
     }
-    return run_mods(m, ws, t, 0.0f, y ? ws.yemb : nullptr, B, vec_out, mods_out, st);
+    if (int rc = run_mods(m, ws, t, t_scalar, y ? ws.yemb : nullptr, B, vec_out, mods_out, st)) return rc;
+    // (nothing behind their launches writes ws.tfeat or ws.hid: the copies see what the next layer read)
+    if (tfeat_out) hipMemcpyAsync(tfeat_out, ws.tfeat, (size_t)B * 256 * 4, hipMemcpyDeviceToDevice, st);
+    if (hid_out) hipMemcpyAsync(hid_out, ws.hid, (size_t)B * D * 4, hipMemcpyDeviceToDevice, st);
+    if (ylabel[0]) {  // class 6 of this call: the vec_in chain, then the time chain
+        char both[sizeof(m->prof.name)];
+        snprintf(both, sizeof(both), "%s ; %s", ylabel, m->prof.name);
+        m->prof.label(6, "%s", both);
+    }
+    LSL_CHECK_LAUNCH("debug mods");
+    return 0;
+} LSL_API_CATCH
+
+int lsl_debug_mods(lsl_model *m, const float *t, const float *y, int32_t B, float *vec_out, float *mods_out, void *workspace,
+                   size_t workspace_bytes, void *stream) {
+    return lsl_debug_mods_ex(m, t, 0.0f, y, B, vec_out, mods_out, nullptr, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
+}
+
+int lsl_debug_mods_steps(lsl_model *m, const float *times, int32_t count, float *mods_out, float *vec_out, void *workspace, size_t workspace_bytes,
+                         void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (int rc = check_debug(m, 0, m && times && count > 0 && mods_out, 1, 1, 1, workspace, workspace_bytes)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const Workspace ws = carve(m, (char *)workspace, 1, 1, 1);
+    if (count > ws.mods_group) return fail(-3, "%d records: a group of this model holds %d (0: class-conditioned, tables per evaluation)", count, ws.mods_group);
+    if (int rc = run_mods_steps(m, ws, times, count, st)) return rc;
+    hipMemcpyAsync(mods_out, ws.mods_all, (size_t)count * m->MODW * 4, hipMemcpyDeviceToDevice, st);
+    if (vec_out) hipMemcpyAsync(vec_out, ws.vec_all, (size_t)count * m->d.hidden * 4, hipMemcpyDeviceToDevice, st);
+    LSL_CHECK_LAUNCH("debug mods (group of records)");
+    return 0;
+} LSL_API_CATCH
+
+int lsl_debug_embed(lsl_model *m, const float *x, const float *x_cond, const int64_t *mask, int32_t B, int32_t T, int32_t L, float *cond_emb_out,
+                    float *h_out, float *hn_out, void *stats_out, void *workspace, size_t workspace_bytes, void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (int rc = check_debug(m, 0, x && x_cond && mask && B > 0 && T > 0 && L > 0, B, T, L, workspace, workspace_bytes)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const Workspace ws = carve(m, (char *)workspace, B, T, L);
+    PassPlan plan;  // of an evaluation with one shared modulation row, as a sampler's
+    if (int rc = plan_pass(m, ws, B, T, L, 0, PlanMode::eval, 0, plan)) return rc;
+    if (stats_out && !plan.emb_stats) return fail(-3, "stats_out: this handle's embedding leaves no row statistics (ln_fuse, no normalize, in_dim <= 32, hidden 256 / 512)");
+    const size_t n = (size_t)plan.n, D = m->d.hidden;
+    if (int rc = prepare_pass(m, ws, x_cond, mask, nullptr, B, T, L, st)) return rc;
+    char clabel[sizeof(m->prof.name)];
+    snprintf(clabel, sizeof(clabel), "%s", m->prof.name);
+    if (cond_emb_out) hipMemcpyAsync(cond_emb_out, ws.cond_emb, n * D * 4, hipMemcpyDeviceToDevice, st);
+    if (int rc = run_embed(m, ws, plan, x, st, h_out)) return rc;
+    if (hn_out) hipMemcpyAsync(hn_out, ws.h, n * D * 4, hipMemcpyDeviceToDevice, st);
+    if (stats_out) hipMemcpyAsync(stats_out, ws.lnstat, n * sizeof(float2), hipMemcpyDeviceToDevice, st);
+    if (m->prof.kernel == 5) {  // class 5 of this call: the cond embedding, then the state embedding
+        char both[sizeof(m->prof.name)];
+        snprintf(both, sizeof(both), "%s ; %s", clabel, m->prof.name);
+        m->prof.label(5, "%s", both);
+    }
+    LSL_CHECK_LAUNCH("debug embed");
+    return 0;
+} LSL_API_CATCH
+
+int lsl_debug_head(lsl_model *m, const float *h, const float *mods, int32_t mod_rows, float *x, float *out, const lsl_step_ex *rec, const float *noise,
+                   uint64_t seed, uint64_t elem_offset, float *trace, const float *saved, float *save_out, int32_t B, int32_t T, int32_t L,
+                   void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!m || !m->has_weights) return fail(-2, "weights not set");
+    const bool shape_ok = B > 0 && T > 0 && L > 0 && (unsigned long long)B * T * L * (unsigned)std::max(m->d.in_dim, m->d.hidden) < (1ull << 31);
+    if (!shape_ok || !h || !mods || (mod_rows != 1 && mod_rows != B) || (rec ? !x : !out)) return fail(-3, "invalid arguments");
+    if (rec && ((rec->flags & LSL_STEP_NO_NETWORK) || (rec->aw != 0.0f && rec->noise_index < 0) || (rec->as != 0.0f && !saved)))
+        return fail(-3, "invalid record");
+    EvalArgs e;
+    e.x = x;
+    e.out = out;
+    e.rec = rec;
+    if (rec) {
+        e.noise = rec->aw != 0.0f ? noise : nullptr;
+        e.seed = seed;
+        e.elem_off = elem_offset;
+        e.trace = trace;
+        e.saved = rec->as != 0.0f ? saved : nullptr;
+        e.save_out = save_out;
+    }
+    const float *fm = mods + (size_t)m->d.depth * 6 * m->d.hidden;  // adaLN: shift, scale
+    return run_head(m, h, fm, mod_rows == 1 ? 0 : m->MODW, B * T * L, T * L, e, (hipStream_t)stream);
 } LSL_API_CATCH
 
 #include "stage1_api.hip.h"

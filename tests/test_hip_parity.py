@@ -16,6 +16,11 @@ BASELINE.json (decoded coordinates within 1e-3) is 4-25x looser than any of them
     (test_hip_gemm.py, gemm_cases.py): one rounding to bf16 (half a unit in the last place) + (K + 2) 2^-24 sum |w x| of accumulation for
     a, q, k, v, GELU(mlp); |gate| (K2 + 3) 2^-24 sum |w z| + 2^-23 |h| for the residual update: derived, not measured
     (profiles/gemm_rowwise_parity.txt)
+  * the fp32 frame - conditioning chain, embeddings, k_ln_inplace, STATS + k_ln_finalize, output head + state update - per element against
+    fp64 references built from the tapped fp32 operands (test_hip_frame.py, frame_cases.py): (K + 3) 2^-24 sum |w x| + 2^-24 per added
+    term for every chain, the LayerNorm statistics term without the bf16 rounding, |am| bar(m) + 2^-22 sum |terms| for the update;
+    derived, with three measured constants (cosf / sinf, __expf, rsqrtf: 4 x the worst seen, at most 16 units of 2^-24)
+    (profiles/frame_rowwise_parity.txt)
   * integer / indexing behaviour (sharding, chunking, batch independence, K-folding, graph replay): bit-exact
 """
 import ctypes as C
