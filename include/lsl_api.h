@@ -48,7 +48,8 @@ extern "C" {
  * 6, later still: lsl_debug_block_ex added the same way.
  * 6, later still: lsl_decode_heads, lsl_class_loss_sums, lsl_class_loss_final added the same way.
  * 6, later still: lsl_pair_distances, lsl_ca_frame_stats, lsl_histogram_columns, lsl_js_distance_density added the same way.
- * 6, later still: lsl_debug_mods_ex, lsl_debug_mods_steps, lsl_debug_embed, lsl_debug_head added the same way. */
+ * 6, later still: lsl_debug_mods_ex, lsl_debug_mods_steps, lsl_debug_embed, lsl_debug_head added the same way.
+ * 6, later still: lsl_weighted_moments_workspace_bytes, lsl_weighted_moments, lsl_affine_weights, lsl_project_wide added the same way. */
 #define LSL_VERSION 6
 
 typedef struct lsl_model lsl_model;
@@ -431,6 +432,35 @@ int lsl_assign_centers(const float *y, int32_t n, int32_t d, const float *center
  *   lsl_assign_centers) is skipped.  The table is ADDED TO.  lag >= n adds nothing and returns 0.  lag >= 1, 1 <= nstates <= 128 (int32 counts
  *   of a workgroup in LDS), S <= 65535. */
 int lsl_transition_counts(const int32_t *dtraj, int32_t S, int32_t n, int32_t lag, int32_t nstates, int64_t *counts, void *stream);
+
+/* Koopman-reweighted TICA on wide feature tables: run_tica of the peptide validation (utils/tica_utils.py:42-48) over tica_features, whose
+ * 300 .. 1344 columns are past the 128 of lsl_lagged_moments / lsl_project.  Three independent calls on one series; device pointers; nothing is
+ * allocated, nothing is synchronised, a refused call enqueues nothing.  No float atomics.
+ *
+ * lsl_weighted_moments: moments f64 [1 + 2 F + 3 F^2] of x [n, F] f32 at lag, m = n - lag, with the weights w f64 [m] (NULL: all ones; negative
+ *   weights are legal): sw = sum_{t<m} w_t, sx [F] = sum w_t x_t, sy [F] = sum w_t x_{t+lag}, xx [F, F] = sum w_t x_t x_t^T, yy [F, F] =
+ *   sum w_t x_{t+lag} x_{t+lag}^T, xy [F, F] = sum w_t x_t x_{t+lag}^T, in that order, full row-major matrices.
+ *   Order.  A row is extended by a virtual column of ones, so sw, sx and sy are sums of the same kind as the matrix entries.  Entry (a, b), a <= b
+ *   for xx and yy: p_t = w_t * (double)x_a (one rounding; exact for NULL), then acc = fma(p_t, (double)x_b, acc) over the rows of a segment in
+ *   ascending t from zero (segment g: t in [1024 g, 1024 (g + 1)) below m); the segments' sums are added in ascending g to a second accumulator,
+ *   which is added to the split's sum and cleared after every segment with (g + 1) % 1024 == 0 and at the end of a time split; time split s holds the
+ *   segments [s q, (s + 1) q), q = ceil(segments / want), want = min(32, ceil(1024 / jobs), segments), jobs = Te (Te + 1) + T^2, Te = ceil((F + 1) /
+ *   64), T = ceil(F / 64); the splits' sums are added in ascending s.  All of it is a function of (n, lag, F) alone: the bits of every output depend
+ *   on (x, w, n, lag, F) only.  xx[b, a] and yy[b, a] are copies of entry (a, b): bit-symmetric.  At most LSL_WMOM_CHAIN = 4130 roundings lie on the
+ *   path to an entry (1 + 1024 + 1024 + 2049 + 32, every n < 2^31): |error| <= 4130 * 2^-53 * sum_t |w_t x_a x_b|.  A NaN in a row reaches only
+ *   the entries that row's value enters.
+ *   129 <= F <= 2048, n >= 2, 1 <= lag < n (else -3; F <= 128 is lsl_lagged_moments').  workspace: lsl_weighted_moments_workspace_bytes(n, F, lag)
+ *   bytes = splits * 3 (F + 1)^2 * 8 (at most 32 splits, one at F = 2048: 101 MB; independent of n beyond that; 0 for a refused shape); -4 if smaller.
+ * lsl_affine_weights: w f64 [m], w[t] = (sum_f x[t, f] u[f]) + c of x [m, F] f32 (row stride F), u f64 [F]: the fused chain over f ascending in
+ *   fp64 from zero, c added last.  1 <= F <= 2048, m >= 1.  The Koopman weights of the first m rows of a series.
+ * lsl_project_wide: lsl_project's contract - y f32 [n, d], y[t, j] = fp32(sum_f (x[t, f] - mean[f]) W[f, j]), the subtraction and the fused chain
+ *   over f ascending in fp64 from zero, one rounding to fp32; lim (or NULL) f32 [2, d] in and out, as there - for 129 <= F <= 2048, 1 <= d <= 64,
+ *   n >= 1.  W streams through LDS in chunks of 32 features in ascending order: a row has the bits of the formula evaluated sequentially. */
+size_t lsl_weighted_moments_workspace_bytes(int32_t n, int32_t F, int32_t lag);
+int lsl_weighted_moments(const float *x, int32_t n, int32_t F, int32_t lag, const double *w, double *moments, void *workspace, size_t workspace_bytes,
+                         void *stream);
+int lsl_affine_weights(const float *x, int32_t m, int32_t F, const double *u, double c, double *w, void *stream);
+int lsl_project_wide(const float *x, int32_t n, int32_t F, const double *mean, const double *W, int32_t d, float *y, float *lim, void *stream);
 
 /* k-means fitting: S independent Lloyd problems y [S, n, d] f32 -> centers [S, k, d] f32 - the microstates of the peptide evaluation
  * (modules/analysis.py:42-44: S = 1, n ~ 10^6, k = 100) and the post_process branch of the NBA / pedestrian test_step (second_stage/nba.py:202-203,

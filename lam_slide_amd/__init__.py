@@ -34,6 +34,10 @@ Public surface (mirrors the reference's for this path only):
                                    <- the structure statistics SIAtom14SampleCallback logs per validation epoch (utils/traj_utils.py
                                       traj_analysis: ramachandran_js, pwd_js, rg_js, tic_js, tic2d_js, val_ca, rmse_contact) of the sampled
                                       atom14 positions on the device (structure_stats.py)
+  run_tica, koopman_weights, weighted_moments, WideTicaModel, KoopmanWeights
+                                   <- ``tica_utils.run_tica``: the Koopman-reweighted TICA over ``tica_features`` (129 .. 2048 columns) on the
+                                      device - ``traj_analysis(..., tica_lagtime=)`` gives tic_js / tic2d_js from positions alone
+                                      (koopman_tica.py)
   Stage1Autoencoder, class_losses, class_loss_sums, ClassMeter, first_stage.{MD17Loss, PedestrianLoss, NBALoss, PeptideLoss}
                                    <- first-stage validation (first_stage/{md17,pedestrian,nba,peptide}.py model_step / validation_step):
                                       encode -> decode with every output head from one trunk (``Stage1Decoder.decode_heads``), the four
@@ -64,10 +68,12 @@ from . import structure_stats
 from .structure_stats import (CaFrameStats, StructureTables, backbone_torsion_quads, ca_atoms, ca_frame_stats, ca_pair_table, column_edges, density_js,
                               histogram_columns, joint_density_js, js_distance_density, pair_distances, tica_atom_selection, tica_features,
                               traj_analysis, triu_pairs)
+from . import koopman_tica
+from .koopman_tica import KoopmanWeights, WideTicaModel, koopman_weights, run_tica, weighted_moments
 from .transport import (CreateTransport, ModelType, PathType, Sampler, SampleResult, Transport, WeightType, as_transport, device_randn,
                         mix_seed, si_reduce)
 
-__all__ = ["LatentSIV3", "CreateTransport", "Transport", "Sampler", "SampleResult", "ModelType", "PathType", "WeightType",
+__all__ = ["koopman_tica", "KoopmanWeights", "WideTicaModel", "koopman_weights", "run_tica", "weighted_moments", "LatentSIV3", "CreateTransport", "Transport", "Sampler", "SampleResult", "ModelType", "PathType", "WeightType",
            "SecondStageSampler", "setup_conditioning", "sample_sharded", "shard_bounds", "min_ade_fde", "sample_rollout", "best_of_k_errors",
            "RolloutSampler", "Stage1Decoder", "Stage1Encoder", "as_transport", "device_randn", "mix_seed", "si_reduce", "Loss", "geom_losses", "geom_loss_sums", "PeptideLoss", "peptide_losses", "peptide_loss_sums", "displacement_rows", "displacement_errors",
            "DisplacementErrors", "DisplacementMeter", "TorsionStats", "dihedral_angles", "angle_histograms", "js_distance", "lagged_products",

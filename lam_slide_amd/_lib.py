@@ -42,6 +42,7 @@ EXPORTED = (
     "lsl_pair_distances", "lsl_ca_frame_stats", "lsl_histogram_columns", "lsl_js_distance_density",
     "lsl_lagged_moments_workspace_bytes", "lsl_lagged_moments", "lsl_project", "lsl_assign_centers", "lsl_transition_counts",
     "lsl_kmeans_workspace_bytes", "lsl_kmeans_step", "lsl_kmeans_nearest_rows",
+    "lsl_weighted_moments_workspace_bytes", "lsl_weighted_moments", "lsl_affine_weights", "lsl_project_wide",
     "lsl_profile_enable", "lsl_profile_read", "lsl_randn", "lsl_rk_lincomb", "lsl_rk_dense", "lsl_rk_error_ratio",
     "lsl_decoder_create", "lsl_decoder_destroy", "lsl_decode_workspace_bytes", "lsl_decode",
     "lsl_encoder_create", "lsl_encoder_destroy", "lsl_encode_workspace_bytes", "lsl_encode",
@@ -225,6 +226,11 @@ def load() -> C.CDLL:
     lib.lsl_project.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.lsl_assign_centers.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.lsl_transition_counts.argtypes = [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p]
+    lib.lsl_weighted_moments_workspace_bytes.argtypes = [C.c_int32] * 3
+    lib.lsl_weighted_moments_workspace_bytes.restype = C.c_size_t
+    lib.lsl_weighted_moments.argtypes = [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.lsl_affine_weights.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+    lib.lsl_project_wide.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.lsl_kmeans_workspace_bytes.argtypes = [C.c_int32] * 4
     lib.lsl_kmeans_workspace_bytes.restype = C.c_size_t
     lib.lsl_kmeans_step.argtypes = [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_double, C.c_double,

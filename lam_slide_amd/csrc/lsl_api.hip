@@ -35,6 +35,7 @@
 #include "k_torsstat.hip.h"
 #include "k_structstat.hip.h"
 #include "k_tica.hip.h"
+#include "k_wtica.hip.h"
 #include "k_kmeans.hip.h"
 #include "k_classloss.hip.h"
 #ifdef LSL_EXPERIMENTS  // measured-and-rejected GEMM structures, built only by tools/build_experiments.sh (never in the product library)
@@ -615,6 +616,70 @@ int lsl_transition_counts(const int32_t *dtraj, int32_t S, int32_t n, int32_t la
     hipLaunchKernelGGL(k_transitions, dim3(tb, (unsigned)S), dim3(256), 0, (hipStream_t)stream, (unsigned long long *)counts, (const int *)dtraj, (int)n,
                        (int)lag, (int)nstates);
     LSL_CHECK_LAUNCH("lsl_transition_counts");
+    return 0;
+} LSL_API_CATCH
+
+// ---- Koopman-reweighted TICA on wide feature tables: weighted lagged moments, affine weights, the wide projection (k_wtica.hip.h) ----
+static const char *wmom_shape_error(int32_t n, int32_t F, int32_t lag) {
+    if (F < LSL_WMOM_MIN_F || F > LSL_WMOM_MAX_F) return "F outside the native form (129..2048 features; 1..128 are lsl_lagged_moments')";
+    if (n < 2) return "n must be at least 2";
+    if (lag < 1 || lag >= n) return "lag outside 1..n-1 (the window has n - lag rows)";
+    return nullptr;
+}
+
+size_t lsl_weighted_moments_workspace_bytes(int32_t n, int32_t F, int32_t lag) {
+    if (wmom_shape_error(n, F, lag)) return 0;
+    return (size_t)wmom_plan(n, F, lag).nsplit * wmom_part_entries(F) * sizeof(double);
+}
+
+int lsl_weighted_moments(const float *x, int32_t n, int32_t F, int32_t lag, const double *w, double *moments, void *workspace, size_t workspace_bytes,
+                         void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!x || !moments || !workspace) return fail(-1, "null argument");
+    if (const char *why = wmom_shape_error(n, F, lag)) return fail(-3, "n = %d, F = %d, lag = %d: %s", n, F, lag, why);
+    const size_t need = lsl_weighted_moments_workspace_bytes(n, F, lag);
+    if (workspace_bytes < need) return fail(-4, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    hipStream_t st = (hipStream_t)stream;
+    const WmomPlan p = wmom_plan(n, F, lag);
+    hipLaunchKernelGGL(k_wmom_tiles, dim3((unsigned)p.jobs, (unsigned)p.nsplit), dim3(256), 0, st, (double *)workspace, x, w, (int)n, (int)F, (int)lag,
+                       p.Te, p.T, p.q);
+    LSL_CHECK_LAUNCH("lsl_weighted_moments");
+    const long long E = 1 + 2LL * F + 3LL * F * F;
+    hipLaunchKernelGGL(k_wmom_final, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, moments, (const double *)workspace, (int)F, p.nsplit);
+    LSL_CHECK_LAUNCH("lsl_weighted_moments (final)");
+    return 0;
+} LSL_API_CATCH
+
+int lsl_affine_weights(const float *x, int32_t m, int32_t F, const double *u, double c, double *w, void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!x || !u || !w) return fail(-1, "null argument");
+    if (m < 1) return fail(-3, "m = %d must be positive", m);
+    if (F < 1 || F > LSL_WMOM_MAX_F) return fail(-3, "F = %d outside the native form (1..%d features)", F, LSL_WMOM_MAX_F);
+    hipLaunchKernelGGL(k_project_wide<true>, dim3((unsigned)(((long long)m + LSL_WPROJ_ROWS - 1) / LSL_WPROJ_ROWS)), dim3(256), 0, (hipStream_t)stream,
+                       (float *)nullptr, w, x, (const double *)nullptr, u, c, (unsigned *)nullptr, (int)m, (int)F, 1);
+    LSL_CHECK_LAUNCH("lsl_affine_weights");
+    return 0;
+} LSL_API_CATCH
+
+int lsl_project_wide(const float *x, int32_t n, int32_t F, const double *mean, const double *W, int32_t d, float *y, float *lim, void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!x || !mean || !W || !y) return fail(-1, "null argument");
+    if (n < 1) return fail(-3, "n = %d must be positive", n);
+    if (F < LSL_WMOM_MIN_F || F > LSL_WMOM_MAX_F)
+        return fail(-3, "F = %d outside the native form (%d..%d features; 1..128 are lsl_project's)", F, LSL_WMOM_MIN_F, LSL_WMOM_MAX_F);
+    if (d < 1 || d > LSL_WPROJ_MAX_D) return fail(-3, "d = %d outside the native form (1..%d output columns)", d, LSL_WPROJ_MAX_D);
+    hipStream_t st = (hipStream_t)stream;
+    if (lim) {
+        hipLaunchKernelGGL(k_lim_keys, dim3(1), dim3(128), 0, st, lim, 2 * (int)d);
+        LSL_CHECK_LAUNCH("lsl_project_wide (limits to keys)");
+    }
+    hipLaunchKernelGGL(k_project_wide<false>, dim3((unsigned)(((long long)n + LSL_WPROJ_ROWS - 1) / LSL_WPROJ_ROWS)), dim3(256), 0, st, y, (double *)nullptr, x,
+                       mean, W, 0.0, (unsigned *)lim, (int)n, (int)F, (int)d);
+    LSL_CHECK_LAUNCH("lsl_project_wide");
+    if (lim) {
+        hipLaunchKernelGGL(k_lim_floats, dim3(1), dim3(128), 0, st, lim, 2 * (int)d);
+        LSL_CHECK_LAUNCH("lsl_project_wide (keys to limits)");
+    }
     return 0;
 } LSL_API_CATCH
 

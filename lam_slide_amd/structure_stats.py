@@ -22,9 +22,9 @@ counts are integers (exact), every float is a sum in a fixed order (a frame has 
 anything else takes a numpy / torch restatement with the same outputs and the same NaN conventions.  ``last_path[name]`` tells which of
 the two ("fused" / "torch") the last call of a function took.
 
-Not here.  ``run_tica``'s Koopman-reweighted deeptime estimate: ``tica_features`` is wider than the F <= 128 of ``lsl_lagged_moments`` /
-``lsl_project``; the TIC projections are the caller's, from any model, and enter ``traj_analysis`` as ``tics_ref`` / ``tics_model``.  Plots,
-superposition and mdtraj I/O: every metric here is invariant under rigid motion.  Neither mdtraj nor deeptime was available where this was
+Not here.  Plots, superposition and mdtraj I/O: every metric here is invariant under rigid motion.  ``run_tica``'s Koopman-reweighted
+estimate over ``tica_features`` is ``koopman_tica.run_tica`` (``traj_analysis(..., tica_lagtime=)``); projections from any other model
+enter ``traj_analysis`` as ``tics_ref`` / ``tics_model``.  Neither mdtraj nor deeptime was available where this was
 written: the statements below are checked against numpy / scipy, parity with a live mdtraj was not checked."""
 from __future__ import annotations
 
@@ -428,7 +428,7 @@ def contact_rmse(contacts_ref: Tensor, n_ref: int, contacts_model: Tensor, n_mod
 
 
 def traj_analysis(pos_model: Tensor, pos_ref: Tensor, aatype, tics_ref: Optional[Tensor] = None, tics_model: Optional[Tensor] = None,
-                  bins: int = 50, tables=None) -> Dict[str, Tensor]:
+                  bins: int = 50, tables=None, *, tica_lagtime: Optional[int] = None, tica_dim: int = 40) -> Dict[str, Tensor]:
     """``utils/traj_utils.py:traj_analysis`` behind the TICA model: pos_model [m, R, 14, 3], pos_ref [n, R, 14, 3] (atom14 positions in
     nanometres, or [.., R * 14, 3]), aatype [R] or a :class:`StructureTables` of it -> {name: float64 0-d tensor on the positions' device}:
 
@@ -440,11 +440,16 @@ def traj_analysis(pos_model: Tensor, pos_ref: Tensor, aatype, tics_ref: Optional
       val_ca           the model's valid frames over its frames: ``tally[3] / tally[0]``
       rmse_contact     ``sqrt(2 / (R (R - 1)) sum (c_ref - c_model)^2)`` of the contact rates, from the integer tables; 0 for R < 2, as the
                        reference's ``except`` gives
-      tic_js, tic2d_js only when ``tics_ref`` [n, >= 2] and ``tics_model`` [m, >= 2] are given (the caller's projections, float32 on the
-                       device): ``compute_js_distance`` of their first two columns and ``compute_joint_js_distance`` of the two
+      tic_js, tic2d_js ``compute_js_distance`` of the first two TIC columns and ``compute_joint_js_distance`` of the two.  From the caller's
+                       projections when ``tics_ref`` [n, >= 2] and ``tics_model`` [m, >= 2] are given (float32 on the device, from any
+                       model); else, when ``tica_lagtime`` is given, from positions alone as the reference does: ``tica_features`` of both
+                       trajectories, ``koopman_tica.run_tica(ref_features, tica_lagtime, tica_dim)``, both projected with that model
+                       (``tica_lagtime >= n`` raises ValueError).  With neither the two keys are absent.
 
     On the device form nothing is read back and, when ``aatype`` is a :class:`StructureTables` already ``on`` the device, nothing is
-    uploaded: no host synchronisation.  ``tables``: the residue tables, for building the index tables from a plain ``aatype``."""
+    uploaded: no host synchronisation - except, with ``tica_lagtime``, the two host eigenproblems of ``run_tica`` (the Koopman step and
+    ``solve_tica``) with their copies (``koopman_tica._to_host`` / ``_to_device``).  ``tables``: the residue tables, for building the
+    index tables from a plain ``aatype``."""
     st = _tables_of(aatype, tables)
     pm, pr = _frames(pos_model, "pos_model"), _frames(pos_ref, "pos_ref")
     dev, R = pm.device, st.R
@@ -481,6 +486,19 @@ def traj_analysis(pos_model: Tensor, pos_ref: Tensor, aatype, tics_ref: Optional
         paths.add(last_path["density_js"])
         out["rg_js"] = density_js(sr.rg, sm.rg, bins)[1]
         paths.add(last_path["density_js"])
+    if tics_ref is None and tica_lagtime is not None:
+        from . import koopman_tica
+        if not 1 <= int(tica_lagtime) < int(pr.shape[0]):
+            raise ValueError(f"tica_lagtime = {tica_lagtime} outside 1..n_ref-1 = {int(pr.shape[0]) - 1}: the window has n_ref - tica_lagtime rows")
+        fr, fm = tica_features(pr, st), tica_features(pm, st)
+        model = koopman_tica.run_tica(fr, int(tica_lagtime), int(tica_dim))
+        paths.add(koopman_tica.last_path["run_tica"])
+        if model.dim < 2:
+            raise ValueError(f"the fitted TICA model has {model.dim} component: tic2d_js needs two (tica_dim = {tica_dim})")
+        tics_ref = model.transform(fr)
+        paths.add(koopman_tica.last_path["transform"])
+        tics_model = model.transform(fm)
+        paths.add(koopman_tica.last_path["transform"])
     if tics_ref is not None:
         if tics_ref.dim() != 2 or tics_model.dim() != 2 or tics_ref.shape[1] < 2 or tics_model.shape[1] < 2:
             raise ValueError(f"expected tics_ref [n, >= 2] and tics_model [m, >= 2], got {tuple(tics_ref.shape)} and {tuple(tics_model.shape)}")
