@@ -30,6 +30,10 @@ MOM_SEG = 1024  # lsl_lagged_moments (csrc/k_tica.hip.h): segment g holds the ti
 MOM_CHAIN = MOM_SEG  # the longest fp64 addition chain inside a segment
 MOM_MAX_F, PROJ_MAX_D = 128, 16  # the native forms of lsl_lagged_moments / lsl_project: features, output columns
 ASG_MAX_K, ASG_MAX_D, ASG_CELLS, ASG_MAX_STATES, TR_MAX_STATES = 1024, 64, 8192, 1024, 128  # lsl_assign_centers, lsl_transition_counts
+KM_SEG, KM_MAX_S = 2048, 65535  # lsl_kmeans_step (csrc/k_kmeans.hip.h): segment g holds the rows [g * KM_SEG, (g + 1) * KM_SEG); series of one call.  Its centres' limits are ASG_*
+WMOM_MIN_F, WMOM_MAX_F, WPROJ_MAX_D = 129, 2048, 64  # the native form of lsl_weighted_moments / lsl_project_wide (csrc/k_wtica.hip.h): features, output columns
+WMOM_SEG, WMOM_CHAIN = 1024, 4130  # lsl_weighted_moments: the rows of a segment, the roundings on the longest path to one entry
+PAIR_MAX_P, CA_MAX_R = 65536, 146  # lsl_pair_distances / lsl_ca_frame_stats (csrc/k_structstat.hip.h): pairs of one call, selected atoms of a frame
 SI_SLAB = 4096  # LSL_SI_SLAB: elements of one trajectory per partial sum of lsl_si_reduce
 
 EXPORTED = (
@@ -289,6 +293,33 @@ def call(dev, name: str, *args) -> None:
     fn = getattr(load(), name)
     with torch.cuda.device(dev):
         check(fn(*args, torch.cuda.current_stream(dev).cuda_stream))
+
+
+def to_host(t: "torch.Tensor"):
+    """A device tensor as a numpy array.  One of the documented synchronising copies of a fit: allowed under
+    ``torch.cuda.set_sync_debug_mode("error")`` by switching to "default" around this copy alone."""
+    if not t.is_cuda:
+        return t.numpy()
+    mode = torch.cuda.get_sync_debug_mode()
+    torch.cuda.set_sync_debug_mode("default")
+    try:
+        return t.cpu().numpy()
+    finally:
+        torch.cuda.set_sync_debug_mode(mode)
+
+
+def to_device(a, dev) -> "torch.Tensor":
+    """A host array on ``dev``: the way back of :func:`to_host`, with the same exception."""
+    import numpy as np
+    t = torch.from_numpy(np.ascontiguousarray(a))
+    if torch.device(dev).type != "cuda":
+        return t
+    mode = torch.cuda.get_sync_debug_mode()
+    torch.cuda.set_sync_debug_mode("default")
+    try:
+        return t.to(dev)
+    finally:
+        torch.cuda.set_sync_debug_mode(mode)
 
 
 def device_form(*tensors, dtype=torch.float32, same_device: bool = True) -> bool:

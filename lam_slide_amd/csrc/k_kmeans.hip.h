@@ -3,8 +3,8 @@
 // k = 100) and the post_process branch of the NBA / pedestrian test_step (second_stage/nba.py:202-203, 228-238: S = 11 264 agents, n = K = 60
 // final frames, k = num_runs = 20, d = 2).
 //
-//      assign   labels[t] = the lowest c that minimises sum_j (y[t, j] - centers[c, j])^2: fp64 differences, the fused sum over j ascending,
-//               centres ascending, strict < (the rule of k_assign); a row that holds a NaN gets -1 and takes no part in anything below
+//      assign   labels[t] = the lowest c that minimises sum_j (y[t, j] - centers[c, j])^2: nearest_centre of k_stat_frag.hip.h, the very
+//               function k_assign calls; a row that holds a NaN gets -1 and takes no part in anything below
 //      update   sum[c, j] = sum of y[t, j] over the rows labelled c in fp64: rows ascending in t within a segment of LSL_KM_SEG rows (segment
 //               g: t in [g SEG, (g + 1) SEG), a function of n alone), the segments added in segment order; count[c] an exact integer; the new
 //               centre fp32(sum / count): one fp64 division, one rounding; an empty cluster keeps its centre bit for bit
@@ -14,13 +14,13 @@
 //  k_kmeans_step   a group of G threads owns (series, segment); a workgroup is 256 threads.  G = 256 in general: one group per workgroup, which
 //                  leaves at once when done[s] is set.  G = 64 (one wave) when the whole series fits a wave's share of the LDS (km_group: a
 //                  function of (n, d, k) alone): four series per workgroup, so S = 11 264 series of 60 rows are 2816 workgroups, not 11 264.
-//                  A group keeps its series' centres in LDS and walks its segment in sub-tiles of rows, staged transposed as in k_assign.
+//                  A group keeps its series' centres in LDS and walks its segment in sub-tiles of rows (stage_rows_transposed).
 //                  Phase A: a thread per row finds the argmin, writes the label to LDS and to memory, compares it with the previous label,
 //                  keeps the winning distance.  Phase B: thread `lane` owns the items (c, j) = lane + q G, q < NQ <= 32, in fp64 registers
 //                  that persist over the sub-tiles of the segment; it walks the sub-tile's labels in LDS (broadcast reads) in ascending t and
 //                  adds y[t, j] where the label is c - the order of the contract, whatever G is - and counts the members as an integer.
 //  k_kmeans_final  one workgroup per series adds the segments in segment order, divides, rounds, writes centres, counts and state, sets done.
-//  k_nearest_rows  the reverse lookup of post_process: rows[s, c] = the lowest t that minimises the same distance; P lanes per (s, c), P = 1
+//  k_nearest_rows  the reverse lookup of post_process: rows[s, c] = the lowest t that minimises the same distance (sq_dist_chain); P lanes per (s, c), P = 1
 //                  for n <= 64 (256 items of many tiny series per workgroup), 64 above (lanes stride over t, then a (distance, t) minimum).
 //
 // Determinism.  No float atomics; one LDS integer atomic, for the changed-label count.  The inertia of a group: every thread adds the winning
@@ -29,13 +29,16 @@
 // series share its workgroup.
 #pragma once
 #include "common.hip.h"
+#include "k_stat_frag.hip.h"
+#include "k_tica.hip.h"
 
-#define LSL_KM_MAX_K 1024   // centres
-#define LSL_KM_MAX_D 64     // coordinates of a centre
-#define LSL_KM_CELLS 8192   // k * d floats of centres in LDS (32 KiB): the limits of k_assign
+#define LSL_KM_MAX_K LSL_ASG_MAX_K  // centres, their coordinates and the k * d floats of centres in LDS: the assignment is k_assign's
+#define LSL_KM_MAX_D LSL_ASG_MAX_D  // (nearest_centre), and so are its limits
+#define LSL_KM_CELLS LSL_ASG_CELLS
+#define LSL_KM_TILE LSL_ASG_TILE    // floats of the row tile in LDS: min(G, LSL_KM_TILE G / (256 d)) rows per pass
+#define LSL_KM_MAX_S 65535  // series of one call (a grid dimension)
 #define LSL_KM_SEG 2048     // rows per segment = the longest fp64 addition chain of a partial sum (10^6 rows: 489 workgroups)
-#define LSL_KM_TILE 4096    // floats of the row tile in LDS: min(G, LSL_KM_TILE G / (256 d)) rows per pass
-#define LSL_KM_MAX_Q 32     // items (c, j) per thread: LSL_KM_CELLS / 256
+#define LSL_KM_MAX_Q (LSL_KM_CELLS / 256)  // items (c, j) per thread
 
 inline int km_segments(int n) { return (int)(((long long)n + LSL_KM_SEG - 1) / LSL_KM_SEG); }
 __host__ __device__ inline int km_rows(int G, int d) {  // rows of a sub-tile of a group of G threads
@@ -80,30 +83,14 @@ __global__ void __launch_bounds__(256) k_kmeans_step(const float *y, const float
     int changed = 0;
     const long long t_first = (long long)g * LSL_KM_SEG, t_last = (n - t_first < LSL_KM_SEG) ? n : t_first + LSL_KM_SEG;  // [t_first, t_last)
     for (long long t0 = t_first; t0 < t_last; t0 += ra) {  // (the same trips in every group of a workgroup: the barriers are uniform)
-        const int rows = (int)((t_last - t0 < ra) ? (t_last - t0) : ra);
-        if (live) {
-            const float *src = yb + (size_t)t0 * d;
-            for (int i = lane; i < rows * d; i += G) {
-                const int r = i / d, j = i - r * d;
-                ytg[j * ra + r] = src[i];  // (transposed: the lanes of a wave read consecutive words)
-            }
-        }
+        const int rows = tile_rows(t_last, t0, ra);
+        if (live) stage_rows_transposed(ytg, yb + (size_t)t0 * d, rows, d, ra, lane, G);
         __syncthreads();
         if (live && lane < rows) {
             const int r = lane;
-            bool nan = false;
-            for (int j = 0; j < d; ++j) nan |= ytg[j * ra + r] != ytg[j * ra + r];
-            int best_c = 0;
-            double best = __builtin_inf();
-            for (int c = 0; c < k; ++c) {
-                const float *cc = csg + c * d;
-                double a = 0.0;
-                for (int j = 0; j < d; ++j) {
-                    const double diff = (double)ytg[j * ra + r] - (double)cc[j];
-                    a = fma(diff, diff, a);
-                }
-                if (a < best) best = a, best_c = c;  // (strict: ties go to the lowest index)
-            }
+            bool nan;
+            double best;
+            const int best_c = nearest_centre(ytg, ra, r, csg, d, k, &best, &nan);
             const int lab = nan ? -1 : best_c;
             labg[r] = lab;
             changed += lab != lb[t0 + r];
@@ -195,8 +182,8 @@ __global__ void __launch_bounds__(256) k_kmeans_final(float *centers, long long 
         done[s] = 1;
 }
 
-// rows[s k + c] = the lowest t that minimises sum_j (y[s, t, j] - centers[s, c, j])^2 (the arithmetic of the assignment; rows that hold a NaN
-// skipped; -1 when the series has no finite row).  P lanes (a power of two <= 64) per item (s, c): lane p walks t = p, p + P, ... ascending with
+// rows[s k + c] = the lowest t that minimises sum_j (y[s, t, j] - centers[s, c, j])^2 (sq_dist_chain: the arithmetic of the assignment; rows
+// that hold a NaN skipped; -1 when the series has no finite row).  P lanes (a power of two <= 64) per item (s, c): lane p walks t = p, p + P, ... ascending with
 // strict <, then the lanes' (distance, t) pairs are reduced: the smaller distance, on equal distances the lower t - what one walk in ascending
 // t gives.  grid ceil(items P / 256), 256 threads.
 __global__ void __launch_bounds__(256) k_nearest_rows(int *rows, const float *y, const float *centers, long long items, int n, int d, int k, int P) {
@@ -208,16 +195,8 @@ __global__ void __launch_bounds__(256) k_nearest_rows(int *rows, const float *y,
     if (live) {
         const float *yb = y + (size_t)(item / k) * n * d, *cc = centers + (size_t)item * d;
         for (int t = lane; t < n; t += P) {
-            const float *yr = yb + (size_t)t * d;
-            bool nan = false;
-            double a = 0.0;
-            for (int j = 0; j < d; ++j) {
-                const float v = yr[j];
-                nan |= v != v;
-                const double diff = (double)v - (double)cc[j];
-                a = fma(diff, diff, a);
-            }
-            if (!nan && a < best) best = a, bt = t;
+            const double a = sq_dist_chain(yb + (size_t)t * d, 1, cc, d);
+            if (a < best) best = a, bt = t;  // (a row that holds a NaN has a NaN distance: it never wins)
         }
     }
     for (int off = P >> 1; off > 0; off >>= 1) {  // (every lane of the wave takes part: no thread has left)

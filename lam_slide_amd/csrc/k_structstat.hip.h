@@ -10,7 +10,7 @@
 //
 // Work split.
 //  k_pair_dist    as k_dihedral: a workgroup of 256 threads owns fpb consecutive frames (fpb * A <= LSL_TORS_LDS_ATOMS), copies their atoms
-//                 to LDS in one coalesced pass and thread i computes item i, i + 256, ... of the fpb * P (frame, pair) items from LDS.
+//                 to LDS (stage_frames of k_stat_frag.hip.h) and thread i computes item i, i + 256, ... of the fpb * P (frame, pair) items from LDS.
 //  k_ca_stats     a workgroup owns a tile of tf consecutive frames (tf <= 256, tf * R <= LSL_CA_LDS_ATOMS) and holds their R selected atoms in
 //                 LDS, coordinate-major with the frame innermost (at[(c R + r) tfs + frame], tfs odd: the threads of the frame pass read
 //                 consecutive words, the threads of the pair pass read words an odd stride apart).  Frame pass: thread f owns frame f - rg in
@@ -18,9 +18,10 @@
 //                 atomic each.  Pair pass: thread p owns the cells p, p + 256, ... of the R x R table with i < j, walks the tile's frames
 //                 with a register count and adds a non-zero count to memory by one int64 atomic.
 //  k_hist_cols    a workgroup owns (a tile of qt columns, LSL_HIST_ROWS rows): the qt edge tables (fp64) and qt * bins int32 counts in LDS,
-//                 qt * (bins + 1) <= LSL_HCOL_CELLS; counts by LDS integer atomics, the non-zero ones added to the int64 table by integer atomics.
-//  k_js_density   a workgroup owns a row: the two int64 totals (exact in any order), then tiles of 256 bins twice - first the sums of the
-//                 two density rows, then the terms; in both the threads compute a tile into LDS and thread 0 adds it in bin order in fp64.
+//                 qt * (bins + 1) <= LSL_HCOL_CELLS; counts by LDS integer atomics, the non-zero ones added to the int64 table by integer
+//                 atomics (flush_counts).
+//  k_js_density   a workgroup owns a row: the two int64 totals (js_totals), then tiles of 256 bins twice - first the sums of the two density
+//                 rows, then the terms; in both the threads compute a tile into LDS and thread 0 adds it in bin order in fp64 (as k_js).
 //
 // Determinism.  The only atomics are integer additions of counts (LDS int32, memory int64): exact in any order.  No float atomics.  A
 // distance is a function of its own two atoms, computed by one thread with a fixed operation sequence (no contraction).  rg of a frame is
@@ -28,6 +29,7 @@
 // Nothing depends on the grid, the tile or the frame's place in the batch: a frame has the same bits alone and inside any batch.
 #pragma once
 #include "common.hip.h"
+#include "k_stat_frag.hip.h"
 #include "k_torsstat.hip.h"
 
 #define LSL_PAIR_MAX_P 65536      // pairs of one call of lsl_pair_distances
@@ -48,12 +50,8 @@ __device__ __forceinline__ float ss_dist(float ax, float ay, float az, float bx,
 // entry outside gives NaN here, nothing is read with it).  grid ceil(F / fpb), 256 threads, fpb * A <= LSL_TORS_LDS_ATOMS.
 __global__ void __launch_bounds__(256) k_pair_dist(float *dist, const float *pos, const int *pairs, long long F, int A, int P, int fpb) {
     __shared__ float atoms[LSL_TORS_LDS_ATOMS * 3];
-    const long long f0 = (long long)blockIdx.x * fpb;
-    const int nf = (int)((F - f0 < fpb) ? (F - f0) : fpb);
-    const int n_float = nf * A * 3;
-    const float *src = pos + (size_t)f0 * A * 3;
-    for (int i = threadIdx.x; i < n_float; i += 256) atoms[i] = src[i];
-    __syncthreads();
+    long long f0;
+    const int nf = stage_frames(atoms, pos, F, A, fpb, &f0);
     const int items = nf * P;  // (<= 2048 * 65536 = 2^27)
     for (int i = threadIdx.x; i < items; i += 256) {
         const int fl = i / P, p = i - fl * P;
@@ -148,7 +146,7 @@ __global__ void __launch_bounds__(256) k_hist_cols(unsigned long long *counts, c
     __shared__ double e[LSL_HCOL_CELLS];
     __shared__ int cnt[LSL_HCOL_CELLS];
     const int q0 = blockIdx.y * qt, nq = (Q - q0 < qt) ? (Q - q0) : qt;
-    const int t0 = blockIdx.x * LSL_HIST_ROWS, nt = (n - t0 < LSL_HIST_ROWS) ? (n - t0) : LSL_HIST_ROWS;
+    const int t0 = blockIdx.x * LSL_HIST_ROWS, nt = tile_rows(n, t0, LSL_HIST_ROWS);
     const double *es = edges + (size_t)q0 * (bins + 1);
     for (int i = threadIdx.x; i < nq * (bins + 1); i += 256) e[i] = es[i];
     for (int i = threadIdx.x; i < nq * bins; i += 256) cnt[i] = 0;
@@ -160,9 +158,7 @@ __global__ void __launch_bounds__(256) k_hist_cols(unsigned long long *counts, c
         if (b >= 0) atomicAdd(&cnt[q * bins + b], 1);
     }
     __syncthreads();
-    unsigned long long *out = counts + (size_t)q0 * bins;
-    for (int i = threadIdx.x; i < nq * bins; i += 256)
-        if (cnt[i]) atomicAdd(&out[i], (unsigned long long)cnt[i]);
+    flush_counts(counts + (size_t)q0 * bins, cnt, nq * bins);
 }
 
 // ---- d. Jensen-Shannon distance of two density histograms ----
@@ -174,14 +170,7 @@ __global__ void __launch_bounds__(256) k_js_density(double *out, const long long
     __shared__ double term[2][256];
     const long long *ra = a + (size_t)blockIdx.x * bins, *rb = b + (size_t)blockIdx.x * bins;
     const double *rm = measure + (size_t)blockIdx.x * bins;
-    long long sa = 0, sb = 0;
-    for (int i = threadIdx.x; i < bins; i += 256) sa += ra[i], sb += rb[i];
-    tot[0][threadIdx.x] = sa, tot[1][threadIdx.x] = sb;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {  // (integers: any order gives the same totals)
-        if ((int)threadIdx.x < w) tot[0][threadIdx.x] += tot[0][threadIdx.x + w], tot[1][threadIdx.x] += tot[1][threadIdx.x + w];
-        __syncthreads();
-    }
+    js_totals(tot, ra, rb, bins);
     const double na = (double)tot[0][0], nb = (double)tot[1][0];
     double first = 0.0, second = 0.0;  // (thread 0's: pass 0 the sums of ha and hb, pass 1 sum rel_entr(p, m) and sum rel_entr(q, m))
     double suma = 0.0, sumb = 0.0;

@@ -14,12 +14,13 @@
 //                     F <= 64, T = 4 above.  The threads of block column 0 also add x_t and x_{t+lag} themselves (sx, sy).
 //  k_moments_final    adds the segments' partials in segment order in fp64.
 //  k_project          a workgroup stages W, mean (fp64) and 64 rows of x in LDS; a thread owns outputs (row, j): the fp64 subtraction, the
-//                     fused chain over f ascending, one rounding to fp32.  Minimum / maximum: LDS integer atomics on the order-preserving
-//                     key of the fp32 value, then one integer atomic per column and workgroup on the caller's table, which k_lim_keys has
-//                     turned into keys before and k_lim_floats turns back after.
-//  k_assign           the centres and a tile of rows (transposed: conflict-free) in LDS, a thread per row, centres ascending, strict <.
+//                     fused chain over f ascending, one rounding to fp32.  Minimum / maximum: lim_init / lim_update / lim_flush of
+//                     k_stat_frag.hip.h - LDS integer atomics on the order-preserving key of the fp32 value, then one integer atomic per
+//                     column and workgroup on the caller's table, which k_lim_keys has turned into keys before and k_lim_floats turns
+//                     back after.
+//  k_assign           the centres and a tile of rows (stage_rows_transposed: conflict-free) in LDS, a thread per row: nearest_centre.
 //  k_transitions      a workgroup owns LSL_TR_ROWS pairs of one series: int32 counts in LDS by LDS integer atomics, the non-zero ones added
-//                     to the int64 table in memory by integer atomics (as k_hist2).
+//                     to the int64 table in memory by integer atomics (flush_counts, as every histogram).
 //
 // Determinism.  The only atomics are integer additions and integer minimum / maximum: no order.  No float atomics.  Every entry of the
 // moments is a direct sum over its own window: the terms of a segment in t order (the longest fp64 addition chain is LSL_MOM_SEG), the
@@ -28,6 +29,7 @@
 // exact products in the same order: the same bits, and so yy.  Nothing below depends on contraction: every fused operation is written fma.
 #pragma once
 #include "common.hip.h"
+#include "k_stat_frag.hip.h"
 
 #define LSL_MOM_MAX_F 128    // features of a row: two tiles of LSL_MOM_ROWS rows in LDS are 32 KiB
 #define LSL_MOM_SEG 1024     // time steps per segment = the longest fp64 addition chain of a partial (10^6 steps: ~1000 workgroups per block chunk)
@@ -129,21 +131,15 @@ __global__ void __launch_bounds__(256) k_moments_final(double *out, const double
 }
 
 // ---- b. projection and running limits ----
-// The order-preserving key of a float: a < b as floats (no NaN) <=> key(a) < key(b) as unsigned integers (-0 below +0).
-__device__ __forceinline__ unsigned tica_key(float v) {
-    const unsigned u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float tica_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
-// lim [2 d] in place: floats -> keys, keys -> floats (one thread per entry; the table's bytes hold keys between the two).
+// lim [2 d] in place: floats -> keys (lim_key of k_stat_frag.hip.h), keys -> floats (one thread per entry; the table's bytes hold keys
+// between the two).
 __global__ void k_lim_keys(float *lim, int count) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < count) ((unsigned *)lim)[i] = tica_key(lim[i]);
+    if (i < count) ((unsigned *)lim)[i] = lim_key(lim[i]);
 }
 __global__ void k_lim_floats(float *lim, int count) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < count) lim[i] = tica_unkey(((const unsigned *)lim)[i]);
+    if (i < count) lim[i] = lim_unkey(((const unsigned *)lim)[i]);
 }
 
 // y[t d + j] = fp32(sum_f (x[t F + f] - mean[f]) W[f d + j]), f ascending; keys (or NULL): [2 d] unsigned, keys[j] = min, keys[d + j] = max
@@ -154,10 +150,10 @@ __global__ void __launch_bounds__(256) k_project(float *y, const float *x, const
     __shared__ unsigned kmin[LSL_PROJ_MAX_D], kmax[LSL_PROJ_MAX_D];
     const int FS = F | 1;  // (an odd row stride: the rows of a wave's lanes fall on different banks)
     const long long t0 = (long long)blockIdx.x * LSL_PROJ_ROWS;
-    const int rows = (int)((n - t0 < LSL_PROJ_ROWS) ? (n - t0) : LSL_PROJ_ROWS);
+    const int rows = tile_rows(n, t0, LSL_PROJ_ROWS);
     for (int i = threadIdx.x; i < F * d; i += 256) Ws[i] = W[i];
     for (int i = threadIdx.x; i < F; i += 256) ms[i] = mean[i];
-    if (threadIdx.x < LSL_PROJ_MAX_D) kmin[threadIdx.x] = 0xffffffffu, kmax[threadIdx.x] = 0u;  // (the keys of NaN patterns: no value has them)
+    lim_init(kmin, kmax, LSL_PROJ_MAX_D);
     const float *src = x + (size_t)t0 * F;
     for (int i = threadIdx.x; i < rows * F; i += 256) {
         const int r = i / F, f = i - r * F;
@@ -171,17 +167,11 @@ __global__ void __launch_bounds__(256) k_project(float *y, const float *x, const
         for (int f = 0; f < F; ++f) acc = fma((double)xr[f] - ms[f], Ws[f * d + j], acc);
         const float v = (float)acc;
         y[(size_t)t0 * d + i] = v;
-        if (keys && v == v) {
-            const unsigned k = tica_key(v);
-            atomicMin(&kmin[j], k), atomicMax(&kmax[j], k);
-        }
+        if (keys) lim_update(kmin, kmax, j, v);
     }
     if (!keys) return;
     __syncthreads();
-    if ((int)threadIdx.x < d && kmin[threadIdx.x] != 0xffffffffu) {  // (a workgroup whose column held only NaN adds nothing)
-        atomicMin(&keys[threadIdx.x], kmin[threadIdx.x]);
-        atomicMax(&keys[d + threadIdx.x], kmax[threadIdx.x]);
-    }
+    lim_flush(keys, kmin, kmax, d);
 }
 
 // ---- c. nearest centre ----
@@ -193,31 +183,17 @@ __global__ void __launch_bounds__(256) k_assign(int *labels, unsigned long long 
     __shared__ float cs[LSL_ASG_CELLS], yt[LSL_ASG_TILE];
     __shared__ int cnt[LSL_ASG_MAX_STATES];
     const long long t0 = (long long)blockIdx.x * ra;
-    const int rows = (int)((n - t0 < ra) ? (n - t0) : ra);
+    const int rows = tile_rows(n, t0, ra);
     for (int i = threadIdx.x; i < k * d; i += 256) cs[i] = centers[i];
     if (state_counts)
         for (int i = threadIdx.x; i < nstates; i += 256) cnt[i] = 0;
-    const float *src = y + (size_t)t0 * d;
-    for (int i = threadIdx.x; i < rows * d; i += 256) {
-        const int r = i / d, j = i - r * d;
-        yt[j * ra + r] = src[i];  // (transposed: the lanes of a wave read consecutive words)
-    }
+    stage_rows_transposed(yt, y + (size_t)t0 * d, rows, d, ra, threadIdx.x, 256);
     __syncthreads();
     const int r = threadIdx.x;
     if (r < rows) {
-        bool nan = false;
-        for (int j = 0; j < d; ++j) nan |= yt[j * ra + r] != yt[j * ra + r];
-        int best_c = 0;
-        double best = __builtin_inf();
-        for (int c = 0; c < k; ++c) {
-            const float *cc = cs + c * d;
-            double acc = 0.0;
-            for (int j = 0; j < d; ++j) {
-                const double diff = (double)yt[j * ra + r] - (double)cc[j];
-                acc = fma(diff, diff, acc);
-            }
-            if (acc < best) best = acc, best_c = c;  // (strict: ties go to the lowest index, as np.argmin)
-        }
+        bool nan;
+        double best;
+        const int best_c = nearest_centre(yt, ra, r, cs, d, k, &best, &nan);
         int lab = -1;
         if (!nan) {
             lab = best_c;
@@ -231,8 +207,7 @@ __global__ void __launch_bounds__(256) k_assign(int *labels, unsigned long long 
     }
     if (!state_counts) return;
     __syncthreads();
-    for (int i = threadIdx.x; i < nstates; i += 256)
-        if (cnt[i]) atomicAdd(&state_counts[i], (unsigned long long)cnt[i]);
+    flush_counts(state_counts, cnt, nstates);
 }
 
 // ---- d. transition counts ----
@@ -242,7 +217,7 @@ __global__ void __launch_bounds__(256) k_transitions(unsigned long long *counts,
     __shared__ int cnt[LSL_TR_MAX_STATES * LSL_TR_MAX_STATES];
     const int cells = ns * ns, m = n - lag;
     const long long t0 = (long long)blockIdx.x * LSL_TR_ROWS;
-    const int rows = (int)((m - t0 < LSL_TR_ROWS) ? (m - t0) : LSL_TR_ROWS);
+    const int rows = tile_rows(m, t0, LSL_TR_ROWS);
     for (int i = threadIdx.x; i < cells; i += 256) cnt[i] = 0;
     __syncthreads();
     const int *ds = dtraj + (size_t)blockIdx.y * n + t0;
@@ -251,7 +226,5 @@ __global__ void __launch_bounds__(256) k_transitions(unsigned long long *counts,
         if ((unsigned)a < (unsigned)ns && (unsigned)b < (unsigned)ns) atomicAdd(&cnt[a * ns + b], 1);
     }
     __syncthreads();
-    unsigned long long *out = counts + (size_t)blockIdx.y * cells;
-    for (int i = threadIdx.x; i < cells; i += 256)
-        if (cnt[i]) atomicAdd(&out[i], (unsigned long long)cnt[i]);
+    flush_counts(counts + (size_t)blockIdx.y * cells, cnt, cells);
 }

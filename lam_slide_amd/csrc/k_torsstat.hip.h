@@ -7,17 +7,18 @@
 //
 // Work split.
 //  k_dihedral     a workgroup of 256 threads owns fpb consecutive frames (fpb * A <= 2048 atoms: one frame of up to LSL_TORS_MAX_A atoms, or
-//                 several small ones), copies their atoms to LDS once (one coalesced pass over contiguous memory) and thread i computes item
+//                 several small ones), copies their atoms to LDS once (stage_frames of k_stat_frag.hip.h) and thread i computes item
 //                 i, i + 256, ... of the fpb * Q (frame, quadruple) items from LDS.  The quadruple table is general: any four atom slots.
 //  k_hist1        a workgroup owns (series, a tile of qt columns with qt * bins <= 8192, 1024 rows): int32 counts in LDS by LDS integer atomics, the
-//                 non-zero ones added to the int64 table in memory by integer atomics.  k_hist2: (series, pair, 1024 rows), bins2^2 <= 8192 cells.
+//                 non-zero ones added to the int64 table in memory by integer atomics (flush_counts).  k_hist2: (series, pair, 1024 rows),
+//                 bins2^2 <= 8192 cells.
 //  k_lag_partial  a workgroup owns (series, channel, a tile of 256 lags, a segment of chunks of 448 time steps).  Per chunk it holds
 //                 x[t0 .. t0 + 448) and x[t0 + k0 .. t0 + k0 + 448 + 256) of its channel in LDS; thread j (lag k0 + j) walks t ascending:
 //                 x[t] is one address for the whole wave (a broadcast), x[t + k0 + j] consecutive addresses over the lanes (no bank conflict).
 //                 The chunk's fp32 sum is added to the thread's fp64 sum of the segment.  k_lag_final adds the segments in segment order
 //                 in fp64 and divides by n - k once.
-//  k_js           a workgroup owns a row: the two int64 totals (integers: exact in any order), then tiles of 256 bins - the threads
-//                 compute the terms of a tile into LDS, thread 0 adds them in bin order in fp64.
+//  k_js           a workgroup owns a row: the two int64 totals (js_totals: integers, exact in any order), then tiles of 256 bins - the
+//                 threads compute the terms of a tile into LDS, thread 0 adds them in bin order in fp64.
 //
 // Determinism.  The only atomics are integer additions (LDS int32, memory int64), and integer addition has no order: counts are exact.
 // No float atomics.  An angle is a function of its own four atoms, computed by one thread with a fixed operation sequence (no
@@ -28,6 +29,7 @@
 // of a row are added in bin order in fp64.
 #pragma once
 #include "common.hip.h"
+#include "k_stat_frag.hip.h"
 
 #define LSL_TORS_MAX_A 2044        // 146 residues of 14 atoms: a frame in LDS (the GEOM_MAX_A entities of lsl_geom_loss_sums hold 2048)
 #define LSL_TORS_MAX_Q 65536       // quadruples of one call of lsl_dihedral_angles
@@ -60,12 +62,8 @@ __device__ __forceinline__ float tors_dihedral(const float *p0, const float *p1,
 // an entry outside gives NaN here, nothing is read with it).  grid ceil(F / fpb), 256 threads, fpb * A <= LSL_TORS_LDS_ATOMS.
 __global__ void __launch_bounds__(256) k_dihedral(float *angles, const float *pos, const int *quads, long long F, int A, int Q, int fpb) {
     __shared__ float atoms[LSL_TORS_LDS_ATOMS * 3];
-    const long long f0 = (long long)blockIdx.x * fpb;
-    const int nf = (int)((F - f0 < fpb) ? (F - f0) : fpb);
-    const int n_float = nf * A * 3;
-    const float *src = pos + (size_t)f0 * A * 3;
-    for (int i = threadIdx.x; i < n_float; i += 256) atoms[i] = src[i];
-    __syncthreads();
+    long long f0;
+    const int nf = stage_frames(atoms, pos, F, A, fpb, &f0);
     const int items = nf * Q;
     for (int i = threadIdx.x; i < items; i += 256) {
         const int fl = i / Q, q = i - fl * Q;
@@ -98,7 +96,7 @@ __global__ void __launch_bounds__(256) k_hist1(unsigned long long *counts, const
     __shared__ double e[LSL_HIST_MAX_BINS + 1];
     __shared__ int cnt[LSL_HIST_CELLS];
     const int s = blockIdx.z, q0 = blockIdx.y * qt, nq = (Q - q0 < qt) ? (Q - q0) : qt;
-    const int t0 = blockIdx.x * LSL_HIST_ROWS, nt = (n - t0 < LSL_HIST_ROWS) ? (n - t0) : LSL_HIST_ROWS;
+    const int t0 = blockIdx.x * LSL_HIST_ROWS, nt = tile_rows(n, t0, LSL_HIST_ROWS);
     for (int i = threadIdx.x; i <= bins; i += 256) e[i] = edges[i];
     for (int i = threadIdx.x; i < nq * bins; i += 256) cnt[i] = 0;
     __syncthreads();
@@ -109,9 +107,7 @@ __global__ void __launch_bounds__(256) k_hist1(unsigned long long *counts, const
         if (b >= 0) atomicAdd(&cnt[q * bins + b], 1);
     }
     __syncthreads();
-    unsigned long long *out = counts + ((size_t)s * Q + q0) * bins;
-    for (int i = threadIdx.x; i < nq * bins; i += 256)
-        if (cnt[i]) atomicAdd(&out[i], (unsigned long long)cnt[i]);
+    flush_counts(counts + ((size_t)s * Q + q0) * bins, cnt, nq * bins);
 }
 
 // counts2[((s P + p) bins2 + ia) bins2 + ib] += number of rows t with x[s, t, pairs[p][0]] in bin ia of ea and x[s, t, pairs[p][1]] in bin
@@ -121,7 +117,7 @@ __global__ void __launch_bounds__(256) k_hist2(unsigned long long *counts2, cons
     __shared__ double ea[LSL_HIST2_MAX_BINS + 1], eb[LSL_HIST2_MAX_BINS + 1];
     __shared__ int cnt[LSL_HIST_CELLS];
     const int s = blockIdx.z, p = blockIdx.y, cells = bins2 * bins2;
-    const int t0 = blockIdx.x * LSL_HIST_ROWS, nt = (n - t0 < LSL_HIST_ROWS) ? (n - t0) : LSL_HIST_ROWS;
+    const int t0 = blockIdx.x * LSL_HIST_ROWS, nt = tile_rows(n, t0, LSL_HIST_ROWS);
     for (int i = threadIdx.x; i <= bins2; i += 256) ea[i] = edges_a[i], eb[i] = edges_b[i];
     for (int i = threadIdx.x; i < cells; i += 256) cnt[i] = 0;
     __syncthreads();
@@ -134,9 +130,7 @@ __global__ void __launch_bounds__(256) k_hist2(unsigned long long *counts2, cons
         }
     }
     __syncthreads();
-    unsigned long long *out = counts2 + ((size_t)s * P + p) * cells;
-    for (int i = threadIdx.x; i < cells; i += 256)
-        if (cnt[i]) atomicAdd(&out[i], (unsigned long long)cnt[i]);
+    flush_counts(counts2 + ((size_t)s * P + p) * cells, cnt, cells);
 }
 
 // ---- c. lagged products ----
@@ -204,14 +198,7 @@ __global__ void __launch_bounds__(256) k_js(double *out, const long long *a, con
     __shared__ long long tot[2][256];
     __shared__ double term[2][256];
     const long long *ra = a + (size_t)blockIdx.x * bins, *rb = b + (size_t)blockIdx.x * bins;
-    long long sa = 0, sb = 0;
-    for (int i = threadIdx.x; i < bins; i += 256) sa += ra[i], sb += rb[i];
-    tot[0][threadIdx.x] = sa, tot[1][threadIdx.x] = sb;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {  // (integers: any order gives the same totals)
-        if ((int)threadIdx.x < w) tot[0][threadIdx.x] += tot[0][threadIdx.x + w], tot[1][threadIdx.x] += tot[1][threadIdx.x + w];
-        __syncthreads();
-    }
+    js_totals(tot, ra, rb, bins);
     const double na = (double)tot[0][0], nb = (double)tot[1][0];
     double left = 0.0, right = 0.0;  // (thread 0's: sum rel_entr(p, m), sum rel_entr(q, m))
     for (int i0 = 0; i0 < bins; i0 += 256) {

@@ -25,9 +25,10 @@
 // Roundings on the longest path to an entry: 1 (the scaling by w_t) + 1024 (level 0) + 1024 (level 1) + 2049 (level 2: n < 2^31 has at most
 // 2^21 segments = 2048 groups of 1024, one more because a split need not start on a group boundary) + 32 (splits) = LSL_WMOM_CHAIN = 4130:
 // every entry within LSL_WMOM_CHAIN 2^-53 sum_t |w_t x_a x_b| of the exact sum.  No atomics at all in the moments; the projection uses
-// the integer minimum / maximum of k_project (k_tica.hip.h) for its limits.
+// the integer minimum / maximum of k_project (lim_init / lim_update / lim_flush of k_stat_frag.hip.h) for its limits.
 #pragma once
 #include "common.hip.h"
+#include "k_stat_frag.hip.h"
 #include "k_tica.hip.h"
 
 #define LSL_WMOM_MIN_F 129     // below: lsl_lagged_moments / lsl_project
@@ -216,8 +217,8 @@ __global__ void __launch_bounds__(256) k_project_wide(float *y, double *wout, co
     const int tid = threadIdx.x, r = tid & 63, v = tid >> 6;
     const int jw = (d + 3) / 4, j0 = v * jw;
     const long long t0 = (long long)blockIdx.x * LSL_WPROJ_ROWS;
-    const int rows = (int)((n - t0 < LSL_WPROJ_ROWS) ? (n - t0) : LSL_WPROJ_ROWS);
-    if (tid < LSL_WPROJ_MAX_D) kmin[tid] = 0xffffffffu, kmax[tid] = 0u;
+    const int rows = tile_rows(n, t0, LSL_WPROJ_ROWS);
+    lim_init(kmin, kmax, LSL_WPROJ_MAX_D);
     double acc[16];
 #pragma unroll
     for (int k = 0; k < 16; ++k) acc[k] = 0.0;
@@ -252,17 +253,11 @@ __global__ void __launch_bounds__(256) k_project_wide(float *y, double *wout, co
             } else {
                 const float val = (float)acc[k];
                 y[((size_t)t0 + r) * d + j] = val;
-                if (keys && val == val) {
-                    const unsigned key = tica_key(val);
-                    atomicMin(&kmin[j], key), atomicMax(&kmax[j], key);
-                }
+                if (keys) lim_update(kmin, kmax, j, val);
             }
         }
     }
     if (AFFINE || !keys) return;
     __syncthreads();
-    if (tid < d && kmin[tid] != 0xffffffffu) {  // (a workgroup whose column held only NaN adds nothing)
-        atomicMin(&keys[tid], kmin[tid]);
-        atomicMax(&keys[d + tid], kmax[tid]);
-    }
+    lim_flush(keys, kmin, kmax, d);
 }

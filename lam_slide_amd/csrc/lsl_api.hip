@@ -565,34 +565,52 @@ int lsl_lagged_moments(const float *x, int32_t S, int32_t n, int32_t F, int32_t 
     return 0;
 } LSL_API_CATCH
 
+// The bracket of a projection with running limits, lsl_project's (k_project) and lsl_project_wide's (`wide`: k_project_wide): lim's floats
+// to keys, the projection, the keys back to floats.  `block`: the threads of the two one-workgroup launches, each entry's own.
+static int project_with_limits(const char *entry, bool wide, unsigned block, const float *x, int n, int F, const double *mean, const double *W, int d,
+                               float *y, float *lim, hipStream_t st) {
+    if (lim) {
+        hipLaunchKernelGGL(k_lim_keys, dim3(1), dim3(block), 0, st, lim, 2 * d);
+        if (hipError_t e = hipGetLastError()) return fail(-10, "%s (limits to keys): %s", entry, hipGetErrorString(e));
+    }
+    if (wide)
+        hipLaunchKernelGGL(k_project_wide<false>, dim3((unsigned)(((long long)n + LSL_WPROJ_ROWS - 1) / LSL_WPROJ_ROWS)), dim3(256), 0, st, y, (double *)nullptr,
+                           x, mean, W, 0.0, (unsigned *)lim, n, F, d);
+    else
+        hipLaunchKernelGGL(k_project, dim3((unsigned)(((long long)n + LSL_PROJ_ROWS - 1) / LSL_PROJ_ROWS)), dim3(256), 0, st, y, x, mean, W, (unsigned *)lim, n, F, d);
+    LSL_CHECK_LAUNCH(entry);
+    if (lim) {
+        hipLaunchKernelGGL(k_lim_floats, dim3(1), dim3(block), 0, st, lim, 2 * d);
+        if (hipError_t e = hipGetLastError()) return fail(-10, "%s (keys to limits): %s", entry, hipGetErrorString(e));
+    }
+    return 0;
+}
+
 int lsl_project(const float *x, int32_t n, int32_t F, const double *mean, const double *W, int32_t d, float *y, float *lim, void *stream) try {
     DeviceGuard dev_guard_((hipStream_t)stream);
     if (!x || !mean || !W || !y) return fail(-1, "null argument");
     if (n < 1) return fail(-3, "n = %d must be positive", n);
     if (F < 1 || F > LSL_MOM_MAX_F) return fail(-3, "F = %d outside the native form (1..%d features)", F, LSL_MOM_MAX_F);
     if (d < 1 || d > LSL_PROJ_MAX_D) return fail(-3, "d = %d outside the native form (1..%d output columns)", d, LSL_PROJ_MAX_D);
-    hipStream_t st = (hipStream_t)stream;
-    if (lim) {
-        hipLaunchKernelGGL(k_lim_keys, dim3(1), dim3(64), 0, st, lim, 2 * (int)d);
-        LSL_CHECK_LAUNCH("lsl_project (limits to keys)");
-    }
-    hipLaunchKernelGGL(k_project, dim3((unsigned)(((long long)n + LSL_PROJ_ROWS - 1) / LSL_PROJ_ROWS)), dim3(256), 0, st, y, x, mean, W, (unsigned *)lim,
-                       (int)n, (int)F, (int)d);
-    LSL_CHECK_LAUNCH("lsl_project");
-    if (lim) {
-        hipLaunchKernelGGL(k_lim_floats, dim3(1), dim3(64), 0, st, lim, 2 * (int)d);
-        LSL_CHECK_LAUNCH("lsl_project (keys to limits)");
-    }
-    return 0;
+    return project_with_limits("lsl_project", false, 64, x, (int)n, (int)F, mean, W, (int)d, y, lim, (hipStream_t)stream);
 } LSL_API_CATCH
+
+// The centres clause of lsl_assign_centers and of the k-means entry points - k centres of d coordinates stay in LDS: 0, or the argument
+// outside the native form ('d', then 'k').
+static char centres_outside(int32_t d, int32_t k) {
+    if (d < 1 || d > LSL_ASG_MAX_D) return 'd';
+    if (k < 1 || k > LSL_ASG_MAX_K || (long long)k * d > LSL_ASG_CELLS) return 'k';
+    return 0;
+}
 
 int lsl_assign_centers(const float *y, int32_t n, int32_t d, const float *centers, int32_t k, const int32_t *map, int32_t nstates, int32_t *labels,
                        int64_t *state_counts, void *stream) try {
     DeviceGuard dev_guard_((hipStream_t)stream);
     if (!y || !centers || !labels) return fail(-1, "null argument");
     if (n < 1) return fail(-3, "n = %d must be positive", n);
-    if (d < 1 || d > LSL_ASG_MAX_D) return fail(-3, "d = %d outside the native form (1..%d coordinates)", d, LSL_ASG_MAX_D);
-    if (k < 1 || k > LSL_ASG_MAX_K || (long long)k * d > LSL_ASG_CELLS)
+    const char outside = centres_outside(d, k);
+    if (outside == 'd') return fail(-3, "d = %d outside the native form (1..%d coordinates)", d, LSL_ASG_MAX_D);
+    if (outside == 'k')
         return fail(-3, "k = %d centres of d = %d outside the native form (1..%d centres, k * d <= %d: the centres stay in LDS)", k, d, LSL_ASG_MAX_K, LSL_ASG_CELLS);
     if ((map || state_counts) && (nstates < 1 || nstates > LSL_ASG_MAX_STATES))
         return fail(-3, "nstates = %d outside 1..%d (a map or a count table needs the number of states)", nstates, LSL_ASG_MAX_STATES);
@@ -668,27 +686,16 @@ int lsl_project_wide(const float *x, int32_t n, int32_t F, const double *mean, c
     if (F < LSL_WMOM_MIN_F || F > LSL_WMOM_MAX_F)
         return fail(-3, "F = %d outside the native form (%d..%d features; 1..128 are lsl_project's)", F, LSL_WMOM_MIN_F, LSL_WMOM_MAX_F);
     if (d < 1 || d > LSL_WPROJ_MAX_D) return fail(-3, "d = %d outside the native form (1..%d output columns)", d, LSL_WPROJ_MAX_D);
-    hipStream_t st = (hipStream_t)stream;
-    if (lim) {
-        hipLaunchKernelGGL(k_lim_keys, dim3(1), dim3(128), 0, st, lim, 2 * (int)d);
-        LSL_CHECK_LAUNCH("lsl_project_wide (limits to keys)");
-    }
-    hipLaunchKernelGGL(k_project_wide<false>, dim3((unsigned)(((long long)n + LSL_WPROJ_ROWS - 1) / LSL_WPROJ_ROWS)), dim3(256), 0, st, y, (double *)nullptr, x,
-                       mean, W, 0.0, (unsigned *)lim, (int)n, (int)F, (int)d);
-    LSL_CHECK_LAUNCH("lsl_project_wide");
-    if (lim) {
-        hipLaunchKernelGGL(k_lim_floats, dim3(1), dim3(128), 0, st, lim, 2 * (int)d);
-        LSL_CHECK_LAUNCH("lsl_project_wide (keys to limits)");
-    }
-    return 0;
+    return project_with_limits("lsl_project_wide", true, 128, x, (int)n, (int)F, mean, W, (int)d, y, lim, (hipStream_t)stream);
 } LSL_API_CATCH
 
 // ---- k-means fitting: one Lloyd step of S independent problems, the reverse lookup of post_process (k_kmeans.hip.h) ----
 static const char *kmeans_shape_error(int32_t S, int32_t n, int32_t d, int32_t k) {
-    if (S < 1 || S > 65535) return "S outside 1..65535 series";
+    if (S < 1 || S > LSL_KM_MAX_S) return "S outside 1..65535 series";
     if (n < 1) return "n must be positive";
-    if (d < 1 || d > LSL_KM_MAX_D) return "d outside the native form (1..64 coordinates)";
-    if (k < 1 || k > LSL_KM_MAX_K || (long long)k * d > LSL_KM_CELLS) return "k outside the native form (1..1024 centres, k * d <= 8192: the centres stay in LDS)";
+    const char outside = centres_outside(d, k);
+    if (outside == 'd') return "d outside the native form (1..64 coordinates)";
+    if (outside == 'k') return "k outside the native form (1..1024 centres, k * d <= 8192: the centres stay in LDS)";
     return nullptr;
 }
 

@@ -31,9 +31,9 @@ from torch import Tensor
 
 from . import _lib
 
-MAX_K, MAX_D, CELLS = 1024, 64, 8192  # LSL_KM_MAX_K, LSL_KM_MAX_D, LSL_KM_CELLS (csrc/k_kmeans.hip.h): the centres of a series stay in LDS
-SEG = 2048  # LSL_KM_SEG: segment g holds the rows [g * SEG, (g + 1) * SEG)
-MAX_S = 65535  # series of one library call; more are chunked
+MAX_K, MAX_D, CELLS = _lib.ASG_MAX_K, _lib.ASG_MAX_D, _lib.ASG_CELLS  # the centres of a series stay in LDS: the limits of assign_centers
+SEG = _lib.KM_SEG  # segment g holds the rows [g * SEG, (g + 1) * SEG)
+MAX_S = _lib.KM_MAX_S  # series of one library call; more are chunked
 
 last_path: Dict[str, str] = {}
 

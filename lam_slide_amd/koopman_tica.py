@@ -9,7 +9,7 @@ a tetrapeptide, past the F <= 128 of ``tica.lagged_moments`` / ``TicaModel.trans
   weighted_covariances, model_from_moments
                       <- the reversible estimator's mean, C0 and C_lag from weighted moments; the model from them
   run_tica            <- ``TICA(lagtime, dim).fit_fetch((x[:-lag], x[lag:], weights))``: a :class:`WideTicaModel`
-  WideTicaModel       <- ``TicaModel`` whose ``transform`` takes 129 <= F <= 2048 and up to 64 output columns on the device
+  WideTicaModel       <- ``TicaModel`` itself: its ``transform`` takes 129 <= F <= 2048 and up to 64 output columns on the device
                          (``lsl_project_wide``); ``tica_histograms`` / ``tica_jsd`` work with it unchanged
 
 The estimator, as mathematics (m = n - lag rows x_t, their partners y_t = x_{t+lag}).
@@ -51,35 +51,13 @@ from .tica import TicaModel, solve_tica
 from .torsion_stats import fused_applies
 
 last_path: Dict[str, str] = {}
-# LSL_WMOM_MIN_F, LSL_WMOM_MAX_F, LSL_WPROJ_MAX_D, LSL_WMOM_SEG, LSL_WMOM_CHAIN (csrc/k_wtica.hip.h): the native form of lsl_weighted_moments /
-# lsl_project_wide, the rows of a segment, the roundings on the longest path to one entry of the moments
-MIN_F, MAX_F, PROJ_MAX_D, WMOM_SEG, WMOM_CHAIN = 129, 2048, 64, 1024, 4130
+# the native form of lsl_weighted_moments / lsl_project_wide, the rows of a segment, the roundings on the longest path to one entry of the moments
+MIN_F, MAX_F, PROJ_MAX_D, WMOM_SEG, WMOM_CHAIN = _lib.WMOM_MIN_F, _lib.WMOM_MAX_F, _lib.WPROJ_MAX_D, _lib.WMOM_SEG, _lib.WMOM_CHAIN
 
 
-def _to_host(t: Tensor) -> np.ndarray:
-    """A device tensor as a numpy array.  One of the documented synchronising copies of a fit: allowed under
-    ``torch.cuda.set_sync_debug_mode("error")`` by switching to "default" around this copy alone."""
-    if not t.is_cuda:
-        return t.numpy()
-    mode = torch.cuda.get_sync_debug_mode()
-    torch.cuda.set_sync_debug_mode("default")
-    try:
-        return t.cpu().numpy()
-    finally:
-        torch.cuda.set_sync_debug_mode(mode)
-
-
-def _to_device(a: np.ndarray, dev) -> Tensor:
-    """A host array on ``dev``: the way back of :func:`_to_host`, with the same exception."""
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    if torch.device(dev).type != "cuda":
-        return t
-    mode = torch.cuda.get_sync_debug_mode()
-    torch.cuda.set_sync_debug_mode("default")
-    try:
-        return t.to(dev)
-    finally:
-        torch.cuda.set_sync_debug_mode(mode)
+_to_host, _to_device = _lib.to_host, _lib.to_device  # the documented synchronising copies of a fit, exempt from the sync debug mode
+TicaModel.path_logs.append(last_path)  # (``last_path["transform"]`` is written here as in ``tica``)
+WideTicaModel = TicaModel  # one class: ``transform`` chooses lsl_project or lsl_project_wide from (F, dim)
 
 
 # ---- a. weighted lagged moments ----
@@ -227,29 +205,6 @@ def weighted_covariances(x: Tensor, lag: int, weights: Optional[Tensor] = None) 
     out = covariances_from_moments(weighted_moments(x, lag, weights))
     last_path["weighted_covariances"] = last_path["weighted_moments"]
     return out
-
-
-class WideTicaModel(TicaModel):
-    """``TicaModel`` for wide tables: ``transform`` runs ``lsl_project_wide`` for ``MIN_F <= F <= MAX_F`` and ``dim <= PROJ_MAX_D`` on the
-    GPU and the parent's code otherwise.  Everything else - ``from_arrays``, ``W``, the kinetic map - is the parent's."""
-
-    def transform(self, x: Tensor, lim: Optional[Tensor] = None) -> Tensor:
-        F, d = self.mean.size, self.dim
-        if x.device not in self._on:  # (the parent's cache of mean and W on a device, filled through the documented upload)
-            self._on[x.device] = (_to_device(self.mean, x.device), _to_device(self.W, x.device))
-        rows = x.numel() // F if x.dim() in (2, 3) and x.shape[-1] == F else 0
-        if not (rows > 0 and fused_applies(x) and MIN_F <= F <= MAX_F and d <= PROJ_MAX_D and rows < 2 ** 31):
-            y = super().transform(x, lim)
-            last_path["transform"] = _tica.last_path["transform"]
-            return y
-        if lim is not None and (tuple(lim.shape) != (2, d) or lim.dtype != torch.float32 or lim.device != x.device or not lim.is_contiguous()):
-            raise ValueError(f"lim must be a contiguous float32 [2, {d}] on {x.device}")
-        mean, W = self._on[x.device]
-        xc, dev = x.detach().contiguous(), x.device
-        y = torch.empty(*x.shape[:-1], d, dtype=torch.float32, device=dev)
-        _lib.call(dev, "lsl_project_wide", xc.data_ptr(), rows, F, mean.data_ptr(), W.data_ptr(), d, y.data_ptr(), None if lim is None else lim.data_ptr())
-        last_path["transform"] = _tica.last_path["transform"] = "fused"
-        return y
 
 
 def model_from_moments(moments, lag: Optional[int] = None, dim: int = 40, epsilon: float = 1e-6, kinetic_map: bool = True) -> WideTicaModel:

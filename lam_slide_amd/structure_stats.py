@@ -37,11 +37,10 @@ from torch import Tensor
 from . import _lib
 from . import torsion_stats as _ts
 from .peptide_loss import residue_tables
-from .tica import _PAIR01, _pair01_on
 from .torsion_stats import _aatype_list, _index_table, fused_applies
 
 last_path: Dict[str, str] = {}
-MAX_P, MAX_R = 65536, 146  # LSL_PAIR_MAX_P, LSL_CA_MAX_R (csrc/k_structstat.hip.h): pairs of one call of lsl_pair_distances, selected atoms of a frame
+MAX_P, MAX_R = _lib.PAIR_MAX_P, _lib.CA_MAX_R  # pairs of one call of lsl_pair_distances, selected atoms of a frame
 PSEUDO_COUNT = 1e-6  # discretize_features' pseudo_count
 # residue_constants.atom_types: the names of the 37 atom37 slots (the first letter is the element atom14_to_mdtraj gives the atom)
 ATOM37_NAMES = ("N", "CA", "C", "CB", "O", "CG", "CG1", "CG2", "OG", "OG1", "SG", "CD", "CD1", "CD2", "ND1", "ND2", "OD1", "OD2", "SD", "CE", "CE1",
@@ -127,8 +126,8 @@ class StructureTables:
         if device not in self._on:
             names = ("ca", "ca_pairs", "quads", "rama", "tica_pairs")
             self._on[device] = {k: torch.from_numpy(getattr(self, k)).to(device) for k in names}
-            if device.type == "cuda" and device not in _pair01_on:
-                _pair01_on[device] = torch.from_numpy(_PAIR01).to(device)
+            if device.type == "cuda":
+                _ts._pair01_on(device)  # (joint_density_js' pair table: with the tables on the device, nothing is uploaded later)
         return self._on[device]
 
 
@@ -382,13 +381,10 @@ def _joint_counts(a: Tensor, b: Tensor, ea: Tensor, eb: Tensor) -> Tuple[Tensor,
     x = torch.stack([a.detach(), b.detach()], dim=1).contiguous()
     n, cells, dev = int(x.shape[0]), int(ea.numel()) - 1, x.device
     if fused_applies(x) and fused_applies(ea, eb, dtype=torch.float64) and ea.device == dev and cells <= _lib.HIST2_MAX_BINS and n < 2 ** 31:
-        if dev not in _pair01_on:
-            _pair01_on[dev] = torch.from_numpy(_PAIR01).to(dev)
         eac, ebc = ea.contiguous(), eb.contiguous()
         own = torch.zeros(2, cells, dtype=torch.int64, device=dev)  # (the 1-D counts the call also makes: not used)
         counts2 = torch.zeros(cells, cells, dtype=torch.int64, device=dev)
-        _lib.call(dev, "lsl_histogram", x.data_ptr(), 1, n, 2, eac.data_ptr(), cells, own.data_ptr(), _pair01_on[dev].data_ptr(), _PAIR01.ctypes.data, 1,
-                  eac.data_ptr(), ebc.data_ptr(), cells, counts2.data_ptr())
+        _ts._hist_pair01(x, eac, own, eac, ebc, counts2)
         return counts2, "fused"
     v = x.cpu().double().numpy()
     c2 = np.histogram2d(v[:, 0], v[:, 1], bins=(ea.cpu().numpy(), eb.cpu().numpy()))[0]

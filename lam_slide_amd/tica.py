@@ -40,8 +40,6 @@ from . import torsion_stats as _ts
 from .torsion_stats import fused_applies, js_distance, lagged_products
 
 last_path: Dict[str, str] = {}
-_PAIR01 = np.array([[0, 1]], dtype=np.int32)
-_pair01_on: dict = {}
 
 
 # ---- features ----
@@ -135,7 +133,9 @@ def tica_dimension(eigenvalues, var_cutoff: float = 0.95) -> int:
 
 class TicaModel:
     """``mean`` [F], ``eigenvectors`` R [F, r], ``eigenvalues`` [r] (numpy float64, on the host), ``dim``, ``kinetic_map``, ``lag``;
-    ``W`` [F, dim] = R[:, :dim], times diag(eigenvalues[:dim]) under the kinetic map.  ``transform`` uploads mean and W once per device."""
+    ``W`` [F, dim] = R[:, :dim], times diag(eigenvalues[:dim]) under the kinetic map.  ``transform`` uploads mean and W once per device
+    (``_lib.to_device``: the upload is exempt from ``torch.cuda.set_sync_debug_mode``)."""
+    path_logs = [last_path]  # every module's ``last_path`` that records "transform"
 
     def __init__(self, mean, eigenvectors, eigenvalues, dim: int, kinetic_map: bool = True, lag: Optional[int] = None) -> None:
         self.mean = np.ascontiguousarray(mean, dtype=np.float64).reshape(-1)
@@ -172,13 +172,14 @@ class TicaModel:
 
     def _tensors(self, dev) -> Tuple[Tensor, Tensor]:
         if dev not in self._on:
-            self._on[dev] = (torch.from_numpy(self.mean).to(dev), torch.from_numpy(self.W).to(dev))
+            self._on[dev] = (_lib.to_device(self.mean, dev), _lib.to_device(self.W, dev))
         return self._on[dev]
 
     def transform(self, x: Tensor, lim: Optional[Tensor] = None) -> Tensor:
         """x [n, F] or [S, n, F] -> y float32 [(S,) n, dim], ``y[t, j] = float32(sum_f (x[t, f] - mean[f]) W[f, j])`` (subtraction and sum in
-        float64, one rounding).  ``lim`` float32 [2, dim] on x's device is updated in place: row 0 the minimum of itself and every y[:, j],
-        row 1 the maximum, NaN values of y ignored - start it at (+inf, -inf)."""
+        float64, one rounding; both library entries run the same fused float64 chain over f ascending).  ``lim`` float32 [2, dim] on x's
+        device is updated in place: row 0 the minimum of itself and every y[:, j], row 1 the maximum, NaN values of y ignored - start it
+        at (+inf, -inf)."""
         F, d = self.mean.size, self.dim
         if x.dim() not in (2, 3) or x.shape[-1] != F:
             raise ValueError(f"expected x [n, {F}] or [S, n, {F}], got {tuple(x.shape)}")
@@ -187,12 +188,18 @@ class TicaModel:
         if lim is not None and (tuple(lim.shape) != (2, d) or lim.dtype != torch.float32 or lim.device != x.device or not lim.is_contiguous()):
             raise ValueError(f"lim must be a contiguous float32 [2, {d}] on {x.device}")
         mean, W = self._tensors(x.device)
-        rows = x.numel() // F
-        if fused_applies(x) and F <= _lib.MOM_MAX_F and d <= _lib.PROJ_MAX_D and rows < 2 ** 31:
+        entry = None  # the library entry, from (F, dim): lsl_project's native form, lsl_project_wide's, or the torch restatement
+        if fused_applies(x) and x.numel() // F < 2 ** 31:
+            if F <= _lib.MOM_MAX_F and d <= _lib.PROJ_MAX_D:
+                entry = "lsl_project"
+            elif _lib.WMOM_MIN_F <= F <= _lib.WMOM_MAX_F and d <= _lib.WPROJ_MAX_D:
+                entry = "lsl_project_wide"
+        for log in self.path_logs:
+            log["transform"] = "fused" if entry else "torch"
+        if entry:
             xc, dev = x.detach().contiguous(), x.device
             y = torch.empty(*x.shape[:-1], d, dtype=torch.float32, device=dev)
-            _lib.call(dev, "lsl_project", xc.data_ptr(), rows, F, mean.data_ptr(), W.data_ptr(), d, y.data_ptr(), None if lim is None else lim.data_ptr())
-            last_path["transform"] = "fused"
+            _lib.call(dev, entry, xc.data_ptr(), x.numel() // F, F, mean.data_ptr(), W.data_ptr(), d, y.data_ptr(), None if lim is None else lim.data_ptr())
             return y
         y = ((x.detach().double() - mean) @ W).float()
         if lim is not None:
@@ -200,7 +207,6 @@ class TicaModel:
             inf = torch.full((), float("inf"), dtype=torch.float32, device=y.device)
             lim[0].copy_(torch.minimum(lim[0], torch.where(nan, inf, flat).amin(dim=0)))
             lim[1].copy_(torch.maximum(lim[1], torch.where(nan, -inf, flat).amax(dim=0)))
-        last_path["transform"] = "torch"
         return y
 
 
@@ -248,15 +254,11 @@ def _counts(y: Tensor, edges: Tensor, ea: Optional[Tensor], eb: Optional[Tensor]
     counts = torch.zeros(1, Q, bins, dtype=torch.int64, device=dev)
     counts2 = torch.zeros(1, 1, bins2, bins2, dtype=torch.int64, device=dev) if two else None
     if fused_applies(x) and edges.is_cuda and bins <= _lib.HIST_MAX_BINS and bins2 <= _lib.HIST2_MAX_BINS and n < 2 ** 31:
-        if two and dev not in _pair01_on:
-            _pair01_on[dev] = torch.from_numpy(_PAIR01).to(dev)
-        _lib.call(dev, "lsl_histogram", x.data_ptr(), 1, n, Q, edges.data_ptr(), bins, counts.data_ptr(),
-                  _pair01_on[dev].data_ptr() if two else None, _PAIR01.ctypes.data if two else None, 1 if two else 0,
-                  ea.data_ptr() if two else None, eb.data_ptr() if two else None, bins2, counts2.data_ptr() if two else None)
+        _ts._hist_pair01(x[0], edges, counts, ea, eb, counts2)
         path = "fused"
     else:
         host = lambda t: None if t is None else t.cpu().numpy()  # noqa: E731
-        c, c2 = _ts._hist_numpy(x, host(edges), _PAIR01 if two else None, host(ea), host(eb))
+        c, c2 = _ts._hist_numpy(x, host(edges), _ts._PAIR01 if two else None, host(ea), host(eb))
         counts += torch.from_numpy(c).to(dev)
         if two:
             counts2 += torch.from_numpy(c2).to(dev)

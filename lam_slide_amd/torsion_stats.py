@@ -192,6 +192,28 @@ def _hist_add(x: Tensor, edges, pairs, ea, eb, counts: Tensor, counts2: Optional
     return "torch"
 
 
+_PAIR01 = np.array([[0, 1]], dtype=np.int32)
+_pair01_dev: dict = {}
+
+
+def _pair01_on(dev) -> Tensor:
+    """The pair table [[0, 1]] on ``dev``: uploaded once per device (a caller that must not upload later asks for it ahead)."""
+    if dev not in _pair01_dev:
+        _pair01_dev[dev] = torch.from_numpy(_PAIR01).to(dev)
+    return _pair01_dev[dev]
+
+
+def _hist_pair01(x: Tensor, edges: Tensor, counts: Tensor, ea: Optional[Tensor] = None, eb: Optional[Tensor] = None,
+                 counts2: Optional[Tensor] = None) -> None:
+    """``lsl_histogram`` of one series with the one pair (0, 1), every table already on the device: x float32 [n, Q] contiguous, ``counts``
+    int64 [Q, bins] += np.histogram of each column on ``edges`` (float64 [bins + 1]); with ``ea`` / ``eb`` (float64 [bins2 + 1]) also
+    ``counts2`` int64 [bins2, bins2] += np.histogram2d(x[:, 0], x[:, 1], bins=(ea, eb))[0].  The caller has checked the native form."""
+    two, dev = ea is not None, x.device
+    _lib.call(dev, "lsl_histogram", x.data_ptr(), 1, int(x.shape[0]), int(x.shape[1]), edges.data_ptr(), edges.numel() - 1, counts.data_ptr(),
+              _pair01_on(dev).data_ptr() if two else None, _PAIR01.ctypes.data if two else None, 1 if two else 0,
+              ea.data_ptr() if two else None, eb.data_ptr() if two else None, ea.numel() - 1 if two else 0, counts2.data_ptr() if two else None)
+
+
 def _hist_setup(Q: int, bins, pairs, bins2, range, range2):
     edges = _edges(range, bins)
     if pairs is None:

@@ -54,7 +54,10 @@ def test_every_limit_the_binding_mirrors_equals_its_macro():
                "HIST_MAX_BINS": "LSL_HIST_MAX_BINS", "HIST2_MAX_BINS": "LSL_HIST2_MAX_BINS", "LAG_CHUNK": "LSL_LAG_CHUNK",
                "LAG_MAX_LAGS": "LSL_LAG_MAX_PART", "LAG_MAX_ROWS": "LSL_LAG_MAX_ROWS", "MOM_SEG": "LSL_MOM_SEG", "MOM_CHAIN": "LSL_MOM_SEG",
                "MOM_MAX_F": "LSL_MOM_MAX_F", "PROJ_MAX_D": "LSL_PROJ_MAX_D", "ASG_MAX_K": "LSL_ASG_MAX_K", "ASG_MAX_D": "LSL_ASG_MAX_D",
-               "ASG_CELLS": "LSL_ASG_CELLS", "ASG_MAX_STATES": "LSL_ASG_MAX_STATES", "TR_MAX_STATES": "LSL_TR_MAX_STATES"}
+               "ASG_CELLS": "LSL_ASG_CELLS", "ASG_MAX_STATES": "LSL_ASG_MAX_STATES", "TR_MAX_STATES": "LSL_TR_MAX_STATES",
+               "KM_SEG": "LSL_KM_SEG", "KM_MAX_S": "LSL_KM_MAX_S", "WMOM_MIN_F": "LSL_WMOM_MIN_F", "WMOM_MAX_F": "LSL_WMOM_MAX_F",
+               "WPROJ_MAX_D": "LSL_WPROJ_MAX_D", "WMOM_SEG": "LSL_WMOM_SEG", "WMOM_CHAIN": "LSL_WMOM_CHAIN", "PAIR_MAX_P": "LSL_PAIR_MAX_P",
+               "CA_MAX_R": "LSL_CA_MAX_R"}
     # every upper-case integer of the binding is in the table, except the ABI version (checked above) and the two step flags
     ints = {k for k, v in vars(_lib).items() if k.isupper() and type(v) is int}
     assert ints - {"ABI_VERSION", "STEP_NO_NETWORK", "STEP_SAVE"} == set(mirrors), ints ^ set(mirrors)

@@ -28,13 +28,18 @@ def test_library_exports_header_and_limits():
         assert re.fullmatch(r"lsl_[a-z_]+", s) and getattr(lib, s).argtypes is not None
     assert lib.lsl_version() == 6 and _lib.ABI_VERSION == 6 and "lsl_kmeans_workspace_bytes, lsl_kmeans_step, lsl_kmeans_nearest_rows added" in header
     src = open(os.path.join(ROOT, "lam_slide_amd", "csrc", "k_kmeans.hip.h")).read()
-    macro = lambda name: int(re.search(r"#define " + name + r" (\d+)", src).group(1))  # noqa: E731
-    assert macro("LSL_KM_MAX_K") == kmeans.MAX_K == 1024 and macro("LSL_KM_MAX_D") == kmeans.MAX_D == 64
-    assert macro("LSL_KM_CELLS") == kmeans.CELLS == 8192 and macro("LSL_KM_SEG") == kmeans.SEG == orc.SEG
-    assert macro("LSL_KM_MAX_Q") * 256 == macro("LSL_KM_CELLS")  # the fp64 register accumulators of a thread
+    asg = open(os.path.join(ROOT, "lam_slide_amd", "csrc", "k_tica.hip.h")).read()
+    macro = lambda name, text=src: int(re.search(r"#define " + name + r" (\d+)", text).group(1))  # noqa: E731
+    # the centres' limits are k_assign's: k_kmeans.hip.h names them and k_tica.hip.h alone holds the numbers
+    for km, own in (("LSL_KM_MAX_K", "LSL_ASG_MAX_K"), ("LSL_KM_MAX_D", "LSL_ASG_MAX_D"), ("LSL_KM_CELLS", "LSL_ASG_CELLS"), ("LSL_KM_TILE", "LSL_ASG_TILE")):
+        assert re.search(r"^#define " + km + " " + own + r"\b", src, re.M), km
+    assert macro("LSL_ASG_MAX_K", asg) == kmeans.MAX_K == 1024 and macro("LSL_ASG_MAX_D", asg) == kmeans.MAX_D == 64
+    assert macro("LSL_ASG_CELLS", asg) == kmeans.CELLS == 8192 and macro("LSL_KM_SEG") == kmeans.SEG == orc.SEG
+    assert re.search(r"^#define LSL_KM_MAX_Q \(LSL_KM_CELLS / 256\)", src, re.M) and kmeans.CELLS // 256 == 32  # the fp64 register accumulators of a thread
     assert kmeans.segments(1) == 1 and kmeans.segments(kmeans.SEG) == 1 and kmeans.segments(kmeans.SEG + 1) == 2
-    # the limits live in the module, not as upper-case integers of the binding
-    assert not [k for k, v in vars(_lib).items() if k.isupper() and type(v) is int and k.startswith("KM")]
+    # the limits live in the binding beside the others; the module's names are aliases of them
+    assert (kmeans.MAX_K, kmeans.MAX_D, kmeans.CELLS, kmeans.SEG, kmeans.MAX_S) == (_lib.ASG_MAX_K, _lib.ASG_MAX_D, _lib.ASG_CELLS, _lib.KM_SEG, _lib.KM_MAX_S)
+    assert macro("LSL_KM_MAX_S") == _lib.KM_MAX_S == 65535
     assert not re.search(r"atomic\w*\([^;]*(float|double)", src)  # integer atomics only
 
 
