@@ -35,6 +35,7 @@ WMOM_MIN_F, WMOM_MAX_F, WPROJ_MAX_D = 129, 2048, 64  # the native form of lsl_we
 WMOM_SEG, WMOM_CHAIN = 1024, 4130  # lsl_weighted_moments: the rows of a segment, the roundings on the longest path to one entry
 PAIR_MAX_P, CA_MAX_R = 65536, 146  # lsl_pair_distances / lsl_ca_frame_stats (csrc/k_structstat.hip.h): pairs of one call, selected atoms of a frame
 SI_SLAB = 4096  # LSL_SI_SLAB: elements of one trajectory per partial sum of lsl_si_reduce
+CLS_MAX_K, CLS_IGNORE = 128, -100  # lsl_class_loss_sums (csrc/k_classloss.hip.h): the classes of one call, the target of an ignored row
 
 EXPORTED = (
     "lsl_version", "lsl_build_info", "lsl_last_error", "lsl_model_create", "lsl_model_set_weights", "lsl_model_destroy",
@@ -329,6 +330,44 @@ def device_form(*tensors, dtype=torch.float32, same_device: bool = True) -> bool
     tensors to be on the same device" instead."""
     dev, grad = tensors[0].device, torch.is_grad_enabled()
     return all(t.is_cuda and t.dtype == dtype and (t.device == dev or not same_device) and not (grad and t.requires_grad) for t in tensors)
+
+
+def flat(x, lead: tuple, trailing: tuple, dtype, dev, shape_error, device_error) -> "torch.Tensor":
+    """One input of a loss entry point made canonical: ``ValueError(shape_error())`` unless x is [*lead, *trailing],
+    ``RuntimeError(device_error())`` unless it is on ``dev``; then detached, the leading axes flattened into one, cast to ``dtype``
+    (uint8: nonzero -> 1) and contiguous - these inputs come out of rearranges and slices, and the library reads dense rows."""
+    if tuple(x.shape) != tuple(lead) + tuple(trailing):
+        raise ValueError(shape_error())
+    if x.device != dev:
+        raise RuntimeError(device_error())
+    x = x.detach().reshape(-1, *trailing)
+    return (x != 0 if dtype == torch.uint8 else x).to(dtype).contiguous()
+
+
+def loss_from_sums(fn: str, entry: str, widths: tuple, n_out: int, sums, required: tuple, optional: tuple, compute, needs: str,
+                   takes: Optional[str] = None) -> "torch.Tensor":
+    """The ``sums=`` bracket of geom_losses / class_losses / peptide_losses: either the tensors (none of ``required`` is ``None``; then
+    ``compute()`` makes the sums) or ``sums=``, never both; the per-frame sums - one float32 [F, w] table per width, all on one GPU -
+    finished by one call of ``entry``.  Returns its float32 [n_out] output."""
+    if sums is None:
+        if any(x is None for x in required):
+            raise TypeError(f"{fn} needs {needs} or sums=")
+        sums = compute()
+    elif any(x is not None for x in required + optional):
+        raise TypeError(f"{fn} takes {takes or needs} or sums=, not both")
+    tables = sums if isinstance(sums, (tuple, list)) else (sums,)
+    ok = len(tables) == len(widths) and all(t.dim() == 2 and t.shape[1] == w and t.shape[0] == tables[0].shape[0] > 0 and t.dtype == torch.float32
+                                            and t.device == tables[0].device for t, w in zip(tables, widths))
+    if not ok:
+        one = len(widths) == 1
+        raise ValueError(f"sums must be float32 {'' if one else '('}{', '.join(f'[F, {w}]' for w in widths)}{'' if one else ')'} with F > 0"
+                         f"{'' if one else ' on one device'}, got " + " and ".join(f"{t.dtype} {tuple(t.shape)}" for t in tables))
+    if not tables[0].is_cuda:
+        raise RuntimeError(f"{fn} runs on the GPU (HIP kernel); there is no CPU fallback")
+    tables = [t.contiguous() for t in tables]
+    out = torch.empty(n_out, dtype=torch.float32, device=tables[0].device)
+    call(out.device, entry, *(t.data_ptr() for t in tables), tables[0].shape[0], out.data_ptr())
+    return out
 
 
 class Scratch:

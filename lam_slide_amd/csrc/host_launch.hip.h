@@ -584,38 +584,50 @@ void launch_dense_small(float *out, const float *in, const float *W, const float
         launch_dense<PRE, POST>(out, in, W, bias, add, rows, I, O, add_stride, st, false, add_mod);
 }
 
-// the five sums of every frame (k_geomloss.hip.h): a wave per frame up to 64 entities, the whole workgroup above
-template <int D, int TEAM>
-void launch_geom_frame(float *sums, const float *pred, const float *target, const unsigned char *mask, int F, int A, hipStream_t st) {
-    constexpr int FPB = 256 / TEAM;
-    auto kern = k_geom_loss_frame<D, TEAM>;
-    if (TEAM == 256) LSL_ALLOW_LDS(kern, geom_team_bytes(LSL_GEOM_MAX_A, D));  // (above 64 KiB at D = 4)
-    hipLaunchKernelGGL(kern, dim3((unsigned)(((long long)F + FPB - 1) / FPB)), dim3(256), FPB * geom_team_bytes(A, D), st, sums, pred, target, mask, F, A);
-}
-template <int D>
-void launch_geom_frame_d(float *sums, const float *pred, const float *target, const unsigned char *mask, int F, int A, hipStream_t st) {
-    if (A <= 64)
-        launch_geom_frame<D, 64>(sums, pred, target, mask, F, A, st);
-    else
-        launch_geom_frame<D, 256>(sums, pred, target, mask, F, A, st);
+// ---- the losses: the team forms of k_loss_frag.hip.h, one dispatcher for D = 1..4, one launch of the quotient finals ----
+// f(std::integral_constant<int, D>) for the D of the call (checked by the caller: 1..4)
+template <class Fn>
+void dispatch_d(int D, Fn f) {
+    switch (D) {
+        case 1: f(std::integral_constant<int, 1>()); break;
+        case 2: f(std::integral_constant<int, 2>()); break;
+        case 3: f(std::integral_constant<int, 3>()); break;
+        default: f(std::integral_constant<int, 4>()); break;
+    }
 }
 
-// the four sums of every peptide frame (k_peptloss.hip.h): a wave per frame up to 64 atoms (R <= 4), the whole workgroup above
+// the five sums of every frame (k_geomloss.hip.h)
+template <int D, int TEAM>
+void launch_geom_frame(float *sums, const float *pred, const float *target, const unsigned char *mask, int F, int A, hipStream_t st) {
+    auto kern = k_geom_loss_frame<D, TEAM>;
+    if (TEAM == 256) LSL_ALLOW_LDS(kern, geom_team_bytes(LSL_GEOM_MAX_A, D));  // (above 64 KiB at D = 4)
+    hipLaunchKernelGGL(kern, dim3(loss_team_grid<TEAM>(F)), dim3(256), (256 / TEAM) * geom_team_bytes(A, D), st, sums, pred, target, mask, F, A);
+}
+
+// the four sums of every peptide frame (k_peptloss.hip.h)
 template <int TEAM>
 void launch_peptide_frame(float *sums, const float *pred, const float *target_frame, const unsigned char *atom14_mask, const float *tors_target,
                           const unsigned char *tors_mask, const long long *aatype, const signed char *restab, int F, int R, int kind, hipStream_t st) {
-    constexpr int FPB = 256 / TEAM;  // (at most 4 * pept_team_bytes(4) or pept_team_bytes(146) = 24.7 KB of LDS: below the 64 KiB default)
-    hipLaunchKernelGGL(k_peptide_loss_frame<TEAM>, dim3((unsigned)(((long long)F + FPB - 1) / FPB)), dim3(256), FPB * pept_team_bytes(R), st, sums, pred,
+    // (at most 4 * pept_team_bytes(4) or pept_team_bytes(146) = 24.7 KB of LDS: below the 64 KiB default)
+    hipLaunchKernelGGL(k_peptide_loss_frame<TEAM>, dim3(loss_team_grid<TEAM>(F)), dim3(256), (256 / TEAM) * pept_team_bytes(R), st, sums, pred,
                        target_frame, atom14_mask, tors_target, tors_mask, aatype, restab, F, R, kind);
 }
 
-// per-agent and per-trajectory displacement errors (k_disperr.hip.h): a wave per sample trajectory up to 64 agents, the whole workgroup above
-template <int D>
+// per-agent and per-trajectory displacement errors (k_disperr.hip.h)
+template <int D, int TEAM>
 void launch_disp_rows(float *rows, float *traj, const float *pred, const float *target, long long units, int B, int Tp, int t0p, int Tt, int t0t,
                       int Tf, int A, hipStream_t st) {
-    if (A <= 64)
-        hipLaunchKernelGGL((k_disp_rows<D, 64>), dim3((unsigned)((units + 3) / 4)), dim3(256), 0, st, rows, traj, pred, target, units, B, Tp, t0p, Tt,
-                           t0t, Tf, A);
-    else
-        hipLaunchKernelGGL((k_disp_rows<D, 256>), dim3((unsigned)units), dim3(256), 0, st, rows, traj, pred, target, units, B, Tp, t0p, Tt, t0t, Tf, A);
+    hipLaunchKernelGGL((k_disp_rows<D, TEAM>), dim3(loss_team_grid<TEAM>(units)), dim3(256), 0, st, rows, traj, pred, target, units, B, Tp, t0p, Tt,
+                       t0t, Tf, A);
+}
+
+// lsl_geom_loss_final / lsl_peptide_loss_final / lsl_class_loss_final: out[0 .. NOUT - 1] from a [F, WA] and, WB > 0, b [F, WB]
+template <int WA, int WB, int NOUT>
+int loss_final(const char *name, const float *a, const float *b, int F, float *out, unsigned long long quots, void *stream) {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!a || (WB > 0 && !b) || !out) return fail(-1, "null argument");
+    if (F <= 0) return fail(-3, "F must be positive");
+    hipLaunchKernelGGL((k_loss_final<WA, WB, NOUT>), dim3(1), dim3(64), 0, (hipStream_t)stream, out, a, b, F, quots);
+    LSL_CHECK_LAUNCH(name);
+    return 0;
 }

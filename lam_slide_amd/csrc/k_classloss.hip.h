@@ -9,7 +9,7 @@
 //      loss = sum_f s_ce / sum_f n,     s_ce = sum of loss over the counted rows (mask nonzero or no mask, and target != -100),
 //      n = rows with a nonzero mask (MaskedCrossEntropyLoss divides by mask.sum()), or without a mask rows with target != -100 (the mean of
 //      nn.CrossEntropyLoss over the non-ignored rows)
-// k_class_loss_frame writes (s_ce, n) of every frame, k_class_loss_final adds the two columns and divides.  With a confusion matrix [K, K]
+// k_class_loss_frame writes (s_ce, n) of every frame, k_loss_final (CLASS_QUOTS) adds the two columns and divides.  With a confusion matrix [K, K]
 // (i64, zeroed by the caller) every counted row with a target in range and no NaN logit adds one to cell [target, argmax] (lowest index
 // among equal maxima) by an integer atomic: exact in any order, so several calls accumulate an epoch.
 //
@@ -25,11 +25,11 @@
 // limit - so the narrow heads keep many waves per CU; no scratch: the row is re-read from LDS in the second pass instead of being kept in
 // K registers indexed at run time.
 //
-// Determinism: no float atomics.  Lane l owns rows l, l + 64, ... of the frame and adds their losses in ascending order, the wave sums by DPP:
-// every order is fixed by (A, K) alone, a frame's two floats have the same bits whatever F, the grid, or the frame's place in the batch.  The
-// final kernel adds the frames in index order in fp64 (lane l adds frames l, l + 64, ...; lane 0 adds the lanes in lane order), one rounding.
+// Orders (k_loss_frag.hip.h, without its teams: always one wave per frame): lane l owns rows l, l + 64, ... of the frame and adds their
+// losses in ascending order, the wave sums by DPP.  Every order is fixed by (A, K) alone.
 #pragma once
 #include "common.hip.h"
+#include "k_loss_frag.hip.h"
 
 #define LSL_CLS_MAX_K 128
 #define LSL_CLS_IGNORE (-100)
@@ -93,18 +93,5 @@ __global__ void __launch_bounds__(64) k_class_loss_frame(float *sums, unsigned l
     }
 }
 
-// out[0] = sum_f s_ce / sum_f n from the [F, 2] sums: columns added over frames in index order in fp64, the quotient rounded once; a batch
-// without a counted row gives 0 / 0 = NaN like the reference.  One workgroup of 64 threads.
-__global__ void __launch_bounds__(64) k_class_loss_final(float *out, const float *sums, int F) {
-    __shared__ double lane_sum[2][64];
-    double s0 = 0.0, s1 = 0.0;
-    for (int f = threadIdx.x; f < F; f += 64) s0 += (double)sums[(size_t)f * 2], s1 += (double)sums[(size_t)f * 2 + 1];
-    lane_sum[0][threadIdx.x] = s0;
-    lane_sum[1][threadIdx.x] = s1;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double num = 0.0, den = 0.0;
-        for (int l = 0; l < 64; ++l) num += lane_sum[0][l], den += lane_sum[1][l];
-        out[0] = (float)(num / den);
-    }
-}
+// lsl_class_loss_final: loss = s_ce / n; a batch without a counted row gives NaN.
+constexpr unsigned long long CLASS_QUOTS = loss_quot(0, 0, 1);

@@ -10,15 +10,13 @@
 // target where the batch holds it, [B, Tt, A, D]: the future frames are addressed by a frame offset each, the reference's permute /
 // reshape / boolean-index copies never exist and nothing waits for the host.
 //
-// Determinism: no atomics.  A team of 64 threads (A <= 64: one wave, four units per workgroup) or 256 threads (one unit per workgroup) owns
-// a unit = one sample trajectory (k, b); thread l owns agents l, l + TEAM, ... in ascending order, walks an agent's frames t = 0 .. Tf - 1
-// in ascending order, e_t = sqrtf(sum_d fmaf(delta_d, delta_d, .)) with d ascending, s += e_t in that order (loads of several frames may be
-// in flight, the additions are not reordered).  The trajectory means add the thread's agents in ascending order, then the wave by DPP, then
-// the four waves of a 256-thread team in wave order.  Every order is fixed by (A, D, Tf) alone: a unit's floats have the same bits whatever
-// K, B, the grid, or the unit's place in the batch.  The final kernel takes k in ascending order and adds in index order in fp64 (lane l
-// adds items l, l + 64, ...; the lanes are added in lane order).  sqrtf and the divisions are the correctly rounded ones.
+// Orders (k_loss_frag.hip.h): the unit is one sample trajectory (k, b), the entities its A agents; a thread walks an agent's frames t = 0 ..
+// Tf - 1 in ascending order, e_t = sqrtf(sum_d fmaf(delta_d, delta_d, .)) with d ascending, s += e_t in that order (loads of several frames
+// may be in flight, the additions are not reordered).  Every order is fixed by (A, D, Tf) alone.  The final kernel takes k in ascending
+// order.  sqrtf and the divisions are the correctly rounded ones.
 #pragma once
 #include "common.hip.h"
+#include "k_loss_frag.hip.h"
 
 #define LSL_DISP_MAX_D 4
 #define LSL_DISP_MAX_UNITS 16777215LL  // K * B < 2^24: a grid of one 256-thread workgroup per unit stays below 2^32 threads, which every launch takes
@@ -29,9 +27,10 @@
 template <int D, int TEAM>
 __global__ void __launch_bounds__(256) k_disp_rows(float *rows, float *traj, const float *pred, const float *target, long long units, int B, int Tp,
                                                    int t0p, int Tt, int t0t, int Tf, int A) {
-    const int team = threadIdx.x / TEAM, tl = threadIdx.x % TEAM;
-    const long long unit = (long long)blockIdx.x * (256 / TEAM) + team;
-    const bool live = unit < units;  // (the last workgroup of the 64-thread form may hold fewer than four units)
+    const LossTeam<TEAM> tm(units);
+    const int tl = tm.tl;
+    const long long unit = tm.unit;
+    const bool live = tm.live;
     const size_t AD = (size_t)A * D;
     float t_ade = 0.0f, t_fde = 0.0f;
     if (live) {
@@ -58,20 +57,11 @@ __global__ void __launch_bounds__(256) k_disp_rows(float *rows, float *traj, con
         }
     }
     if (!traj) return;  // (uniform over the grid)
-    t_ade = wave_sum_dpp(t_ade);
-    t_fde = wave_sum_dpp(t_fde);
+    float v[2] = {t_ade, t_fde};
     const float n_ade = (float)Tf * (float)A, n_fde = (float)A;
-    if constexpr (TEAM == 64) {
-        if (live && tl == 0) traj[(size_t)unit * 2] = t_ade / n_ade, traj[(size_t)unit * 2 + 1] = t_fde / n_fde;
-    } else {
-        __shared__ float wsum[4][2];  // (the 256-thread form only)
-        if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6][0] = t_ade, wsum[threadIdx.x >> 6][1] = t_fde;
-        __syncthreads();
-        if (live && threadIdx.x < 2) {  // thread c combines column c of the four waves in wave order
-            const float v = ((wsum[0][threadIdx.x] + wsum[1][threadIdx.x]) + wsum[2][threadIdx.x]) + wsum[3][threadIdx.x];
-            traj[(size_t)unit * 2 + threadIdx.x] = v / (threadIdx.x == 0 ? n_ade : n_fde);
-        }
-    }
+    team_sums<TEAM>(live, v, [&](int k, float tot) {
+        if (live) traj[(size_t)unit * 2 + k] = tot / (k == 0 ? n_ade : n_fde);
+    });
 }
 
 // agents[(b A + a) * 2 + c] = min over k = 0 .. R - 1 of rows[k, b, a, c], k ascending, the two columns on their own, a NaN of any sample
@@ -97,19 +87,11 @@ __global__ void __launch_bounds__(256) k_disp_final(float *agents, double *total
     __syncthreads();  // (the first wave reads back what all four wrote: the barrier orders a workgroup's global stores and loads)
     if (threadIdx.x < 64) {
         double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-        for (long long i = threadIdx.x; i < BA; i += 64) {
-            if (mask && !mask[i]) continue;
-            s[0] += (double)agents[(size_t)i * 2], s[1] += (double)agents[(size_t)i * 2 + 1], s[2] += 1.0;
-        }
-        if (traj)
-            for (long long u = threadIdx.x; u < RB; u += 64) s[3] += (double)traj[(size_t)u * 2], s[4] += (double)traj[(size_t)u * 2 + 1];
+        s[2] = lane_rows_add<2, 0>(s, agents, nullptr, BA, threadIdx.x, mask);
+        if (traj) lane_rows_add<2, 0>(s + 3, traj, nullptr, RB, threadIdx.x);
 #pragma unroll
         for (int c = 0; c < 5; ++c) lane_sum[c][threadIdx.x] = s[c];
     }
     __syncthreads();
-    if (threadIdx.x < 5) {  // thread c adds column c over the lanes in lane order
-        double tot = 0.0;
-        for (int l = 0; l < 64; ++l) tot += lane_sum[threadIdx.x][l];
-        totals[threadIdx.x] = tot;
-    }
+    if (threadIdx.x < 5) totals[threadIdx.x] = lane_order_total(lane_sum[threadIdx.x]);
 }

@@ -4,7 +4,7 @@
 //      pos_loss        = sum_f s_mse / sum_f n,        s_mse  = sum_a m_a mean_d (p - t)^2
 //      dist            = sum_f s_norm / sum_f n,       s_norm = sum_a m_a ||p_a - t_a||,            n = sum_a m_a
 //      inter_dist_loss = sum_f s_pair / sum_f n_pair,  s_pair = sum_ij m_i m_j (||p_i - p_j|| - ||t_i - t_j||)^2,   n_pair = n^2
-// k_geom_loss_frame writes the five floats (s_mse, s_norm, n, s_pair, n_pair) of every frame, k_geom_loss_final adds the columns and divides.
+// k_geom_loss_frame writes the five floats (s_mse, s_norm, n, s_pair, n_pair) of every frame, k_loss_final (GEOM_QUOTS) adds the columns and divides.
 // The reference's two torch.cdist matrices [F, A, A] and its elementwise passes over them never exist: a frame's positions and mask sit in
 // LDS (A <= 2048, D <= 4: at most 66 KiB), entity i walks j = 0 .. A-1 with broadcast reads.  Distances are sqrt(sum_d (x_i - x_j)^2) of
 // coordinate differences (never a Gram matrix: cdist's matmul form for A > 25 cancels where this does not), so the diagonal is an exact 0.
@@ -12,13 +12,11 @@
 // Masked-out entities are SKIPPED (a select on m_i, a wave-uniform branch on m_j), where the reference multiplies by the mask: the two differ
 // only when a masked-out position is not finite (0 * inf = NaN there, nothing here).
 //
-// Determinism: no atomics.  A team of 64 threads (A <= 64: one wave, four frames per workgroup) or 256 threads (one frame per workgroup) owns a
-// frame; thread l owns entities l, l + TEAM, ... in ascending order, adds entity i's pair terms over ascending j into a row sum of its own and
-// the row sums into its accumulator, the wave sums by DPP, the four waves of a 256-thread team combine in wave order.  Every order is fixed by
-// (A, D) alone: a frame's five floats have the same bits whatever F, the grid, or the frame's place in the batch.  The final kernel adds the
-// frames in index order in fp64 (lane l adds frames l, l + 64, ...; lane 0 adds the lanes in lane order) and rounds each quotient once.
+// Orders (k_loss_frag.hip.h): the unit is a frame, the entities its A positions; thread l adds entity i's pair terms over ascending j into a
+// row sum of its own and the row sums into its accumulator.  Every order is fixed by (A, D) alone.
 #pragma once
 #include "common.hip.h"
+#include "k_loss_frag.hip.h"
 
 #define LSL_GEOM_MAX_A 2048
 #define LSL_GEOM_MAX_D 4
@@ -31,12 +29,12 @@ __host__ __device__ inline size_t geom_team_bytes(int A, int D) { return (size_t
 template <int D, int TEAM>
 __global__ void __launch_bounds__(256) k_geom_loss_frame(float *sums, const float *pred, const float *target, const unsigned char *mask, int F, int A) {
     extern __shared__ __align__(16) unsigned char geom_lds[];
-    const int team = threadIdx.x / TEAM, tl = threadIdx.x % TEAM;
-    const int AD = A * D;
-    float *sp = reinterpret_cast<float *>(geom_lds + (size_t)team * geom_team_bytes(A, D)), *st = sp + AD;
+    const LossTeam<TEAM> tm(F);
+    const int tl = tm.tl, AD = A * D;
+    const long long frame = tm.unit;
+    const bool live = tm.live;
+    float *sp = reinterpret_cast<float *>(geom_lds + (size_t)tm.team * geom_team_bytes(A, D)), *st = sp + AD;
     unsigned char *sm = reinterpret_cast<unsigned char *>(st + AD);
-    const long long frame = (long long)blockIdx.x * (256 / TEAM) + team;
-    const bool live = frame < F;  // (the last workgroup of the 64-thread form may hold fewer than four frames)
     if (live) {
         const float *gp = pred + (size_t)frame * AD, *gt = target + (size_t)frame * AD;
         const unsigned char *gm = mask + (size_t)frame * A;
@@ -74,51 +72,13 @@ __global__ void __launch_bounds__(256) k_geom_loss_frame(float *sums, const floa
             s_pair += mi ? row : 0.0f;
         }
     }
-    s_mse = wave_sum_dpp(s_mse);
-    s_norm = wave_sum_dpp(s_norm);
-    s_n = wave_sum_dpp(s_n);
-    s_pair = wave_sum_dpp(s_pair);
-    if constexpr (TEAM == 64) {
-        if (live && tl == 0) {
-            float *o = sums + (size_t)frame * 5;
-            o[0] = s_mse, o[1] = s_norm, o[2] = s_n, o[3] = s_pair, o[4] = s_n * s_n;  // (n <= 2048: n^2 is exact in fp32)
-        }
-    } else {
-        __shared__ float wsum[4][4];  // (the 256-thread form only)
-        if ((threadIdx.x & 63) == 0) {
-            float *w = wsum[threadIdx.x >> 6];
-            w[0] = s_mse, w[1] = s_norm, w[2] = s_n, w[3] = s_pair;
-        }
-        __syncthreads();
-        if (threadIdx.x < 4) {  // thread k combines value k of the four waves in wave order
-            const float v = ((wsum[0][threadIdx.x] + wsum[1][threadIdx.x]) + wsum[2][threadIdx.x]) + wsum[3][threadIdx.x];
-            float *o = sums + (size_t)frame * 5;
-            o[threadIdx.x] = v;
-            if (threadIdx.x == 2) o[4] = v * v;
-        }
-    }
+    float v[4] = {s_mse, s_norm, s_n, s_pair};
+    float *o = sums + (size_t)frame * 5;
+    team_sums<TEAM>(live, v, [&](int k, float tot) {
+        o[k] = tot;
+        if (k == 2) o[4] = tot * tot;  // (n <= 2048: n^2 is exact in fp32)
+    });
 }
 
-// out[0..2] = pos_loss, dist, inter_dist_loss from the [F, 5] sums: columns added over frames in index order in fp64, each quotient rounded
-// once; a batch without a real entity gives 0 / 0 = NaN like the reference.  One workgroup of 64 threads.
-__global__ void __launch_bounds__(64) k_geom_loss_final(float *out, const float *sums, int F) {
-    __shared__ double lane_sum[5][64];
-    double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int f = threadIdx.x; f < F; f += 64) {
-#pragma unroll
-        for (int k = 0; k < 5; ++k) s[k] += (double)sums[(size_t)f * 5 + k];
-    }
-#pragma unroll
-    for (int k = 0; k < 5; ++k) lane_sum[k][threadIdx.x] = s[k];
-    __syncthreads();
-    if (threadIdx.x < 5) {  // thread k adds column k over the lanes in lane order
-        double tot = 0.0;
-        for (int l = 0; l < 64; ++l) tot += lane_sum[threadIdx.x][l];
-        lane_sum[threadIdx.x][0] = tot;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const double num = lane_sum[threadIdx.x == 0 ? 0 : threadIdx.x == 1 ? 1 : 3][0], den = lane_sum[threadIdx.x == 2 ? 4 : 2][0];
-        out[threadIdx.x] = (float)(num / den);
-    }
-}
+// lsl_geom_loss_final: pos_loss, dist, inter_dist_loss = s_mse / n, s_norm / n, s_pair / n_pair; a batch without a real entity gives NaN.
+constexpr unsigned long long GEOM_QUOTS = loss_quot(0, 0, 2) | loss_quot(1, 1, 2) | loss_quot(2, 3, 4);

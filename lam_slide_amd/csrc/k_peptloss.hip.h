@@ -3,7 +3,7 @@
 // pred [F, R, 14, 3] are the decoded atom14 positions of F = B*T frames of R residues:
 //      pos_frame_loss = sum_f s_frame / sum_f n,      s_frame = sum_ra m_ra mean_d (local(pred)_rad - target_frame_rad)^2,   n = sum_ra m_ra
 //      torsion_loss   = sum_f s_tors / sum_f n_tors,  s_tors  = sum_rk w_rk l_rk,                                             n_tors = sum_rk w_rk
-// k_peptide_loss_frame writes the four floats (s_frame, n, s_tors, n_tors) of every frame, k_peptide_loss_final adds their columns and the
+// k_peptide_loss_frame writes the four floats (s_frame, n, s_tors, n_tors) of every frame, k_loss_final (PEPT_QUOTS) adds their columns and the
 // five columns of k_geom_loss_frame (A = R*14, D = 3, the same mask) and divides: pos_loss, pos_frame_loss, inter_distance_loss, norm_loss,
 // torsion_loss.
 //
@@ -23,11 +23,8 @@
 // normalised rounding noise; its own torsions_mask is 0 exactly there.  An aatype outside 0..20 makes the four sums of its frame NaN: it
 // is staged as "no type" (no table row is read with it) and the lane that staged it poisons its four accumulators.
 //
-// Determinism: no atomics.  A team of 64 threads (R*14 <= 64 atoms, the threshold of k_geom_loss_frame: one wave, four frames per workgroup
-// - the tetrapeptides, R = 4) or of 256 threads (one frame per workgroup) owns a frame.  The frame's R*21 work items are its R*14 atoms
-// followed by its R*7 torsions; thread l takes items l, l + TEAM, ... in ascending order, the wave sums by DPP, the four waves of a
-// 256-thread team combine in wave order.  Every order is fixed by R alone: a frame's four floats have the same bits whatever F, the grid,
-// or the frame's place in the batch.  The final kernel adds the frames in index order in fp64 and rounds each quotient once.
+// Orders (k_loss_frag.hip.h): the unit is a frame, the entities its R*14 atoms (the threshold of k_geom_loss_frame: a wave per frame for the
+// tetrapeptides, R = 4); the frame's R*21 work items are its R*14 atoms followed by its R*7 torsions.  Every order is fixed by R alone.
 #pragma once
 #include "common.hip.h"
 #include "k_geomloss.hip.h"
@@ -73,12 +70,12 @@ __global__ void __launch_bounds__(256) k_peptide_loss_frame(float *sums, const f
                                                             const signed char *restab, int F, int R, int kind) {
     extern __shared__ __align__(16) unsigned char pept_lds[];
     __shared__ signed char tab[LSL_PEPT_TYPES * LSL_PEPT_TAB];
-    const int team = threadIdx.x / TEAM, tl = threadIdx.x % TEAM;
-    const int A = R * 14;
-    float *sp = reinterpret_cast<float *>(pept_lds + (size_t)team * pept_team_bytes(R));
+    const LossTeam<TEAM> tm(F);
+    const int tl = tm.tl, A = R * 14;
+    const long long frame = tm.unit;
+    const bool live = tm.live;
+    float *sp = reinterpret_cast<float *>(pept_lds + (size_t)tm.team * pept_team_bytes(R));
     signed char *sa = reinterpret_cast<signed char *>(sp + A * 3);
-    const long long frame = (long long)blockIdx.x * (256 / TEAM) + team;
-    const bool live = frame < F;  // (the last workgroup of the 64-thread form may hold fewer than four frames)
     float s_frame = 0.0f, s_n = 0.0f, s_tors = 0.0f, s_nt = 0.0f;
     for (int e = threadIdx.x; e < LSL_PEPT_TYPES * LSL_PEPT_TAB; e += 256) tab[e] = restab[e];
     if (live) {
@@ -143,6 +140,8 @@ __global__ void __launch_bounds__(256) k_peptide_loss_frame(float *sums, const f
             }
         }
     }
+    // team_sums<TEAM> of the four values, written out: through the fragment this kernel gained six instructions and lsl_peptide_loss_sums
+    // 0.1 us at the tetrapeptide shape, outside the parent's spread (profiles/loss_fragments.txt)
     s_frame = wave_sum_dpp(s_frame);
     s_n = wave_sum_dpp(s_n);
     s_tors = wave_sum_dpp(s_tors);
@@ -164,31 +163,7 @@ __global__ void __launch_bounds__(256) k_peptide_loss_frame(float *sums, const f
     }
 }
 
-// out[0..4] = pos_loss, pos_frame_loss, inter_distance_loss, norm_loss, torsion_loss from geom [F, 5] (s_mse, s_norm, n, s_pair, n_pair) and
-// pept [F, 4] (s_frame, n, s_tors, n_tors): the nine columns added over frames in index order in fp64 (lane l adds frames l, l + 64, ...;
-// thread k adds column k over the lanes in lane order), each quotient rounded once; 0 / 0 = NaN like the reference.  One workgroup of 64.
-__global__ void __launch_bounds__(64) k_peptide_loss_final(float *out, const float *geom, const float *pept, int F) {
-    __shared__ double lane_sum[9][64];
-    double s[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int f = threadIdx.x; f < F; f += 64) {
-#pragma unroll
-        for (int k = 0; k < 5; ++k) s[k] += (double)geom[(size_t)f * 5 + k];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) s[5 + k] += (double)pept[(size_t)f * 4 + k];
-    }
-#pragma unroll
-    for (int k = 0; k < 9; ++k) lane_sum[k][threadIdx.x] = s[k];
-    __syncthreads();
-    if (threadIdx.x < 9) {
-        double tot = 0.0;
-        for (int l = 0; l < 64; ++l) tot += lane_sum[threadIdx.x][l];
-        lane_sum[threadIdx.x][0] = tot;
-    }
-    __syncthreads();
-    if (threadIdx.x < 5) {
-        // column:           s_mse / n | s_frame / n (pept) | s_pair / n_pair | s_norm / n | s_tors / n_tors
-        const int num = threadIdx.x == 0 ? 0 : threadIdx.x == 1 ? 5 : threadIdx.x == 2 ? 3 : threadIdx.x == 3 ? 1 : 7;
-        const int den = threadIdx.x == 0 ? 2 : threadIdx.x == 1 ? 6 : threadIdx.x == 2 ? 4 : threadIdx.x == 3 ? 2 : 8;
-        out[threadIdx.x] = (float)(lane_sum[num][0] / lane_sum[den][0]);
-    }
-}
+// lsl_peptide_loss_final: pos_loss, pos_frame_loss, inter_distance_loss, norm_loss, torsion_loss from geom [F, 5] (columns 0..4: s_mse,
+// s_norm, n, s_pair, n_pair) and pept [F, 4] (columns 5..8: s_frame, n, s_tors, n_tors).
+constexpr unsigned long long PEPT_QUOTS = loss_quot(0, 0, 2) | loss_quot(1, 5, 6) | loss_quot(2, 3, 4) | loss_quot(3, 1, 2) | loss_quot(4, 7, 8);
+//                                           s_mse / n          s_frame / n (pept)   s_pair / n_pair      s_norm / n           s_tors / n_tors

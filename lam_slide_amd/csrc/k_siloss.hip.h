@@ -8,13 +8,13 @@
 // the same idea as the affine step records of the samplers.  Bandwidth-bound passes over B * T*L*C floats next to a network that moves
 // thousands of bytes per token.
 //
-// Determinism: no atomics.  A trajectory is cut into slabs of a FIXED 4096 elements (a constant: not a function of B, T, L or the pass size);
-// inside a slab thread i owns elements 4 (i + 256 j) + k (j, k = 0..3) and adds their squares in (j, k) order, the wave sums by DPP, the four
-// waves combine in wave order, the slabs of a trajectory are added in index order in fp64 and rounded once.  The order of every sum is fixed by
-// construction, so a trajectory's loss has the same bits in any batch, shard or pass.  The 16-byte and the scalar access forms read the same
-// elements into the same registers: which one runs (alignment) does not change a bit either.
+// Orders (k_loss_frag.hip.h; the team is the workgroup): a trajectory is cut into slabs of a FIXED 4096 elements (a constant: not a function
+// of B, T, L or the pass size); inside a slab thread i owns elements 4 (i + 256 j) + k (j, k = 0..3) and adds their squares in (j, k) order;
+// the slabs of a trajectory are added in fp64 and rounded once.  A trajectory's loss has the same bits in any batch, shard or pass.  The
+// 16-byte and the scalar access forms read the same elements into the same registers: which one runs (alignment) does not change a bit.
 #pragma once
 #include "common.hip.h"
+#include "k_loss_frag.hip.h"
 
 #define LSL_SI_SLAB_ELEMS 4096
 
@@ -91,7 +91,7 @@ __global__ void __launch_bounds__(256) k_si_loss_partial(float *partial, const f
             s = fmaf(v, v, s);
         }
     }
-    s = wave_sum_dpp(s);
+    s = wave_sum_dpp(s);  // (team_sums<256> of one value, written out: through the fragment this kernel gains an instruction, profiles/loss_fragments.txt)
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) partial[(size_t)b * gridDim.x + blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
@@ -104,12 +104,8 @@ __global__ void __launch_bounds__(64) k_si_loss_final(float *loss, const float *
     const unsigned b = blockIdx.x;
     const float *p = partial + (size_t)b * slabs;
     double s = 0.0;
-    for (int i = threadIdx.x; i < slabs; i += 64) s += (double)p[i];
+    lane_rows_add<1, 0>(&s, p, nullptr, slabs, threadIdx.x);
     lane_sum[threadIdx.x] = s;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        double tot = 0.0;
-        for (int l = 0; l < 64; ++l) tot += lane_sum[l];
-        loss[b] = (float)((double)rows[b].w * tot / (double)per);
-    }
+    if (threadIdx.x == 0) loss[b] = (float)((double)rows[b].w * lane_order_total(lane_sum) / (double)per);
 }

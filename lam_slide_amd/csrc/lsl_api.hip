@@ -301,23 +301,18 @@ int lsl_geom_loss_sums(const float *pred, const float *target, const uint8_t *ma
     if (A < 1 || A > LSL_GEOM_MAX_A) return fail(-3, "A = %d outside the native form (1..%d entities)", A, LSL_GEOM_MAX_A);
     if (D < 1 || D > LSL_GEOM_MAX_D) return fail(-3, "D = %d outside the native form (1..%d coordinates)", D, LSL_GEOM_MAX_D);
     hipStream_t st = (hipStream_t)stream;
-    switch (D) {
-        case 1: launch_geom_frame_d<1>(sums, pred, target, mask, F, A, st); break;
-        case 2: launch_geom_frame_d<2>(sums, pred, target, mask, F, A, st); break;
-        case 3: launch_geom_frame_d<3>(sums, pred, target, mask, F, A, st); break;
-        default: launch_geom_frame_d<4>(sums, pred, target, mask, F, A, st); break;
-    }
+    dispatch_d(D, [&](auto d) {
+        if (loss_team(A) == 64)
+            launch_geom_frame<d(), 64>(sums, pred, target, mask, F, A, st);
+        else
+            launch_geom_frame<d(), 256>(sums, pred, target, mask, F, A, st);
+    });
     LSL_CHECK_LAUNCH("lsl_geom_loss_sums");
     return 0;
 } LSL_API_CATCH
 
 int lsl_geom_loss_final(const float *sums, int32_t F, float *out, void *stream) try {
-    DeviceGuard dev_guard_((hipStream_t)stream);
-    if (!sums || !out) return fail(-1, "null argument");
-    if (F <= 0) return fail(-3, "F must be positive");
-    hipLaunchKernelGGL(k_geom_loss_final, dim3(1), dim3(64), 0, (hipStream_t)stream, out, sums, (int)F);
-    LSL_CHECK_LAUNCH("lsl_geom_loss_final");
-    return 0;
+    return loss_final<5, 0, 3>("lsl_geom_loss_final", sums, nullptr, F, out, GEOM_QUOTS, stream);
 } LSL_API_CATCH
 
 // ---- frame-local and torsion losses of the decoded peptide positions (k_peptloss.hip.h) ----
@@ -329,7 +324,7 @@ int lsl_peptide_loss_sums(const float *pred, const float *target_frame, const ui
     if (R < 1 || R > LSL_PEPT_MAX_R) return fail(-3, "R = %d outside the native form (1..%d residues)", R, LSL_PEPT_MAX_R);
     if (kind != 0 && kind != 1) return fail(-3, "kind = %d: 0 (MaskedCosineLoss) or 1 (MaskedCosineLossV2)", kind);
     hipStream_t st = (hipStream_t)stream;
-    if (R * 14 <= 64)
+    if (loss_team(R * 14) == 64)
         launch_peptide_frame<64>(sums, pred, target_frame, atom14_mask, tors_target, tors_mask, (const long long *)aatype, (const signed char *)restab, F, R, kind, st);
     else
         launch_peptide_frame<256>(sums, pred, target_frame, atom14_mask, tors_target, tors_mask, (const long long *)aatype, (const signed char *)restab, F, R, kind, st);
@@ -338,12 +333,7 @@ int lsl_peptide_loss_sums(const float *pred, const float *target_frame, const ui
 } LSL_API_CATCH
 
 int lsl_peptide_loss_final(const float *geom_sums, const float *pept_sums, int32_t F, float *out, void *stream) try {
-    DeviceGuard dev_guard_((hipStream_t)stream);
-    if (!geom_sums || !pept_sums || !out) return fail(-1, "null argument");
-    if (F <= 0) return fail(-3, "F must be positive");
-    hipLaunchKernelGGL(k_peptide_loss_final, dim3(1), dim3(64), 0, (hipStream_t)stream, out, geom_sums, pept_sums, (int)F);
-    LSL_CHECK_LAUNCH("lsl_peptide_loss_final");
-    return 0;
+    return loss_final<5, 4, 5>("lsl_peptide_loss_final", geom_sums, pept_sums, F, out, PEPT_QUOTS, stream);
 } LSL_API_CATCH
 
 // ---- displacement errors of the decoded positions: ADE / FDE and best-of-K (k_disperr.hip.h) ----
@@ -360,12 +350,12 @@ int lsl_disp_error_rows(const float *pred, const float *target, int32_t K, int32
     if (t0t < 0 || (long long)t0t + Tf > Tt) return fail(-3, "frames %d..%d outside target's %d frames", t0t, t0t + Tf - 1, Tt);
     hipStream_t st = (hipStream_t)stream;
     const long long units = (long long)K * B;
-    switch (D) {
-        case 1: launch_disp_rows<1>(rows, traj, pred, target, units, B, Tp, t0p, Tt, t0t, Tf, A, st); break;
-        case 2: launch_disp_rows<2>(rows, traj, pred, target, units, B, Tp, t0p, Tt, t0t, Tf, A, st); break;
-        case 3: launch_disp_rows<3>(rows, traj, pred, target, units, B, Tp, t0p, Tt, t0t, Tf, A, st); break;
-        default: launch_disp_rows<4>(rows, traj, pred, target, units, B, Tp, t0p, Tt, t0t, Tf, A, st); break;
-    }
+    dispatch_d(D, [&](auto d) {
+        if (loss_team(A) == 64)
+            launch_disp_rows<d(), 64>(rows, traj, pred, target, units, B, Tp, t0p, Tt, t0t, Tf, A, st);
+        else
+            launch_disp_rows<d(), 256>(rows, traj, pred, target, units, B, Tp, t0p, Tt, t0t, Tf, A, st);
+    });
     LSL_CHECK_LAUNCH("lsl_disp_error_rows");
     return 0;
 } LSL_API_CATCH

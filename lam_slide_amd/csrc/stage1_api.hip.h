@@ -101,12 +101,7 @@ int lsl_class_loss_sums(const float *logits, const int64_t *target, const uint8_
 } LSL_API_CATCH
 
 int lsl_class_loss_final(const float *sums, int32_t F, float *out, void *stream) try {
-    DeviceGuard dev_guard_((hipStream_t)stream);
-    if (!sums || !out) return fail(-1, "null argument");
-    if (F <= 0) return fail(-3, "F must be positive");
-    hipLaunchKernelGGL(k_class_loss_final, dim3(1), dim3(64), 0, (hipStream_t)stream, out, sums, (int)F);
-    LSL_CHECK_LAUNCH("lsl_class_loss_final");
-    return 0;
+    return loss_final<2, 0, 1>("lsl_class_loss_final", sums, nullptr, F, out, CLASS_QUOTS, stream);
 } LSL_API_CATCH
 
 int lsl_encoder_create(const lsl_encoder_desc *desc, const lsl_encoder_weights *w, lsl_encoder **out) try {

@@ -22,8 +22,7 @@ from . import _lib, losses as _geo, peptide_loss as _pep
 from .decoder import Stage1Decoder
 from .encoder import Stage1Encoder
 
-MAX_K = 128  # LSL_CLS_MAX_K: the classes of one lsl_class_loss_sums call (csrc/k_classloss.hip.h)
-IGNORE_INDEX = -100
+MAX_K, IGNORE_INDEX = _lib.CLS_MAX_K, _lib.CLS_IGNORE  # the classes of one lsl_class_loss_sums call, the target of an ignored row
 SUM_COLUMNS = ("s_ce", "n")
 
 
@@ -75,23 +74,21 @@ class Stage1Autoencoder:
 # ---- class losses ----
 def _rows(logits: Tensor, target: Tensor, mask: Optional[Tensor]) -> Tuple[Tensor, Tensor, Optional[Tensor]]:
     """[..., A, K] / [..., A] -> contiguous float32 [F, A, K], int64 [F, A] and uint8 [F, A] (or None) on the logits' device."""
-    if logits.dim() < 2 or tuple(target.shape) != tuple(logits.shape[:-1]) or (mask is not None and tuple(mask.shape) != tuple(target.shape)):
-        raise ValueError(f"expected logits [..., A, K], target [..., A] and mask [..., A] or None, got {tuple(logits.shape)}, {tuple(target.shape)} and "
-                         f"{None if mask is None else tuple(mask.shape)}")
+    shape = lambda: (f"expected logits [..., A, K], target [..., A] and mask [..., A] or None, got {tuple(logits.shape)}, "  # noqa: E731
+                     f"{tuple(target.shape)} and {None if mask is None else tuple(mask.shape)}")
+    device = lambda: (f"Expected all tensors to be on the same device, logits are on {logits.device}, target on {target.device}"  # noqa: E731
+                      + ("" if mask is None else f", mask on {mask.device}"))
+    if logits.dim() < 2:
+        raise ValueError(shape())
+    lead, (A, K) = tuple(logits.shape[:-2]), logits.shape[-2:]
     if target.is_floating_point() or target.dtype == torch.bool:
         raise ValueError(f"target must hold class indices (integers), got {target.dtype}")
-    A, K = int(logits.shape[-2]), int(logits.shape[-1])
     if not 1 <= K <= MAX_K:
         raise ValueError(f"K = {K} outside the native form (1..{MAX_K} classes)")
     if A < 1 or logits.numel() == 0:
         raise ValueError("no rows")
-    if target.device != logits.device or (mask is not None and mask.device != logits.device):
-        raise RuntimeError(f"Expected all tensors to be on the same device, logits are on {logits.device}, target on {target.device}"
-                           + ("" if mask is None else f", mask on {mask.device}"))
-    lg = logits.detach().reshape(-1, A, K).float().contiguous()
-    tg = target.detach().reshape(-1, A).to(torch.int64).contiguous()
-    mk = None if mask is None else (mask.detach().reshape(-1, A) != 0).to(torch.uint8).contiguous()
-    return lg, tg, mk
+    return tuple(None if x is None else _lib.flat(x, lead, trailing, dtype, logits.device, shape, device)
+                 for x, trailing, dtype in ((logits, (A, K), torch.float32), (target, (A,), torch.int64), (mask, (A,), torch.uint8)))
 
 
 def native_classes(K: int) -> bool:
@@ -128,20 +125,8 @@ def class_losses(logits: Optional[Tensor] = None, target: Optional[Tensor] = Non
     """0-dim float32: MaskedCrossEntropyLoss(label_smoothing)(logits, target, mask) of the reference - or, without a mask,
     nn.CrossEntropyLoss(label_smoothing=...)(logits, target) - for logits [..., A, K], or of ``sums`` [F, 2] from :func:`class_loss_sums`.
     The frames are added in index order in fp64 and the quotient is rounded once; no counted row gives NaN like the reference."""
-    if sums is None:
-        if logits is None or target is None:
-            raise TypeError("class_losses needs (logits, target[, mask]) or sums=")
-        sums = class_loss_sums(logits, target, mask, label_smoothing, confusion)
-    elif logits is not None or target is not None or mask is not None:
-        raise TypeError("class_losses takes (logits, target[, mask]) or sums=, not both")
-    if sums.dim() != 2 or sums.shape[1] != 2 or sums.shape[0] == 0 or sums.dtype != torch.float32:
-        raise ValueError(f"sums must be float32 [F, 2] with F > 0, got {sums.dtype} {tuple(sums.shape)}")
-    if not sums.is_cuda:
-        raise RuntimeError("class_losses runs on the GPU (HIP kernel); there is no CPU fallback")
-    sums = sums.contiguous()
-    out = torch.empty(1, dtype=torch.float32, device=sums.device)
-    _lib.call(sums.device, "lsl_class_loss_final", sums.data_ptr(), sums.shape[0], out.data_ptr())
-    return out[0]
+    return _lib.loss_from_sums("class_losses", "lsl_class_loss_final", (2,), 1, sums, (logits, target), (mask,),
+                               lambda: class_loss_sums(logits, target, mask, label_smoothing, confusion), "(logits, target[, mask])")[0]
 
 
 class ClassMeter:
@@ -394,16 +379,7 @@ class PeptideLoss(_TrajectoryLoss):
             got = _pep.peptide_losses(pos, target, target_frame, atom14_mask, tors_target, tors_mask, aatype, kind=kind, residue_tables=self.tables)
         else:
             self.last_paths["geometry"] = "generic"
-            B, R = pos.shape[:2]
-            flat3 = lambda x: x.reshape(-1, 3)  # noqa: E731  "B R A D -> (B R A) D"
-            mask_flat = atom14_mask.reshape(-1)
-            got = {"pos_loss": self._call("loss_pos", flat3(pos), flat3(target), mask_flat),
-                   "pos_frame_loss": self._call("loss_pos_frame", flat3(_pep.backbone_local(pos)), flat3(target_frame), mask_flat),
-                   "inter_distance_loss": self._call("loss_inter_distance", pos.reshape(B, R * 14, 3), target.reshape(B, R * 14, 3),
-                                                     atom14_mask.reshape(B, R * 14)),
-                   "norm_loss": self._call("loss_norm", flat3(pos), flat3(target), mask_flat),
-                   "torsion_loss": self._call("loss_torsion", preds=_pep.torsion_angles(pos, aatype, self.tables).reshape(-1, 2),
-                                              targets=tors_target.reshape(-1, 2), mask=tors_mask.reshape(-1))}
+            got = _pep.generic_terms(self, 1, pos, target, target_frame, atom14_mask, tors_target, tors_mask, aatype)
         res = self._class_term("loss_res_type", "CrossEntropyLoss", False, preds["aatype"], aatype, None)
         loss_total = (self.loss_pos_weight * got["pos_loss"] + self.loss_pos_frame_weight * got["pos_frame_loss"]
                       + self.loss_inter_distance_weight * got["inter_distance_loss"] + self.loss_res_type_weight * res

@@ -25,15 +25,15 @@ SUM_COLUMNS = ("s_mse", "s_norm", "n", "s_pair", "n_pair")
 def _frames(pred: Tensor, target: Tensor, mask: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
     """[..., A, D] / [..., A] -> contiguous float32 [F, A, D] x 2 and uint8 [F, A] on pred's device (``si_reduce`` refuses what is not
     contiguous; these inputs come out of rearranges and slices, so they are made contiguous instead)."""
-    if pred.dim() < 2 or tuple(target.shape) != tuple(pred.shape) or tuple(mask.shape) != tuple(pred.shape[:-1]):
-        raise ValueError(f"expected pred and target [..., A, D] and mask [..., A], got {tuple(pred.shape)}, {tuple(target.shape)} and {tuple(mask.shape)}")
-    if target.device != pred.device or mask.device != pred.device:
-        raise RuntimeError(f"Expected all tensors to be on the same device, pred is on {pred.device}, target on {target.device}, mask on {mask.device}")
-    A, D = int(pred.shape[-2]), int(pred.shape[-1])
-    p = pred.detach().reshape(-1, A, D).float().contiguous()
-    t = target.detach().reshape(-1, A, D).float().contiguous()
-    m = (mask.detach().reshape(-1, A) != 0).to(torch.uint8).contiguous()
-    return p, t, m
+    shape = lambda: (f"expected pred and target [..., A, D] and mask [..., A], got {tuple(pred.shape)}, {tuple(target.shape)} and "  # noqa: E731
+                     f"{tuple(mask.shape)}")
+    device = lambda: (f"Expected all tensors to be on the same device, pred is on {pred.device}, target on {target.device}, "  # noqa: E731
+                      f"mask on {mask.device}")
+    if pred.dim() < 2:
+        raise ValueError(shape())
+    lead, (A, D) = tuple(pred.shape[:-2]), pred.shape[-2:]
+    return tuple(_lib.flat(x, lead, trailing, dtype, pred.device, shape, device)
+                 for x, trailing, dtype in ((pred, (A, D), torch.float32), (target, (A, D), torch.float32), (mask, (A,), torch.uint8)))
 
 
 def native_shape(A: int, D: int) -> bool:
@@ -63,19 +63,8 @@ def geom_losses(pred: Optional[Tensor] = None, target: Optional[Tensor] = None, 
     """{"pos_loss", "dist", "inter_dist_loss"} as 0-dim float32 tensors: the reference's MaskedMSELoss, MaskedNormLoss and
     InterDistanceLoss of (pred, target, mask), or of ``sums`` [F, 5] from :func:`geom_loss_sums`.  The frames are added in index order in
     fp64 and each quotient is rounded once; a batch without a real entity gives NaN like the reference."""
-    if sums is None:
-        if pred is None or target is None or mask is None:
-            raise TypeError("geom_losses needs (pred, target, mask) or sums=")
-        sums = geom_loss_sums(pred, target, mask)
-    elif pred is not None or target is not None or mask is not None:
-        raise TypeError("geom_losses takes (pred, target, mask) or sums=, not both")
-    if not sums.is_cuda:
-        raise RuntimeError("geom_losses runs on the GPU (HIP kernel); there is no CPU fallback")
-    if sums.dim() != 2 or sums.shape[1] != 5 or sums.shape[0] == 0 or sums.dtype != torch.float32:
-        raise ValueError(f"sums must be float32 [F, 5] with F > 0, got {sums.dtype} {tuple(sums.shape)}")
-    sums = sums.contiguous()
-    out = torch.empty(3, dtype=torch.float32, device=sums.device)
-    _lib.call(sums.device, "lsl_geom_loss_final", sums.data_ptr(), sums.shape[0], out.data_ptr())
+    out = _lib.loss_from_sums("geom_losses", "lsl_geom_loss_final", (5,), 3, sums, (pred, target, mask), (),
+                              lambda: geom_loss_sums(pred, target, mask), "(pred, target, mask)")
     return {"pos_loss": out[0], "dist": out[1], "inter_dist_loss": out[2]}
 
 

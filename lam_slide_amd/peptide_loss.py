@@ -183,22 +183,15 @@ def _peptide_frames(pred: Tensor, target_frame: Tensor, atom14_mask: Tensor, tor
     if pred.dim() < 3 or tuple(pred.shape[-2:]) != (14, 3):
         raise ValueError(f"expected pred [..., R, 14, 3], got {tuple(pred.shape)}")
     lead, R = tuple(pred.shape[:-3]), int(pred.shape[-3])
-    want = {"target_frame": (target_frame, lead + (R, 14, 3)), "atom14_mask": (atom14_mask, lead + (R, 14)), "tors_target": (tors_target, lead + (R, 7, 2)),
-            "tors_mask": (tors_mask, lead + (R, 7)), "aatype": (aatype, lead + (R,))}
-    for name, (x, shape) in want.items():
-        if tuple(x.shape) != shape:
-            raise ValueError(f"expected {name} {list(shape)} for pred {tuple(pred.shape)}, got {tuple(x.shape)}")
-        if x.device != pred.device:
-            raise RuntimeError(f"Expected all tensors to be on the same device, pred is on {pred.device}, {name} on {x.device}")
+    specs = (("pred", pred, (R, 14, 3), torch.float32), ("target_frame", target_frame, (R, 14, 3), torch.float32),
+             ("atom14_mask", atom14_mask, (R, 14), torch.uint8), ("tors_target", tors_target, (R, 7, 2), torch.float32),
+             ("tors_mask", tors_mask, (R, 7), torch.uint8), ("aatype", aatype, (R,), torch.int64))
     if aatype.is_floating_point() or aatype.dtype == torch.bool:
         raise ValueError(f"aatype must hold integers, got {aatype.dtype}")
-    p = pred.detach().reshape(-1, R, 14, 3).float().contiguous()
-    tf = target_frame.detach().reshape(-1, R, 14, 3).float().contiguous()
-    am = (atom14_mask.detach().reshape(-1, R, 14) != 0).to(torch.uint8).contiguous()
-    tt = tors_target.detach().reshape(-1, R, 7, 2).float().contiguous()
-    tm = (tors_mask.detach().reshape(-1, R, 7) != 0).to(torch.uint8).contiguous()
-    aa = aatype.detach().reshape(-1, R).to(torch.int64).contiguous()
-    return p, tf, am, tt, tm, aa
+    return tuple(_lib.flat(x, lead, trailing, dtype, pred.device,
+                           lambda: f"expected {name} {list(lead + trailing)} for pred {tuple(pred.shape)}, got {tuple(x.shape)}",
+                           lambda: f"Expected all tensors to be on the same device, pred is on {pred.device}, {name} on {x.device}")
+                 for name, x, trailing, dtype in specs)
 
 
 @torch.no_grad()
@@ -240,29 +233,18 @@ def peptide_losses(pred: Optional[Tensor] = None, target: Optional[Tensor] = Non
     ``sums = (geom_sums [F, 5], peptide_sums [F, 4])`` from ``geom_loss_sums`` (entities = R * 14 atoms, mask = atom14_mask) and
     :func:`peptide_loss_sums` - one launch.  Frames are added in index order in fp64, each quotient is rounded once; 0 / 0 is NaN like the
     reference."""
-    given = (pred, target, target_frame, atom14_mask, tors_target, tors_mask, aatype)
-    if sums is None:
-        if any(x is None for x in given):
-            raise TypeError("peptide_losses needs (pred, target, target_frame, atom14_mask, tors_target, tors_mask, aatype) or sums=")
+    def both_sums():
         if not pred.is_cuda:
             raise RuntimeError("peptide_losses runs on the GPU (HIP kernel); there is no CPU fallback")
         pept = peptide_loss_sums(pred, target_frame, atom14_mask, tors_target, tors_mask, aatype, kind=kind, residue_tables=residue_tables)
         if tuple(target.shape) != tuple(pred.shape):
             raise ValueError(f"expected target {tuple(pred.shape)}, got {tuple(target.shape)}")
         A = int(pred.shape[-3]) * 14
-        geom = geom_loss_sums(pred.reshape(-1, A, 3), target.reshape(-1, A, 3), atom14_mask.reshape(-1, A))
-    else:
-        if any(x is not None for x in given):
-            raise TypeError("peptide_losses takes the tensors or sums=, not both")
-        geom, pept = sums
-    if not (geom.is_cuda and pept.is_cuda):
-        raise RuntimeError("peptide_losses runs on the GPU (HIP kernel); there is no CPU fallback")
-    ok = geom.dim() == 2 and pept.dim() == 2 and geom.shape[1] == 5 and pept.shape[1] == 4 and geom.shape[0] == pept.shape[0] > 0
-    if not ok or geom.dtype != torch.float32 or pept.dtype != torch.float32 or geom.device != pept.device:
-        raise ValueError(f"sums must be float32 ([F, 5], [F, 4]) with F > 0 on one device, got {geom.dtype} {tuple(geom.shape)} and {pept.dtype} {tuple(pept.shape)}")
-    geom, pept = geom.contiguous(), pept.contiguous()
-    out = torch.empty(5, dtype=torch.float32, device=geom.device)
-    _lib.call(geom.device, "lsl_peptide_loss_final", geom.data_ptr(), pept.data_ptr(), geom.shape[0], out.data_ptr())
+        return geom_loss_sums(pred.reshape(-1, A, 3), target.reshape(-1, A, 3), atom14_mask.reshape(-1, A)), pept
+
+    out = _lib.loss_from_sums("peptide_losses", "lsl_peptide_loss_final", (5, 4), 5, sums,
+                              (pred, target, target_frame, atom14_mask, tors_target, tors_mask, aatype), (), both_sums,
+                              "(pred, target, target_frame, atom14_mask, tors_target, tors_mask, aatype)", "the tensors")
     return {k: out[i] for i, k in enumerate(LOSS_KEYS)}
 
 
@@ -270,6 +252,24 @@ def peptide_losses(pred: Optional[Tensor] = None, target: Optional[Tensor] = Non
 _DEFAULTS = {"loss_pos": ("MaskedMSELoss", masked_mse), "loss_pos_frame": ("MaskedMSELoss", masked_mse), "loss_norm": ("MaskedNormLoss", masked_norm),
              "loss_torsion": ("MaskedCosineLoss", masked_cosine), "loss_inter_distance": ("MaskedMSELoss", masked_mse)}
 _TORSION_KINDS = {"MaskedCosineLoss": KIND_COSINE, "MaskedCosineLossV2": KIND_COSINE_V2}
+
+
+def generic_terms(loss: nn.Module, lead: int, pos: Tensor, target: Tensor, target_frame: Tensor, atom14_mask: Tensor, tors_target: Tensor,
+                  tors_mask: Tensor, aatype: Tensor) -> Dict[str, Tensor]:
+    """The five terms from the modules of ``loss`` (``loss._call``: the module of a slot or the torch restatement of its default) on the
+    torch geometry of this file, each called on the layout the reference rearranges to.  pos [..., R, 14, 3] with ``lead`` leading axes -
+    (B, T) in the second stage, (B) in the first - flattened to frames."""
+    R = int(pos.shape[lead])
+    flat3 = lambda x: x.reshape(-1, 3)  # noqa: E731  "... R A D -> (... R A) D"
+    mask_flat = atom14_mask.reshape(-1)
+    frames = pos.reshape(-1, R, 14, 3)
+    return {"pos_loss": loss._call("loss_pos", flat3(pos), flat3(target), mask_flat),
+            "pos_frame_loss": loss._call("loss_pos_frame", flat3(backbone_local(frames)), flat3(target_frame), mask_flat),
+            "inter_distance_loss": loss._call("loss_inter_distance", pos.reshape(-1, R * 14, 3), target.reshape(-1, R * 14, 3),
+                                              atom14_mask.reshape(-1, R * 14)),
+            "norm_loss": loss._call("loss_norm", flat3(pos), flat3(target), mask_flat),
+            "torsion_loss": loss._call("loss_torsion", preds=torsion_angles(frames, aatype.reshape(-1, R), loss.tables).reshape(-1, 2),
+                                       targets=tors_target.reshape(-1, 2), mask=tors_mask.reshape(-1))}
 
 
 class PeptideLoss(nn.Module):
@@ -355,17 +355,7 @@ class PeptideLoss(nn.Module):
                                      residue_tables=self.tables)
             else:
                 self.last_path = "generic"
-                B, T, R = pos.shape[:3]
-                flat3 = lambda x: x.reshape(-1, 3)  # noqa: E731  "B T R A D -> (B T R A) D"
-                mask_flat = atom14_mask.reshape(-1)
-                frames = pos.reshape(B * T, R, 14, 3)
-                got = {"pos_loss": self._call("loss_pos", flat3(pos), flat3(target), mask_flat),
-                       "pos_frame_loss": self._call("loss_pos_frame", flat3(backbone_local(frames)), flat3(target_frame), mask_flat),
-                       "inter_distance_loss": self._call("loss_inter_distance", pos.reshape(B * T, R * 14, 3), target.reshape(B * T, R * 14, 3),
-                                                         atom14_mask.reshape(B * T, R * 14)),
-                       "norm_loss": self._call("loss_norm", flat3(pos), flat3(target), mask_flat),
-                       "torsion_loss": self._call("loss_torsion", preds=self.calc_torsions(frames, aatype.reshape(B * T, R)).reshape(-1, 2),
-                                                  targets=tors_target.reshape(-1, 2), mask=tors_mask.reshape(-1))}
+                got = generic_terms(self, 2, pos, target, target_frame, atom14_mask, tors_target, tors_mask, aatype)
             for k in LOSS_KEYS:
                 losses[k] = got[k]
             losses["loss"] = losses["loss"] + self.loss_pos_weight * got["pos_loss"]

@@ -104,8 +104,8 @@ def test_class_loss_definition_equals_torch_cross_entropy(golden):
 def test_limits_equal_their_macros():
     from lam_slide_amd import _lib, decoder, first_stage
     src = open(os.path.join(_lib.SRC_DIR, "k_classloss.hip.h")).read()
-    assert first_stage.MAX_K == int(re.search(r"#define LSL_CLS_MAX_K (\d+)", src).group(1)) == 128
-    assert first_stage.IGNORE_INDEX == int(re.search(r"#define LSL_CLS_IGNORE \((-\d+)\)", src).group(1)) == -100
+    assert first_stage.MAX_K == _lib.CLS_MAX_K == int(re.search(r"#define LSL_CLS_MAX_K (\d+)", src).group(1)) == 128
+    assert first_stage.IGNORE_INDEX == _lib.CLS_IGNORE == int(re.search(r"#define LSL_CLS_IGNORE \((-\d+)\)", src).group(1)) == -100
     header = open(os.path.join(ROOT, "include", "lsl_api.h")).read()
     assert decoder.MAX_HEADS == int(re.search(r"#define LSL_DECODE_MAX_HEADS (\d+)", header).group(1)) == 8
 

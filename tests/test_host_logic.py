@@ -57,7 +57,7 @@ def test_every_limit_the_binding_mirrors_equals_its_macro():
                "ASG_CELLS": "LSL_ASG_CELLS", "ASG_MAX_STATES": "LSL_ASG_MAX_STATES", "TR_MAX_STATES": "LSL_TR_MAX_STATES",
                "KM_SEG": "LSL_KM_SEG", "KM_MAX_S": "LSL_KM_MAX_S", "WMOM_MIN_F": "LSL_WMOM_MIN_F", "WMOM_MAX_F": "LSL_WMOM_MAX_F",
                "WPROJ_MAX_D": "LSL_WPROJ_MAX_D", "WMOM_SEG": "LSL_WMOM_SEG", "WMOM_CHAIN": "LSL_WMOM_CHAIN", "PAIR_MAX_P": "LSL_PAIR_MAX_P",
-               "CA_MAX_R": "LSL_CA_MAX_R"}
+               "CA_MAX_R": "LSL_CA_MAX_R", "CLS_MAX_K": "LSL_CLS_MAX_K", "CLS_IGNORE": "LSL_CLS_IGNORE"}
     # every upper-case integer of the binding is in the table, except the ABI version (checked above) and the two step flags
     ints = {k for k, v in vars(_lib).items() if k.isupper() and type(v) is int}
     assert ints - {"ABI_VERSION", "STEP_NO_NETWORK", "STEP_SAVE"} == set(mirrors), ints ^ set(mirrors)

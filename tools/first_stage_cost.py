@@ -96,6 +96,6 @@ with torch.no_grad():
             kernels()
             agree = abs(float(out[0]) - float(restated())) / abs(float(restated()))
             print(f"  {h} (K = {K}, {'masked' if masked else 'no mask'}): lsl_class_loss_sums + lsl_class_loss_final {k_ms * 1e3:8.1f} us per pair (min {k_lo * 1e3:.1f}, "
-                  f"max {k_hi * 1e3:.1f}); alone: k_class_loss_frame {f_ms * 1e3:.1f} us, k_class_loss_final {e_ms * 1e3:.1f} us")
+                  f"max {k_hi * 1e3:.1f}); alone: k_class_loss_frame {f_ms * 1e3:.1f} us, k_loss_final<2, 0, 1> {e_ms * 1e3:.1f} us")
             print(f"      the reference's formula through torch: {t_ms * 1e3:8.1f} us (min {t_lo * 1e3:.1f}, max {t_hi * 1e3:.1f}); kernels / torch = {k_ms / t_ms:.3f}; "
                   f"values agree to {agree:.1e}")

@@ -90,7 +90,7 @@ with torch.no_grad():
         assert tr.last_path == "fused"
         print(f"{name}: F = {B} x {T} = {F_} frames, A = {A}, D = {D}; backbone {kw['hidden_size']} x {kw['depth']}, L = {L}")
         print(f"  lsl_geom_loss_sums + lsl_geom_loss_final: {k_ms * 1e3:9.1f} us per pair of launches (min {k_lo * 1e3:.1f}, max {k_hi * 1e3:.1f})")
-        print(f"    each alone, back to back: k_geom_loss_frame {f_ms * 1e3:.1f} us, k_geom_loss_final {e_ms * 1e3:.1f} us")
+        print(f"    each alone, back to back: k_geom_loss_frame {f_ms * 1e3:.1f} us, k_loss_final<5, 0, 3> {e_ms * 1e3:.1f} us")
         print(f"  torch restatement of the three modules:   {t_ms * 1e3:9.1f} us (min {t_lo * 1e3:.1f}, max {t_hi * 1e3:.1f}); "
               f"kernels / torch = {k_ms / t_ms:.3f}; values agree to {dev_rel:.1e}")
         print(f"  one training_losses (one lsl_si_loss):    {s_ms * 1e3:9.1f} us (min {s_lo * 1e3:.1f}, max {s_hi * 1e3:.1f}); "
