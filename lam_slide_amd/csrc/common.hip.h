@@ -45,7 +45,7 @@ __device__ __forceinline__ f32x16 mfma32(bf16x8 a, bf16x8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
-__device__ __forceinline__ int acc_row(int reg, int hf) { return (reg & 3) + 8 * (reg >> 2) + 4 * hf; }
+__host__ __device__ __forceinline__ constexpr int acc_row(int reg, int hf) { return (reg & 3) + 8 * (reg >> 2) + 4 * hf; }
 
 __device__ __forceinline__ u16 f2bf(float f) {
     __bf16 b = (__bf16)f;  // v_cvt_pk_bf16_f32: round to nearest even, NaN stays NaN

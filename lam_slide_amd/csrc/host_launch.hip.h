@@ -175,11 +175,9 @@ void launch_gemm_glds(const GemmArgs &g, const Epi &epi, hipStream_t st) {
 // features.  Same bits as the tile kernels below (tools/lin1_harness.hip), so the choice between them may depend on the launch size.
 // THE instance list (head width, hidden): gates and launch go through it.  Per entry: 8 waves; 4 waves as well at hidden 512; the LNF form at 8.
 #define LSL_LIN1_TS_INSTANCES(X) X(32, 128) X(32, 256) X(32, 384) X(32, 512) X(16, 128) X(16, 256) X(16, 384) X(16, 512)
-template <int V>
-using int_c = std::integral_constant<int, V>;
 template <class Fn>
 bool with_linear1_ts_instance(int hdp, int D, Fn &&fn) {  // fn(head width, hidden) as integral constants; false: no such instance
-#define X(H, K) if (hdp == H && D == K) return fn(int_c<H>{}, int_c<K>{}), true;
+#define X(H, K) if (hdp == H && D == K) return fn(ic<H>{}, ic<K>{}), true;
     LSL_LIN1_TS_INSTANCES(X)
 #undef X
     return false;
@@ -252,7 +250,7 @@ void launch_linear1_ts(int hdp, int D, int waves, bool lnf, const Lin1Args &a, h
 #define LSL_LIN2_WS_INSTANCES(X) X(1536, 3, 3) X(1280, 4, 4) X(768, 3, 3) X(384, 3, 3)
 template <class Fn>
 bool with_linear2_ws_instance(int K2, Fn &&fn) {
-#define X(K, NCH, NS) if (K2 == K) return fn(int_c<K>{}, int_c<NCH>{}, int_c<NS>{}), true;
+#define X(K, NCH, NS) if (K2 == K) return fn(ic<K>{}, ic<NCH>{}, ic<NS>{}), true;
     LSL_LIN2_WS_INSTANCES(X)
 #undef X
     return false;
@@ -585,14 +583,14 @@ void launch_dense_small(float *out, const float *in, const float *W, const float
 }
 
 // ---- the losses: the team forms of k_loss_frag.hip.h, one dispatcher for D = 1..4, one launch of the quotient finals ----
-// f(std::integral_constant<int, D>) for the D of the call (checked by the caller: 1..4)
+// f(ic<D>) for the D of the call (checked by the caller: 1..4)
 template <class Fn>
 void dispatch_d(int D, Fn f) {
     switch (D) {
-        case 1: f(std::integral_constant<int, 1>()); break;
-        case 2: f(std::integral_constant<int, 2>()); break;
-        case 3: f(std::integral_constant<int, 3>()); break;
-        default: f(std::integral_constant<int, 4>()); break;
+        case 1: f(ic<1>()); break;
+        case 2: f(ic<2>()); break;
+        case 3: f(ic<3>()); break;
+        default: f(ic<4>()); break;
     }
 }
 

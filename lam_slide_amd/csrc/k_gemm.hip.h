@@ -18,7 +18,7 @@
 // load-bound.  The epilogue therefore transposes each wave's sub-tile through wave-private LDS (reusing the
 // operand ring) and writes whole 128/256-byte row segments, 16 B per lane.
 #pragma once
-#include "common.hip.h"
+#include "k_mm_frag.hip.h"
 
 struct GemmArgs {
     const u16 *W;  // [F][K] bf16
@@ -29,17 +29,7 @@ struct GemmArgs {
                 // loads, bit1 skip LDS reads + MFMAs, bit2 skip epilogue.  The product library ignores the field.
 };
 
-// byte offset of 16-byte chunk `chunk` of row `row` inside a [rows][BK] bf16 stage image (BK = 64 or 32)
-template <int BK>
-__device__ __forceinline__ int swz_bk(int row, int chunk) {
-    if (BK == 64) return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4);
-    return row * 64 + ((chunk ^ ((row >> 2) & 3)) << 4);
-}
-
-// wave-private output staging: rows of CH 16-byte chunks, chunk index XOR-swizzled by the row so that both the
-// column-wise accumulator writes and the row-wise 16-byte reads spread over the banks
-template <int CH>
-__device__ __forceinline__ int stage_off(int row, int chunk) { return (row * CH + (chunk ^ (row & (CH - 1)))) << 4; }
+// The [rows][BK] bf16 stage image is swz_bk<BK>, the wave-private output staging (rows of eight 16-byte chunks) stage_off: k_mm_frag.hip.h
 
 template <int BF, int BT, int NWF, int NWT, int BK, int NS, bool PERSIST, class Epi>
 struct GemmCfg {
@@ -161,7 +151,7 @@ __global__ void __launch_bounds__(NWF *NWT * 64, (NWF * NWT / 4 > 2 ? NWF * NWT 
 #pragma unroll
         for (int i = 0; i < MI; ++i)
 #pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
+            for (int q4 = 0; q4 < 4; ++q4) {  // (restates acc_from_bias for the NJ tiles of a row at once: 5j)
                 const float4 b = *reinterpret_cast<const float4 *>(bias_lds + f_base + wf * WF + i * 32 + 8 * q4 + 4 * hf);
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) {
@@ -285,15 +275,13 @@ struct EpiLinear1 {
     template <int MI, int NJ>
     static constexpr int min_store_ops() { return MI * NJ * 2; }
 
-    static __device__ __forceinline__ int soff(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
-
     template <int MI, int NJ>
     __device__ __forceinline__ void run(f32x16 (&acc)[MI][NJ], char *stage, int f_wave, int n_wave, int lane, int F, int N) const {
         static_assert(MI % 2 == 0, "feature slabs are 64 wide");
         constexpr int NCO = HDP == 32 ? 8 : 4;  // rotation pairs a lane owns per head
         // opaque copy of the lane id: without it hipcc hoists every per-lane 64-bit address of this epilogue out of the persistent tile
         // loop and keeps them alive across the main loop - as scratch spills (15 pointer pairs)
-        asm volatile("" : "+v"(lane));
+        asm volatile("" : "+v"(lane));  // (opaque_lane on the parameter itself)
         const int r = lane & 31, hf = lane >> 5;
         const int tr = lane >> 3, c = lane & 7;  // read-back: token row within a group of 8, 8-feature chunk
 #pragma unroll
@@ -303,7 +291,7 @@ struct EpiLinear1 {
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
                 const unsigned nn = (unsigned)min(n_wave + j * 32 + r, N - 1);
-                const unsigned n1 = div_magic ? __umulhi(nn, div_magic) : nn;
+                const unsigned n1 = div_magic ? __umulhi(nn, div_magic) : nn;  // (restates token_pos, k_mm_frag.hip.h: profiles/matmul_fragments.txt 5j)
                 const unsigned pos = mod_magic ? n1 - __umulhi(n1, mod_magic) * (unsigned)pos_mod : 0u;
                 int csec = -1;
                 float4 co[NCO];
@@ -320,6 +308,7 @@ struct EpiLinear1 {
                     for (int e = 0; e < 16; ++e) x[e] = a[e];
                     if (sec < 2) {
                         if (sec != csec) {  // (a wave tile usually lies in one section: loaded once per token column)
+                            // (the table rows and the pair rotations below restate rope_rows / rope_pair, which k_linear1_ts calls: 5j)
                             const float4 *tab = (sec == 0 ? rope_q : rope_k) + (size_t)pos * (HDP / 2) + 2 * hf;
 #pragma unroll
                             for (int k = 0; k < NCO; ++k) co[k] = tab[4 * (k >> 1) + (k & 1)];
@@ -330,7 +319,7 @@ struct EpiLinear1 {
                             float ss = 0.0f;
 #pragma unroll
                             for (int e = 0; e < 16; ++e) ss = fmaf(x[e], x[e], ss);
-                            ss = half_pair_sum(ss);
+                            ss = half_pair_sum(ss);  // (restates qk_factor: 5j)
                             const float rr = rsqrtf(fmaf(ss, inv_hd, 1e-6f)) * post;
 #pragma unroll
                             for (int k = 0; k < 8; ++k) {
@@ -345,7 +334,7 @@ struct EpiLinear1 {
                                 sa = fmaf(x[e], x[e], sa);
                                 sb = fmaf(x[8 + e], x[8 + e], sb);
                             }
-                            sa = half_pair_sum(sa);
+                            sa = half_pair_sum(sa);  // (restates qk_factor: 5j)
                             sb = half_pair_sum(sb);
                             const float ra = rsqrtf(fmaf(sa, inv_hd, 1e-6f)) * post, rb = rsqrtf(fmaf(sb, inv_hd, 1e-6f)) * post;
 #pragma unroll
@@ -362,7 +351,7 @@ struct EpiLinear1 {
 #pragma unroll
                             for (int e = 0; e < 4; ++e) x[4 * g + e] = gelu_fast(x[4 * g + e]);
                             const u32x2 pk = {pack2(x[4 * g], x[4 * g + 1]), pack2(x[4 * g + 2], x[4 * g + 3])};
-                            *reinterpret_cast<u32x2 *>(stage + soff(r, 4 * ii + g) + 8 * hf) = pk;
+                            *reinterpret_cast<u32x2 *>(stage + stage_off(r, 4 * ii + g) + 8 * hf) = pk;
                             __builtin_amdgcn_sched_barrier(0);
                         }
                     }
@@ -370,7 +359,7 @@ struct EpiLinear1 {
 #pragma unroll
                         for (int g = 0; g < 4; ++g) {
                             const u32x2 pk = {pack2(x[4 * g], x[4 * g + 1]), pack2(x[4 * g + 2], x[4 * g + 3])};
-                            *reinterpret_cast<u32x2 *>(stage + soff(r, 4 * ii + g) + 8 * hf) = pk;
+                            *reinterpret_cast<u32x2 *>(stage + stage_off(r, 4 * ii + g) + 8 * hf) = pk;
                         }
                     }
                 }
@@ -382,7 +371,7 @@ struct EpiLinear1 {
 #pragma unroll
                 for (int row0 = 0; row0 < 32; row0 += 8) {
                     const int row = row0 + tr, n = n_wave + j * 32 + row;
-                    const u32x4 pk = *reinterpret_cast<const u32x4 *>(stage + soff(row, c));
+                    const u32x4 pk = *reinterpret_cast<const u32x4 *>(stage + stage_off(row, c));
                     if (f_ok && n < N && !LSL_PROBE(probe, 16)) {
                         u16 *dst = to_qkv ? qkv + (size_t)n * (3 * HHD) + f : z + (size_t)n * (HHD + M) + (f - 2 * HHD);
                         store16(dst, pk, probe & 32);
@@ -422,8 +411,7 @@ struct EpiLinear1 {
         // L1 where it uses them)
         {
             const unsigned nn = (unsigned)min(n_wave + j * 32 + 16 * hb + tr, N - 1);
-            const unsigned n1 = div_magic ? __umulhi(nn, div_magic) : nn;
-            const unsigned pos = mod_magic ? n1 - __umulhi(n1, mod_magic) * (unsigned)pos_mod : 0u;
+            const unsigned pos = token_pos(nn, div_magic, mod_magic, pos_mod);
             const float2 *tab = rope + (size_t)pos * (HDP / 2) + (d >> 1);
             k.c0 = *reinterpret_cast<const float4 *>(tab);
             k.c1 = *reinterpret_cast<const float4 *>(tab + 2);
@@ -506,7 +494,7 @@ struct EpiLinear2 {
 
     template <int MI, int NJ>
     __device__ __forceinline__ void run(f32x16 (&acc)[MI][NJ], char *stage, int f_wave, int n_wave, int lane, int F, int N) const {
-        constexpr int WT = NJ * 32, CH = 8;  // 32 fp32 features = 8 chunks of 16 B per staged token row
+        constexpr int WT = NJ * 32;  // (32 fp32 features = 8 chunks of 16 B per staged token row)
         const int r = lane & 31, hf = lane >> 5;
         const int chunk = lane & 7;
 #pragma unroll
@@ -518,7 +506,7 @@ struct EpiLinear2 {
 #pragma unroll
                 for (int q4 = 0; q4 < 4; ++q4) {
                     const float4 v = make_float4(acc[i][j][4 * q4], acc[i][j][4 * q4 + 1], acc[i][j][4 * q4 + 2], acc[i][j][4 * q4 + 3]);
-                    *reinterpret_cast<float4 *>(stage + stage_off<CH>(j * 32 + r, 2 * q4 + hf)) = v;
+                    *reinterpret_cast<float4 *>(stage + stage_off(j * 32 + r, 2 * q4 + hf)) = v;
                 }
             __builtin_amdgcn_sched_barrier(0);  // one slab's temporaries live at a time (VGPR budget)
             // 8 lanes cover the 128-byte slab of one token row; 8 token rows per instruction
@@ -527,15 +515,11 @@ struct EpiLinear2 {
 #pragma unroll 2
             for (int row0 = 0; row0 < WT; row0 += 8) {
                 const int row = row0 + (lane >> 3), n = n_wave + row;
-                const float4 a = *reinterpret_cast<const float4 *>(stage + stage_off<CH>(row, chunk));
+                const float4 a = *reinterpret_cast<const float4 *>(stage + stage_off(row, chunk));
                 if (n < N) {
                     const float4 gt = *reinterpret_cast<const float4 *>(gate + (size_t)((unsigned)n / (unsigned)tokens_per_traj) * mod_stride + f);
                     float *hp = h + (size_t)n * D + f;
-                    float4 hv = *reinterpret_cast<float4 *>(hp);
-                    hv.x = fmaf(gt.x, a.x + b.x, hv.x);
-                    hv.y = fmaf(gt.y, a.y + b.y, hv.y);
-                    hv.z = fmaf(gt.z, a.z + b.z, hv.z);
-                    hv.w = fmaf(gt.w, a.w + b.w, hv.w);
+                    const float4 hv = gate_update4(gt, a.x, a.y, a.z, a.w, b, *reinterpret_cast<float4 *>(hp));
                     store16(hp, __builtin_bit_cast(u32x4, hv), probe & 32);
                 }
             }
@@ -562,7 +546,7 @@ struct EpiLinear2 {
 #pragma unroll
         for (int it = 0; it < 2; ++it) {
             const int n = min(n_wave + j * 32 + 16 * hb + 8 * it + (lane >> 3), N - 1);
-            const unsigned traj = tpt_magic ? __umulhi((unsigned)n, tpt_magic) : (unsigned)n;
+            const unsigned traj = magic_div((unsigned)n, tpt_magic);
             k.gt[it] = *reinterpret_cast<const float4 *>(gate + (size_t)traj * mod_stride + fc);
             k.hv[it] = *reinterpret_cast<const float4 *>(h + (size_t)n * D + fc);
         }
@@ -584,12 +568,7 @@ struct EpiLinear2 {
         const int f = f_wave + i * 32 + 4 * chunk;
         float4 out[2];
 #pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            out[it].x = fmaf(k.gt[it].x, k.a[it].x + k.b.x, k.hv[it].x);
-            out[it].y = fmaf(k.gt[it].y, k.a[it].y + k.b.y, k.hv[it].y);
-            out[it].z = fmaf(k.gt[it].z, k.a[it].z + k.b.z, k.hv[it].z);
-            out[it].w = fmaf(k.gt[it].w, k.a[it].w + k.b.w, k.hv[it].w);
-        }
+        for (int it = 0; it < 2; ++it) out[it] = gate_update4(k.gt[it], k.a[it].x, k.a[it].y, k.a[it].z, k.a[it].w, k.b, k.hv[it]);
         if (C + 1 < 4 * MI) fetch<(C + 1) % (4 * MI)>(acc, stage, f_wave, n_wave, lane, F, N, k);
 #pragma unroll
         for (int it = 0; it < 2; ++it) {

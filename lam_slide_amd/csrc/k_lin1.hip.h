@@ -32,9 +32,7 @@
 // Bits: every output element is bias + the k-ascending chain of 16-deep MFMA steps, then EpiLinear1's arithmetic in the same order:
 // identical to k_gemm_glds for any launch size (tools/lin1_harness.hip compares the two kernels bit for bit).
 #pragma once
-#include <type_traits>
-
-#include "common.hip.h"
+#include "k_mm_frag.hip.h"
 
 struct Lin1Args {
     const u16 *W;       // [F][K] bf16 (rows padded to 256 by packing.py)
@@ -177,6 +175,7 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) k_linear1_ts(Lin1Args g) {
         if (C::LPR == 64 || lane < C::LPR) {
             // (s_nop 4 on the first piece: src / dst may come straight from a scalar ALU instruction and nothing pads the 5 wait states of
             // "SALU writes SGPR -> VMEM reads it" inside asm; the later pieces read the same registers, long since written)
+            // (k_tail's piece is this statement with m0 = dst: one function for both moved six instances here - profiles/matmul_fragments.txt 5a)
             if (I == 0 || decltype(ic)::value >= 4)
                 asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %0, %1 offset:%4" ::"v"(ls), "s"(src), "s"(dst), "n"(16 * I), "n"(ROWB * I) : "memory", "scc");
             else
@@ -188,16 +187,7 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) k_linear1_ts(Lin1Args g) {
     auto issue = [&](int blk, int slot) __attribute__((always_inline)) {
         const char *src = req_src(blk);
         const unsigned dst = req_dst(slot);
-        issue_piece(src, dst, std::integral_constant<int, 0>());
-        issue_piece(src, dst, std::integral_constant<int, 1>());
-        issue_piece(src, dst, std::integral_constant<int, 2>());
-        issue_piece(src, dst, std::integral_constant<int, 3>());
-        if (PPW == 8) {
-            issue_piece(src, dst, std::integral_constant<int, 4>());
-            issue_piece(src, dst, std::integral_constant<int, 5>());
-            issue_piece(src, dst, std::integral_constant<int, 6>());
-            issue_piece(src, dst, std::integral_constant<int, 7>());
-        }
+        static_for<PPW>([&](auto pc) __attribute__((always_inline)) { issue_piece(src, dst, pc); });
     };
     const int aoff = r * C::PITCH + 16 * hf;  // A fragment of k-step ks: + 32 ks
 
@@ -224,7 +214,7 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) k_linear1_ts(Lin1Args g) {
         dma_slot = 2;
     }
 
-    auto init_acc = [&](f32x16 &a, int blk) __attribute__((always_inline)) {
+    auto init_acc = [&](f32x16 &a, int blk) __attribute__((always_inline)) {  // (restates acc_from_bias: every instance moved through it - 5b)
 #pragma unroll
         for (int q4 = 0; q4 < 4; ++q4) {
             const float4 b = *reinterpret_cast<const float4 *>(bias_lds + blk * 32 + 8 * q4 + 4 * hf);
@@ -253,10 +243,10 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) k_linear1_ts(Lin1Args g) {
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
     };
-    // wave-private staging: [32 tokens][64 features] bf16 = 128-byte rows of eight 16-byte chunks, chunk index XOR (row & 7).
-    //   write (accumulator layout): lane (token r, half hf), block half ii, feature group q: 8 bytes at r 128 + 16 ((4 ii + q) ^ (r & 7)) + 8 hf
-    //                               = wr0 ^ (64 ii + 16 q): one per-lane register, the XOR constant is compile-time
-    //   read (row-wise): lane (tr = lane >> 3, c = lane & 7), rows row0 + tr, row0 = 0, 8, 16, 24: rd0 + 128 row0 (immediates)
+    // wave-private staging: [32 tokens][64 features] bf16, the stage_off image (k_mm_frag.hip.h, whose static_assert holds these two to it).
+    //   write (accumulator layout): lane (token r, half hf), block half ii, feature group q: stage_off(r, 4 ii + q) + 8 hf = wr0 ^ (64 ii + 16 q):
+    //                               one per-lane register, the XOR constant is compile-time
+    //   read (row-wise): lane (tr = lane >> 3, c = lane & 7), rows row0 + tr, row0 = 0, 8, 16, 24: stage_off(row0 + tr, c) = rd0 + 128 row0 (immediates)
     const unsigned wr0 = (unsigned)(size_t)(LDS_PTR(char))(stage) + r * 128 + 8 * hf + ((r & 7) << 4);
     const unsigned rd0 = (unsigned)(size_t)(LDS_PTR(char))(stage) + (lane >> 3) * 128 + (((lane & 7) ^ ((lane >> 3) & 7)) << 4);
     // A finished 64-feature slab (blocks b_even, b_even + 1) leaves the staging image as whole 128-byte row segments, 8 token rows per store
@@ -288,8 +278,8 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) k_linear1_ts(Lin1Args g) {
         for (int i = 0; i < 2; ++i) pk[i] = *reinterpret_cast<const LDS_PTR(u32x4)>(rd0 + 1024 * (2 * half + i));
     };
     auto flush_store = [&](int half, const u32x4 (&pk)[2]) __attribute__((always_inline)) {
-        asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 nt\n\ts_nop 1" ::"v"(fl_voff + (2 * half) * fl_stride8), "v"(pk[0]), "s"(fl_base) : "memory");
-        asm volatile("global_store_dwordx4 %0, %1, %2 nt\n\ts_nop 1" ::"v"(fl_voff + (2 * half + 1) * fl_stride8), "v"(pk[1]), "s"(fl_base) : "memory");
+        stream_store16<true>(fl_voff + (2 * half) * fl_stride8, pk[0], fl_base);
+        stream_store16<false>(fl_voff + (2 * half + 1) * fl_stride8, pk[1], fl_base);
     };
     auto flush_store_visible = [&](int half, const u32x4 (&pk)[2]) __attribute__((always_inline)) {
 #pragma unroll
@@ -300,7 +290,7 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) k_linear1_ts(Lin1Args g) {
         const u32x2 pk = {pack2(v0, v1), pack2(v2, v3)};
         *reinterpret_cast<LDS_PTR(u32x2)>(wr0 ^ (unsigned)(64 * ii + 16 * q)) = pk;
     };
-    // EpiLinear1's arithmetic on one accumulator tile (k_gemm.hip.h: EpiLinear1::run; same operations in the same order), cut into 8 slices
+    // EpiLinear1's arithmetic on one accumulator tile (k_gemm.hip.h: EpiLinear1::run; the same qk_factor / rope_pair calls), cut into 8 slices
     // so that each can sit behind 1/8 of the next block's MFMAs; c0 / c1 carry values between slices; result into half `ii` of the staging
     // image, one group of 4 features (8 bytes) at a time
     auto epi_slice = [&](auto sec_c, int s, const f32x16 &a, int ii, float &c0, float &c1) __attribute__((always_inline)) {
@@ -311,17 +301,12 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) k_linear1_ts(Lin1Args g) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) c0 = fmaf(a[8 * s + e], a[8 * s + e], c0);
             }
-            if (s == 1) c0 = rsqrtf(fmaf(half_pair_sum(c0), g.inv_hd, 1e-6f)) * post;
+            if (s == 1) c0 = qk_factor(c0, g.inv_hd, post);
             if (s >= 2 && s < 6) {
                 const int q = s - 2;
                 float o[4];
 #pragma unroll
-                for (int kk = 0; kk < 2; ++kk) {
-                    const int k = 2 * q + kk;
-                    const float x0 = a[2 * k], x1 = a[2 * k + 1];
-                    o[2 * kk] = c0 * fmaf(co[k].x, x0, -co[k].y * x1);
-                    o[2 * kk + 1] = c0 * fmaf(co[k].z, x0, co[k].w * x1);
-                }
+                for (int kk = 0; kk < 2; ++kk) rope_pair(c0, co[2 * q + kk], a[2 * (2 * q + kk)], a[2 * (2 * q + kk) + 1], o[2 * kk], o[2 * kk + 1]);
                 put_group(ii, q, o[0], o[1], o[2], o[3]);
             }
         } else if constexpr (SEC == LIN1_QK) {  // two 16-wide heads per block: accumulator rows 0-15 and 16-31
@@ -334,21 +319,15 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) k_linear1_ts(Lin1Args g) {
                 c1 = 0.0f;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) c1 = fmaf(a[8 + e], a[8 + e], c1);
-                c0 = rsqrtf(fmaf(half_pair_sum(c0), g.inv_hd, 1e-6f)) * post;
-                c1 = rsqrtf(fmaf(half_pair_sum(c1), g.inv_hd, 1e-6f)) * post;
+                c0 = qk_factor(c0, g.inv_hd, post);
+                c1 = qk_factor(c1, g.inv_hd, post);
             }
             if (s >= 2 && s < 6) {
                 const int q = s - 2;
                 const float rr = q < 2 ? c0 : c1;
                 float o[4];
 #pragma unroll
-                for (int kk = 0; kk < 2; ++kk) {
-                    const int k = 2 * q + kk;
-                    const float x0 = a[2 * k], x1 = a[2 * k + 1];
-                    const float4 cf = co[k & (NCO - 1)];
-                    o[2 * kk] = rr * fmaf(cf.x, x0, -cf.y * x1);
-                    o[2 * kk + 1] = rr * fmaf(cf.z, x0, cf.w * x1);
-                }
+                for (int kk = 0; kk < 2; ++kk) rope_pair(rr, co[(2 * q + kk) & (NCO - 1)], a[2 * (2 * q + kk)], a[2 * (2 * q + kk) + 1], o[2 * kk], o[2 * kk + 1]);
                 put_group(ii, q, o[0], o[1], o[2], o[3]);
             }
         } else if constexpr (SEC == LIN1_MLP) {
@@ -376,28 +355,29 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) k_linear1_ts(Lin1Args g) {
 #pragma unroll
             for (int ks = 0; ks < PD; ++ks) fr[ks] = as_bf16x8(*reinterpret_cast<const u32x4 *>(sb + 32 * ks));
         }
-        side(std::integral_constant<int, -1>());
-#define LIN1_SIDE(S) if (s == S) side(std::integral_constant<int, S>());
+        side(ic<-1>());
+        auto side_of = [&](int s) __attribute__((always_inline)) {  // side(ic<s>()) for the unrolled slice counter
+            static_for<8>([&](auto sc) __attribute__((always_inline)) { if (s == decltype(sc)::value) side(sc); });
+        };
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
 #pragma unroll
             for (int m = 0; m < MPS; ++m) {
-                if (m == MH) { LIN1_SIDE(0) LIN1_SIDE(1) LIN1_SIDE(2) LIN1_SIDE(3) LIN1_SIDE(4) LIN1_SIDE(5) LIN1_SIDE(6) LIN1_SIDE(7) }
+                if (m == MH) side_of(s);
                 if (DO_MFMA) {
                     const int ks = s * MPS + m;
                     ac = mfma32(fr[ks % PD], xreg[ks], ac);
                     if (ks + PD < KS) fr[ks % PD] = as_bf16x8(*reinterpret_cast<const u32x4 *>(sb + 32 * (ks + PD)));
                 }
             }
-            if (MH == MPS) { LIN1_SIDE(0) LIN1_SIDE(1) LIN1_SIDE(2) LIN1_SIDE(3) LIN1_SIDE(4) LIN1_SIDE(5) LIN1_SIDE(6) LIN1_SIDE(7) }  // (one MFMA per slice)
+            if (MH == MPS) side_of(s);  // (one MFMA per slice)
             if (DO_EPI) epi_slice(sec_c, s, ae, PAR, c0, c1);
             __builtin_amdgcn_sched_barrier(0);
         }
-#undef LIN1_SIDE
         if (decltype(mfma_c)::value != 0) slot_c = next_slot(slot_c);
     };
-    std::integral_constant<int, 0> I0;
-    std::integral_constant<int, 1> I1;
+    ic<0> I0;
+    ic<1> I1;
     auto no_side = [](auto) __attribute__((always_inline)) {};
     // fused step: MFMAs of block e + 1 beside the epilogue of block e (parity PAR = e & 1, section SEC).  FLUSH (PAR == 0 steps except the first
     // of a segment): the slab (e - 2, e - 1) is complete in the staging image and leaves during this step; PREV_FLUSHED: the previous step did
@@ -427,17 +407,17 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) k_linear1_ts(Lin1Args g) {
             constexpr int PS = PPW / 4;  // pieces per slice: 1 (8 waves), 2 (4 waves)
             if (!B2) {
                 if (SL >= 2 && SL < 6) {
-                    issue_piece(src, dst, std::integral_constant<int, (SL >= 2 && SL < 6) ? PS * (SL - 2) : 0>());
-                    if (PS == 2) issue_piece(src, dst, std::integral_constant<int, (SL >= 2 && SL < 6) ? PS * (SL - 2) + 1 : 0>());
+                    issue_piece(src, dst, ic<(SL >= 2 && SL < 6) ? PS * (SL - 2) : 0>());
+                    if (PS == 2) issue_piece(src, dst, ic<(SL >= 2 && SL < 6) ? PS * (SL - 2) + 1 : 0>());
                 }
             } else if (PAR == 1) {  // both blocks of the next pair: their pieces behind the 8 slices (PAR == 1 steps never flush)
                 if (SL >= 0 && SL < 4) {
-                    issue_piece(src, dst, std::integral_constant<int, (SL >= 0 && SL < 4) ? PS * SL : 0>());
-                    if (PS == 2) issue_piece(src, dst, std::integral_constant<int, (SL >= 0 && SL < 4) ? PS * SL + 1 : 0>());
+                    issue_piece(src, dst, ic<(SL >= 0 && SL < 4) ? PS * SL : 0>());
+                    if (PS == 2) issue_piece(src, dst, ic<(SL >= 0 && SL < 4) ? PS * SL + 1 : 0>());
                 }
                 if (SL >= 4 && SL < 8) {
-                    issue_piece(src2, dst2, std::integral_constant<int, (SL >= 4 && SL < 8) ? PS * (SL - 4) : 0>());
-                    if (PS == 2) issue_piece(src2, dst2, std::integral_constant<int, (SL >= 4 && SL < 8) ? PS * (SL - 4) + 1 : 0>());
+                    issue_piece(src2, dst2, ic<(SL >= 4 && SL < 8) ? PS * (SL - 4) : 0>());
+                    if (PS == 2) issue_piece(src2, dst2, ic<(SL >= 4 && SL < 8) ? PS * (SL - 4) + 1 : 0>());
                 }
             }
         });
@@ -463,20 +443,15 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) k_linear1_ts(Lin1Args g) {
         }
         if (e < eb) fused(sec_c, I0, I1, I0, e);
     };
-    auto load_co = [&](const float4 *tab, unsigned pos) __attribute__((always_inline)) {
-        const float4 *t = tab + (size_t)pos * (HDP / 2) + 2 * hf;
-#pragma unroll
-        for (int k = 0; k < NCO; ++k) co[k] = t[4 * (k >> 1) + (k & 1)];
-    };
-    std::integral_constant<int, LIN1_QK> SQK;
-    std::integral_constant<int, LIN1_V> SV;
-    std::integral_constant<int, LIN1_MLP> SMLP;
+    auto load_co = [&](const float4 *tab, unsigned pos) __attribute__((always_inline)) { rope_rows<HDP>(co, tab, pos, hf); };
+    ic<LIN1_QK> SQK;
+    ic<LIN1_V> SV;
+    ic<LIN1_MLP> SMLP;
 
     // The wave's tokens as B fragments of all k-steps (X is padded to whole tiles): whole 128-byte lines per 8 lanes (8 rows x 128 B per
     // instruction: 8 cache lines, where a fragment-shaped load of one k-step touches 32 - the texture-address unit then needs ~ 58 cycles
     // per instruction, 15 000 cycles for a workgroup's 256: measured), then - finish_x - line by line through the wave's staging image into
-    // fragment order, in place: line j of every row holds the k-steps 4 j .. 4 j + 3; chunk c of row t sits at t 128 + 16 (c ^ ((t >> 1) & 7)),
-    // conflict-free for both accesses.
+    // fragment order, in place: line_to_frags of k_mm_frag.hip.h, written out here.
     constexpr bool XLINES = LIN1_XLOAD != 0 && (K <= 384 || LIN1_XLOAD >= 2);  // (K = 512: 7 more spilled registers for - 1.7 %: not taken)
     auto load_x = [&](int nw) __attribute__((always_inline)) {
         if (!XLINES) {
@@ -484,15 +459,12 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) k_linear1_ts(Lin1Args g) {
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) xreg[ks] = as_bf16x8(*reinterpret_cast<const u32x4 *>(xr + 16 * ks));
         } else {
-            const u16 *xr = g.X + (size_t)(nw + (lane >> 3)) * K + 8 * (lane & 7);
-#pragma unroll
-            for (int j = 0; j < KS / 4; ++j)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) xreg[4 * j + q] = as_bf16x8(*reinterpret_cast<const u32x4 *>(xr + (size_t)(8 * q) * K + 64 * j));
+            load_lines<KS>(xreg, g.X, nw, K, lane);
         }
     };
     auto finish_x = [&]() __attribute__((always_inline)) {
         if (!XLINES) return;
+        // (restates line_to_frags, held to stage_off_pair by its static_assert: through the call twelve instances compiled to other text - 5c)
         const unsigned t0 = lane >> 3;  // row of instruction q: t0 + 8 q, (row >> 1) & 7 = ((t0 >> 1) + 4 q) & 7
         const unsigned xw = (unsigned)(size_t)(LDS_PTR(char))(stage) + t0 * 128;
         const unsigned xr0 = (unsigned)(size_t)(LDS_PTR(char))(stage) + r * 128;
@@ -513,7 +485,7 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) k_linear1_ts(Lin1Args g) {
     // per element as k_ln_modulate (one rounding to bf16); the statistics are combined in another order, so the operand can differ from the
     // default path's by an ulp of bf16 here and there: the form is a property of the model handle, never of the launch.
     float *const ln_tab = bias_lds + ((g.F + 3) & ~3);  // [LN_SLOTS][2][K]: 1 + scale, shift
-    auto traj_of = [&](unsigned n) __attribute__((always_inline)) { return g.ln_tpt_magic ? __umulhi(n, g.ln_tpt_magic) : n; };
+    auto traj_of = [&](unsigned n) __attribute__((always_inline)) { return magic_div(n, g.ln_tpt_magic); };
     auto load_x_lnf = [&](int tile_, int nw) __attribute__((always_inline)) {
         typedef __attribute__((ext_vector_type(4))) float f4;
         const float *xf = reinterpret_cast<const float *>(g.X);
@@ -585,8 +557,7 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) k_linear1_ts(Lin1Args g) {
             finish_x();
         }
         const unsigned nn = (unsigned)min(n_wave + r, g.N - 1);
-        const unsigned n1 = g.div_magic ? __umulhi(nn, g.div_magic) : nn;
-        const unsigned pos = g.mod_magic ? n1 - __umulhi(n1, g.mod_magic) * (unsigned)g.pos_mod : 0u;
+        const unsigned pos = token_pos(nn, g.div_magic, g.mod_magic, g.pos_mod);
 
         // first block of the segment: MFMAs only.  The activation loads sit in the vector-memory queue behind the ring's DMA requests, so the
         // per-step counted wait does not apply here.  A later segment's loads were issued BEFORE the previous segment's last four slab stores
@@ -653,8 +624,7 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) k_linear1_ts(Lin1Args g) {
             if constexpr (!LNF) load_x(nw);
             if (b1 - 1 >= 2 * qb) {  // the drain below is not a q / k block: co is free for the next segment's q table
                 const unsigned nn2 = (unsigned)min(nw + r, g.N - 1);
-                const unsigned m1 = g.div_magic ? __umulhi(nn2, g.div_magic) : nn2;
-                load_co(g.rope_q, g.mod_magic ? m1 - __umulhi(m1, g.mod_magic) * (unsigned)g.pos_mod : 0u);
+                load_co(g.rope_q, token_pos(nn2, g.div_magic, g.mod_magic, g.pos_mod));
                 co_ready = true;
             }
             asm volatile("" ::: "memory");

@@ -30,9 +30,7 @@
 // Bits: every output element = the k-ascending chain of 16-deep MFMA steps from zero, + bias, fma with the gate onto the residual:
 // identical to the tile kernels for any launch size (tools/lin2_harness.hip compares the two bit for bit).
 #pragma once
-#include <type_traits>
-
-#include "common.hip.h"
+#include "k_mm_frag.hip.h"
 
 struct Lin2Args {
     const u16 *Wp;      // packed by k_lin2_pack: [F / 32][2][K / 32][64 lanes] x 16 B
@@ -55,14 +53,6 @@ struct Lin2Args {
 #ifndef LIN2_PD
 #define LIN2_PD 2  // token fragments requested this many k-steps ahead of their MFMA
 #endif
-
-template <int N, int I = 0, class F>
-__device__ __forceinline__ void static_for(F &f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>());
-        static_for<N, I + 1>(f);
-    }
-}
 
 template <int K, int NCH, int NS, bool HB2>
 struct Lin2Cfg {
@@ -91,7 +81,7 @@ struct Lin2Cfg {
 };
 
 // W [F][K] row-major -> fragment order of k_linear2_ws: [F / 32][2 halves][K / 32 k-steps][64 lanes] x 8 bf16, lane (r = lane & 31, hf =
-// lane >> 5) of k-step ks of half o = W[32 fb + r][o K/2 + 16 ks + 8 hf .. + 7]: the A operand of mfma32 as it is loaded (common.hip.h)
+// lane >> 5) of k-step ks of half o = W[32 fb + r][o K/2 + 16 ks + 8 hf .. + 7]: afrag_src<32> (k_mm_frag.hip.h)
 __global__ void __launch_bounds__(256) k_lin2_pack(u16 *out, const u16 *W, int F, int K) {
     const int ksh = K / 32;
     const long total = (long)(F / 32) * 2 * ksh * 64;
@@ -101,8 +91,7 @@ __global__ void __launch_bounds__(256) k_lin2_pack(u16 *out, const u16 *W, int F
         const int ks = (int)(t % ksh);
         t /= ksh;
         const int o = (int)(t & 1), fb = (int)(t >> 1);
-        const u16 *src = W + (size_t)(32 * fb + (lane & 31)) * K + o * (K / 2) + 16 * ks + 8 * (lane >> 5);
-        *reinterpret_cast<u32x4 *>(out + i * 8) = *reinterpret_cast<const u32x4 *>(src);
+        *reinterpret_cast<u32x4 *>(out + i * 8) = *reinterpret_cast<const u32x4 *>(W + afrag_src<32>(32 * fb, o * (K / 2), ks, lane, K));
     }
 }
 
@@ -141,6 +130,8 @@ __global__ void __launch_bounds__(512, 2) k_linear2_ws(Lin2Args g) {
     // (waited for below with a builtin that hipcc's wait-count pass sees: left pending, it would put s_waitcnt vmcnt(0) in front of the first
     // use of each register INSIDE the loops, which at run time also drains the LDS-DMA requests and touches it cannot see)
     // ---- bias of the slice and the gate rows of the trajectories this range spans ----
+    // (the three token -> trajectory selects below restate magic_div, k_mm_frag.hip.h: wrapped in the function they moved all eight instances,
+    // <1536, 3, 3> from 250 to 256 VGPRs, <384, 3, 3> from 5 waves to 4 - profiles/matmul_fragments.txt 5d)
     const int n_lo = blk0 * 32, n_hi = min(blk1 * 32, g.N) - 1;
     const unsigned traj_lo = g.mod_stride ? (g.tpt_magic ? __umulhi((unsigned)n_lo, g.tpt_magic) : (unsigned)n_lo) : 0u;
     {
@@ -277,12 +268,9 @@ __global__ void __launch_bounds__(512, 2) k_linear2_ws(Lin2Args g) {
     const unsigned hbuf_lds = lds0 + C::HBUF + p * C::HB_PER_WAVE;
     const unsigned row_bytes = 4u * g.F;
     auto hb_off = [](int b) __attribute__((always_inline)) { return HB2 ? (b & 1) * 4096 : 0; };
-    auto opaque_lane = [&]() __attribute__((always_inline)) {
-        int l = lane;
-        asm volatile("" : "+v"(l));
-        return l;
-    };
-    // residual rows of block b of the range -> the wave's LDS image: 4 LDS-DMA instructions of 8 rows x 128 B, slot (row, s) <- chunk s ^ (row & 7)
+    auto opaque_lane = [&]() __attribute__((always_inline)) { return ::opaque_lane(lane); };
+    // residual rows of block b of the range -> the wave's LDS image: 4 LDS-DMA instructions of 8 rows x 128 B, slot (row, s) <- chunk s ^ (row & 7):
+    // the stage_off image of k_mm_frag.hip.h, whose static_assert holds the three sites below to it (per-lane forms of its inverse: 5e)
     auto h_request = [&](int b) __attribute__((always_inline)) {
         const int l = opaque_lane(), tr = l >> 3, ch = (l & 7) ^ (tr & 7);
 #pragma unroll
@@ -332,11 +320,7 @@ __global__ void __launch_bounds__(512, 2) k_linear2_ws(Lin2Args g) {
             const float4 bs = *reinterpret_cast<const float4 *>(bp + 8 * q);
             const float4 gt = *reinterpret_cast<const float4 *>(gp + 8 * q);
             float4 *hp = reinterpret_cast<float4 *>(hrow + 16 * ((2 * q + hh) ^ (rr & 7)));
-            float4 hv = *hp;
-            hv.x = fmaf(gt.x, acc[4 * q] + bs.x, hv.x);
-            hv.y = fmaf(gt.y, acc[4 * q + 1] + bs.y, hv.y);
-            hv.z = fmaf(gt.z, acc[4 * q + 2] + bs.z, hv.z);
-            hv.w = fmaf(gt.w, acc[4 * q + 3] + bs.w, hv.w);
+            const float4 hv = gate_update4(gt, acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3], bs, *hp);
             *hp = hv;
             if constexpr (LNS) w[q] = hv;
         }
@@ -350,7 +334,7 @@ __global__ void __launch_bounds__(512, 2) k_linear2_ws(Lin2Args g) {
         if (ragged) {
             if (n < g.N) store16(reinterpret_cast<char *>(g.h) + voff, v, true);
         } else
-            asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 nt\n\ts_nop 1" ::"v"(voff), "v"(v), "s"(g.h) : "memory");
+            stream_store16<true>(voff, v, g.h);
     };
 
     // hi block-step m (1 .. nblk): chain of block B = m - 1 from the lo wave's hand-off, epilogue of block B - 1.  Vector-memory order of a

@@ -23,9 +23,8 @@
 //
 // Reference lines: latent_si_v31.py:45-63,168-188; mmdit.py:11-22,85-148,184-249; integrators.py:29-37,103-120.
 #pragma once
-#include "common.hip.h"
+#include "k_mm_frag.hip.h"
 #include "k_small.hip.h"
-#include <type_traits>
 
 typedef __attribute__((ext_vector_type(4))) float f32x4v;
 
@@ -62,7 +61,7 @@ __global__ void __launch_bounds__(256) k_res_pack(u16 *wout, float *pout, ResPac
         u16 *dst = (second ? wb + RES_W1_ELEMS : wb) + (size_t)tile * 16 * K;
         for (int i = tid; i < nks * 64; i += 256) {
             const int ks = i >> 6, lane = i & 63;
-            *reinterpret_cast<u32x4 *>(dst + (size_t)i * 8) = *reinterpret_cast<const u32x4 *>(src + (size_t)(tile * 16 + (lane & 15)) * K + 32 * ks + 8 * (lane >> 4));
+            *reinterpret_cast<u32x4 *>(dst + (size_t)i * 8) = *reinterpret_cast<const u32x4 *>(src + afrag_src<16>(tile * 16, 0, ks, lane, K));
         }
     } else {
         for (int i = tid; i < RES_P_SHIFT; i += 256)
@@ -140,9 +139,7 @@ __device__ __forceinline__ float row16_sum(float v) {
     return v;
 }
 
-// byte offset of 16-byte chunk c of row r in a bf16 image with 256-byte chunk groups (a: one group per row; z: three)
-__device__ __forceinline__ int res_swz(int row, int chunk) { return ((chunk & ~15) | ((chunk ^ row) & 15)) << 4; }
-
+// (the bf16 images a and z are swizzled by res_swz, k_mm_frag.hip.h: 256-byte chunk groups, a: one group per row; z: three)
 constexpr int RES_NW = 8, RES_NTHR = RES_NW * 64;
 
 // max over the 4 lanes {l, l^16, l^32, l^48} (see col_sum4)
@@ -199,6 +196,7 @@ __global__ void __launch_bounds__(RES_NTHR, 2) k_resident(ResArgs A) {
     int r16 = lane & 15, g4 = lane >> 4;
     // hipcc hoists every per-lane address of the phases below (dozens of 64-bit pairs) out of the step / block loops and then spills them;
     // declaring the lane coordinates "modified" at the top of a loop body keeps each address computation next to its use
+    // (opaque_lane of k_mm_frag.hip.h on the four lane coordinates at once: they are variables of the whole kernel here, not of a phase)
 #define RES_OPAQUE_LANE() asm volatile("" : "+v"(tid), "+v"(lane), "+v"(r16), "+v"(g4))
     const int b = blockIdx.x, n_t = A.n_t, C = A.C, T = A.T, L = A.L;
     const size_t xoff = (size_t)b * n_t * C;
@@ -513,7 +511,7 @@ __global__ void __launch_bounds__(RES_NTHR, 2) k_resident(ResArgs A) {
                         float ss = 0.0f;
 #pragma unroll
                         for (int e = 0; e < 8; ++e) ss = fmaf(v[e], v[e], ss);
-                        ss = col_sum4(ss);
+                        ss = col_sum4(ss);  // (qk_factor's formula over the 16x16 tile's four row groups; the scales are not folded into the table here)
                         const float rr = rsqrtf(fmaf(ss, 1.0f / RES_HD, 1e-6f)) * post;
                         const int pos = temporal ? pos_t[nt] : pos_l[nt];
 #pragma unroll
@@ -681,9 +679,9 @@ __global__ void __launch_bounds__(RES_NTHR, 2) k_resident(ResArgs A) {
                         *reinterpret_cast<u32x4 *>(zs + (size_t)n * 768 + res_swz(n, 4 * hh + c)) = w;
                     }
                 };
-                if (S <= 2) quad_attention(std::integral_constant<int, 2>{});
-                else if (S <= 4) quad_attention(std::integral_constant<int, 4>{});
-                else quad_attention(std::integral_constant<int, 8>{});
+                if (S <= 2) quad_attention(ic<2>{});
+                else if (S <= 4) quad_attention(ic<4>{});
+                else quad_attention(ic<8>{});
             }
             res_barrier();
             RES_STAMP(2);
@@ -720,7 +718,7 @@ __global__ void __launch_bounds__(RES_NTHR, 2) k_resident(ResArgs A) {
                     const int n = 16 * nt + r16;
                     if (n < n_t) {
                         float *hp = hs + (size_t)n * RES_HS + f0 + 4 * g4;
-                        hv[nt].x = fmaf(gt.x, acc[nt][0], hv[nt].x);
+                        hv[nt].x = fmaf(gt.x, acc[nt][0], hv[nt].x);  // (not gate_update4: the accumulators started from b2, there is no add)
                         hv[nt].y = fmaf(gt.y, acc[nt][1], hv[nt].y);
                         hv[nt].z = fmaf(gt.z, acc[nt][2], hv[nt].z);
                         hv[nt].w = fmaf(gt.w, acc[nt][3], hv[nt].w);

@@ -36,9 +36,7 @@
 // gate onto the residual like EpiLinear2 (k_gemm.hip.h); row statistics two-pass in fp32 like k_ln_modulate_v4 with another summation tree.
 // Not bit-identical to the linear2 / LayerNorm kernels it replaces (same numerics class: fp32 accumulation of bf16 products).
 #pragma once
-#include <type_traits>
-
-#include "common.hip.h"
+#include "k_mm_frag.hip.h"
 
 struct TailArgs {
     const u16 *wt;       // packed weight stream of this sub-block (k_tail_pack)
@@ -76,6 +74,7 @@ struct TailCfg {
 };
 
 // Weight stream of one sub-block.  16-byte piece i = lane (r = lane & 31, hf = lane >> 5) of fragment f of chunk c:
+//   (U and Wo fragments are afrag_src<32>, k_mm_frag.hip.h; D(j) is the same rows with its own column permutation)
 //   c < CO                      Wo:  fragment f = 2 ft + s -> W2[32 ft + r][32 c + 16 s + 8 hf + 0..7]
 //   then e = c - CO: e = 0 U(0); odd e < 2 MB - 1: U((e + 1) / 2); even e: D(e / 2 - 1); e = 2 MB - 1: D(MB - 1)
 //   U(j): fragment ks -> W1[3 HHD + 32 j + r][16 ks + 8 hf + 0..7]
@@ -91,13 +90,13 @@ __global__ void __launch_bounds__(256) k_tail_pack(u16 *out, const u16 *W1, cons
         u32x4 v;
         if (c < CO) {
             const int ft = f >> 1, s = f & 1;
-            v = *reinterpret_cast<const u32x4 *>(W2 + (size_t)(32 * ft + r) * K2 + 32 * c + 16 * s + 8 * hf);
+            v = *reinterpret_cast<const u32x4 *>(W2 + afrag_src<32>(32 * ft, 32 * c, s, lane, K2));
         } else {
             const int e = c - CO;
             const bool up = e == 0 || ((e & 1) && e < 2 * MB - 1);
             if (up) {
                 const int j = e == 0 ? 0 : (e + 1) >> 1;
-                v = *reinterpret_cast<const u32x4 *>(W1 + (size_t)(3 * HHD + 32 * j + r) * D + 16 * f + 8 * hf);
+                v = *reinterpret_cast<const u32x4 *>(W1 + afrag_src<32>(3 * HHD + 32 * j, 0, f, lane, D));
             } else {
                 const int j = e == 2 * MB - 1 ? MB - 1 : (e >> 1) - 1;
                 const int ft = f >> 1, s = f & 1;
@@ -136,17 +135,13 @@ __global__ void __launch_bounds__(512, 2) k_tail(TailArgs g) {
     // is laundered INSIDE that phase: hipcc cannot hoist those values out of the round loop, where - with the output tile, the activations and
     // two accumulator tiles resident - they would live in scratch, and a scratch reload inside the chunk loop is a vector-memory operation
     // whose wait also waits for the ring requests just issued.
-    auto fresh_lane = [&]() __attribute__((always_inline)) {
-        int l = lane;
-        asm volatile("" : "+v"(l));
-        return l;
-    };
+    auto fresh_lane = [&]() __attribute__((always_inline)) { return opaque_lane(lane); };
     // ---- weight ring: the stream's chunk k -> slot k mod 4; wave w requests fragments PPW w .. PPW w + PPW - 1 of a chunk, one LDS-DMA
     // instruction each (inline asm on purpose, k_lin1.hip.h: behind the builtin hipcc waits for the request in front of the next LDS access)
     const unsigned lds0 = (unsigned)(size_t)(LDS_PTR(char))(smem);
     const char *const w_base = reinterpret_cast<const char *>(g.wt) + (size_t)wave * PPW * 1024;
-    auto issue_piece = [&](const char *src, unsigned dst, auto ic) __attribute__((always_inline)) {
-        constexpr int I = decltype(ic)::value;
+    auto issue_piece = [&](const char *src, unsigned dst, auto pc) __attribute__((always_inline)) {
+        constexpr int I = decltype(pc)::value;
         const unsigned ls = (unsigned)fresh_lane() * 16u;
         asm volatile("s_add_u32 m0, %2, 0\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %0, %1 offset:%3" ::"v"(ls), "s"(src), "s"(dst), "n"(1024 * I) : "memory", "scc");
     };
@@ -162,22 +157,15 @@ __global__ void __launch_bounds__(512, 2) k_tail(TailArgs g) {
     static_assert(PPW >= 1 && PPW <= 2 && CHF >= 8, "2 PPW pieces per wave and pair, behind MFMAs 1, 3, 5, 7 of a chunk");
     auto issue_q = [&](auto qc) __attribute__((always_inline)) {  // piece q of the pair: chunk q / PPW, fragment q % PPW of the wave's PPW
         constexpr int Q = decltype(qc)::value;
-        if constexpr (Q < 2 * PPW) issue_piece(d_src + (Q / PPW) * CH, d_dst + (Q / PPW) * CH, std::integral_constant<int, Q % PPW>());
-    };
-    auto issue_pair = [&]() __attribute__((always_inline)) {
-        pair_begin();
-        issue_q(std::integral_constant<int, 0>());
-        issue_q(std::integral_constant<int, 1>());
-        issue_q(std::integral_constant<int, 2>());
-        issue_q(std::integral_constant<int, 3>());
+        if constexpr (Q < 2 * PPW) issue_piece(d_src + (Q / PPW) * CH, d_dst + (Q / PPW) * CH, ic<Q % PPW>());
     };
     // behind MFMA f of the pair's first chunk (DMA = 1): one piece behind MFMAs 1, 3, 5, 7
     auto dma_behind = [&](int f, auto dma_c) __attribute__((always_inline)) {
         if constexpr (decltype(dma_c)::value != 0) {
-            if (f == 1) issue_q(std::integral_constant<int, 0>());
-            if (f == 3) issue_q(std::integral_constant<int, 1>());
-            if (f == 5) issue_q(std::integral_constant<int, 2>());
-            if (f == 7) issue_q(std::integral_constant<int, 3>());
+            if (f == 1) issue_q(ic<0>());
+            if (f == 3) issue_q(ic<1>());
+            if (f == 5) issue_q(ic<2>());
+            if (f == 7) issue_q(ic<3>());
         }
     };
     int slot_c = 0;  // slot of the next chunk this wave computes
@@ -193,32 +181,15 @@ __global__ void __launch_bounds__(512, 2) k_tail(TailArgs g) {
     auto next_slot = [&]() __attribute__((always_inline)) { slot_c = (slot_c + 1) & (NS - 1); };
     auto frag = [&](const char *sb, int f) __attribute__((always_inline)) { return as_bf16x8(*reinterpret_cast<const u32x4 *>(sb + f * 1024)); };
 
-    std::integral_constant<int, 0> E0;
-    issue_pair();
+    ic<0> E0;
+    pair_begin();  // (the stream's first pair)
+    static_for<4>(issue_q);
     __syncthreads();  // bias table
 
     const unsigned st0 = (unsigned)(size_t)(LDS_PTR(char))(aimg);
     const unsigned b1_base = (unsigned)(size_t)(LDS_PTR(char))(smem + C::RING + C::WAVE);  // (uniform)
-    // rows of a [tokens][K] bf16 matrix as MFMA B fragments (k_lin1.hip.h load_x / finish_x): whole 128-byte lines per 8 lanes (8 rows per
-    // instruction), then line by line through the wave's staging image into fragment order: line j of every row holds the k-steps
-    // 4 j .. 4 j + 3; chunk c of row t sits at t 128 + 16 (c ^ ((t >> 1) & 7)), conflict-free for both accesses
-    auto load_rows = [&](auto &xreg, auto ks_c, const u16 *X, int n0, int stride) __attribute__((always_inline)) {
-        constexpr int NK = decltype(ks_c)::value;
-        const int l = fresh_lane(), chunk = l & 7, rowi = l >> 3;
-        const u16 *xr = X + (size_t)(n0 + rowi) * stride + 8 * chunk;
-#pragma unroll
-        for (int j = 0; j < NK / 4; ++j)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) xreg[4 * j + q] = as_bf16x8(*reinterpret_cast<const u32x4 *>(xr + (size_t)(8 * q) * stride + 64 * j));
-    };
-    auto finish_line = [&](bf16x8 (&x4)[4]) __attribute__((always_inline)) {  // one line (4 row-wise registers) -> its 4 fragments, in place
-        const int l = fresh_lane(), chunk = l & 7, rowi = l >> 3, r = l & 31, hf = l >> 5;
-        const unsigned xw = st0 + rowi * 128, xr0 = st0 + r * 128;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) *reinterpret_cast<LDS_PTR(u32x4)>(xw + 1024 * q + (((chunk ^ ((rowi >> 1) + 4 * q)) & 7) << 4)) = as_u32x4(x4[q]);
-#pragma unroll
-        for (int m = 0; m < 4; ++m) x4[m] = as_bf16x8(*reinterpret_cast<const LDS_PTR(u32x4)>(xr0 + ((((2 * m + hf) ^ (r >> 1)) & 7) << 4)));
-    };
+    // (rows of a [tokens][K] bf16 matrix become MFMA B fragments by load_lines and, line by line, line_to_frags: k_mm_frag.hip.h)
+    auto finish_line = [&](bf16x8 (&x4)[4]) __attribute__((always_inline)) { line_to_frags(x4, st0, fresh_lane()); };
     constexpr int NPF = NT < 4 ? NT : 4;  // feature tiles of h in flight per wave
     auto load_h = [&](f32x4_t (&v)[4], unsigned hoff, int ft) __attribute__((always_inline)) {  // rows (lane >> 3) + 8 i, 128 bytes of feature tile ft
 #pragma unroll
@@ -230,10 +201,7 @@ __global__ void __launch_bounds__(512, 2) k_tail(TailArgs g) {
         if (wt >= w1) {  // (uniform) no tile for this wave in the last round: pass the round's barriers, keep requesting
             for (int c = 0; c < NPAIR; ++c) {
                 pair_head(E0);
-                issue_q(std::integral_constant<int, 0>());
-                issue_q(std::integral_constant<int, 1>());
-                issue_q(std::integral_constant<int, 2>());
-                issue_q(std::integral_constant<int, 3>());
+                static_for<4>(issue_q);
             }
             continue;
         }
@@ -247,7 +215,7 @@ __global__ void __launch_bounds__(512, 2) k_tail(TailArgs g) {
         // ---- attention half: out^T += Wo z^T ----
         {
             bf16x8 zreg[KZ];
-            load_rows(zreg, std::integral_constant<int, KZ>(), g.Z, n_wave, g.zw);
+            load_lines<KZ>(zreg, g.Z, n_wave, g.zw, fresh_lane());
 #pragma unroll
             for (int j = 0; j < KZ / 4; ++j) finish_line(*reinterpret_cast<bf16x8(*)[4]>(&zreg[4 * j]));
 #pragma unroll
@@ -261,7 +229,7 @@ __global__ void __launch_bounds__(512, 2) k_tail(TailArgs g) {
                 for (int f = 0; f < CHF; ++f) {
                     out[f >> 1] = mfma32(fr[f % PD], zreg[2 * c + (f & 1)], out[f >> 1]);
                     if (f + PD < CHF) fr[f % PD] = frag(sb, f + PD);
-                    if ((c & 1) == 0) dma_behind(f, std::integral_constant<int, 1>());
+                    if ((c & 1) == 0) dma_behind(f, ic<1>());
                 }
                 next_slot();
                 __builtin_amdgcn_sched_barrier(0);  // (one chunk's fragments and temporaries live at a time)
@@ -274,7 +242,7 @@ __global__ void __launch_bounds__(512, 2) k_tail(TailArgs g) {
         bf16x8 areg[KR];
         {
             bf16x8 raw[KS];
-            load_rows(raw, std::integral_constant<int, KS>(), g.A, n_wave, D);
+            load_lines<KS>(raw, g.A, n_wave, D, fresh_lane());
 #pragma unroll
             for (int j = 0; j < KR / 4; ++j) {
                 finish_line(*reinterpret_cast<bf16x8(*)[4]>(&raw[4 * j]));
@@ -308,11 +276,7 @@ __global__ void __launch_bounds__(512, 2) k_tail(TailArgs g) {
             {
                 unsigned ba = b1_base + 16u * (unsigned)(fresh_lane() >> 5) + 128u * (unsigned)j;
                 asm volatile("" : "+v"(ba));  // (one per-lane base + immediates; no strength-reduced running pointer)
-#pragma unroll
-                for (int q4 = 0; q4 < 4; ++q4) {
-                    const f32x4_t b = *reinterpret_cast<const LDS_PTR(f32x4_t)>(ba + 32 * q4);
-                    uc[4 * q4] = b[0]; uc[4 * q4 + 1] = b[1]; uc[4 * q4 + 2] = b[2]; uc[4 * q4 + 3] = b[3];
-                }
+                acc_from_bias(uc, reinterpret_cast<const LDS_PTR(f32x4_t)>(ba));
             }
             const int l16 = fresh_lane() * 16;
             const char *sb = smem + slot_c * CH + l16;
@@ -355,8 +319,8 @@ __global__ void __launch_bounds__(512, 2) k_tail(TailArgs g) {
             next_slot();
             __builtin_amdgcn_sched_barrier(0);
         };
-        std::integral_constant<int, 0> I0;
-        std::integral_constant<int, 1> I1;
+        ic<0> I0;
+        ic<1> I1;
         constexpr int S8 = CHF / 8 > 0 ? CHF / 8 : 1, S4 = CHF / 4;  // one pair behind every S8-th MFMA: 8 words per chunk; every S4-th: 4 words
         // pair (U0, U1): GELU(0) whole behind U(1)
         pair_head(E0);
@@ -388,9 +352,11 @@ __global__ void __launch_bounds__(512, 2) k_tail(TailArgs g) {
         // ---- epilogue: h += gate (out + b2); LayerNorm + modulate of the next sub-block ----
         const int le = fresh_lane(), chunk = le & 7, rowi = le >> 3, r = le & 31, hf = le >> 5;
         const int n_r = min(n_wave + r, g.N - 1);
-        const unsigned traj = g.tpt_magic ? __umulhi((unsigned)n_r, g.tpt_magic) : (unsigned)n_r;
+        const unsigned traj = magic_div((unsigned)n_r, g.tpt_magic);
         const size_t mo = (size_t)traj * g.mod_stride;
-        const unsigned wr_row = st0 + rowi * 128 + (((chunk ^ rowi) & 7) << 4);  // row-wise access: rows rowi + 8 i (same swizzle: (row & 7) = rowi)
+        // (the four staging addresses below restate stage_off, k_mm_frag.hip.h, whose static_assert holds these forms to it: through the
+        // function this kernel compiled to other text, two instructions fewer - profiles/matmul_fragments.txt 5f - and keeps the parent's)
+        const unsigned wr_row = st0 + rowi * 128 + (((chunk ^ rowi) & 7) << 4);  // row-wise access: rows rowi + 8 i at + 1024 i (same swizzle: (row & 7) = rowi)
         const unsigned hoff = (unsigned)(n_wave + rowi) * (unsigned)(4 * D) + 16u * chunk;  // (a pass's h stays below 4 GiB: host-checked)
         float sum = 0.0f;
 #pragma unroll
@@ -405,10 +371,8 @@ __global__ void __launch_bounds__(512, 2) k_tail(TailArgs g) {
                 const float4 gt = *reinterpret_cast<const float4 *>(g.gate + mo + f);
                 const float4 bb = *reinterpret_cast<const float4 *>(g.b2 + f);
                 f32x16 &o = out[ft];
-                o[4 * q] = fmaf(gt.x, o[4 * q] + bb.x, hq[0]);
-                o[4 * q + 1] = fmaf(gt.y, o[4 * q + 1] + bb.y, hq[1]);
-                o[4 * q + 2] = fmaf(gt.z, o[4 * q + 2] + bb.z, hq[2]);
-                o[4 * q + 3] = fmaf(gt.w, o[4 * q + 3] + bb.w, hq[3]);
+                const float4 hn = gate_update4(gt, o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3], bb, make_float4(hq[0], hq[1], hq[2], hq[3]));
+                o[4 * q] = hn.x; o[4 * q + 1] = hn.y; o[4 * q + 2] = hn.z; o[4 * q + 3] = hn.w;
                 sum += (o[4 * q] + o[4 * q + 1]) + (o[4 * q + 2] + o[4 * q + 3]);
             }
 #pragma unroll

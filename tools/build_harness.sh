@@ -16,14 +16,14 @@ lin1|lin2)
   if printf '%s\n' "${flags[@]:-}" | grep -qiE "PROBE|PRIO|ALL_PLAIN|DRAIN_NT|HI_FIRST|DEPHASE"; then
     cp "$root/lam_slide_amd/csrc/k_${which}.hip.h" "$root/tools/_exp/k_${which}_probed.hip.h"
     patch -s "$root/tools/_exp/k_${which}_probed.hip.h" < "$root/tools/experiments/${which}_probes.patch"
-    sed -i 's#"common.hip.h"#"../../lam_slide_amd/csrc/common.hip.h"#' "$root/tools/_exp/k_${which}_probed.hip.h"
+    sed -i 's#"k_mm_frag.hip.h"#"../../lam_slide_amd/csrc/k_mm_frag.hip.h"#' "$root/tools/_exp/k_${which}_probed.hip.h"
     flags+=("-D$(echo $which | tr a-z A-Z)_PROBED")
   fi ;;
 tail)
   if printf '%s\n' "${flags[@]:-}" | grep -q "TAIL_STAMP"; then  # cycle sums per phase (z rows / O phase / a rows / mlp / epilogue)
     cp "$root/lam_slide_amd/csrc/k_tail.hip.h" "$root/tools/_exp/k_tail_stamped.hip.h"
     patch -s "$root/tools/_exp/k_tail_stamped.hip.h" < "$root/tools/experiments/tail_stamps.patch"
-    sed -i 's#"common.hip.h"#"../../lam_slide_amd/csrc/common.hip.h"#' "$root/tools/_exp/k_tail_stamped.hip.h"
+    sed -i 's#"k_mm_frag.hip.h"#"../../lam_slide_amd/csrc/k_mm_frag.hip.h"#' "$root/tools/_exp/k_tail_stamped.hip.h"
     flags+=("-DTAIL_STAMPED")
   fi ;;
 esac
