@@ -49,7 +49,8 @@ extern "C" {
  * 6, later still: lsl_decode_heads, lsl_class_loss_sums, lsl_class_loss_final added the same way.
  * 6, later still: lsl_pair_distances, lsl_ca_frame_stats, lsl_histogram_columns, lsl_js_distance_density added the same way.
  * 6, later still: lsl_debug_mods_ex, lsl_debug_mods_steps, lsl_debug_embed, lsl_debug_head added the same way.
- * 6, later still: lsl_weighted_moments_workspace_bytes, lsl_weighted_moments, lsl_affine_weights, lsl_project_wide added the same way. */
+ * 6, later still: lsl_weighted_moments_workspace_bytes, lsl_weighted_moments, lsl_affine_weights, lsl_project_wide added the same way.
+ * 6, later still: lsl_msm_active_set, lsl_msm_reversible_step, lsl_msm_transition_matrix added the same way. */
 #define LSL_VERSION 6
 
 typedef struct lsl_model lsl_model;
@@ -490,6 +491,38 @@ size_t lsl_kmeans_workspace_bytes(int32_t S, int32_t n, int32_t d, int32_t k);
 int lsl_kmeans_step(const float *y, int32_t S, int32_t n, int32_t d, float *centers, int32_t k, int32_t *labels, int64_t *counts, double *state,
                     int32_t *done, int32_t update, double rel_tol, double center_tol, void *workspace, size_t workspace_bytes, void *stream);
 int lsl_kmeans_nearest_rows(const float *y, int32_t S, int32_t n, int32_t d, const float *centers, int32_t k, int32_t *rows, void *stream);
+
+/* Reversible maximum-likelihood Markov state models: what estimate_markov_model does behind the count matrix (eval_peptide.py:245-288,
+ * modules/analysis.py:47-56: the microstate model, the coarse model and the sampled trajectory's model of every peptide).  S independent count
+ * matrices, one resident workgroup each; device pointers; nothing is allocated, nothing is synchronised, a refused call enqueues nothing.  No
+ * atomics.  The estimator is fixed here as mathematics; parity with a live pyemma is not claimed.
+ *
+ * For one count matrix C i64 [ns, ns] (an entry <= 0 counts as 0, the total below 2^53):
+ *   active set A   the largest strongly connected component (by states) of the graph i -> j where C_ij > 0; a component of one state counts
+ *                  only if C_ii > 0; among components of equal size the one holding the lowest state index; no candidate: A empty.
+ *   restriction    C~ = C[A, A], c_i = sum_j C~_ij, K = C~ + C~^T (counts between A and the rest are dropped).
+ *   iteration      x0_i = sum_j K_ij / sum_ij K_ij (from exact integers, one division).  Step: q_i = c_i / x_i, y_i = sum_{j : K_ij != 0}
+ *                  K_ij / (q_i + q_j), x'_i = y_i / sum_i y_i, err = max_i |x_i - x'_i| / ((x_i + x'_i) / 2).  The step is counted, then the
+ *                  series stops when !(err > maxerr) or when the count reaches maxiter (maxerr < 0 never stops early).
+ *   result         pi = x; X_ij = K_ij / (q_i + q_j) (0 where K_ij = 0), T_ij = X_ij / sum_j X_ij.  |A| = 1: T = [1], pi = [1], no step.
+ *
+ * lsl_msm_active_set: active i32 [S, ns] (0/1) and n_active i32 [S] of counts i64 [S, ns, ns].
+ * lsl_msm_reversible_step: at most `iters` further steps of every series whose done[s] is 0, never past maxiter in total.  x f64 [S, ns] (0
+ *   outside A), n_iter i32 [S], err f64 [S] and done i32 [S] are the state, in and out: a call resumes exactly where the last one stopped, so
+ *   ceil(maxiter / iters) calls are enqueued with no host synchronisation - a series whose done[s] is set leaves before it loads anything and
+ *   none of its buffers is touched.  restart != 0 first sets the state from the counts, whatever it held: x0, n_iter = 0, err = 0, and done
+ *   for |A| <= 1.  done[s] = 1: the stop test held (converged); 2: maxiter steps were counted and the last did not pass it.
+ *   Order.  y_i: with NSP = 32 / 64 / 128 the padded size (the least that holds ns), part h < 8 of row i adds its terms of the columns
+ *   [h NSP / 8, (h + 1) NSP / 8) in ascending j from zero, and the eight parts are added in ascending h; sum_i y_i: a balanced
+ *   tree over each group of min(NSP, 64) rows (row i with i ^ 1, then ^ 2, ...; a row outside A adds +0), the two groups of NSP = 128 in order.  A function of (ns, A) alone: a series has the same bits alone,
+ *   inside any batch and however the steps are split over calls.  Every division is IEEE fp64; a zero entry of K is skipped, not divided.
+ * lsl_msm_transition_matrix: T f64 [S, ns, ns] = the identity with the block of A written in (row sums of X in ascending j), pi f64 [S, ns]
+ *   = x on A and 0 outside: the embedding of eval_peptide.py:261-271.
+ * 1 <= ns <= 128 (fp64 K of a series stays in LDS), 1 <= S <= 65535, iters >= 0, maxiter >= 0, maxerr not NaN (else -3). */
+int lsl_msm_active_set(const int64_t *counts, int32_t S, int32_t ns, int32_t *active, int32_t *n_active, void *stream);
+int lsl_msm_reversible_step(const int64_t *counts, const int32_t *active, int32_t S, int32_t ns, int32_t iters, int32_t maxiter, double maxerr,
+                            int32_t restart, double *x, int32_t *n_iter, double *err, int32_t *done, void *stream);
+int lsl_msm_transition_matrix(const int64_t *counts, const int32_t *active, const double *x, int32_t S, int32_t ns, double *T, double *pi, void *stream);
 
 /* Sampler loop (Sampler.sample_ode / sample_sde inner loops): applies n_steps affine updates to io->x
  * in place.  noise: device [n_noise, B*T*L*C] standard-normal draws, slice s belongs to step s (the

@@ -30,6 +30,10 @@ Public surface (mirrors the reference's for this path only):
   kmeans_fit, nearest_rows, KMeansResult, fit_microstates
                                    <- k-means fitting on the device (kmeans.py): ``analysis.get_kmeans`` of the peptide evaluation and the
                                       ``post_process`` branch of the NBA / pedestrian test_step (``displacement_errors(post_process=True)``)
+  estimate_markov_model, MarkovModel, active_set, pcca_assignments, markov_state_block
+                                   <- the Markov state models of analyze_trajectory (eval_peptide.py:245-288, modules/analysis.py:47-56): the
+                                      largest connected set, the reversible maximum-likelihood estimate of the microstate, coarse and
+                                      trajectory models on the device, PCCA+ assignments by the inner simplex algorithm on the host (msm.py)
   traj_analysis, StructureTables, pair_distances, ca_frame_stats, tica_features, density_js, joint_density_js, ...
                                    <- the structure statistics SIAtom14SampleCallback logs per validation epoch (utils/traj_utils.py
                                       traj_analysis: ramachandran_js, pwd_js, rg_js, tic_js, tic2d_js, val_ca, rmse_contact) of the sampled
@@ -64,6 +68,8 @@ from .tica import (TicaHistograms, TicaModel, assign_centers, cossin_features, f
                    tica_autocovariance, tica_covariances, tica_dimension, tica_histograms, tica_jsd, transition_counts)
 from .torsion_stats import (TorsionStats, angle_histograms, decorrelation, dihedral_angles, eval_torsion_quads, js_distance, lagged_products,
                             summary_metrics, topology_atoms)
+from . import msm
+from .msm import MarkovModel, active_set, estimate_markov_model, markov_state_block, pcca_assignments
 from . import structure_stats
 from .structure_stats import (CaFrameStats, StructureTables, backbone_torsion_quads, ca_atoms, ca_frame_stats, ca_pair_table, column_edges, density_js,
                               histogram_columns, joint_density_js, js_distance_density, pair_distances, tica_atom_selection, tica_features,
@@ -73,7 +79,7 @@ from .koopman_tica import KoopmanWeights, WideTicaModel, koopman_weights, run_ti
 from .transport import (CreateTransport, ModelType, PathType, Sampler, SampleResult, Transport, WeightType, as_transport, device_randn,
                         mix_seed, si_reduce)
 
-__all__ = ["koopman_tica", "KoopmanWeights", "WideTicaModel", "koopman_weights", "run_tica", "weighted_moments", "LatentSIV3", "CreateTransport", "Transport", "Sampler", "SampleResult", "ModelType", "PathType", "WeightType",
+__all__ = ["msm", "MarkovModel", "active_set", "estimate_markov_model", "markov_state_block", "pcca_assignments", "koopman_tica", "KoopmanWeights", "WideTicaModel", "koopman_weights", "run_tica", "weighted_moments", "LatentSIV3", "CreateTransport", "Transport", "Sampler", "SampleResult", "ModelType", "PathType", "WeightType",
            "SecondStageSampler", "setup_conditioning", "sample_sharded", "shard_bounds", "min_ade_fde", "sample_rollout", "best_of_k_errors",
            "RolloutSampler", "Stage1Decoder", "Stage1Encoder", "as_transport", "device_randn", "mix_seed", "si_reduce", "Loss", "geom_losses", "geom_loss_sums", "PeptideLoss", "peptide_losses", "peptide_loss_sums", "displacement_rows", "displacement_errors",
            "DisplacementErrors", "DisplacementMeter", "TorsionStats", "dihedral_angles", "angle_histograms", "js_distance", "lagged_products",

@@ -2,7 +2,7 @@
 // network evaluation (latent_si_v31.py:168-188) and of the sampler loops (integrators.py:67-78,103-120)
 // on the caller's stream.  No allocation, no synchronisation, no host<->device copies.
 // One translation unit: this file = the entry points of the sampling path (model handle, forward, fused sampler + opt-in hipGraph replay,
-// noise, Runge-Kutta state arithmetic, the stochastic-interpolant objective around one evaluation, the geometry losses of the decoded positions, the peptide frame and torsion losses, the displacement errors (ADE / FDE, best-of-K), the torsion statistics (dihedrals, histograms, lagged products, JS distance), the TICA and state statistics (lagged second moments, projection, nearest centre, transition counts), debug taps); host_common / host_launch / host_eval.hip.h = what they enqueue (host_graph.hip.h: the replay cache); decode_host.hip.h +
+// noise, Runge-Kutta state arithmetic, the stochastic-interpolant objective around one evaluation, the geometry losses of the decoded positions, the peptide frame and torsion losses, the displacement errors (ADE / FDE, best-of-K), the torsion statistics (dihedrals, histograms, lagged products, JS distance), the TICA and state statistics (lagged second moments, projection, nearest centre, transition counts), the reversible Markov state models (active set, row-sum iteration, transition matrix), debug taps); host_common / host_launch / host_eval.hip.h = what they enqueue (host_graph.hip.h: the replay cache); decode_host.hip.h +
 // stage1_api.hip.h = the frozen stage-1 encode / decode beside the path (every decoder head from one trunk) and the class losses of those heads.
 #include "../../include/lsl_api.h"
 
@@ -37,6 +37,7 @@
 #include "k_tica.hip.h"
 #include "k_wtica.hip.h"
 #include "k_kmeans.hip.h"
+#include "k_msm.hip.h"
 #include "k_classloss.hip.h"
 #ifdef LSL_EXPERIMENTS  // measured-and-rejected GEMM structures, built only by tools/build_experiments.sh (never in the product library)
 #include "k_gemm_pp.hip.h"        // tools/experiments/ (on the include path of tools/build_experiments.sh only)
@@ -735,6 +736,55 @@ int lsl_kmeans_nearest_rows(const float *y, int32_t S, int32_t n, int32_t d, con
     hipLaunchKernelGGL(k_nearest_rows, dim3((unsigned)((items * P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (int *)rows, y, centers, items, (int)n,
                        (int)d, (int)k, P);
     LSL_CHECK_LAUNCH("lsl_kmeans_nearest_rows");
+    return 0;
+} LSL_API_CATCH
+
+// ---- reversible maximum-likelihood Markov state models: active set, the row-sum iteration, the embedded transition matrix (k_msm.hip.h) ----
+static const char *msm_shape_error(int32_t S, int32_t ns) {
+    if (S < 1 || S > LSL_MSM_MAX_S) return "S outside 1..65535 series";
+    if (ns < 1 || ns > LSL_MSM_MAX_STATES) return "ns outside the native form (1..128 states: fp64 K of a series stays in LDS)";
+    return nullptr;
+}
+
+int lsl_msm_active_set(const int64_t *counts, int32_t S, int32_t ns, int32_t *active, int32_t *n_active, void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!counts || !active || !n_active) return fail(-1, "null argument");
+    if (const char *why = msm_shape_error(S, ns)) return fail(-3, "S = %d, ns = %d: %s", S, ns, why);
+    hipLaunchKernelGGL(k_msm_active, dim3((unsigned)S), dim3(128), 0, (hipStream_t)stream, (const long long *)counts, (int)ns, (int *)active, (int *)n_active);
+    LSL_CHECK_LAUNCH("lsl_msm_active_set");
+    return 0;
+} LSL_API_CATCH
+
+int lsl_msm_reversible_step(const int64_t *counts, const int32_t *active, int32_t S, int32_t ns, int32_t iters, int32_t maxiter, double maxerr,
+                            int32_t restart, double *x, int32_t *n_iter, double *err, int32_t *done, void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!counts || !active || !x || !n_iter || !err || !done) return fail(-1, "null argument");
+    if (const char *why = msm_shape_error(S, ns)) return fail(-3, "S = %d, ns = %d: %s", S, ns, why);
+    if (iters < 0 || maxiter < 0) return fail(-3, "iters = %d and maxiter = %d must not be negative", iters, maxiter);
+    if (maxerr != maxerr) return fail(-3, "maxerr is NaN (a negative maxerr never stops early)");
+    hipStream_t st = (hipStream_t)stream;
+#define LSL_MSM_LAUNCH(NSP) hipLaunchKernelGGL(k_msm_step<NSP>, dim3((unsigned)S), dim3(LSL_MSM_PARTS * NSP), 0, st, (const long long *)counts, (const int *)active, (int)ns, (int)iters, (int)maxiter, maxerr, (int)restart, x, (int *)n_iter, err, (int *)done)
+    const int pad = msm_pad(ns);
+    if (pad == 32) LSL_MSM_LAUNCH(32);
+    else if (pad == 64) LSL_MSM_LAUNCH(64);
+    else LSL_MSM_LAUNCH(128);
+#undef LSL_MSM_LAUNCH
+    LSL_CHECK_LAUNCH("lsl_msm_reversible_step");
+    return 0;
+} LSL_API_CATCH
+
+int lsl_msm_transition_matrix(const int64_t *counts, const int32_t *active, const double *x, int32_t S, int32_t ns, double *T, double *pi, void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!counts || !active || !x || !T || !pi) return fail(-1, "null argument");
+    if (const char *why = msm_shape_error(S, ns)) return fail(-3, "S = %d, ns = %d: %s", S, ns, why);
+    hipStream_t st = (hipStream_t)stream;
+#define LSL_MSM_LAUNCH(NSP) hipLaunchKernelGGL(k_msm_tmatrix<NSP>, dim3((unsigned)S), dim3(256), 0, st, (const long long *)counts, (const int *)active, x, (int)ns, T, pi)
+    const int pad = msm_pad(ns);
+    if (pad == 32) LSL_MSM_LAUNCH(32);
+    else if (pad == 64) LSL_MSM_LAUNCH(64);
+    else LSL_MSM_LAUNCH(128);
+#undef LSL_MSM_LAUNCH
+    LSL_CHECK_LAUNCH("lsl_msm_transition_matrix");
     return 0;
 } LSL_API_CATCH
 

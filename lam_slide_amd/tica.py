@@ -24,7 +24,8 @@ numpy / torch float64 restatement with the same outputs.  ``last_path[name]`` te
                          ``kmeans.kmeans_fit`` of the projected reference, centres ready for ``assign_centers`` (pyemma's own seeded
                          k-means++ stream is not reproduced: centres pyemma fitted enter ``assign_centers`` directly)
 
-Not here: the reversible maximum-likelihood MSM estimate and PCCA (they take the count matrix ``transition_counts`` returns), plots.  The estimator is fixed as
+Not here: plots.  The reversible maximum-likelihood MSM estimate of the count matrix ``transition_counts`` returns and PCCA+ by the inner simplex
+algorithm are ``lam_slide_amd.msm``.  The estimator is fixed as
 mathematics below and checked against numpy / scipy; parity with a live pyemma was not checked - a model pyemma fitted enters through
 ``TicaModel.from_arrays``."""
 from __future__ import annotations
