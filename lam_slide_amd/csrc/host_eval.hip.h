@@ -325,6 +325,11 @@ struct EvalArgs {
     float *save_out = nullptr;
     const float *mods_ready = nullptr;  // this record's row of the group table (run_mods_steps), or nullptr
 };
+// THE place where a record becomes the update the kernels apply (k_small_frag.hip.h: StepUpdate) - for the head and for k_state_affine
+StepUpdate step_update(const EvalArgs &e) {
+    const lsl_step_ex r = e.rec ? *e.rec : lsl_step_ex{};
+    return StepUpdate{e.noise, e.trace, e.saved, e.save_out, (unsigned long long)e.seed, (unsigned long long)e.elem_off, r.ax, r.am, r.aw, r.as, (unsigned)r.noise_index};
+}
 
 // The state embedding of an evaluation: ws.h = x_in(x) + ws.cond_emb, with what the pass plan attaches to it (ln_fuse handles: the rows'
 // statistics for the first sub-block's linear1; normalize models: the in-place LayerNorm).  h_tap (lsl_debug_embed): ws.h in front of the LayerNorm.
@@ -347,11 +352,9 @@ int run_embed(lsl_model *m, const Workspace &ws, const PassPlan &p, const float 
 // update of e.x fused into it
 int run_head(lsl_model *m, const float *h, const float *fm, int mod_stride, int n, int tpt, const EvalArgs &e, hipStream_t st) {
     const int D = m->d.hidden;
-    const lsl_step_ex r = e.rec ? *e.rec : lsl_step_ex{};
+    const HeadArgs a{e.x, e.out, h, fm, fm + D, mod_stride, m->w.out_w, m->w.out_b, n, m->d.in_dim, tpt, e.rec ? 1 : 0, step_update(e)};
     m->prof.begin(4, st);
-    DISPATCH_D(D, launch_head_t, e.x, e.out, h, fm, fm + D, mod_stride, m->w.out_w, m->w.out_b, n, m->d.in_dim, tpt, e.rec ? 1 : 0,
-               r.ax, r.am, r.aw, e.noise, (unsigned long long)e.seed, (unsigned)r.noise_index, (unsigned long long)e.elem_off, e.trace, r.as,
-               e.saved, e.save_out, st, &m->prof);
+    DISPATCH_D(D, launch_head_mfma, a, st, &m->prof);
     m->prof.end(4, st);
     LSL_CHECK_LAUNCH("head");
     return 0;
@@ -444,8 +447,8 @@ int resident_sample(lsl_model *m, const lsl_io *io, const lsl_step *steps, int n
     const ResWorkspace ws = carve_resident(m, (char *)workspace, B, T, L, have_y);
     const int rows = have_y ? B : 1;
     if (have_y) {
-        launch_dense_small<false, true>(ws.hid, io->y, w.vec_w1, w.vec_b1, nullptr, B, d.vec_in_dim, D, 0, st);
-        launch_dense_small<false, false>(ws.yemb, ws.hid, w.vec_w2, w.vec_b2, nullptr, B, D, D, 0, st);
+        launch_dense<false, true>(ws.hid, io->y, w.vec_w1, w.vec_b1, nullptr, B, d.vec_in_dim, D, 0, st);
+        launch_dense<false, false>(ws.yemb, ws.hid, w.vec_w2, w.vec_b2, nullptr, B, D, D, 0, st);
         LSL_CHECK_LAUNCH("vec_in");
     }
     ResArgs a;
@@ -492,9 +495,9 @@ int resident_sample(lsl_model *m, const lsl_io *io, const lsl_step *steps, int n
         // conditioning vector -> modulation tables of the group's steps (latent_si_v31.py:176-178, mmdit.py:184-197); the tiled kernel
         // is used for any row count, so a trajectory's tables do not depend on the batch it is sampled in
         hipLaunchKernelGGL(k_time_features_steps, dim3((rt * 128 + 255) / 256), dim3(256), 0, st, ws.tfeat, tt, ns, rows, w.time_freqs);
-        launch_dense_small<false, true>(ws.hid, ws.tfeat, w.time_w1, w.time_b1, nullptr, rt, 256, D, 0, st);
-        launch_dense_small<false, false>(ws.vec, ws.hid, w.time_w2, w.time_b2, have_y ? ws.yemb : nullptr, rt, D, D, D, st, have_y ? B : 0);
-        launch_dense_small<true, false>(ws.mods, ws.vec, w.mod_w, w.mod_b, nullptr, rt, D, m->MODW, 0, st);
+        launch_dense<false, true>(ws.hid, ws.tfeat, w.time_w1, w.time_b1, nullptr, rt, 256, D, 0, st);
+        launch_dense<false, false>(ws.vec, ws.hid, w.time_w2, w.time_b2, have_y ? ws.yemb : nullptr, rt, D, D, D, st, false, have_y ? B : 0);
+        launch_dense<true, false>(ws.mods, ws.vec, w.mod_w, w.mod_b, nullptr, rt, D, m->MODW, 0, st);
         LSL_CHECK_LAUNCH("modulation");
         a.step0 = (unsigned)s0;
         a.n_steps = ns;

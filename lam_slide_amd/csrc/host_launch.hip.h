@@ -6,19 +6,30 @@
 // Inside the anonymous namespace opened by host_common.hip.h.
 #pragma once
 
-// Rejected structures and A/B arms (ping-pong / drain GEMMs, tilings 6 / 8 / 13-18 / 23-26 / 29, the scalar output head, every LSL_* tuning knob)
-// live in tools/experiments/host_launch_experiments.hip.h, on the include path of tools/build_experiments.sh only; the product has empty hooks.
+// One launch of the output head (run_head fills it): the rows h [n, D] with their modulation rows, the projection, and either `out` or
+// the record's update u of x (do_step)
+struct HeadArgs {
+    float *x, *out;
+    const float *h, *shift, *scale;
+    int mod_stride;
+    const float *Wo, *bo;
+    int n, C, tpt, do_step;
+    StepUpdate u;
+};
+
+// Rejected structures and A/B arms (ping-pong / drain GEMMs, tilings 6 / 8 / 13-18 / 23-26 / 29, the scalar output head k_head_step of
+// tools/experiments/k_head_scalar.hip.h, every LSL_* tuning knob) live in tools/experiments/host_launch_experiments.hip.h, on the include path
+// of tools/build_experiments.sh only; the product has empty hooks.
 #ifdef LSL_EXPERIMENTS
 constexpr bool lsl_experiments = true;
 template <int NE, int VEC>
-bool launch_head_experiment(float *, float *, const float *, const float *, const float *, int, const float *, const float *, int, int, int, int, float, float,
-                            float, const float *, unsigned long long, unsigned, unsigned long long, float *, float, const float *, float *, hipStream_t);
+bool launch_head_experiment(const HeadArgs &, hipStream_t);
 template <class Epi>
 bool launch_gemm_experiment(int, const GemmArgs &, const Epi &, hipStream_t, bool);
 #else
 constexpr bool lsl_experiments = false;
-template <int NE, int VEC, class... A>
-bool launch_head_experiment(A...) { return false; }
+template <int NE, int VEC>
+bool launch_head_experiment(const HeadArgs &, hipStream_t) { return false; }
 template <class Epi>
 bool launch_gemm_experiment(int, const GemmArgs &, const Epi &, hipStream_t, bool) { return false; }
 #endif
@@ -66,28 +77,21 @@ void launch_ln_inplace_t(float *h, int n, float eps, hipStream_t st) {
     hipLaunchKernelGGL((k_ln_inplace<NE, VEC>), dim3((n + 3) / 4), dim3(256), 0, st, h, n, eps);
 }
 template <int NE, int VEC>
-void launch_head_mfma(float *x, float *out, const float *h, const float *shift, const float *scale, int stride, const float *Wo,
-                      const float *bo, int n, int C, int tpt, int do_step, float ax, float am, float aw, const float *noise,
-                      unsigned long long seed, unsigned step, unsigned long long eo, float *trace, float as, const float *saved, float *save_out,
-                      hipStream_t st, Profiler *pr = nullptr) {
+void launch_head_mfma(const HeadArgs &a, hipStream_t st, Profiler *pr = nullptr) {
+    if (launch_head_experiment<NE, VEC>(a, st)) return;  // (-DLSL_EXPERIMENTS builds only)
     auto kern = k_head_step_mfma<NE, VEC>;
-    const size_t lds = head_mfma_lds_bytes<NE>(C <= 32);
+    const size_t lds = head_mfma_lds_bytes<NE>(a.C <= 32);
     LSL_ALLOW_LDS(kern, head_mfma_lds_bytes<NE>(false));
     // two workgroups per CU where the LDS image allows it (any hidden size with <= 32 channels): one workgroup's LayerNorm / weight-load latencies under the other's MFMAs
     static const int per_cu = tune_int("LSL_HEAD_PER_CU", 2);
     const int wgs = device_cus() * (per_cu >= 2 && 2 * lds <= LDS_BUDGET ? 2 : 1);
-    if (pr) pr->label(4, "k_head_step_mfma<%d, %d> (%s, %d per CU)", NE, VEC, C <= 32 ? "one slab" : "cycled slabs", wgs / device_cus());
-    hipLaunchKernelGGL(kern, dim3(std::min((n + HEAD_TOK - 1) / HEAD_TOK, wgs)), dim3(256), lds, st, x, out, h, shift, scale, stride,
-                       Wo, bo, n, C, tpt, do_step, ax, am, aw, noise, seed, step, eo, trace, as, saved, save_out);
+    if (pr) pr->label(4, "k_head_step_mfma<%d, %d> (%s, %d per CU)", NE, VEC, a.C <= 32 ? "one slab" : "cycled slabs", wgs / device_cus());
+    hipLaunchKernelGGL(kern, dim3(std::min((a.n + HEAD_TOK - 1) / HEAD_TOK, wgs)), dim3(256), lds, st, a.x, a.out, a.h, a.shift, a.scale, a.mod_stride,
+                       a.Wo, a.bo, a.n, a.C, a.tpt, a.do_step, a.u);
 }
-
-template <int NE, int VEC>
-void launch_head_t(float *x, float *out, const float *h, const float *shift, const float *scale, int stride, const float *Wo,
-                   const float *bo, int n, int C, int tpt, int do_step, float ax, float am, float aw, const float *noise,
-                   unsigned long long seed, unsigned step, unsigned long long eo, float *trace, float as, const float *saved, float *save_out,
-                   hipStream_t st, Profiler *pr = nullptr) {
-    if (launch_head_experiment<NE, VEC>(x, out, h, shift, scale, stride, Wo, bo, n, C, tpt, do_step, ax, am, aw, noise, seed, step, eo, trace, as, saved, save_out, st)) return;
-    launch_head_mfma<NE, VEC>(x, out, h, shift, scale, stride, Wo, bo, n, C, tpt, do_step, ax, am, aw, noise, seed, step, eo, trace, as, saved, save_out, st, pr);
+// a record without a network evaluation, on the n elements behind x (k_state_affine)
+void launch_state_affine(float *x, unsigned long long n, const StepUpdate &u, hipStream_t st) {
+    hipLaunchKernelGGL(k_state_affine, dim3((unsigned)std::min<unsigned long long>((n + 255) / 256, 2048)), dim3(256), 0, st, x, n, u);
 }
 
 #define DISPATCH_D(D, FN, ...)                          \
@@ -554,7 +558,8 @@ void launch_dense(float *out, const float *in, const float *W, const float *bias
     if (single && rows == 1 && I <= 512) {
         named("k_dense_rows", 0);
         hipLaunchKernelGGL((k_dense_rows<PRE, POST>), dim3((O + 3) / 4), dim3(256), 0, st, out, in, W, bias, add, rows, I, O, add_stride, add_mod);
-    } else if ((I == 128 || I == 256) && tune_int("LSL_DENSE_MFMA", 1)) {  // many rows, usual widths: the fp32 matrix pipe (k_dense_mfma)
+    } else if ((I == 128 || I == 256) && tune_int("LSL_DENSE_MFMA", 1)) {  // usual widths, any row count: the fp32 matrix pipe (k_dense_mfma) - the
+                                                                            // general path's class-conditioned batches and the short chains in front of k_resident
         const dim3 grid((O + 31) / 32, (rows + 31) / 32);
         named("k_dense_mfma", I / 4);
         if (I == 128) hipLaunchKernelGGL((k_dense_mfma<PRE, POST, 32>), grid, dim3(256), 0, st, out, in, W, bias, add, rows, I, O, add_stride, add_mod);
@@ -567,19 +572,6 @@ void launch_dense(float *out, const float *in, const float *W, const float *bias
         named("k_dense_rows", 0);
         hipLaunchKernelGGL((k_dense_rows<PRE, POST>), dim3((O + 3) / 4), dim3(256), 0, st, out, in, W, bias, add, rows, I, O, add_stride, add_mod);
     }
-}
-
-// the short GEMM chains in front of the trajectory-resident kernel (k_dense_mfma: latency-optimised; one kernel for any row count)
-template <bool PRE, bool POST>
-void launch_dense_small(float *out, const float *in, const float *W, const float *bias, const float *add, int rows, int I, int O,
-                        int add_stride, hipStream_t st, int add_mod = 0) {
-    const dim3 grid((O + 31) / 32, (rows + 31) / 32);
-    if (I == 128)
-        hipLaunchKernelGGL((k_dense_mfma<PRE, POST, 32>), grid, dim3(256), 0, st, out, in, W, bias, add, rows, I, O, add_stride, add_mod);
-    else if (I == 256)
-        hipLaunchKernelGGL((k_dense_mfma<PRE, POST, 64>), grid, dim3(256), 0, st, out, in, W, bias, add, rows, I, O, add_stride, add_mod);
-    else
-        launch_dense<PRE, POST>(out, in, W, bias, add, rows, I, O, add_stride, st, false, add_mod);
 }
 
 // ---- the losses: the team forms of k_loss_frag.hip.h, one dispatcher for D = 1..4, one launch of the quotient finals ----

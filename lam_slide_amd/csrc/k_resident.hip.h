@@ -25,8 +25,7 @@
 #pragma once
 #include "k_mm_frag.hip.h"
 #include "k_small.hip.h"
-
-typedef __attribute__((ext_vector_type(4))) float f32x4v;
+#include "k_small_frag.hip.h"
 
 constexpr int RES_D = 128, RES_H = 4, RES_HD = 32, RES_HHD = 128, RES_M = 256, RES_F1 = 640, RES_K2 = 384;
 constexpr int RES_MAX_STEPS = 48, RES_MAX_BLOCKS = 16, RES_MAX_C = 32;
@@ -109,14 +108,7 @@ struct ResLds {
 };
 
 __device__ __forceinline__ f32x4v mfma16(bf16x8 a, bf16x8 b, f32x4v c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-// exact fp32 multiply-add (v_mfma_f32_16x16x4_f32): four k-steps from one float4 per operand.  Lane (r16, g4) supplies A[row r16][k] and
-// B[k][col r16] for the k values {4 g4 + e}; any k order is fine as long as both operands use the same one.
-__device__ __forceinline__ f32x4v mfma16_f32x4(float4 a, float4 b, f32x4v c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, c, 0, 0, 0);
-}
+// (the exact fp32 form, mfma16_f32x4: k_small_frag.hip.h)
 
 // sum over the 4 lanes {l, l^16, l^32, l^48} (the four 4-feature row groups of a 16x16 accumulator column): two VALU lane exchanges
 // (gfx950 v_permlane16_swap / v_permlane32_swap; with both operands = v the two results are the values of the even and of the odd
@@ -753,6 +745,9 @@ __global__ void __launch_bounds__(RES_NTHR, 2) k_resident(ResArgs A) {
                 const size_t e = xoff + (size_t)n * C + h_c0;
                 float *xp = xs + n * RES_XS + h_c0;
                 const float4 xo = *reinterpret_cast<const float4 *>(xp);
+                // (restates step_value / step_noise of k_small_frag.hip.h four wide, without the saved-state term: through either fragment both
+                // instances spill more scalar registers - profiles/small_fragments.txt section 5d.  The noise of step s is element
+                // elem_offset + e of the stream under step index step0 + s, like every other record's.)
                 float xn[4] = {sp.y * xo.x + sp.z * acc[0], sp.y * xo.y + sp.z * acc[1], sp.y * xo.z + sp.z * acc[2], sp.y * xo.w + sp.z * acc[3]};
                 if (sp.w != 0.0f) {
 #pragma unroll

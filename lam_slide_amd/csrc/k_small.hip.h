@@ -3,6 +3,7 @@
 // These carry < 1 % of the FLOPs and stay in fp32 on purpose ("Accuracy target").
 #pragma once
 #include "common.hip.h"
+#include "k_small_frag.hip.h"
 
 // ---------------------------------------------------------------------------------------------------
 // RoPE table: tab[p][j] = (cos, sin)(p * theta^(-2j/hd)), angle in fp64 then rounded (mmdit.py:75-82).
@@ -135,12 +136,7 @@ __global__ void __launch_bounds__(256) k_dense_rows(float *out, const float *in,
                 if (i < I) s = fmaf(w[k], PRE_SILU ? silu(v[r][k]) : v[r][k], s);
             }
             s = wave_sum(s);
-            if (lane == 0) {
-                s += bo;
-                if (add) s += add[(size_t)(add_mod ? b % add_mod : b) * add_stride + o];
-                if (POST_SILU) s = silu(s);
-                out[(size_t)b * O + o] = s;
-            }
+            if (lane == 0) dense_store<POST_SILU>(out, s, bo, add, b, o, O, add_stride, add_mod);
         }
     }
 }
@@ -191,10 +187,7 @@ __global__ void __launch_bounds__(256) k_dense_tiled(float *out, const float *in
         for (int j = 0; j < 4; ++j) {
             const int o = o0 + 4 * tx + j;
             if (o >= O) continue;
-            float v = acc[i][j] + bias[o];
-            if (add) v += add[(size_t)(add_mod ? b % add_mod : b) * add_stride + o];
-            if (POST_SILU) v = silu(v);
-            out[(size_t)b * O + o] = v;
+            dense_store<POST_SILU>(out, acc[i][j], bias[o], add, b, o, O, add_stride, add_mod);
         }
     }
 }
@@ -207,11 +200,10 @@ __global__ void __launch_bounds__(256) k_dense_tiled(float *out, const float *in
 // every operand byte of a wave is requested before its first MFMA, and the four partial tiles meet in LDS in a fixed order.
 // One kernel for every batch size (the choice depends on the model only), so a trajectory's tables do not depend on its batch.
 // Also taken by the general path for class-conditioned batches of the usual widths (I = 128 / 256): NBA +0.9 % at 1 024 rows, +3.6 % at 64.
-typedef __attribute__((ext_vector_type(16))) float f32x16_d;
 template <bool PRE_SILU, bool POST_SILU, int KQ>  // KQ = I / 4 (k per wave): 32 or 64
 __global__ void __launch_bounds__(256) k_dense_mfma(float *out, const float *in, const float *W, const float *bias, const float *add,
                                                     int rows, int I, int O, int add_stride, int add_mod) {
-    __shared__ float Ps[4][32][33];
+    __shared__ PartTile Ps[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hf = lane >> 5;
     const int r0 = blockIdx.y * 32, o0 = blockIdx.x * 32;
     const float *ap = in + (size_t)min(r0 + r, rows - 1) * I + wave * KQ + 4 * hf;
@@ -222,18 +214,14 @@ __global__ void __launch_bounds__(256) k_dense_mfma(float *out, const float *in,
         a[j] = *reinterpret_cast<const float4 *>(ap + 8 * j);
         w[j] = *reinterpret_cast<const float4 *>(wp + 8 * j);
     }
-    f32x16_d acc;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
+    f32x16 acc = f32x16_zero();
 #pragma unroll
     for (int j = 0; j < KQ / 8; ++j) {
         float4 av = a[j];
         if (PRE_SILU) av = make_float4(silu(av.x), silu(av.y), silu(av.z), silu(av.w));
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, w[j].x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, w[j].y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, w[j].z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, w[j].w, acc, 0, 0, 0);
+        acc = mfma32_f32x4(av, w[j], acc);
     }
+    // (restates part_scatter: through the call every instance compiles to other text - profiles/small_fragments.txt section 5b)
 #pragma unroll
     for (int e = 0; e < 16; ++e) Ps[wave][acc_row(e, hf)][r] = acc[e];  // (row of the tile = input row, column = output)
     __syncthreads();
@@ -241,10 +229,7 @@ __global__ void __launch_bounds__(256) k_dense_mfma(float *out, const float *in,
     for (int q = 0; q < 4; ++q) {
         const int idx = tid + 256 * q, row = idx >> 5, col = idx & 31, b = r0 + row, o = o0 + col;
         if (b >= rows || o >= O) continue;
-        float v = ((Ps[0][row][col] + Ps[1][row][col]) + Ps[2][row][col]) + Ps[3][row][col] + bias[o];
-        if (add) v += add[(size_t)(add_mod ? b % add_mod : b) * add_stride + o];
-        if (POST_SILU) v = silu(v);
-        out[(size_t)b * O + o] = v;
+        dense_store<POST_SILU>(out, part_sum(Ps, row, col), bias[o], add, b, o, O, add_stride, add_mod);
     }
 }
 
@@ -418,16 +403,9 @@ __global__ void __launch_bounds__(256) k_embed_mfma(float *out, const float *in,
             else addv[e] = base[(size_t)n * D + d0 + r];
         }
         const float b0 = MODE == 0 ? bias[d0 + r] + bias2[d0 + r] : 0.0f;
-        f32x16_d acc;
+        f32x16 acc = f32x16_zero();
 #pragma unroll
-        for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
-#pragma unroll
-        for (int j = 0; j < CK; ++j) {
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j].x, w[j].x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j].y, w[j].y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j].z, w[j].z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j].w, w[j].w, acc, 0, 0, 0);
-        }
+        for (int j = 0; j < CK; ++j) acc = mfma32_f32x4(a[j], w[j], acc);
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int n = n0 + acc_row(e, hf);
@@ -510,15 +488,13 @@ __global__ void __launch_bounds__(256) k_ln_modulate(u16 *a, const float *h, con
             const int d = 2 * lane + 128 * k;
             const float2 sc = *reinterpret_cast<const float2 *>(scale + mo + d);
             const float2 sf = *reinterpret_cast<const float2 *>(shift + mo + d);
-            const float y0 = (v[2 * k] - mean) * rstd * (1.0f + sc.x) + sf.x;
-            const float y1 = (v[2 * k + 1] - mean) * rstd * (1.0f + sc.y) + sf.y;
-            *reinterpret_cast<unsigned *>(arow + d) = pack2(y0, y1);
+            *reinterpret_cast<unsigned *>(arow + d) = pack2(ln_mod_scale(v[2 * k], mean, rstd, sc.x, sf.x), ln_mod_scale(v[2 * k + 1], mean, rstd, sc.y, sf.y));
         }
     } else {
 #pragma unroll
         for (int k = 0; k < NE; ++k) {
             const int d = lane + 64 * k;
-            arow[d] = f2bf((v[k] - mean) * rstd * (1.0f + scale[mo + d]) + shift[mo + d]);
+            arow[d] = f2bf(ln_mod_scale(v[k], mean, rstd, scale[mo + d], shift[mo + d]));
         }
     }
 }
@@ -560,8 +536,8 @@ __global__ void __launch_bounds__(256) k_ln_modulate_v4(u16 *a, const float *h, 
             const int d = 4 * lane + 256 * k;
             const float4 sc = *reinterpret_cast<const float4 *>(scale + mo + d);
             const float4 sf = *reinterpret_cast<const float4 *>(shift + mo + d);
-            const u32x2 pk = {pack2((v[k].x - mean) * rstd * (1.0f + sc.x) + sf.x, (v[k].y - mean) * rstd * (1.0f + sc.y) + sf.y),
-                              pack2((v[k].z - mean) * rstd * (1.0f + sc.z) + sf.z, (v[k].w - mean) * rstd * (1.0f + sc.w) + sf.w)};
+            const u32x2 pk = {pack2(ln_mod_scale(v[k].x, mean, rstd, sc.x, sf.x), ln_mod_scale(v[k].y, mean, rstd, sc.y, sf.y)),
+                              pack2(ln_mod_scale(v[k].z, mean, rstd, sc.z, sf.z), ln_mod_scale(v[k].w, mean, rstd, sc.w, sf.w))};
             store8(a + (size_t)n * D + d, pk, nt);
         }
 #pragma unroll
@@ -639,59 +615,20 @@ __global__ void __launch_bounds__(256) k_rk_error_partial(float *partial, const 
         const float q = rk_sum(k, i) / (atol + rtol * fmaxf(fabsf(y0[i]), fabsf(y1[i])));
         s += q * q;
     }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+    const float total = block_tree_sum(red, s);
+    if (threadIdx.x == 0) partial[blockIdx.x] = total;
 }
 // *ratio = sqrt(sum_b partial[b] / n)
 __global__ void __launch_bounds__(256) k_rk_error_final(float *ratio, const float *partial, int n_partial, unsigned long long n) {
     __shared__ double red[256];
     double s = 0.0;
     for (int b = threadIdx.x; b < n_partial; b += 256) s += (double)partial[b];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *ratio = (float)sqrt(red[0] / (double)n);
+    const double total = block_tree_sum(red, s);
+    if (threadIdx.x == 0) *ratio = (float)sqrt(total / (double)n);
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Philox4x32-10 + Box-Muller: standard normal for (seed, step, element).  Documented stream:
-// counter = (elem/4 lo, elem/4 hi, step, 0), key = (seed lo, seed hi); element e takes output e % 4
-// after Box-Muller on the pairs (r0,r1) -> (z0,z1), (r2,r3) -> (z2,z3).
-__device__ __forceinline__ void philox4x32_10(unsigned (&c)[4], unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0];
-        const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c[2];
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c[1] ^ k0;
-        const unsigned n1 = (unsigned)p1;
-        const unsigned n2 = (unsigned)(p0 >> 32) ^ c[3] ^ k1;
-        const unsigned n3 = (unsigned)p0;
-        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
-__device__ __forceinline__ float philox_normal(unsigned long long seed, unsigned step, unsigned long long elem) {
-    const unsigned long long blk = elem >> 2;
-    unsigned c[4] = {(unsigned)blk, (unsigned)(blk >> 32), step, 0u};
-    philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32));
-    const int pair = (int)(elem & 2);
-    const float u1 = ((float)c[pair] + 1.0f) * 2.3283064365386963e-10f;  // (0, 1]
-    const float u2 = (float)c[pair + 1] * 2.3283064365386963e-10f;
-    const float rad = sqrtf(-2.0f * __logf(u1));
-    float sn, cs;
-    __sincosf(6.283185307179586f * u2, &sn, &cs);
-    return (elem & 1) ? rad * sn : rad * cs;
-}
-
+// Device noise and the records of lsl_sample_ex (the stream, StepUpdate and step_apply: k_small_frag.hip.h).
 // Initial state of a sampling call, x_0 ~ N(0, 1) (lightning_base.py:231 torch.randn_like(x_cond)): the same documented stream as the
 // per-step noise, under the reserved step index LSL_INIT_STEP, so that a sharded run (elem_offset = global index of the rank's first
 // element) draws exactly the slice of the unsharded run.
@@ -702,148 +639,37 @@ __global__ void __launch_bounds__(256) k_randn(float *x, unsigned long long n, u
 }
 
 // A record of lsl_sample_ex without a network evaluation: x <- ax x + aw w + as saved (the noise injection of a Heun step), optionally
-// copied to the saved-state buffer and to the trace.  Same noise addressing as the output-head kernels.
-__global__ void __launch_bounds__(256) k_state_affine(float *x, unsigned long long n, float ax, float aw, float as, const float *noise,
-                                                      unsigned long long seed, unsigned step, unsigned long long elem_offset, const float *saved,
-                                                      float *save_out, float *trace) {
-    for (unsigned long long e = (unsigned long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (unsigned long long)gridDim.x * 256) {
-        float xn = ax * x[e];
-        if (aw != 0.0f) xn += aw * (noise ? noise[e] : philox_normal(seed, step, elem_offset + e));
-        if (saved) xn += as * saved[e];
-        x[e] = xn;
-        if (trace) trace[e] = xn;
-        if (save_out) save_out[e] = xn;
-    }
+// copied to the saved-state buffer and to the trace: step_apply without the network term.
+__global__ void __launch_bounds__(256) k_state_affine(float *x, unsigned long long n, StepUpdate u) {
+    for (unsigned long long e = (unsigned long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (unsigned long long)gridDim.x * 256) step_apply<false>(u, x, e, x[e], 0.0f);
 }
 
 // ---------------------------------------------------------------------------------------------------
 // Output head fused with the sampler update (latent_si_v31.py:185-187 + the affine step of lsl_step):
-//   m = Linear_{D->C}(LayerNorm_{1e-6}(h) * (1 + scale) + shift)          (fp32 FMA chain, exact fp32 weights)
-//   STEP: x <- ax * x + am * m + aw * w        else: out <- m
-// Persistent workgroups walk 32-token tiles.  Phase 1: each wave normalises + modulates 8 token rows into LDS (fp32).
-// Phase 2: thread (token, cg) accumulates 4 consecutive output channels over D, reading the token row and the
-// transposed weight slab W_s[cg][d] (float4 = 4 channels) from LDS; slabs of 32 channels are cycled for C > 32.
-// LDS rows are padded (+4 floats / +1 float4) so the 8 tokens / 8 channel groups of a wave hit distinct banks.
+//   m = Linear_{D->C}(LayerNorm_{1e-6}(h) * (1 + scale) + shift)          (exact fp32 weights)
+//   do_step: the record's update of x with m (step_apply)                 else: out <- m
+// Persistent workgroups walk 32-token tiles; each wave normalises + modulates 8 token rows into LDS (fp32), rows padded by 4 floats.  The
+// [32 tokens x D] x [D x 32 channels] product runs on v_mfma_f32_32x32x2_f32 (exact fp32 multiply-add, 1/16 of the bf16 rate - ample here)
+// instead of LDS-fed scalar FMAs (tools/experiments/k_head_scalar.hip.h), which were LDS-bandwidth bound (5 ds_read_b128 per 16 FMAs, 82 KB
+// of LDS reads per token).  The four waves split k; W^T fragments stay in registers across token tiles (C <= 32; wider outputs cycle slabs of
+// 32 channels); the next tile's h rows are requested before the current tile's product, so the single workgroup a CU holds never waits
+// on HBM with nothing else to do.
 constexpr int HEAD_TOK = 32;
 template <int NE>
-constexpr size_t head_lds_bytes() { return (size_t)8 * (NE * 64 + 1) * 16 + (size_t)HEAD_TOK * (NE * 64 + 4) * 4; }
-
-template <int NE, int VEC>
-__global__ void __launch_bounds__(256) k_head_step(float *x, float *out, const float *h, const float *shift,
-                                                   const float *scale, int mod_stride, const float *Wo, const float *bo,
-                                                   int N, int C, int tokens_per_traj, int do_step, float ax, float am,
-                                                   float aw, const float *noise, unsigned long long seed, unsigned step,
-                                                   unsigned long long elem_offset, float *trace, float as, const float *saved,
-                                                   float *save_out) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int D = NE * 64, AS = D + 4, WS = D + 1, RPW = HEAD_TOK / 4;  // rows per wave
-    float4 *Ws = reinterpret_cast<float4 *>(smem);                    // [8][WS]
-    float *As = reinterpret_cast<float *>(smem + (size_t)8 * WS * 16);  // [HEAD_TOK][AS]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int tk = tid >> 3, cg = tid & 7;
-    const int n_tiles = (N + HEAD_TOK - 1) / HEAD_TOK;
-    const bool w_resident = C <= 32;  // one 32-channel slab: fill it once per workgroup, then walk token tiles
-
-    auto fill_w = [&](int c0) {
-#pragma unroll 8
-        for (int i = tid; i < 32 * D; i += 256) {
-            const int cl = i / D, d = i - cl * D, c = c0 + cl;
-            reinterpret_cast<float *>(&Ws[(cl >> 2) * WS + d])[cl & 3] = c < C ? Wo[(size_t)c * D + d] : 0.0f;
-        }
-    };
-    if (w_resident) fill_w(0);
-
-    for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int n0 = tile * HEAD_TOK;
-        // phase 1: all of this wave's rows are requested before any reduction, so their latencies overlap
-        float v[RPW][NE];
-#pragma unroll
-        for (int i = 0; i < RPW; ++i) {
-            const int n = min(n0 + wave + 4 * i, N - 1);
-            row_load<NE, VEC>(h + (size_t)n * D, lane, v[i]);
-        }
-        __syncthreads();  // previous tile's phase 2 has finished reading As (and Ws when not resident)
-#pragma unroll
-        for (int i = 0; i < RPW; ++i) {
-            const int n = min(n0 + wave + 4 * i, N - 1);
-            float mean, rstd;
-            row_stats<NE>(v[i], 1e-6f, mean, rstd);
-            const size_t mo = (size_t)(n / tokens_per_traj) * mod_stride;
-#pragma unroll
-            for (int k = 0; k < NE; ++k) {
-                const int d = row_col<NE, VEC>(lane, k);
-                As[(wave + 4 * i) * AS + d] = (v[i][k] - mean) * rstd * (1.0f + scale[mo + d]) + shift[mo + d];
-            }
-        }
-        const int n = n0 + tk;
-        for (int c0 = 0; c0 < C; c0 += 32) {
-            if (!w_resident) {
-                if (c0) __syncthreads();  // previous slab fully consumed
-                fill_w(c0);
-            }
-            __syncthreads();  // As (and Ws) visible
-            float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
-            const float *ar = As + tk * AS;
-            const float4 *wr = Ws + cg * WS;
-#pragma unroll 2
-            for (int d = 0; d < D; d += 4) {
-                const float4 av = *reinterpret_cast<const float4 *>(ar + d);
-                const float4 w0 = wr[d], w1 = wr[d + 1], w2 = wr[d + 2], w3 = wr[d + 3];
-                a0 = fmaf(av.x, w0.x, a0); a1 = fmaf(av.x, w0.y, a1); a2 = fmaf(av.x, w0.z, a2); a3 = fmaf(av.x, w0.w, a3);
-                a0 = fmaf(av.y, w1.x, a0); a1 = fmaf(av.y, w1.y, a1); a2 = fmaf(av.y, w1.z, a2); a3 = fmaf(av.y, w1.w, a3);
-                a0 = fmaf(av.z, w2.x, a0); a1 = fmaf(av.z, w2.y, a1); a2 = fmaf(av.z, w2.z, a2); a3 = fmaf(av.z, w2.w, a3);
-                a0 = fmaf(av.w, w3.x, a0); a1 = fmaf(av.w, w3.y, a1); a2 = fmaf(av.w, w3.z, a2); a3 = fmaf(av.w, w3.w, a3);
-            }
-            if (n < N) {
-                const float acc[4] = {a0, a1, a2, a3};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int c = c0 + 4 * cg + j;
-                    if (c < C) {
-                        const float m = acc[j] + bo[c];
-                        const size_t e = (size_t)n * C + c;
-                        if (do_step) {
-                            float xn = ax * x[e] + am * m;
-                            if (aw != 0.0f) xn += aw * (noise ? noise[e] : philox_normal(seed, step, elem_offset + e));
-                            if (saved) xn += as * saved[e];  // (lsl_step_ex: a state kept by an earlier record, e.g. Heun's x_hat)
-                            x[e] = xn;
-                            if (trace) trace[e] = xn;
-                            if (save_out) save_out[e] = xn;
-                        } else {
-                            out[e] = m;
-                        }
-                    }
-                }
-            }
-        }
-    }
-}
-
-
-// ---------------------------------------------------------------------------------------------------
-// Output head + state update, fp32 MFMA form.  Same contract as k_head_step; the [32 tokens x D] x [D x 32 channels] product runs on
-// v_mfma_f32_32x32x2_f32 (exact fp32 multiply-add, 1/16 of the bf16 rate - ample here) instead of LDS-fed scalar FMAs, which were
-// LDS-bandwidth bound (5 ds_read_b128 per 16 FMAs, 82 KB of LDS reads per token).  The four waves split k; W^T fragments stay in
-// registers across token tiles (C <= 32); the next tile's h rows are requested before the current tile's product, so the single
-// workgroup a CU holds never waits on HBM with nothing else to do.
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-template <int NE>
 constexpr size_t head_mfma_lds_bytes(bool one_slab) {  // one_slab (C <= 32): the partial products overlay the activation rows, dead by then
-    constexpr size_t rows = (size_t)HEAD_TOK * (NE * 64 + 4) * 4, parts = (size_t)4 * 32 * 33 * 4;
+    constexpr size_t rows = (size_t)HEAD_TOK * (NE * 64 + 4) * 4, parts = (size_t)PART_FLOATS * 4;
     return one_slab ? (rows > parts ? rows : parts) : rows + parts;
 }
 
 template <int NE, int VEC>
 __global__ void __launch_bounds__(256) k_head_step_mfma(float *x, float *out, const float *h, const float *shift, const float *scale,
                                                         int mod_stride, const float *Wo, const float *bo, int N, int C, int tokens_per_traj,
-                                                        int do_step, float ax, float am, float aw, const float *noise, unsigned long long seed,
-                                                        unsigned step, unsigned long long elem_offset, float *trace, float as,
-                                                        const float *saved, float *save_out) {
+                                                        int do_step, StepUpdate u) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int D = NE * 64, AS = D + 4, RPW = HEAD_TOK / 4, KW = D / 4, JS = KW / 8;  // k range per wave, 8-deep steps per wave
     float *As = reinterpret_cast<float *>(smem);  // [HEAD_TOK][AS]  LayerNorm'ed + modulated rows
     const bool w_resident = C <= 32;
-    float *Ps = w_resident ? As : As + HEAD_TOK * AS;  // [4][32][33] per-wave partial products (token, channel); one slab: over the dead rows
+    PartTile *Ps = reinterpret_cast<PartTile *>(w_resident ? As : As + HEAD_TOK * AS);  // [4] per-wave partial products (token, channel); one slab: over the dead rows
                                                         // (66 instead of 83 KB at hidden 512: two workgroups per CU)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, hf = lane >> 5;
@@ -893,13 +719,13 @@ __global__ void __launch_bounds__(256) k_head_step_mfma(float *x, float *out, co
             row_stats<NE, true>(v[i], 1e-6f, mean, rstd);  // (two waves per SIMD: the DPP form, the LDS-queue round trips of wave_sum were exposed)
             if (one_traj) {
 #pragma unroll
-                for (int k = 0; k < NE; ++k) As[(wave + 4 * i) * AS + row_col<NE, VEC>(lane, k)] = (v[i][k] - mean) * rstd * sc1[k] + sh[k];
+                for (int k = 0; k < NE; ++k) As[(wave + 4 * i) * AS + row_col<NE, VEC>(lane, k)] = ln_mod(v[i][k], mean, rstd, sc1[k], sh[k]);
             } else {
                 const size_t mo = (size_t)(n / tokens_per_traj) * mod_stride;
 #pragma unroll
                 for (int k = 0; k < NE; ++k) {
                     const int d = row_col<NE, VEC>(lane, k);
-                    As[(wave + 4 * i) * AS + d] = (v[i][k] - mean) * rstd * (1.0f + scale[mo + d]) + shift[mo + d];
+                    As[(wave + 4 * i) * AS + d] = ln_mod_scale(v[i][k], mean, rstd, scale[mo + d], shift[mo + d]);
                 }
             }
         }
@@ -915,40 +741,22 @@ __global__ void __launch_bounds__(256) k_head_step_mfma(float *x, float *out, co
         }
         for (int c0 = 0; c0 < C; c0 += 32) {
             if (!w_resident) load_w(c0);
-            f32x16_t acc;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
+            f32x16 acc = f32x16_zero();
             const float *ar = As + r * AS + wave * KW + 4 * hf;
 #pragma unroll
-            for (int j = 0; j < JS; ++j) {
-                const float4 av = *reinterpret_cast<const float4 *>(ar + 8 * j);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, wf[j].x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, wf[j].y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, wf[j].z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, wf[j].w, acc, 0, 0, 0);
-            }
+            for (int j = 0; j < JS; ++j) acc = mfma32_f32x4(*reinterpret_cast<const float4 *>(ar + 8 * j), wf[j], acc);
             if (c0 || w_resident) __syncthreads();  // the previous slab's partials have been consumed / every wave has read its activation rows
-#pragma unroll
-            for (int e = 0; e < 16; ++e) Ps[(wave * 32 + acc_row(e, hf)) * 33 + r] = acc[e];
+            part_scatter(Ps, wave, r, hf, acc);  // (row of the tile = token, column = channel)
             __syncthreads();
             if (n < N) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int cl = 4 * cg + j, c = c0 + cl;
                     if (c < C) {
-                        const float m = ((Ps[(0 * 32 + tk) * 33 + cl] + Ps[(1 * 32 + tk) * 33 + cl]) + Ps[(2 * 32 + tk) * 33 + cl]) +
-                                        Ps[(3 * 32 + tk) * 33 + cl] + bo[c];
+                        const float m = part_sum(Ps, tk, cl) + bo[c];
                         const size_t e = (size_t)n * C + c;
-                        if (do_step) {
-                            float xn = ax * (w_resident ? xs[j] : x[e]) + am * m;
-                            if (aw != 0.0f) xn += aw * (noise ? noise[e] : philox_normal(seed, step, elem_offset + e));
-                            if (saved) xn += as * saved[e];  // (lsl_step_ex: a state kept by an earlier record, e.g. Heun's x_hat)
-                            x[e] = xn;
-                            if (trace) trace[e] = xn;
-                            if (save_out) save_out[e] = xn;
-                        } else {
-                            out[e] = m;
-                        }
+                        if (do_step) step_apply<true>(u, x, e, w_resident ? xs[j] : x[e], m);
+                        else out[e] = m;
                     }
                 }
             }

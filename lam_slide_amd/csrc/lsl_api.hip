@@ -39,9 +39,10 @@
 #include "k_kmeans.hip.h"
 #include "k_msm.hip.h"
 #include "k_classloss.hip.h"
-#ifdef LSL_EXPERIMENTS  // measured-and-rejected GEMM structures, built only by tools/build_experiments.sh (never in the product library)
+#ifdef LSL_EXPERIMENTS  // measured-and-rejected structures, built only by tools/build_experiments.sh (never in the product library)
 #include "k_gemm_pp.hip.h"        // tools/experiments/ (on the include path of tools/build_experiments.sh only)
 #include "k_gemm_drain.hip.h"
+#include "k_head_scalar.hip.h"    // the scalar-FMA output head
 #endif
 
 #include "host_common.hip.h"
@@ -886,10 +887,7 @@ static int sample_enqueue(lsl_model *m, const lsl_io *io, const lsl_step_ex *ste
             e.saved = sp.as != 0.0f ? ws.saved : nullptr;  // (the pass's own copy: a pass runs all records for its trajectories)
             e.save_out = (sp.flags & LSL_STEP_SAVE) ? ws.saved : nullptr;
             if (sp.flags & LSL_STEP_NO_NETWORK) {
-                const unsigned long long ne = (unsigned long long)ps.bc * per;
-                hipLaunchKernelGGL(k_state_affine, dim3((unsigned)std::min<unsigned long long>((ne + 255) / 256, 2048)), dim3(256), 0, st,
-                                   e.x, ne, sp.ax, sp.aw, sp.as, e.noise, (unsigned long long)seed, (unsigned)sp.noise_index,
-                                   (unsigned long long)e.elem_off, e.saved, e.save_out, e.trace);
+                launch_state_affine(e.x, (unsigned long long)ps.bc * per, step_update(e), st);
                 LSL_CHECK_LAUNCH("state update");
                 continue;
             }

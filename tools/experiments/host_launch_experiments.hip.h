@@ -68,17 +68,15 @@ bool launch_gemm_experiment(int variant, const GemmArgs &g, const Epi &epi, hipS
     return false;
 }
 
-// LSL_HEAD_MFMA=0: the scalar-FMA output head (A/B measurements)
+// LSL_HEAD_MFMA=0: the scalar-FMA output head (k_head_scalar.hip.h; A/B measurements)
 template <int NE, int VEC>
-bool launch_head_experiment(float *x, float *out, const float *h, const float *shift, const float *scale, int stride, const float *Wo, const float *bo, int n,
-                            int C, int tpt, int do_step, float ax, float am, float aw, const float *noise, unsigned long long seed, unsigned step,
-                            unsigned long long eo, float *trace, float as, const float *saved, float *save_out, hipStream_t st) {
+bool launch_head_experiment(const HeadArgs &a, hipStream_t st) {
     static const int mfma = tune_int("LSL_HEAD_MFMA", 1);
     if (mfma) return false;
     auto kern = k_head_step<NE, VEC>;
     constexpr size_t lds = head_lds_bytes<NE>();
     LSL_ALLOW_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, dim3(std::min((n + HEAD_TOK - 1) / HEAD_TOK, 256)), dim3(256), lds, st, x, out, h, shift, scale, stride, Wo, bo, n, C, tpt,
-                       do_step, ax, am, aw, noise, seed, step, eo, trace, as, saved, save_out);
+    hipLaunchKernelGGL(kern, dim3(std::min((a.n + HEAD_TOK - 1) / HEAD_TOK, 256)), dim3(256), lds, st, a.x, a.out, a.h, a.shift, a.scale, a.mod_stride, a.Wo,
+                       a.bo, a.n, a.C, a.tpt, a.do_step, a.u);
     return true;
 }
