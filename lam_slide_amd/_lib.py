@@ -128,20 +128,42 @@ class SiRow(C.Structure):  # lsl_si_row
 STEP_NO_NETWORK, STEP_SAVE = 1, 2
 
 
+# The translation units of the library and the compile options each adds to BASE_FLAGS: kernels whose best options differ get a unit of
+# their own (csrc/unit_lin1.hip: profiles/lin1_unit.txt), everything else is csrc/lsl_api.hip.  No device call crosses units (no -fgpu-rdc).
+BASE_FLAGS = ("-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wno-unused-value")
+UNITS = (("lsl_api.hip", ()), ("unit_lin1.hip", ("-fno-slp-vectorize",)))
+BUILD_DIR = os.path.join(_HERE, "build")  # the units' object files
+
+
+def unit_options(extra) -> str:
+    """What lsl_build_info() reports for a unit: the options of every unit, then its own."""
+    return " ".join(BASE_FLAGS[:1] + tuple(extra))
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
-    """Compile the HIP sources for gfx950 into the in-tree shared library (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(SRC_DIR, f) for f in sorted(os.listdir(SRC_DIR))] + [os.path.join(INCLUDE_DIR, "lsl_api.h")]
+    """Compile the HIP sources for gfx950 into the in-tree shared library (hipcc cross-compiles without a GPU): one object per unit of UNITS,
+    compiled side by side (at most 16 compiler jobs), linked into one library."""
+    from concurrent.futures import ThreadPoolExecutor
+    srcs = [os.path.join(SRC_DIR, f) for f in sorted(os.listdir(SRC_DIR))] + [os.path.join(INCLUDE_DIR, "lsl_api.h"), os.path.abspath(__file__)]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cmd = [hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-shared", "-fPIC", "-fvisibility=hidden", "-Wno-unused-value",
-           "-Wl,--version-script=" + os.path.join(SRC_DIR, "exports.map"), "-o", LIB_PATH, os.path.join(SRC_DIR, "lsl_api.hip")]
-    res = subprocess.run(cmd, capture_output=True, text=True)
-    if verbose or res.returncode != 0:
-        print(" ".join(cmd))
-        print(res.stdout + res.stderr)
-    if res.returncode != 0:
-        raise RuntimeError("hipcc failed building liblamslide_hip.so")
+    os.makedirs(BUILD_DIR, exist_ok=True)
+
+    def run(cmd):
+        res = subprocess.run(cmd, capture_output=True, text=True)
+        if verbose or res.returncode != 0:
+            print(" ".join(cmd))
+            print(res.stdout + res.stderr)
+        if res.returncode != 0:
+            raise RuntimeError("hipcc failed building liblamslide_hip.so")
+
+    objs = [os.path.join(BUILD_DIR, os.path.splitext(name)[0] + ".o") for name, _ in UNITS]
+    cmds = [[hipcc, *BASE_FLAGS, *extra, f'-DLSL_UNIT_OPTIONS="{unit_options(extra)}"', "-c", os.path.join(SRC_DIR, name), "-o", obj]
+            for (name, extra), obj in zip(UNITS, objs)]
+    with ThreadPoolExecutor(max_workers=min(16, len(cmds))) as pool:
+        list(pool.map(run, cmds))
+    run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + os.path.join(SRC_DIR, "exports.map"), "-o", LIB_PATH, *objs])
     return LIB_PATH
 
 

@@ -1,5 +1,5 @@
 // Host side, part 1 of 4: error convention (fail, LSL_API_CATCH: the exception tail of every entry point), the model handle, the scratch
-// layout of a pass (carve), pass size, per-device one-time kernel attributes and the device guard.  Included by lsl_api.hip only (one
+// layout of a pass (carve), pass size, per-device one-time kernel attributes and the device guard.  Included by lsl_api.hip only (the main
 // translation unit; everything here has internal linkage).
 #pragma once
 
@@ -160,27 +160,7 @@ int default_chunk(const lsl_model *m, int B, int T, int L) {
     return (int)c;
 }
 
-template <typename K>
-void allow_lds(K kernel, size_t bytes) {
-    hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-// The dynamic-LDS attribute is a property of (kernel, device): one flag per device ordinal and per call site.
-struct DevOnce {
-    std::atomic<unsigned long long> bits{0};
-    bool first() {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        const unsigned long long bit = 1ull << (dev & 63);
-        if (bits.load(std::memory_order_relaxed) & bit) return false;
-        bits.fetch_or(bit, std::memory_order_relaxed);
-        return true;
-    }
-};
-#define LSL_ALLOW_LDS(kern, bytes)                  \
-    do {                                            \
-        static DevOnce once_;                       \
-        if (once_.first()) allow_lds(kern, bytes);  \
-    } while (0)
+#include "host_lds.hip.h"  // allow_lds, DevOnce, LSL_ALLOW_LDS
 
 // Calls may arrive with a current device other than the stream's (a model used on a second GPU of the process): launches,
 // attributes and the CU count must follow the STREAM's device.

@@ -177,8 +177,8 @@ void launch_gemm_glds(const GemmArgs &g, const Epi &epi, hipStream_t st) {
 
 // linear1 on the token-stationary kernel (k_lin1.hip.h): hidden sizes 128 / 256 / 384 / 512, sections (q | k | v | mlp) on multiples of 64
 // features.  Same bits as the tile kernels below (tools/lin1_harness.hip), so the choice between them may depend on the launch size.
-// THE instance list (head width, hidden): gates and launch go through it.  Per entry: 8 waves; 4 waves as well at hidden 512; the LNF form at 8.
-#define LSL_LIN1_TS_INSTANCES(X) X(32, 128) X(32, 256) X(32, 384) X(32, 512) X(16, 128) X(16, 256) X(16, 384) X(16, 512)
+// The kernel lives in unit_lin1.hip (its own compile options); k_lin1.hip.h gives this unit the configuration, THE instance list
+// (LSL_LIN1_TS_INSTANCES: gates and launch go through it) and lsl_lin1_launch.
 template <class Fn>
 bool with_linear1_ts_instance(int hdp, int D, Fn &&fn) {  // fn(head width, hidden) as integral constants; false: no such instance
 #define X(H, K) if (hdp == H && D == K) return fn(ic<H>{}, ic<K>{}), true;
@@ -189,8 +189,6 @@ bool with_linear1_ts_instance(int hdp, int D, Fn &&fn) {  // fn(head width, hidd
 template <int HDP, int K, int NW = 8, bool LNF = false>
 void launch_linear1_ts_t(const Lin1Args &a, hipStream_t st) {
     using C = Lin1Cfg<HDP, K, NW>;
-    auto kern = k_linear1_ts<HDP, K, NW, LNF>;
-    LSL_ALLOW_LDS(kern, LDS_BUDGET);
     const int ntile = (a.N + C::TT - 1) / C::TT, nb = a.F / 32;
     const long units = (long)ntile * nb;
     int grid = (int)std::min<long>(device_cus(), units / 2);
@@ -200,7 +198,7 @@ void launch_linear1_ts_t(const Lin1Args &a, hipStream_t st) {
     const int wpt = std::min(device_cus() / ntile, nb / 2);
     b.wpt = align && wpt >= 2 ? wpt : 0;
     if (b.wpt) grid = b.wpt * ntile;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), LNF ? C::lds_bytes_lnf(a.F) : C::lds_bytes(a.F), st, b);
+    lsl_lin1_launch(HDP, K, NW, LNF, b, grid, LNF ? C::lds_bytes_lnf(a.F) : C::lds_bytes(a.F), st);
 }
 // K = 512, few tokens (md17_bench B = 1: 7 680): 4-wave workgroups on 128-token tiles - twice the tiles, half the activation prologue per
 // workgroup, one wave per SIMD (512 registers: no scratch).  Same bits (tools/lin1_harness.hip -DLIN1_NW=4); 3 840 tokens 24.0 -> 19.9 us,

@@ -94,6 +94,20 @@ struct Lin1Cfg {
     static constexpr size_t lds_bytes_lnf(int F) { return lds_bytes(F) + (size_t)LN_SLOTS * 2 * K * 4; }
 };
 
+// THE instance list (head width, hidden): the gates and the launch of host_launch.hip.h and the instantiations of unit_lin1.hip go through
+// it.  Per entry: 8 waves; 4 waves as well at hidden 512; the LNF form at 8.
+#define LSL_LIN1_TS_INSTANCES(X) X(32, 128) X(32, 256) X(32, 384) X(32, 512) X(16, 128) X(16, 256) X(16, 384) X(16, 512)
+
+// The kernel is compiled in a translation unit of its own (unit_lin1.hip: its compile options are chosen for this kernel alone and move no
+// other kernel).  The main unit (lsl_api.hip, which defines LSL_LIN1_HOST_SIDE) sees the argument block, the configuration and these two functions:
+// lsl_lin1_launch starts k_linear1_ts<hdp, K, waves, lnf> on `grid` workgroups with `lds` bytes of dynamic LDS (grid, lds and a.wpt are the
+// caller's: launch_linear1_ts_t) and sets the dynamic-LDS attribute, which has to happen where the kernel symbol is defined; false: no such
+// instance.  lsl_lin1_unit_options: the options unit_lin1.hip was compiled with (lsl_build_info).
+bool lsl_lin1_launch(int hdp, int K, int waves, bool lnf, const Lin1Args &a, int grid, size_t lds, hipStream_t st);
+const char *lsl_lin1_unit_options();
+
+#ifndef LSL_LIN1_HOST_SIDE
+
 enum { LIN1_QK = 0, LIN1_V = 1, LIN1_MLP = 2 };
 
 #ifndef LIN1_XLOAD
@@ -444,6 +458,14 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) k_linear1_ts(Lin1Args g) {
         if (e < eb) fused(sec_c, I0, I1, I0, e);
     };
     auto load_co = [&](const float4 *tab, unsigned pos) __attribute__((always_inline)) { rope_rows<HDP>(co, tab, pos, hf); };
+    // The rotation rows consumed at a chosen place.  Left to their first use - a rotation inside a fused step, behind that step's slab stores
+    // and ring requests, which are asm and which hipcc therefore cannot count - the wait for them is a vmcnt(0) that drains those too; where
+    // the first use sits in a block loop (the k section's), in EVERY iteration.  (The same in front of the segment head's wait, for the
+    // table a segment requests there, measured no faster: profiles/lin1_unit.txt.)
+    auto co_arrived = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int k = 0; k < NCO; ++k) asm volatile("" ::"v"(co[k].w));  // (every row: hipcc orders the loads as it likes)
+    };
     ic<LIN1_QK> SQK;
     ic<LIN1_V> SV;
     ic<LIN1_MLP> SMLP;
@@ -499,18 +521,21 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) k_linear1_ts(Lin1Args g) {
             *reinterpret_cast<f4 *>(ln_tab + (size_t)slot * 2 * K + col) = f4{1.0f + sc[0], 1.0f + sc[1], 1.0f + sc[2], 1.0f + sc[3]};
             *reinterpret_cast<f4 *>(ln_tab + (size_t)slot * 2 * K + K + col) = sh;
         }
-        const unsigned rowi = lane >> 3, chunk = lane & 7;
+        // (every per-lane address of this phase comes from a lane id laundered here, and the table rows are 32-bit LDS offsets: derived from
+        // the kernel's `lane`, hipcc hoists them out of the segment loop and keeps them - 64-bit pairs - in scratch across the block loops)
+        const unsigned l = (unsigned)opaque_lane(lane), rowi = l >> 3, chunk = l & 7, rl = l & 31, hl = l >> 5;
         const unsigned sbase = (unsigned)(size_t)(LDS_PTR(char))(stage);
-        const unsigned xr0 = sbase + r * 128;
+        const unsigned xr0 = sbase + rl * 128;
+        const unsigned tab0 = (unsigned)(size_t)(LDS_PTR(char))(ln_tab) + 16 * chunk;
         const float *xr = xf + (size_t)(nw + rowi) * K + 4 * chunk;
-        float2 st[4];        // (rstd, -mean rstd) of rows rowi + 8 q
-        const float *tb[4];  // their trajectory's table row, at the lane's first column
+        float2 st[4];    // (rstd, -mean rstd) of rows rowi + 8 q
+        unsigned tb[4];  // their trajectory's table row, at the lane's first column (LDS byte offset)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const unsigned nn = (unsigned)min(nw + (int)rowi + 8 * q, g.N - 1);
             st[q] = g.ln_stat[nn];
             const unsigned slot = g.ln_mod_stride ? min(traj_of(nn) - t_first, (unsigned)(C::LN_SLOTS - 1)) : 0u;
-            tb[q] = ln_tab + (size_t)slot * 2 * K + 4 * chunk;
+            tb[q] = tab0 + slot * (2 * K * 4);
         }
         __syncthreads();  // the table is complete (every wave left the previous segment's long ago: a segment has at least one block barrier)
 #pragma unroll
@@ -525,7 +550,7 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) k_linear1_ts(Lin1Args g) {
                 const unsigned row = rowi + 8 * q, sw = (row >> 1) & 7;
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {
-                    const f4 sc = *reinterpret_cast<const f4 *>(tb[q] + 64 * p + 32 * e), sh = *reinterpret_cast<const f4 *>(tb[q] + K + 64 * p + 32 * e);
+                    const f4 sc = *reinterpret_cast<const LDS_PTR(f4)>(tb[q] + 4 * (64 * p + 32 * e)), sh = *reinterpret_cast<const LDS_PTR(f4)>(tb[q] + 4 * (K + 64 * p + 32 * e));
                     f4 x = v[e][q];
 #pragma unroll
                     for (int c = 0; c < 4; ++c) x[c] = fmaf(x[c], st[q].x, st[q].y) * sc[c] + sh[c];
@@ -535,7 +560,7 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) k_linear1_ts(Lin1Args g) {
             }
 #pragma unroll
             for (int m = 0; m < 4; ++m)
-                xreg[4 * p + m] = as_bf16x8(*reinterpret_cast<const LDS_PTR(u32x4)>(xr0 + ((((2 * m + hf) ^ (r >> 1)) & 7) << 4)));
+                xreg[4 * p + m] = as_bf16x8(*reinterpret_cast<const LDS_PTR(u32x4)>(xr0 + ((((2 * m + hl) ^ (rl >> 1)) & 7) << 4)));
             __builtin_amdgcn_sched_barrier(0);  // (one pass's rows at a time)
         }
     };
@@ -600,6 +625,7 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) k_linear1_ts(Lin1Args g) {
                 if (lo == qb) {  // entering the k section (otherwise the segment started inside it and co holds the k table)
                     load_co(g.rope_k, pos);
                     post = 1.0f;
+                    co_arrived();  // (in front of the block loop: the last stores are a step old, the ring's requests are due at the next head)
                 }
                 run(SQK, lo, hi);
             }
@@ -652,3 +678,5 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) k_linear1_ts(Lin1Args g) {
     }
     wait_vmcnt<0>();  // the ring's run-ahead requests must not land in LDS after the workgroup has gone
 }
+
+#endif  // LSL_LIN1_HOST_SIDE

@@ -1,7 +1,7 @@
 // Host side of liblamslide_hip.so: the C ABI of include/lsl_api.h.  Enqueues the kernel sequence of one
 // network evaluation (latent_si_v31.py:168-188) and of the sampler loops (integrators.py:67-78,103-120)
 // on the caller's stream.  No allocation, no synchronisation, no host<->device copies.
-// One translation unit: this file = the entry points of the sampling path (model handle, forward, fused sampler + opt-in hipGraph replay,
+// The main translation unit (the token-stationary linear1 kernel and its launcher are unit_lin1.hip): this file = the entry points of the sampling path (model handle, forward, fused sampler + opt-in hipGraph replay,
 // noise, Runge-Kutta state arithmetic, the stochastic-interpolant objective around one evaluation, the geometry losses of the decoded positions, the peptide frame and torsion losses, the displacement errors (ADE / FDE, best-of-K), the torsion statistics (dihedrals, histograms, lagged products, JS distance), the TICA and state statistics (lagged second moments, projection, nearest centre, transition counts), the reversible Markov state models (active set, row-sum iteration, transition matrix), debug taps); host_common / host_launch / host_eval.hip.h = what they enqueue (host_graph.hip.h: the replay cache); decode_host.hip.h +
 // stage1_api.hip.h = the frozen stage-1 encode / decode beside the path (every decoder head from one trunk) and the class losses of those heads.
 #include "../../include/lsl_api.h"
@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <initializer_list>
+#include <string>
 #include <vector>
 
 #include <atomic>
@@ -23,6 +24,7 @@
 
 #include "k_attn.hip.h"
 #include "k_gemm.hip.h"
+#define LSL_LIN1_HOST_SIDE  // the kernel body is compiled in unit_lin1.hip
 #include "k_lin1.hip.h"
 #include "k_lin2.hip.h"
 #include "k_tail.hip.h"
@@ -45,6 +47,10 @@
 #include "k_head_scalar.hip.h"    // the scalar-FMA output head
 #endif
 
+#ifndef LSL_UNIT_OPTIONS
+#define LSL_UNIT_OPTIONS ""  // (the options this unit was compiled with: lam_slide_amd/_lib.py passes them)
+#endif
+
 #include "host_common.hip.h"
 #include "host_launch.hip.h"
 #include "host_eval.hip.h"
@@ -56,7 +62,10 @@
 extern "C" {
 
 int lsl_version(void) { return LSL_VERSION; }
-const char *lsl_build_info(void) { return "clang " __clang_version__ " gfx950"; }
+const char *lsl_build_info(void) {  // compiler, target, and the compile options of each translation unit (lam_slide_amd/_lib.py UNITS)
+    static const std::string info = std::string("clang " __clang_version__ " gfx950; lsl_api.hip: " LSL_UNIT_OPTIONS "; unit_lin1.hip: ") + lsl_lin1_unit_options();
+    return info.c_str();
+}
 const char *lsl_last_error(void) { return g_err; }
 
 int lsl_model_create(const lsl_model_desc *desc, lsl_model **out) try {

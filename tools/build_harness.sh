@@ -27,5 +27,13 @@ tail)
     flags+=("-DTAIL_STAMPED")
   fi ;;
 esac
-/opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -std=c++17 -Wno-unused-value -I"$root/tools" "${flags[@]:-}" "$root/tools/${which}_harness.hip" -o "$root/tools/_exp/$name"
+# lin1: the kernel under test is compiled here, in the harness's translation unit, so it gets the options of the kernel's own unit in the
+# library (lam_slide_amd/_lib.py UNITS, unit_lin1.hip) - the harness measures and compares the code the product ships
+unit_flags=()
+if [ "$which" = lin1 ]; then
+  read -r -a unit_flags < <(cd "$root" && python3 -c "
+from lam_slide_amd import _lib
+print(*dict(_lib.UNITS)['unit_lin1.hip'])")
+fi
+/opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -std=c++17 -Wno-unused-value -I"$root/tools" "${unit_flags[@]:-}" "${flags[@]:-}" "$root/tools/${which}_harness.hip" -o "$root/tools/_exp/$name"
 echo "built tools/_exp/$name"

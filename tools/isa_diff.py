@@ -16,14 +16,14 @@ import isa_scan
 
 
 def notes(so_path):
-    """{kernel symbol: its metadata lines} from llvm-readelf --notes of the extracted code object"""
+    """{kernel symbol: its metadata lines} from llvm-readelf --notes of the extracted code objects"""
     with tempfile.TemporaryDirectory() as td:
         dst = os.path.join(td, "lib.so")
         with open(so_path, "rb") as f, open(dst, "wb") as g:
             g.write(f.read())
         subprocess.run([os.path.join(isa_scan.LLVM, "llvm-objdump"), "--offloading", dst], check=True, capture_output=True, cwd=td)
-        obj = [f for f in os.listdir(td) if "gfx950" in f][0]
-        text = subprocess.run([os.path.join(isa_scan.LLVM, "llvm-readelf"), "--notes", os.path.join(td, obj)], check=True, capture_output=True, text=True).stdout
+        text = "".join(subprocess.run([os.path.join(isa_scan.LLVM, "llvm-readelf"), "--notes", os.path.join(td, obj)], check=True, capture_output=True,
+                                      text=True).stdout for obj in sorted(f for f in os.listdir(td) if "gfx950" in f))  # (one code object per unit)
     keep = ("agpr_count", "vgpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "group_segment_fixed_size", "private_segment_fixed_size",
             "kernarg_segment_size", "max_flat_workgroup_size", "uses_dynamic_stack")
     out = {}

@@ -40,9 +40,9 @@ def disassemble(so_path: str) -> str:
         objs = [f for f in os.listdir(td) if "gfx950" in f]
         if not objs:
             raise RuntimeError("no gfx950 code object in " + so_path)
-        res = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--mcpu=gfx950", os.path.join(td, objs[0])], check=True,
-                             capture_output=True, text=True)
-        return res.stdout
+        # (one code object per translation unit of the library: lam_slide_amd/_lib.py UNITS)
+        return "".join(subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--mcpu=gfx950", os.path.join(td, o)], check=True,
+                                      capture_output=True, text=True).stdout for o in sorted(objs))
 
 
 _REG = re.compile(r"\b([vsa])(?:\[(\d+):(\d+)\]|(\d+)\b)")
