@@ -128,10 +128,11 @@ class SiRow(C.Structure):  # lsl_si_row
 STEP_NO_NETWORK, STEP_SAVE = 1, 2
 
 
-# The translation units of the library and the compile options each adds to BASE_FLAGS: kernels whose best options differ get a unit of
-# their own (csrc/unit_lin1.hip: profiles/lin1_unit.txt), everything else is csrc/lsl_api.hip.  No device call crosses units (no -fgpu-rdc).
+# The translation units of the library and the compile options each adds to BASE_FLAGS: a unit per family of entry points (the sampling
+# path, the losses, the evaluation statistics, the frozen stage 1), plus a unit where a kernel's best options differ (csrc/unit_lin1.hip:
+# profiles/lin1_unit.txt).  The families share no state and no kernel; no device call crosses units (no -fgpu-rdc).
 BASE_FLAGS = ("-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wno-unused-value")
-UNITS = (("lsl_api.hip", ()), ("unit_lin1.hip", ("-fno-slp-vectorize",)))
+UNITS = (("lsl_api.hip", ()), ("unit_lin1.hip", ("-fno-slp-vectorize",)), ("unit_loss.hip", ()), ("unit_stat.hip", ()), ("unit_stage1.hip", ()))
 BUILD_DIR = os.path.join(_HERE, "build")  # the units' object files
 
 

@@ -1,7 +1,14 @@
 // Host side of lsl_decode / lsl_encode: the handles, what their two create calls check and build alike (stage1_check, stage1_make), the
 // scratch layout of a call (stage1_carve, sized by dec_carve / enc_carve) and the launch helpers of the frozen stage-1 decode and encode
-// (kernels in k_decode.hip.h; the entry points themselves in stage1_api.hip.h).
+// (kernels in k_decode.hip.h; the entry points themselves in unit_stage1.hip).
 #pragma once
+#include <algorithm>
+#include <initializer_list>
+#include <new>
+#include <vector>
+
+#include "../../include/lsl_api.h"
+#include "host_api.hip.h"
 #include "k_decode.hip.h"
 
 struct lsl_encoder {

@@ -1,37 +1,16 @@
-// Host side, part 1 of 4: error convention (fail, LSL_API_CATCH: the exception tail of every entry point), the model handle, the scratch
-// layout of a pass (carve), pass size, per-device one-time kernel attributes and the device guard.  Included by lsl_api.hip only (the main
-// translation unit; everything here has internal linkage).
+// The sampling path's handle and scratch: the model handle with its profiler and replay cache, the scratch layout of a pass (carve), the
+// pass size.  Part of lsl_api.hip, which includes the kernel headers first.
 #pragma once
+#include <algorithm>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
 
-namespace {
-
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define LSL_CHECK_LAUNCH(name)                                                     \
-    do {                                                                           \
-        hipError_t e_ = hipGetLastError();                                         \
-        if (e_ != hipSuccess) return fail(-10, "%s: %s", name, hipGetErrorString(e_)); \
-    } while (0)
-
-// Behind the function-try-block of every C entry point: no exception crosses the ABI
-#define LSL_API_CATCH                                \
-    catch (const std::bad_alloc &) {                 \
-        return fail(-5, "out of host memory");       \
-    } catch (...) {                                  \
-        return fail(-11, "unexpected C++ exception"); \
-    }
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-}  // namespace
+#include "../../include/lsl_api.h"
+#include "common.hip.h"
+#include "host_api.hip.h"
+#include "host_lds.hip.h"
 
 struct Profiler {
     int kernel = -1, cap = 0, used = 0;
@@ -160,20 +139,4 @@ int default_chunk(const lsl_model *m, int B, int T, int L) {
     return (int)c;
 }
 
-#include "host_lds.hip.h"  // allow_lds, DevOnce, LSL_ALLOW_LDS
-
-// Calls may arrive with a current device other than the stream's (a model used on a second GPU of the process): launches,
-// attributes and the CU count must follow the STREAM's device.
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(hipStream_t st) {
-        int cur = 0, want = 0;
-        if (hipGetDevice(&cur) != hipSuccess) return;
-        if (hipStreamGetDevice(st, &want) != hipSuccess) { (void)hipGetLastError(); return; }
-        if (want != cur && hipSetDevice(want) == hipSuccess) prev = cur;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
+}  // namespace

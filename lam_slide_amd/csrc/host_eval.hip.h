@@ -1,7 +1,10 @@
-// Host side, part 3 of 4: the plan of a pass (which kernel and instance every launch of its sub-blocks runs, decided and checked before the
-// first launch; the profiler's labels are read off it); the kernel sequence of one network evaluation (conditioning tables, sub-blocks,
-// embedding, head), of a pass, of a call's passes, and of the trajectory-resident sampler; argument checks of a call.  Inside the anonymous namespace opened by host_common.hip.h.
+// The sampling path's plan and kernel sequences: the plan of a pass (which kernel and instance every launch of its sub-blocks runs, decided
+// and checked before the first launch; the profiler's labels are read off it); the kernel sequence of one network evaluation, of a pass, of
+// a call's passes, and of the trajectory-resident sampler; argument checks of a call.
 #pragma once
+#include "host_launch.hip.h"
+
+namespace {
 
 // ---- pieces of one evaluation ----------------------------------------------------------------------
 
@@ -557,3 +560,4 @@ int for_each_pass(lsl_model *m, const Workspace &ws, const lsl_io *io, int chunk
     return 0;
 }
 
+}  // namespace

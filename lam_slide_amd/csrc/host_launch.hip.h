@@ -1,10 +1,15 @@
-// Host side, part 2 of 4: one launch helper per kernel family - grid / LDS arithmetic of a chosen kernel - and, next to it, the rule that
-// chooses among the family's instances (which depends on the model and on T, L only where results could differ, never on the batch).  The
-// sub-block's rules (linear1, attention, linear2 / tail) are asked by plan_pass (host_eval.hip.h) only: their launchers are a switch over
-// what the plan says.  Each family's instances are listed ONCE (LSL_LIN1_TS_INSTANCES, LSL_LIN2_WS_INSTANCES; the switches of launch_gemm
-// and launch_attention_t), and a gate that depends on a kernel's LDS need asks the kernel's own config for it.
-// Inside the anonymous namespace opened by host_common.hip.h.
+// The sampling path's launch rules: one launch helper per kernel family - grid / LDS arithmetic of a chosen kernel - and, next to it, the
+// rule that chooses among the family's instances (which depends on the model and on T, L only where results could differ, never on the
+// batch).  The sub-block's rules (linear1, attention, linear2 / tail) are asked by plan_pass (host_eval.hip.h) only: their launchers are a
+// switch over what the plan says.  Each family's instances are listed ONCE (LSL_LIN1_TS_INSTANCES, LSL_LIN2_WS_INSTANCES; the switches of
+// launch_gemm and launch_attention_t), and a gate that depends on a kernel's LDS need asks the kernel's own config for it.
 #pragma once
+#include <atomic>
+#include <type_traits>
+
+#include "host_common.hip.h"
+
+namespace {
 
 // One launch of the output head (run_head fills it): the rows h [n, D] with their modulation rows, the projection, and either `out` or
 // the record's update u of x (do_step)
@@ -171,9 +176,13 @@ void launch_gemm_glds(const GemmArgs &g, const Epi &epi, hipStream_t st) {
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NWF * NWT * 64), lds, st, g, epi);
 }
 
+}  // namespace
+
 #ifdef LSL_EXPERIMENTS
 #include "host_launch_experiments.hip.h"  // (needs launch_gemm_glds / device_cus above)
 #endif
+
+namespace {
 
 // linear1 on the token-stationary kernel (k_lin1.hip.h): hidden sizes 128 / 256 / 384 / 512, sections (q | k | v | mlp) on multiples of 64
 // features.  Same bits as the tile kernels below (tools/lin1_harness.hip), so the choice between them may depend on the launch size.
@@ -572,50 +581,4 @@ void launch_dense(float *out, const float *in, const float *W, const float *bias
     }
 }
 
-// ---- the losses: the team forms of k_loss_frag.hip.h, one dispatcher for D = 1..4, one launch of the quotient finals ----
-// f(ic<D>) for the D of the call (checked by the caller: 1..4)
-template <class Fn>
-void dispatch_d(int D, Fn f) {
-    switch (D) {
-        case 1: f(ic<1>()); break;
-        case 2: f(ic<2>()); break;
-        case 3: f(ic<3>()); break;
-        default: f(ic<4>()); break;
-    }
-}
-
-// the five sums of every frame (k_geomloss.hip.h)
-template <int D, int TEAM>
-void launch_geom_frame(float *sums, const float *pred, const float *target, const unsigned char *mask, int F, int A, hipStream_t st) {
-    auto kern = k_geom_loss_frame<D, TEAM>;
-    if (TEAM == 256) LSL_ALLOW_LDS(kern, geom_team_bytes(LSL_GEOM_MAX_A, D));  // (above 64 KiB at D = 4)
-    hipLaunchKernelGGL(kern, dim3(loss_team_grid<TEAM>(F)), dim3(256), (256 / TEAM) * geom_team_bytes(A, D), st, sums, pred, target, mask, F, A);
-}
-
-// the four sums of every peptide frame (k_peptloss.hip.h)
-template <int TEAM>
-void launch_peptide_frame(float *sums, const float *pred, const float *target_frame, const unsigned char *atom14_mask, const float *tors_target,
-                          const unsigned char *tors_mask, const long long *aatype, const signed char *restab, int F, int R, int kind, hipStream_t st) {
-    // (at most 4 * pept_team_bytes(4) or pept_team_bytes(146) = 24.7 KB of LDS: below the 64 KiB default)
-    hipLaunchKernelGGL(k_peptide_loss_frame<TEAM>, dim3(loss_team_grid<TEAM>(F)), dim3(256), (256 / TEAM) * pept_team_bytes(R), st, sums, pred,
-                       target_frame, atom14_mask, tors_target, tors_mask, aatype, restab, F, R, kind);
-}
-
-// per-agent and per-trajectory displacement errors (k_disperr.hip.h)
-template <int D, int TEAM>
-void launch_disp_rows(float *rows, float *traj, const float *pred, const float *target, long long units, int B, int Tp, int t0p, int Tt, int t0t,
-                      int Tf, int A, hipStream_t st) {
-    hipLaunchKernelGGL((k_disp_rows<D, TEAM>), dim3(loss_team_grid<TEAM>(units)), dim3(256), 0, st, rows, traj, pred, target, units, B, Tp, t0p, Tt,
-                       t0t, Tf, A);
-}
-
-// lsl_geom_loss_final / lsl_peptide_loss_final / lsl_class_loss_final: out[0 .. NOUT - 1] from a [F, WA] and, WB > 0, b [F, WB]
-template <int WA, int WB, int NOUT>
-int loss_final(const char *name, const float *a, const float *b, int F, float *out, unsigned long long quots, void *stream) {
-    DeviceGuard dev_guard_((hipStream_t)stream);
-    if (!a || (WB > 0 && !b) || !out) return fail(-1, "null argument");
-    if (F <= 0) return fail(-3, "F must be positive");
-    hipLaunchKernelGGL((k_loss_final<WA, WB, NOUT>), dim3(1), dim3(64), 0, (hipStream_t)stream, out, a, b, F, quots);
-    LSL_CHECK_LAUNCH(name);
-    return 0;
-}
+}  // namespace

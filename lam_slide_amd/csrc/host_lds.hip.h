@@ -1,7 +1,12 @@
 // Per-device one-time kernel attributes: the dynamic-LDS allowance of a kernel (LSL_ALLOW_LDS at its launch site).  The attribute is set
-// through the kernel's symbol, so a translation unit that defines kernels includes this: host_common.hip.h (lsl_api.hip) and unit_lin1.hip,
-// each inside its anonymous namespace.
+// through the kernel's symbol, so every translation unit that launches a kernel with more than 64 KiB of dynamic LDS includes this and
+// sets the attribute itself: the state (one flag per call site) is the unit's own.
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+
+namespace {
 
 template <typename K>
 void allow_lds(K kernel, size_t bytes) {
@@ -19,6 +24,9 @@ struct DevOnce {
         return true;
     }
 };
+
+}  // namespace
+
 #define LSL_ALLOW_LDS(kern, bytes)                  \
     do {                                            \
         static DevOnce once_;                       \

@@ -99,12 +99,11 @@ struct Lin1Cfg {
 #define LSL_LIN1_TS_INSTANCES(X) X(32, 128) X(32, 256) X(32, 384) X(32, 512) X(16, 128) X(16, 256) X(16, 384) X(16, 512)
 
 // The kernel is compiled in a translation unit of its own (unit_lin1.hip: its compile options are chosen for this kernel alone and move no
-// other kernel).  The main unit (lsl_api.hip, which defines LSL_LIN1_HOST_SIDE) sees the argument block, the configuration and these two functions:
+// other kernel).  The sampling path's unit (lsl_api.hip, which defines LSL_LIN1_HOST_SIDE) sees the argument block, the configuration and one function:
 // lsl_lin1_launch starts k_linear1_ts<hdp, K, waves, lnf> on `grid` workgroups with `lds` bytes of dynamic LDS (grid, lds and a.wpt are the
 // caller's: launch_linear1_ts_t) and sets the dynamic-LDS attribute, which has to happen where the kernel symbol is defined; false: no such
-// instance.  lsl_lin1_unit_options: the options unit_lin1.hip was compiled with (lsl_build_info).
+// instance.
 bool lsl_lin1_launch(int hdp, int K, int waves, bool lnf, const Lin1Args &a, int grid, size_t lds, hipStream_t st);
-const char *lsl_lin1_unit_options();
 
 #ifndef LSL_LIN1_HOST_SIDE
 

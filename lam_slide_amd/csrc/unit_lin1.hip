@@ -5,17 +5,14 @@
 // No device call crosses the units (no -fgpu-rdc); the plan and the dispatch stay in lsl_api.hip.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #include "k_lin1.hip.h"
 
-#ifndef LSL_UNIT_OPTIONS
-#define LSL_UNIT_OPTIONS ""
-#endif
+#include "host_api.hip.h"
+#include "host_lds.hip.h"
+
+LSL_UNIT_INFO;
 
 namespace {
-
-#include "host_lds.hip.h"
 
 template <int HDP, int K, int NW, bool LNF>
 void launch(const Lin1Args &a, int grid, size_t lds, hipStream_t st) {
@@ -43,5 +40,3 @@ bool lsl_lin1_launch(int hdp, int K, int waves, bool lnf, const Lin1Args &a, int
 #undef X
     return false;
 }
-
-const char *lsl_lin1_unit_options() { return LSL_UNIT_OPTIONS; }

@@ -1,6 +1,10 @@
-// Host side, part 4 of 4: C entry points of the frozen stage-1 decoder / encoder (decode_host.hip.h holds their launch helpers) and of the
-// class losses of the decoder heads (k_classloss.hip.h).  Inside the extern "C" block of lsl_api.hip.
-#pragma once
+// The frozen stage-1 model's translation unit of liblamslide_hip.so (include/lsl_api.h): the encoder and decoder handles, lsl_encode,
+// lsl_decode and lsl_decode_heads (every decoder head from one trunk).  decode_host.hip.h holds their scratch layout and launch helpers.
+#include "decode_host.hip.h"
+
+LSL_UNIT_INFO;
+
+extern "C" {
 
 int lsl_decoder_create(const lsl_decoder_desc *desc, const lsl_decoder_weights *w, lsl_decoder **out) try {
     if (!desc || !w || !out) return fail(-1, "null decoder argument");
@@ -85,25 +89,6 @@ int lsl_decode_heads(lsl_decoder *dec, const lsl_decoder_head *heads, int32_t n_
     return decode_call(dec, heads, n_heads, z, entities, frames, L, A, outs, workspace, workspace_bytes, (hipStream_t)stream, "lsl_decode_heads");
 } LSL_API_CATCH
 
-// ---- class losses of the decoder heads (k_classloss.hip.h) ----
-int lsl_class_loss_sums(const float *logits, const int64_t *target, const uint8_t *mask, int32_t F, int32_t A, int32_t K, float label_smoothing,
-                        float *sums, int64_t *confusion, void *stream) try {
-    DeviceGuard dev_guard_((hipStream_t)stream);
-    if (!logits || !target || !sums) return fail(-1, "null argument");
-    if (F <= 0) return fail(-3, "F must be positive");
-    if (A < 1) return fail(-3, "A = %d: at least one row per frame", A);
-    if (K < 1 || K > LSL_CLS_MAX_K) return fail(-3, "K = %d outside the native form (1..%d classes)", K, LSL_CLS_MAX_K);
-    if (!(label_smoothing >= 0.0f && label_smoothing < 1.0f)) return fail(-3, "label_smoothing = %g outside [0, 1)", (double)label_smoothing);
-    hipLaunchKernelGGL(k_class_loss_frame, dim3((unsigned)F), dim3(64), class_tile_bytes(K), (hipStream_t)stream, sums, (unsigned long long *)confusion, logits,
-                       (const long long *)target, mask, (int)A, (int)K, label_smoothing);
-    LSL_CHECK_LAUNCH("lsl_class_loss_sums");
-    return 0;
-} LSL_API_CATCH
-
-int lsl_class_loss_final(const float *sums, int32_t F, float *out, void *stream) try {
-    return loss_final<2, 0, 1>("lsl_class_loss_final", sums, nullptr, F, out, CLASS_QUOTS, stream);
-} LSL_API_CATCH
-
 int lsl_encoder_create(const lsl_encoder_desc *desc, const lsl_encoder_weights *w, lsl_encoder **out) try {
     if (!desc || !w || !out) return fail(-1, "null encoder argument");
     const lsl_encoder_desc &d = *desc;
@@ -148,3 +133,5 @@ int lsl_encode(lsl_encoder *enc, const float *x, const int64_t *entities, const 
     LSL_CHECK_LAUNCH("lsl_encode");
     return 0;
 } LSL_API_CATCH
+
+}  // extern "C"

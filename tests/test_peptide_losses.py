@@ -290,7 +290,8 @@ def test_library_exports_and_header_declare_the_peptide_losses():
     assert "lsl_peptide_loss_sums, lsl_peptide_loss_final added" in header
     src = open(os.path.join(ROOT, "lam_slide_amd", "csrc", "k_peptloss.hip.h")).read()
     assert "#define LSL_PEPT_MAX_R (LSL_GEOM_MAX_A / 14)" in src and pl.MAX_R == _lib.GEOM_MAX_A // 14 == 146
-    assert "k_peptloss.hip.h" in open(os.path.join(ROOT, "lam_slide_amd", "csrc", "lsl_api.hip")).read()
+    # (compiled into the library: some translation unit includes it)
+    assert any('#include "k_peptloss.hip.h"' in open(os.path.join(_lib.SRC_DIR, unit)).read() for unit, _ in _lib.UNITS)
 
 
 def test_entry_points_validate_arguments_without_gpu():

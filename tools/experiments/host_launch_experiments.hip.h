@@ -1,7 +1,9 @@
 // Host-side launchers of the measured-and-rejected structures and A/B arms: included by lam_slide_amd/csrc/host_launch.hip.h ONLY in
 // -DLSL_EXPERIMENTS builds (tools/build_experiments.sh puts tools/experiments/ on the include path); the product library has empty hooks
-// in their place.  Inside the anonymous namespace of host_common.hip.h, behind launch_gemm_glds / device_cus / tune_int.
+// in their place.  Behind launch_gemm_glds / device_cus / tune_int of that file.
 #pragma once
+
+namespace {
 
 template <int BK, int NS, int NB, class Epi>
 void launch_gemm_pp_t(const GemmArgs &g, const Epi &epi, hipStream_t st) {
@@ -80,3 +82,5 @@ bool launch_head_experiment(const HeadArgs &a, hipStream_t st) {
                        a.bo, a.n, a.C, a.tpt, a.do_step, a.u);
     return true;
 }
+
+}  // namespace
