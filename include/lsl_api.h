@@ -50,7 +50,8 @@ extern "C" {
  * 6, later still: lsl_pair_distances, lsl_ca_frame_stats, lsl_histogram_columns, lsl_js_distance_density added the same way.
  * 6, later still: lsl_debug_mods_ex, lsl_debug_mods_steps, lsl_debug_embed, lsl_debug_head added the same way.
  * 6, later still: lsl_weighted_moments_workspace_bytes, lsl_weighted_moments, lsl_affine_weights, lsl_project_wide added the same way.
- * 6, later still: lsl_msm_active_set, lsl_msm_reversible_step, lsl_msm_transition_matrix added the same way. */
+ * 6, later still: lsl_msm_active_set, lsl_msm_reversible_step, lsl_msm_transition_matrix added the same way.
+ * 6, later still: lsl_superpose, lsl_atom_rmsf_workspace_bytes, lsl_atom_rmsf added the same way. */
 #define LSL_VERSION 6
 
 typedef struct lsl_model lsl_model;
@@ -523,6 +524,40 @@ int lsl_msm_active_set(const int64_t *counts, int32_t S, int32_t ns, int32_t *ac
 int lsl_msm_reversible_step(const int64_t *counts, const int32_t *active, int32_t S, int32_t ns, int32_t iters, int32_t maxiter, double maxerr,
                             int32_t restart, double *x, int32_t *n_iter, double *err, int32_t *done, void *stream);
 int lsl_msm_transition_matrix(const int64_t *counts, const int32_t *active, const double *x, int32_t S, int32_t ns, double *T, double *pi, void *stream);
+
+/* Rigid superposition of a sampled trajectory: what the reference does through mdtraj before a trajectory is written or analysed
+ * (eval_peptide.py:347 traj.superpose(traj); utils/traj_utils.py:54-60 create_trajectory = center_coordinates() then superpose(traj, 0)) -
+ * the Kabsch fit of every frame onto a reference, its RMSD, and the per-atom mean and RMSF.  Device pointers unless named host; nothing is
+ * allocated, nothing is synchronised, a refused call enqueues nothing.  No atomics.  All arithmetic is fp64 on the exact fp32 inputs in a
+ * fixed order, every output is rounded once: a frame has the same bits alone and inside any batch, an atom the same bits at any A.  The
+ * functions are fixed here as mathematics; mdtraj fits in float32 by QCP, parity with a live mdtraj is not claimed.
+ *
+ * lsl_superpose: for each of F frames x = pos[f] [A, 3] f32 and its reference y = ref[0] (ref_frames == 1) or ref[f] (ref_frames == F), over the
+ *   n_sel selected atoms sel i32 [n_sel] (sel_host: the same table in HOST memory, range-checked: outside 0..A-1 is -3; both NULL: all A
+ *   atoms, n_sel == A):
+ *     cx, cy  the centroids of the selection (lane l of a wave adds the selected atoms l, l + 64, .. in order, the 64 lanes are combined by the
+ *             butterfly lane ^ 1, ^ 2, .. ^ 32; one division by n_sel) - every sum below has this order;
+ *     S       = sum_i (x_i - cx)(y_i - cy)^T;  R = the proper rotation (det +1, never a reflection) minimising sum_i |R (x_i - cx) - (y_i - cy)|^2:
+ *             the unit eigenvector q of the largest eigenvalue of Horn's 4 x 4 matrix K(S) by 8 cyclic Jacobi sweeps (a fixed count), its
+ *             first nonzero component positive, R = R(q).  S == 0 exactly (one selected atom, coincident atoms) gives R = 1;
+ *     out     f32 [F, A, 3] = R (x_a - cx) + cy for EVERY atom a of the frame; an atom with fixed[a] != 0 (fixed u8 [A], or NULL) is copied
+ *             through unchanged (the zeroed padding slots of an atom14 frame);
+ *     rmsd    f32 [F] = sqrt(sum_i |R (x_i - cx) - (y_i - cy)|^2 / n_sel), from the fp64 residuals (a frame against itself gives 0, not 1e-7);
+ *     rot     f64 [F, 3, 3] = R;  trans f64 [F, 3] = cy - R cx:  out = R x + trans.
+ *   flags = LSL_SUP_CENTER_ONLY: out = x - cx (center_coordinates), rot = 1, trans = -cx; ref is not read and may be NULL, rmsd must be NULL.
+ *   Each output may be NULL; all NULL is 0 without a launch.  out may be pos (a frame is in LDS before it is written); out must not overlap
+ *   ref (-3).  A frame holding NaN among its selected atoms (or its reference's) gives NaN for that frame only.  1 <= A <= 2044 (a frame
+ *   in LDS), 1 <= n_sel <= 2044, F >= 1, ref_frames 1 or F.
+ * lsl_atom_rmsf: mean_out f64 [A, 3] = mean_f pos[f, a] and rmsf_out f32 [A] = sqrt(mean_f |pos[f, a] - mean_a|^2) of pos [F, A, 3] f32, each
+ *   may be NULL.  The frames are split in segments of 128; a column's sum is the segments' sums (frames in order) added in segment order,
+ *   the second pass ((x - mean)^2 per coordinate) likewise, then (sx + sy) + sz, one division by F, one square root.  workspace: device
+ *   memory of lsl_atom_rmsf_workspace_bytes(F, A) bytes (0 for a refused shape; too small: -4).  A >= 1, 1 <= F <= 8388480. */
+#define LSL_SUP_CENTER_ONLY 1
+int lsl_superpose(const float *pos, const float *ref, int32_t ref_frames, const int32_t *sel, const int32_t *sel_host, int32_t n_sel,
+                  const uint8_t *fixed, int64_t F, int32_t A, int32_t flags, float *out, float *rmsd, double *rot, double *trans, void *stream);
+size_t lsl_atom_rmsf_workspace_bytes(int64_t F, int32_t A);
+int lsl_atom_rmsf(const float *pos, int64_t F, int32_t A, double *mean_out, float *rmsf_out, void *workspace, size_t workspace_bytes,
+                  void *stream);
 
 /* Sampler loop (Sampler.sample_ode / sample_sde inner loops): applies n_steps affine updates to io->x
  * in place.  noise: device [n_noise, B*T*L*C] standard-normal draws, slice s belongs to step s (the

@@ -47,6 +47,11 @@ Public surface (mirrors the reference's for this path only):
                                       encode -> decode with every output head from one trunk (``Stage1Decoder.decode_heads``), the four
                                       first-stage ``Loss`` classes with their cross-entropy terms and the accuracy / precision / recall
                                       counts on the device (first_stage.py)
+  superpose.superpose, center_coordinates, rmsd, rmsf, superpose_atom14, create_trajectory
+                                   <- rigid superposition of the sampled positions on the device (superpose.py): the Kabsch fit mdtraj's
+                                      ``traj.superpose`` runs before a trajectory is written (eval_peptide.py:347) or analysed
+                                      (utils/traj_utils.py create_trajectory), its RMSD, and the per-atom RMSF.  ``superpose`` names the
+                                      module here; the function is ``superpose.superpose``
   install()                        <- rebinds the reference's module-level ``Sampler`` (lightning_base.py:10); see dropin.py
 The compute lives in liblamslide_hip.so (include/lsl_api.h); build it with ``__graft_entry__.build()``.
 """
@@ -76,6 +81,8 @@ from .structure_stats import (CaFrameStats, StructureTables, backbone_torsion_qu
                               traj_analysis, triu_pairs)
 from . import koopman_tica
 from .koopman_tica import KoopmanWeights, WideTicaModel, koopman_weights, run_tica, weighted_moments
+from . import superpose
+from .superpose import center_coordinates, create_trajectory, rmsd, rmsf, superpose_atom14
 from .transport import (CreateTransport, ModelType, PathType, Sampler, SampleResult, Transport, WeightType, as_transport, device_randn,
                         mix_seed, si_reduce)
 
@@ -89,4 +96,5 @@ __all__ = ["msm", "MarkovModel", "active_set", "estimate_markov_model", "markov_
            "structure_stats", "traj_analysis", "StructureTables", "CaFrameStats", "pair_distances", "ca_frame_stats", "tica_features", "column_edges",
            "histogram_columns", "js_distance_density", "density_js", "joint_density_js", "ca_atoms", "ca_pair_table", "backbone_torsion_quads",
            "tica_atom_selection", "triu_pairs",
+           "superpose", "center_coordinates", "create_trajectory", "rmsd", "rmsf", "superpose_atom14",
            "first_stage", "Stage1Autoencoder", "ClassMeter", "class_losses", "class_loss_sums"]

@@ -49,6 +49,7 @@ EXPORTED = (
     "lsl_kmeans_workspace_bytes", "lsl_kmeans_step", "lsl_kmeans_nearest_rows",
     "lsl_weighted_moments_workspace_bytes", "lsl_weighted_moments", "lsl_affine_weights", "lsl_project_wide",
     "lsl_msm_active_set", "lsl_msm_reversible_step", "lsl_msm_transition_matrix",
+    "lsl_superpose", "lsl_atom_rmsf_workspace_bytes", "lsl_atom_rmsf",
     "lsl_profile_enable", "lsl_profile_read", "lsl_randn", "lsl_rk_lincomb", "lsl_rk_dense", "lsl_rk_error_ratio",
     "lsl_decoder_create", "lsl_decoder_destroy", "lsl_decode_workspace_bytes", "lsl_decode",
     "lsl_encoder_create", "lsl_encoder_destroy", "lsl_encode_workspace_bytes", "lsl_encode",
@@ -268,6 +269,10 @@ def load() -> C.CDLL:
     lib.lsl_msm_active_set.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.lsl_msm_reversible_step.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_double, C.c_int32] + [C.c_void_p] * 5
     lib.lsl_msm_transition_matrix.argtypes = [C.c_void_p] * 3 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.lsl_superpose.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 5
+    lib.lsl_atom_rmsf_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
+    lib.lsl_atom_rmsf_workspace_bytes.restype = C.c_size_t
+    lib.lsl_atom_rmsf.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.lsl_randn.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
     lib.lsl_rk_lincomb.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.c_int32, C.c_uint64, C.c_void_p]
     lib.lsl_rk_dense.argtypes = [C.c_void_p] * 6 + [C.c_float, C.c_uint64, C.c_void_p]

@@ -1,5 +1,5 @@
 // The evaluation statistics' translation unit of liblamslide_hip.so (include/lsl_api.h): torsion and structure statistics of a sampled
-// peptide trajectory, TICA and Koopman-reweighted TICA, k-means fitting, and the reversible Markov state models.
+// peptide trajectory, TICA and Koopman-reweighted TICA, k-means fitting, the reversible Markov state models, and rigid superposition.
 #include "../../include/lsl_api.h"
 
 #include <hip/hip_runtime.h>
@@ -12,6 +12,7 @@
 #include "k_wtica.hip.h"
 #include "k_kmeans.hip.h"
 #include "k_msm.hip.h"
+#include "k_superpose.hip.h"
 
 #include "host_api.hip.h"
 
@@ -432,6 +433,73 @@ int lsl_msm_transition_matrix(const int64_t *counts, const int32_t *active, cons
     else LSL_MSM_LAUNCH(128);
 #undef LSL_MSM_LAUNCH
     LSL_CHECK_LAUNCH("lsl_msm_transition_matrix");
+    return 0;
+} LSL_API_CATCH
+
+// ---- rigid superposition of a sampled trajectory: Kabsch fit, RMSD, per-atom mean and RMSF (k_superpose.hip.h) ----
+int lsl_superpose(const float *pos, const float *ref, int32_t ref_frames, const int32_t *sel, const int32_t *sel_host, int32_t n_sel,
+                  const uint8_t *fixed, int64_t F, int32_t A, int32_t flags, float *out, float *rmsd, double *rot, double *trans, void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    const bool center_only = (flags & LSL_SUP_CENTER_ONLY) != 0;
+    if (!pos || (!ref && !center_only) || (sel == nullptr) != (sel_host == nullptr))
+        return fail(-1, "null argument (a fit needs ref; sel and its host copy come together)");
+    if (flags & ~LSL_SUP_CENTER_ONLY) return fail(-3, "flags = %d: only LSL_SUP_CENTER_ONLY (%d) is defined", flags, LSL_SUP_CENTER_ONLY);
+    if (A < 1 || A > LSL_TORS_MAX_A) return fail(-3, "A = %d outside the native form (1..%d atoms of a frame)", A, LSL_TORS_MAX_A);
+    const int fpb = LSL_TORS_LDS_ATOMS / A;
+    if (F < 1 || (F + fpb - 1) / fpb > 0x7fffffffLL) return fail(-3, "F = %lld frames: 1 .. %lld at A = %d", (long long)F, 0x7fffffffLL * fpb, A);
+    if (sel ? (n_sel < 1 || n_sel > LSL_TORS_MAX_A) : n_sel != A)
+        return fail(-3, "n_sel = %d outside 1..%d selected atoms (without a table: all A = %d atoms)", n_sel, LSL_TORS_MAX_A, A);
+    for (int i = 0; sel && i < n_sel; ++i)
+        if (sel_host[i] < 0 || sel_host[i] >= A) return fail(-3, "sel[%d] = %d outside the frame's atoms 0..%d", i, sel_host[i], A - 1);
+    if (center_only && rmsd) return fail(-3, "rmsd with LSL_SUP_CENTER_ONLY: there is no reference to measure against");
+    if (!center_only) {
+        if (ref_frames != 1 && (int64_t)ref_frames != F) return fail(-3, "ref_frames = %d: one shared reference frame (1) or one per frame (F = %lld)", ref_frames, (long long)F);
+        const size_t frame_bytes = (size_t)A * 3 * sizeof(float);
+        const char *ob = (const char *)out, *rb = (const char *)ref;
+        if (out && ob < rb + (size_t)ref_frames * frame_bytes && rb < ob + (size_t)F * frame_bytes)
+            return fail(-3, "out overlaps ref: the reference is read while the frames are written (copy the reference first)");
+    }
+    if (!out && !rmsd && !rot && !trans) return 0;  // (nothing asked for)
+    hipLaunchKernelGGL(k_superpose, dim3((unsigned)((F + fpb - 1) / fpb)), dim3(256), 0, (hipStream_t)stream, out, rmsd, rot, trans, pos, ref,
+                       (const int *)sel, (const unsigned char *)fixed, (long long)F, (int)A, (int)n_sel, fpb, (int)(!center_only && ref_frames != 1),
+                       (int)center_only);
+    LSL_CHECK_LAUNCH("lsl_superpose");
+    return 0;
+} LSL_API_CATCH
+
+static const char *rmsf_shape_error(int64_t F, int32_t A) {
+    if (A < 1) return "A must be positive";
+    if (F < 1 || (F + LSL_RMSF_SEG - 1) / LSL_RMSF_SEG > 65535) return "F outside 1..8388480 frames (65535 segments)";
+    return nullptr;
+}
+
+size_t lsl_atom_rmsf_workspace_bytes(int64_t F, int32_t A) {
+    if (rmsf_shape_error(F, A)) return 0;
+    return 2 * (size_t)((F + LSL_RMSF_SEG - 1) / LSL_RMSF_SEG) * 3 * (size_t)A * sizeof(double);
+}
+
+int lsl_atom_rmsf(const float *pos, int64_t F, int32_t A, double *mean_out, float *rmsf_out, void *workspace, size_t workspace_bytes,
+                  void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!pos || !workspace) return fail(-1, "null argument");
+    if (const char *why = rmsf_shape_error(F, A)) return fail(-3, "F = %lld, A = %d: %s", (long long)F, A, why);
+    const size_t need = lsl_atom_rmsf_workspace_bytes(F, A);
+    if (workspace_bytes < need) return fail(-4, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    if (!mean_out && !rmsf_out) return 0;  // (nothing asked for)
+    hipStream_t st = (hipStream_t)stream;
+    const int nseg = (int)((F + LSL_RMSF_SEG - 1) / LSL_RMSF_SEG);
+    const long long C = 3LL * A;
+    double *first = (double *)workspace, *second = first + (size_t)nseg * C;
+    const dim3 grid((unsigned)((C + 63) / 64), (unsigned)nseg);
+    hipLaunchKernelGGL(k_atom_mean_partial<false>, grid, dim3(64), 0, st, first, (const double *)nullptr, pos, (long long)F, C, nseg);
+    LSL_CHECK_LAUNCH("lsl_atom_rmsf");
+    if (rmsf_out) {
+        hipLaunchKernelGGL(k_atom_mean_partial<true>, grid, dim3(64), 0, st, second, (const double *)first, pos, (long long)F, C, nseg);
+        LSL_CHECK_LAUNCH("lsl_atom_rmsf (second pass)");
+    }
+    hipLaunchKernelGGL(k_atom_rmsf_final, dim3((unsigned)(((long long)A + 255) / 256)), dim3(256), 0, st, mean_out, rmsf_out, (const double *)first,
+                       (const double *)second, (long long)F, (int)A, nseg);
+    LSL_CHECK_LAUNCH("lsl_atom_rmsf (final)");
     return 0;
 } LSL_API_CATCH
 

@@ -334,9 +334,18 @@ class RolloutSampler:
         }
 
     @torch.no_grad()
-    def sample_rollout(self, cond_pos: Tensor, res: Tensor, res_mask: Tensor, num_rollouts: int = 1) -> Tensor:
+    def sample_rollout(self, cond_pos: Tensor, res: Tensor, res_mask: Tensor, num_rollouts: int = 1, superpose: bool = False,
+                       tables=None) -> Tensor:
+        """``superpose=True``: the frames are fitted onto the first one (the conditioning frame) on the device, in place, as
+        ``eval_peptide.py:347`` does with ``traj_pred.superpose(traj_pred)`` - ``superpose.superpose_atom14(positions, res, frame=0)``,
+        fitted on the heavy atoms of the residue types ``res``; ``tables``: the residue tables that selection is built from (None: the
+        host application's).  The default leaves the positions as they were sampled."""
         def one(pos):
             out = self.model.sample(self.create_batch(pos=pos, res=res, res_mask=res_mask))[self.key]
             return out.squeeze(0) if out.dim() == cond_pos.dim() + 2 else out
 
-        return sample_rollout(one, cond_pos, num_rollouts, shift=self.model.shift, scale=self.model.scale)
+        positions = sample_rollout(one, cond_pos, num_rollouts, shift=self.model.shift, scale=self.model.scale)
+        if superpose:
+            from .superpose import superpose_atom14
+            positions = superpose_atom14(positions, res, frame=0, tables=tables, out=positions if positions.is_contiguous() else None)
+        return positions

@@ -22,7 +22,8 @@ counts are integers (exact), every float is a sum in a fixed order (a frame has 
 anything else takes a numpy / torch restatement with the same outputs and the same NaN conventions.  ``last_path[name]`` tells which of
 the two ("fused" / "torch") the last call of a function took.
 
-Not here.  Plots, superposition and mdtraj I/O: every metric here is invariant under rigid motion.  ``run_tica``'s Koopman-reweighted
+Not here.  Plots and mdtraj I/O.  Every metric here is invariant under rigid motion; superposition, RMSD and RMSF of the same positions
+are ``lam_slide_amd.superpose``.  ``run_tica``'s Koopman-reweighted
 estimate over ``tica_features`` is ``koopman_tica.run_tica`` (``traj_analysis(..., tica_lagtime=)``); projections from any other model
 enter ``traj_analysis`` as ``tics_ref`` / ``tics_model``.  Neither mdtraj nor deeptime was available where this was
 written: the statements below are checked against numpy / scipy, parity with a live mdtraj was not checked."""
@@ -104,7 +105,8 @@ def triu_pairs(idx) -> np.ndarray:
 class StructureTables:
     """The index tables of one peptide, built once (host int32 arrays) and put on a device once (``on(device)``): ``ca`` [R],
     ``ca_pairs`` [P, 2] (frame indices of ``ca_pair_table``, P may be 0), ``quads`` [3 (R - 1), 4] = phi | psi | omega with ``n_tors``
-    rows each, ``rama`` [2, 4] = the first phi and the first psi, ``tica_pairs`` = ``triu_pairs(tica_atom_selection(aatype))``.  Pass it
+    rows each, ``rama`` [2, 4] = the first phi and the first psi, ``tica_pairs`` = ``triu_pairs(tica_atom_selection(aatype))``, ``topology``
+    [n] = ``topology_atoms(aatype)`` (the heavy atoms ``superpose.superpose_atom14`` fits on) and ``padding`` bool [R * 14] = every other slot.  Pass it
     where a function takes ``aatype`` to keep the tables on the device between calls: with it, ``traj_analysis`` uploads nothing."""
 
     def __init__(self, aatype, tables=None, offset: int = 3) -> None:
@@ -119,12 +121,15 @@ class StructureTables:
         self.quads = i32(np.concatenate(bb), 4)
         self.rama = i32(np.concatenate([bb.phi[:1], bb.psi[:1]]), 4)
         self.tica_pairs = i32(triu_pairs(tica_atom_selection(self.aatype, tables)), 2)
+        self.topology = i32(_ts.topology_atoms(self.aatype, tables), 0)
+        self.padding = np.ones(self.R * 14, dtype=bool)
+        self.padding[self.topology] = False
         self._on: dict = {}
 
     def on(self, device) -> Dict[str, Tensor]:
         device = torch.device(device)
         if device not in self._on:
-            names = ("ca", "ca_pairs", "quads", "rama", "tica_pairs")
+            names = ("ca", "ca_pairs", "quads", "rama", "tica_pairs", "topology", "padding")
             self._on[device] = {k: torch.from_numpy(getattr(self, k)).to(device) for k in names}
             if device.type == "cuda":
                 _ts._pair01_on(device)  # (joint_density_js' pair table: with the tables on the device, nothing is uploaded later)
