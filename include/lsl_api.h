@@ -51,7 +51,8 @@ extern "C" {
  * 6, later still: lsl_debug_mods_ex, lsl_debug_mods_steps, lsl_debug_embed, lsl_debug_head added the same way.
  * 6, later still: lsl_weighted_moments_workspace_bytes, lsl_weighted_moments, lsl_affine_weights, lsl_project_wide added the same way.
  * 6, later still: lsl_msm_active_set, lsl_msm_reversible_step, lsl_msm_transition_matrix added the same way.
- * 6, later still: lsl_superpose, lsl_atom_rmsf_workspace_bytes, lsl_atom_rmsf added the same way. */
+ * 6, later still: lsl_superpose, lsl_atom_rmsf_workspace_bytes, lsl_atom_rmsf added the same way.
+ * 6, later still: lsl_dopri_workspace_bytes, lsl_dopri_begin, lsl_dopri_advance, lsl_debug_dopri_coeffs added the same way. */
 #define LSL_VERSION 6
 
 typedef struct lsl_model lsl_model;
@@ -593,6 +594,57 @@ int lsl_rk_lincomb(float *out, const float *const *x, const float *c, int32_t n_
 int lsl_rk_dense(float *out, const float *a, const float *b, const float *c, const float *d, const float *e, float x, uint64_t n, void *stream);
 int lsl_rk_error_ratio(float *ratio, const float *y0, const float *y1, const float *const *k, const float *c, int32_t n_k, float atol, float rtol,
                        uint64_t n, void *scratch, void *stream);
+
+/* Adaptive Dormand-Prince 5(4) with the step controller on the device (lam_slide_amd/transport.py: dopri5_solve is the host restatement;
+ * csrc/k_dopri5.hip.h the kernels).  The controller's state lives in the caller's workspace; every kernel of an attempt reads it there, so
+ * an attempt takes no host value, is enqueued without a synchronisation, and is replayed as a hipGraph under the rule of lsl_sample
+ * (LSL_GRAPH: the first attempt of a key runs eagerly, the second is captured, later ones replay; same bits).  State arithmetic: the
+ * rounding contract of lsl_rk_* above; time and controller arithmetic: fp64.  The error norm runs over the whole state [B,T,L,C].
+ *
+ * The workspace (lsl_dopri_workspace_bytes) starts with the records a caller reads back with one small copy:
+ *   LSL_DOPRI_CTL_OFFSET    lsl_dopri_ctl
+ *   LSL_DOPRI_LOG_OFFSET    fp64 [LSL_DOPRI_MAX_ATTEMPTS][4]: row a = (t, dt, ratio, accepted) of attempt a (a < accepted + rejected)
+ *   LSL_DOPRI_STATE_OFFSET  fp32 [B,T,L,C]: the current state y (the solution at lsl_dopri_ctl.t)
+ * behind them nine more state-sized buffers (stage state, network output, k_1..k_7), the time vector, the reduction scratch, the network's
+ * workspace (lsl_workspace_bytes) and the output times.
+ *
+ *   lsl_dopri_begin    io->x = y(grid[0]) (read only; io->t / io->out unused); grid: n_out non-decreasing output times on the host;
+ *                      out: device [n_out][B,T,L,C].  Writes out[j] = y for every leading j with grid[j] <= grid[0], evaluates f(t0, y) and
+ *                      chooses the first step size (Hairer's rule, one more evaluation).  The network is given the time t (reverse: 1 - t)
+ *                      rounded to fp32; the drift is vx y + vm net(y, t) with (vx, vm) of the path and prediction evaluated in fp64 at that
+ *                      fp32 time.  max_steps <= LSL_DOPRI_MAX_ATTEMPTS.
+ *   lsl_dopri_advance  n_attempts attempts: six stages, the error ratio, accept (ratio <= 1) or reject, the next step size
+ *                      dt min(10, max(0.9 ratio^-0.2, ratio < 1 ? 1 : 0.2)) (dt 10 at ratio 0); an accepted step writes every pending out[j]
+ *                      with grid[j] <= t + dt by 4th-order dense output.  Same io (x_cond, mask, y, B, T, L) and workspace as begin.  Once
+ *                      `done` is set (the last output time reached, or status != 0) an attempt changes nothing: enqueue as many as convenient,
+ *                      read the controller, repeat while !done.
+ * Device pointers in, nothing allocated, nothing synchronised; a refused call enqueues nothing. */
+#define LSL_DOPRI_MAX_ATTEMPTS 100000
+#define LSL_DOPRI_CTL_OFFSET 0
+#define LSL_DOPRI_LOG_OFFSET 256
+#define LSL_DOPRI_STATE_OFFSET (256 + 32 * LSL_DOPRI_MAX_ATTEMPTS)
+enum { LSL_PATH_LINEAR = 0, LSL_PATH_GVP = 1, LSL_PATH_VP = 2 };                               /* path.py: ICPlan, GVPCPlan, VPCPlan */
+enum { LSL_PRED_VELOCITY = 0, LSL_PRED_DATA = 1, LSL_PRED_NOISE = 2, LSL_PRED_SCORE = 3 };     /* transport.py: ModelType */
+enum { LSL_DOPRI_OK = 0, LSL_DOPRI_MAX_STEPS = 1, LSL_DOPRI_NON_FINITE = 2 };                  /* lsl_dopri_ctl.status */
+typedef struct lsl_dopri_desc {
+    int32_t path_type, model_type, reverse, max_steps;
+    double rtol, atol; /* (the kernels take them rounded to fp32, as lsl_rk_error_ratio does) */
+} lsl_dopri_desc;
+typedef struct lsl_dopri_ctl {
+    double t, dt, t_lo;          /* current time; the step size of the next attempt; where the last accepted step began */
+    double ratio, t_new, dt_next; /* the current attempt's decision: error ratio, t + dt, the step size that follows */
+    double rtol, atol;
+    float *out;                  /* lsl_dopri_begin's out */
+    int32_t accept, out_end;     /* decision: 1 = accepted; an accepted step writes out[next_out .. out_end) */
+    int32_t accepted, rejected, nfe, next_out, done, status;
+    int32_t n_out, max_steps, path_type, model_type, reverse;
+} lsl_dopri_ctl;
+size_t lsl_dopri_workspace_bytes(const lsl_model *m, int32_t B, int32_t T, int32_t L, int32_t n_out);
+int lsl_dopri_begin(lsl_model *m, const lsl_io *io, const lsl_dopri_desc *desc, const double *grid, int32_t n_out, float *out, void *workspace,
+                    size_t workspace_bytes, void *stream);
+int lsl_dopri_advance(lsl_model *m, const lsl_io *io, int32_t n_attempts, void *workspace, size_t workspace_bytes, void *stream);
+/* Test hook: out[i] = (vx, vm) of the drift vx y + vm net(y, t) at the fp32 times t[0..n), fp64, as the kernels of lsl_dopri_* evaluate them */
+int lsl_debug_dopri_coeffs(int32_t path_type, int32_t model_type, const float *t, int32_t n, double *out, void *stream);
 
 /* Test hooks: run a single kernel of the path on caller buffers (parity tests of intermediates). */
 int lsl_debug_block(lsl_model *m, int32_t block_index /* 0..2*depth-1 */, const float *h_in, float *h_out,

@@ -51,6 +51,7 @@ EXPORTED = (
     "lsl_msm_active_set", "lsl_msm_reversible_step", "lsl_msm_transition_matrix",
     "lsl_superpose", "lsl_atom_rmsf_workspace_bytes", "lsl_atom_rmsf",
     "lsl_profile_enable", "lsl_profile_read", "lsl_randn", "lsl_rk_lincomb", "lsl_rk_dense", "lsl_rk_error_ratio",
+    "lsl_dopri_workspace_bytes", "lsl_dopri_begin", "lsl_dopri_advance", "lsl_debug_dopri_coeffs",
     "lsl_decoder_create", "lsl_decoder_destroy", "lsl_decode_workspace_bytes", "lsl_decode",
     "lsl_encoder_create", "lsl_encoder_destroy", "lsl_encode_workspace_bytes", "lsl_encode",
     "lsl_decode_heads", "lsl_class_loss_sums", "lsl_class_loss_final",
@@ -127,6 +128,25 @@ class SiRow(C.Structure):  # lsl_si_row
 
 
 STEP_NO_NETWORK, STEP_SAVE = 1, 2
+
+
+class DopriDesc(C.Structure):  # lsl_dopri_desc
+    _fields_ = [(n, C.c_int32) for n in ("path_type", "model_type", "reverse", "max_steps")] + [("rtol", C.c_double), ("atol", C.c_double)]
+
+
+class DopriCtl(C.Structure):  # lsl_dopri_ctl
+    _fields_ = [(n, C.c_double) for n in ("t", "dt", "t_lo", "ratio", "t_new", "dt_next", "rtol", "atol")] + [("out", C.c_void_p)] + [
+        (n, C.c_int32) for n in ("accept", "out_end", "accepted", "rejected", "nfe", "next_out", "done", "status", "n_out", "max_steps", "path_type",
+                                 "model_type", "reverse")]
+
+
+class Dopri:
+    """The constants of lsl_dopri_* (include/lsl_api.h; tests/test_dopri5_controller.py holds them against the header)."""
+    MAX_ATTEMPTS = 100000  # LSL_DOPRI_MAX_ATTEMPTS
+    CTL_OFFSET, LOG_OFFSET, STATE_OFFSET = 0, 256, 256 + 32 * MAX_ATTEMPTS  # LSL_DOPRI_*_OFFSET
+    PATHS = {"LINEAR": 0, "GVP": 1, "VP": 2}  # LSL_PATH_*
+    PREDICTIONS = {"VELOCITY": 0, "DATA": 1, "NOISE": 2, "SCORE": 3}  # LSL_PRED_*
+    STATUS_MAX_STEPS, STATUS_NON_FINITE = 1, 2  # lsl_dopri_ctl.status
 
 
 # The translation units of the library and the compile options each adds to BASE_FLAGS: a unit per family of entry points (the sampling
@@ -278,6 +298,12 @@ def load() -> C.CDLL:
     lib.lsl_rk_dense.argtypes = [C.c_void_p] * 6 + [C.c_float, C.c_uint64, C.c_void_p]
     lib.lsl_rk_error_ratio.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.c_int32, C.c_float, C.c_float,
                                        C.c_uint64, C.c_void_p, C.c_void_p]
+    lib.lsl_dopri_workspace_bytes.argtypes = [C.c_void_p] + [C.c_int32] * 4
+    lib.lsl_dopri_workspace_bytes.restype = C.c_size_t
+    lib.lsl_dopri_begin.argtypes = [C.c_void_p, C.POINTER(IO), C.POINTER(DopriDesc), C.POINTER(C.c_double), C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
+                                    C.c_void_p]
+    lib.lsl_dopri_advance.argtypes = [C.c_void_p, C.POINTER(IO), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.lsl_debug_dopri_coeffs.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     lib.lsl_profile_enable.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     lib.lsl_profile_read.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
     lib.lsl_decoder_create.argtypes = [C.POINTER(DecoderDesc), C.POINTER(DecoderWeights), C.POINTER(C.c_void_p)]

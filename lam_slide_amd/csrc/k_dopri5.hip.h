@@ -1,0 +1,300 @@
+// Adaptive Dormand-Prince 5(4) with the step controller on the device (lsl_dopri_begin / lsl_dopri_advance; the host restatement is
+// lam_slide_amd/transport.py: dopri5_solve around Sampler._vel).  The controller record (include/lsl_api.h: lsl_dopri_ctl) lives in device
+// memory: every kernel reads the time, the step size and the decision of the attempt there, so an attempt's launches take the same arguments
+// every time.  No kernel reads a field that another workgroup of the same launch writes: the fields are written by single-workgroup
+// kernels (k_dp_init's first thread, k_dp_first_step, k_dp_control, k_dp_apply) and read by the launches behind them.
+//
+// State arithmetic: the contract of k_rk_* (k_small.hip.h) - rounded fp32 products added to the rounded running sum in list order, the
+// error norm's fixed reduction.  Coefficients that carry the step size are formed in fp64 (dt * beta) and rounded to fp32 once, as the host
+// loop hands them to lsl_rk_lincomb.  Times, the drift coefficients (vx, vm) and the controller run in fp64, products rounded one by one
+// (dp_mul) so that the expressions of Transport.velocity_coeffs / _Schedule are followed rounding for rounding.
+#pragma once
+#include "../../include/lsl_api.h"
+#include "k_small.hip.h"
+
+// a rounded fp64 product (see rk_mul)
+__device__ __forceinline__ double dp_mul(double a, double b) {
+    double p = a * b;
+    asm volatile("" : "+v"(p));
+    return p;
+}
+
+// (vx, vm) of velocity = vx x + vm net(x, t): Transport.velocity_coeffs over _Schedule.alpha / sigma / drift_terms and score_coeffs, in
+// their expression order (transport.py:158-226, path.py:21-206 of the reference)
+__device__ inline void dp_velocity_coeffs(int path, int pred, double t, double &vx, double &vm) {
+    if (pred == LSL_PRED_VELOCITY) {
+        vx = 0.0;
+        vm = 1.0;
+        return;
+    }
+    constexpr double PI = 3.141592653589793, SMIN = 0.1, SMAX = 20.0;
+    double a, s, ds, k, var;  // alpha, sigma, d sigma / dt, drift_mean = k x, drift_var
+    if (path == LSL_PATH_VP) {
+        const double u = 1.0 - t;
+        const double lm = dp_mul(dp_mul(-0.25, dp_mul(u, u)), SMAX - SMIN) - dp_mul(dp_mul(0.5, u), SMIN);
+        const double dlm = dp_mul(dp_mul(0.5, u), SMAX - SMIN) + 0.5 * SMIN;
+        a = exp(lm);
+        const double e2 = exp(dp_mul(2.0, lm));
+        s = sqrt(1.0 - e2);
+        ds = dp_mul(e2, dp_mul(2.0, dlm)) / dp_mul(-2.0, s);
+        const double beta = SMIN + dp_mul(u, SMAX - SMIN);
+        k = dp_mul(-0.5, beta);
+        var = beta / 2.0;
+    } else {
+        double ratio;
+        if (path == LSL_PATH_LINEAR) {
+            a = t;
+            s = 1.0 - t;
+            ds = -1.0;
+            ratio = t != 0.0 ? 1.0 / t : HUGE_VAL;
+        } else {
+            const double h = dp_mul(t, PI) / 2.0;
+            a = sin(h);
+            s = cos(h);
+            ds = dp_mul(-PI / 2.0, sin(h));
+            ratio = PI / dp_mul(2.0, tan(h));
+        }
+        k = -ratio;
+        var = dp_mul(dp_mul(ratio, s), s) - dp_mul(s, ds);
+    }
+    double sx, sm;  // score = sx x + sm net
+    if (pred == LSL_PRED_SCORE) {
+        sx = 0.0;
+        sm = 1.0;
+    } else if (pred == LSL_PRED_NOISE) {
+        sx = 0.0;
+        sm = -1.0 / s;
+    } else {
+        const double s2 = dp_mul(s, s);
+        sx = -1.0 / s2;
+        sm = a / s2;
+    }
+    vx = -k + dp_mul(var, sx);
+    vm = dp_mul(var, sm);
+}
+
+// the fp32 time the network is given for the solver time t + alpha dt (reverse: 1 - that time, as Sampler rounds _f32(1 - t))
+__device__ __forceinline__ float dp_net_time(double t, double dt, double alpha, int reverse) {
+    const double ts = t + dp_mul(alpha, dt);
+    return reverse ? (float)(1.0 - ts) : (float)ts;
+}
+
+// A linear combination whose coefficients may carry the step size: term j is (dt c[j] if bit j of dt_mask else c[j]) x[j]
+struct DpTerms {
+    const float *x[8];
+    double c[8];
+    unsigned dt_mask;
+    int n;
+};
+__device__ __forceinline__ RkTerms dp_terms(const DpTerms &d, double dt) {
+    RkTerms r;
+    r.n = d.n;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        r.x[j] = d.x[j];
+        r.c[j] = (float)((d.dt_mask >> j) & 1u ? dp_mul(dt, d.c[j]) : d.c[j]);
+    }
+    return r;
+}
+
+// the drift of an evaluation: k[i] = fp32(vx) x[i] + fp32(vm) net[i] (Sampler._vel), (vx, vm) at the fp32 time the network was given
+struct DpDrift {
+    float vx, vm;
+    __device__ DpDrift(const lsl_dopri_ctl *ctl, double alpha) {
+        double x, m;
+        dp_velocity_coeffs(ctl->path_type, ctl->model_type, (double)dp_net_time(ctl->t, ctl->dt, alpha, ctl->reverse), x, m);
+        vx = (float)x;
+        vm = (float)m;
+    }
+    __device__ __forceinline__ float operator()(float xi, float ni) const { return rk_mul(vx, xi) + rk_mul(vm, ni); }
+};
+
+struct DpGridChunk {
+    double g[32];
+};
+// grid[off + i] = chunk.g[i]: the output times reach the device as kernel arguments
+__global__ void k_dp_grid(double *grid, DpGridChunk chunk, int off, int count) {
+    if ((int)threadIdx.x < count) grid[off + threadIdx.x] = chunk.g[threadIdx.x];
+}
+
+// Begin: y = stage = y0, out[j] = y0 for the n_lead leading output times, the network's time vector at t0, the controller's first state
+__global__ void __launch_bounds__(256) k_dp_init(lsl_dopri_ctl *ctl, lsl_dopri_desc desc, float *out, int n_out, int n_lead, double t0, float *y, float *stage,
+                                                 const float *y0, float *tvec, int B, unsigned long long n) {
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) {
+        const float v = y0[i];
+        y[i] = v;
+        stage[i] = v;
+        for (int j = 0; j < n_lead; ++j) out[(unsigned long long)j * n + i] = v;
+    }
+    if (blockIdx.x != 0) return;
+    for (int b = threadIdx.x; b < B; b += 256) tvec[b] = dp_net_time(t0, 0.0, 0.0, desc.reverse);
+    if (threadIdx.x == 0) {
+        lsl_dopri_ctl c = {};
+        c.t = c.t_lo = t0;
+        c.rtol = desc.rtol;
+        c.atol = desc.atol;
+        c.out = out;
+        c.next_out = n_lead;
+        c.n_out = n_out;
+        c.max_steps = desc.max_steps;
+        c.path_type = desc.path_type;
+        c.model_type = desc.model_type;
+        c.reverse = desc.reverse;
+        *ctl = c;
+    }
+}
+
+// k[i] = drift of the evaluation at t + alpha dt on the stage state (begin: f0 and the evaluation of Hairer's rule)
+__global__ void __launch_bounds__(256) k_dp_drift(const lsl_dopri_ctl *ctl, float *k, const float *stage, const float *net, double alpha, unsigned long long n) {
+    const DpDrift drift(ctl, alpha);
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) k[i] = drift(stage[i], net[i]);
+}
+
+// Hairer's initial step (Hairer, Norsett, Wanner I, II.4), one workgroup.  FIRST: d0 = |y|, d1 = |f0| in the error norm -> dt = h0, ratio = d1.
+// Second: d2 = |f1 - f0| / h0 -> dt = min(100 h0, h1); a grid that ends at t0 is done, max_steps = 0 is a failure.
+template <bool FIRST>
+__global__ void __launch_bounds__(256) k_dp_first_step(lsl_dopri_ctl *ctl, const float *part0, const float *part1, int n_partial, const double *grid,
+                                                       unsigned long long n) {
+    __shared__ double red[256];
+    const double r0 = (double)rk_error_root(red, part0, n_partial, n);
+    __syncthreads();
+    const double r1 = FIRST ? (double)rk_error_root(red, part1, n_partial, n) : 0.0;
+    if (threadIdx.x != 0) return;
+    if (FIRST) {
+        ctl->dt = r0 < 1e-5 || r1 < 1e-5 ? 1e-6 : dp_mul(0.01, r0) / r1;
+        ctl->ratio = r1;
+        ctl->nfe = 1;
+        return;
+    }
+    const double h0 = ctl->dt, d1 = ctl->ratio, d2 = r0 / h0;
+    const double h1 = d1 <= 1e-15 && d2 <= 1e-15 ? fmax(1e-6, dp_mul(h0, 1e-3)) : pow(0.01 / fmax(d1, d2), 1.0 / 5.0);
+    ctl->dt = fmin(dp_mul(100.0, h0), h1);
+    ctl->ratio = 0.0;
+    ctl->nfe = 2;
+    if (!(grid[ctl->n_out - 1] > ctl->t)) ctl->done = 1;
+    else if (ctl->max_steps <= 0) {
+        ctl->status = LSL_DOPRI_MAX_STEPS;
+        ctl->done = 1;
+    }
+}
+
+// The launch between two network evaluations.  k_prev != nullptr: k_prev = drift of the evaluation at t + alpha_prev dt (stage state and
+// network output still in place); then stage = the terms' combination (y + sum_j fp32(dt beta_j) k_j) and the time vector of the next
+// evaluation, t + alpha dt.
+__global__ void __launch_bounds__(256) k_dp_stage(const lsl_dopri_ctl *ctl, float *stage, const float *net, float *k_prev, DpTerms terms, double alpha_prev,
+                                                  double alpha, float *tvec, int B, unsigned long long n) {
+    if (ctl->done) return;
+    const RkTerms r = dp_terms(terms, ctl->dt);
+    if (k_prev) {
+        const DpDrift drift(ctl, alpha_prev);
+        for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) {
+            k_prev[i] = drift(stage[i], net[i]);
+            stage[i] = rk_sum(r, i);
+        }
+    } else {
+        for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) stage[i] = rk_sum(r, i);
+    }
+    if (blockIdx.x == 0)
+        for (int b = threadIdx.x; b < B; b += 256) tvec[b] = dp_net_time(ctl->t, ctl->dt, alpha, ctl->reverse);
+}
+
+// Behind the last evaluation: k_last = its drift (the stage state is the 5th-order solution y1), then k_rk_error_partial's sums of
+// ((sum_j fp32(dt c_err_j) k_j) / (atol + rtol max(|y|, |y1|)))^2 in k_rk_error_partial's launch shape
+__global__ void __launch_bounds__(256) k_dp_error(const lsl_dopri_ctl *ctl, float *partial, const float *y, const float *stage, const float *net, float *k_last,
+                                                  DpTerms err, unsigned long long n) {
+    if (ctl->done) return;
+    __shared__ float red[256];
+    const RkTerms r = dp_terms(err, ctl->dt);
+    const DpDrift drift(ctl, 1.0);
+    const float atol = (float)ctl->atol, rtol = (float)ctl->rtol;
+    float s = 0.0f;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) {
+        k_last[i] = drift(stage[i], net[i]);
+        s = rk_error_add(s, r, y, stage, atol, rtol, i);
+    }
+    const float total = block_tree_sum(red, s);
+    if (threadIdx.x == 0) partial[blockIdx.x] = total;
+}
+
+// The decision of the attempt, one workgroup: ratio (k_rk_error_final's value), accept iff ratio <= 1, the step size that follows, the output
+// times an accepted step covers, the attempt's row of the log.  Writes decision fields only; k_dp_apply moves the controller on.
+__global__ void __launch_bounds__(256) k_dp_control(lsl_dopri_ctl *ctl, double *log, const float *partial, int n_partial, const double *grid, unsigned long long n) {
+    if (ctl->done) return;
+    __shared__ double red[256];
+    const double ratio = (double)rk_error_root(red, partial, n_partial, n);
+    if (threadIdx.x != 0) return;
+    const double t = ctl->t, dt = ctl->dt;
+    const int accept = ratio <= 1.0;
+    double factor = 10.0;
+    if (ratio != 0.0) factor = fmin(10.0, fmax(0.9 / pow(ratio, 0.2), ratio < 1.0 ? 1.0 : 0.2));
+    const double t_new = t + dt;
+    int j = ctl->next_out;
+    if (accept)
+        while (j < ctl->n_out && grid[j] <= t_new) ++j;
+    ctl->ratio = ratio;
+    ctl->accept = accept;
+    ctl->t_new = t_new;
+    ctl->dt_next = dp_mul(dt, factor);
+    ctl->out_end = j;
+    double *row = log + 4 * (size_t)(ctl->accepted + ctl->rejected);
+    row[0] = t;
+    row[1] = dt;
+    row[2] = ratio;
+    row[3] = (double)accept;
+}
+
+// An accepted step, element-wise: the mid-point and the dense-output coefficients of dopri5_solve (each sum in its list order; the mid-point
+// passes through `mid`, the network output's buffer), every pending output time of the step by rk_poly4, then y <- y1, k_1 <- k_7
+__global__ void __launch_bounds__(256) k_dp_commit(const lsl_dopri_ctl *ctl, const double *grid, float *y, const float *y1, float *mid, float *k_first,
+                                                   const float *k_last, DpTerms t_mid, DpTerms t_a, DpTerms t_b, DpTerms t_c, DpTerms t_d,
+                                                   unsigned long long n) {
+    if (ctl->done || !ctl->accept) return;
+    const double dt = ctl->dt, t_lo = ctl->t, t_new = ctl->t_new;
+    const int j0 = ctl->next_out, j1 = ctl->out_end;
+    float *out = ctl->out;
+    const RkTerms rm = dp_terms(t_mid, dt), ra = dp_terms(t_a, dt), rb = dp_terms(t_b, dt), rc = dp_terms(t_c, dt), rd = dp_terms(t_d, dt);
+    const bool flat = !(t_new > t_lo);  // (a step that did not move the time: the state itself, as the host loop returns it)
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) {
+        const float yn = y1[i];
+        if (j0 < j1) {
+            mid[i] = rk_sum(rm, i);
+            const float a = rk_sum(ra, i), b = rk_sum(rb, i), c = rk_sum(rc, i), d = rk_sum(rd, i), e = y[i];
+            for (int j = j0; j < j1; ++j)
+                out[(unsigned long long)j * n + i] = flat ? yn : rk_poly4(a, b, c, d, e, (float)((grid[j] - t_lo) / (t_new - t_lo)));
+        }
+        y[i] = yn;
+        k_first[i] = k_last[i];
+    }
+}
+
+// The controller moves on, one thread: an accepted step advances the time and the output cursor; the next step size; the counters; done at
+// the last output time, on a non-finite ratio, and when another attempt would exceed max_steps
+__global__ void k_dp_apply(lsl_dopri_ctl *ctl, const double *grid) {
+    if (ctl->done) return;
+    ctl->nfe += 6;
+    if (!isfinite(ctl->ratio)) {
+        ctl->rejected += 1;
+        ctl->status = LSL_DOPRI_NON_FINITE;
+        ctl->done = 1;
+        return;
+    }
+    if (ctl->accept) {
+        ctl->t_lo = ctl->t;
+        ctl->t = ctl->t_new;
+        ctl->next_out = ctl->out_end;
+        ctl->accepted += 1;
+    } else
+        ctl->rejected += 1;
+    ctl->dt = ctl->dt_next;
+    if (ctl->t >= grid[ctl->n_out - 1]) ctl->done = 1;
+    else if (ctl->accepted + ctl->rejected >= ctl->max_steps) {
+        ctl->status = LSL_DOPRI_MAX_STEPS;
+        ctl->done = 1;
+    }
+}
+
+// lsl_debug_dopri_coeffs: out[i] = (vx, vm) at the fp32 time t[i]
+__global__ void k_dp_coeffs(int path, int pred, const float *t, int n, double *out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dp_velocity_coeffs(path, pred, (double)t[i], out[2 * i], out[2 * i + 1]);
+}

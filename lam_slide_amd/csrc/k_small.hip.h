@@ -595,36 +595,49 @@ __device__ __forceinline__ float rk_sum(const RkTerms &t, unsigned long long i) 
 __global__ void __launch_bounds__(256) k_rk_lincomb(float *out, RkTerms t, unsigned long long n) {
     for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) out[i] = rk_sum(t, i);
 }
-// out[i] = e + x (d + x (c + x (b + x a))): the quartic dense output of an accepted step (rk_common.py: _interp_evaluate)
+// e + x (d + x (c + x (b + x a))): the quartic dense output of an accepted step (rk_common.py: _interp_evaluate), Horner form
+__device__ __forceinline__ float rk_poly4(float a, float b, float c, float d, float e, float x) {
+    float v = b + rk_mul(x, a);
+    v = c + rk_mul(x, v);
+    v = d + rk_mul(x, v);
+    return e + rk_mul(x, v);
+}
+// out[i] = rk_poly4 of the five coefficient arrays at x
 __global__ void __launch_bounds__(256) k_rk_poly4(float *out, const float *a, const float *b, const float *c, const float *d, const float *e, float x,
                                                   unsigned long long n) {
-    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) {
-        float v = b[i] + rk_mul(x, a[i]);
-        v = c[i] + rk_mul(x, v);
-        v = d[i] + rk_mul(x, v);
-        out[i] = e[i] + rk_mul(x, v);
-    }
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256)
+        out[i] = rk_poly4(a[i], b[i], c[i], d[i], e[i], x);
 }
+// s + (err[i] / (atol + rtol max(|y0[i]|, |y1[i]|)))^2: one element of a thread's sum of the error norm
+__device__ __forceinline__ float rk_error_add(float s, const RkTerms &k, const float *y0, const float *y1, float atol, float rtol, unsigned long long i) {
+    const float q = rk_sum(k, i) / (atol + rtol * fmaxf(fabsf(y0[i]), fabsf(y1[i])));
+    return s + q * q;
+}
+// the launch shape of the error norm's partial sums (fixed for a given n: the sum's order is part of the contract)
+inline unsigned rk_error_blocks(unsigned long long n) { return (unsigned)(n + 255 < 2048ull * 256 ? (n + 255) / 256 : 2048); }
 // partial[b] = sum over block b's elements of (err[i] / (atol + rtol max(|y0[i]|, |y1[i]|)))^2, err = sum_j c[j] k[j]: fixed grid-stride
 // assignment, per-thread sums in element order, fixed tree over the block (deterministic)
 __global__ void __launch_bounds__(256) k_rk_error_partial(float *partial, const float *y0, const float *y1, RkTerms k, float atol, float rtol,
                                                           unsigned long long n) {
     __shared__ float red[256];
     float s = 0.0f;
-    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) {
-        const float q = rk_sum(k, i) / (atol + rtol * fmaxf(fabsf(y0[i]), fabsf(y1[i])));
-        s += q * q;
-    }
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256)
+        s = rk_error_add(s, k, y0, y1, atol, rtol, i);
     const float total = block_tree_sum(red, s);
     if (threadIdx.x == 0) partial[blockIdx.x] = total;
 }
-// *ratio = sqrt(sum_b partial[b] / n)
-__global__ void __launch_bounds__(256) k_rk_error_final(float *ratio, const float *partial, int n_partial, unsigned long long n) {
-    __shared__ double red[256];
+// sqrt(sum_b partial[b] / n) on every thread of a 256-thread workgroup (red: 256 doubles of LDS)
+__device__ __forceinline__ float rk_error_root(double *red, const float *partial, int n_partial, unsigned long long n) {
     double s = 0.0;
     for (int b = threadIdx.x; b < n_partial; b += 256) s += (double)partial[b];
     const double total = block_tree_sum(red, s);
-    if (threadIdx.x == 0) *ratio = (float)sqrt(total / (double)n);
+    return (float)sqrt(total / (double)n);
+}
+// *ratio = rk_error_root
+__global__ void __launch_bounds__(256) k_rk_error_final(float *ratio, const float *partial, int n_partial, unsigned long long n) {
+    __shared__ double red[256];
+    const float r = rk_error_root(red, partial, n_partial, n);
+    if (threadIdx.x == 0) *ratio = r;
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -629,6 +629,15 @@ class Sampler:
         self.last_kernels: Optional[str] = None  # "general" | "resident" (lsl_sampler_path) after a fused call
         self.elem_offset = 0  # global element index of this rank's first state element (device noise stream)
         self._rk_ops: Dict[Any, "_RkOps"] = {}  # per device: the library's Runge-Kutta arithmetic (scratch buffers allocated once)
+        self.ode_max_steps = 100000  # attempts (accepted + rejected) after which an adaptive solve gives up
+        # controller="device": attempts enqueued between two reads of the controller record (the one synchronisation of a chunk).  Attempts
+        # behind the one that finishes change nothing but each costs a whole attempt.  Measured (tools/dopri5_cost.py,
+        # profiles/dopri5_cost.txt): at the peptide and md17 shapes an attempt is 4-6 ms of device work, 2 / 4 / 8 are within 0.3 % of
+        # each other and at most 0.6 % ahead of 1 - so the smallest of them, whose idle attempt at the end of a call costs least
+        self.attempts_per_poll = 2
+        self.last_ode_stats: Optional[Dict[str, int]] = None
+        self.last_ode_log: Optional[Tensor] = None    # controller="device": float64 [attempts, 4] rows (t, dt, ratio, accepted)
+        self.last_ode_state: Optional[Tensor] = None  # controller="device": the state at the end of the last accepted step
 
     def next_call_seed(self, draw: bool = True) -> int:
         """Seed of this call's device-noise stream.  The call counter advances on every call (ranks of a sharded run stay in step even
@@ -832,9 +841,18 @@ class Sampler:
         return v + g * (sx * x + sm * out), g
 
     # ---- reference API --------------------------------------------------------------------------------------
-    def sample_ode(self, *, sampling_method="dopri5", num_steps=50, atol=1e-6, rtol=1e-3, reverse=False):
+    def sample_ode(self, *, sampling_method="dopri5", num_steps=50, atol=1e-6, rtol=1e-3, reverse=False, controller="host"):
+        """``controller`` (this package's extra, adaptive ``dopri5`` only): ``"host"`` keeps the step controller in Python around the
+        library's network and Runge-Kutta calls (:func:`dopri5_solve`); ``"device"`` runs the whole solve inside the library
+        (``lsl_dopri_begin`` / ``lsl_dopri_advance``: controller state in device memory, attempts replayed as a hipGraph, the host reads the
+        controller once per ``attempts_per_poll`` attempts) and needs a ``lam_slide_amd.LatentSIV3`` on a GPU behind ``model``.  Either way
+        the error norm runs over the whole state, as in torchdiffeq: the steps of a trajectory depend on the batch it is sampled in."""
+        if controller not in ("host", "device"):
+            raise ValueError(f"controller must be 'host' or 'device', got {controller!r}")
+        if controller == "device" and sampling_method != "dopri5":
+            raise ValueError(f"controller='device' is the adaptive dopri5 solver's; {sampling_method!r} has no step controller")
         if sampling_method == "dopri5" or sampling_method in FIXED_GRID_RK_METHODS:
-            return self._sample_ode_dopri5(num_steps=num_steps, atol=atol, rtol=rtol, reverse=reverse, method=sampling_method)
+            return self._sample_ode_dopri5(num_steps=num_steps, atol=atol, rtol=rtol, reverse=reverse, method=sampling_method, controller=controller)
         if sampling_method != "euler":
             # Other torchdiffeq solvers: not implemented here.  When this class stands in for the reference's Sampler (dropin.install) and
             # was given the reference's own Transport object, hand the call to the class it replaced instead of breaking a flow that worked
@@ -866,7 +884,68 @@ class Sampler:
 
         return _sample
 
-    def _sample_ode_dopri5(self, *, num_steps, atol, rtol, reverse, method="dopri5"):
+    def run_dopri_device(self, net: LatentSIV3, init: Tensor, grid: Sequence[float], rtol: float, atol: float, reverse: bool,
+                         model_kwargs: Dict[str, Any]) -> Tensor:
+        """The adaptive solve inside the library: ``lsl_dopri_begin``, then ``lsl_dopri_advance`` in chunks of ``attempts_per_poll`` attempts
+        with one read of the controller record (128 bytes, the one synchronisation) behind each.  Returns float32 [len(grid), *init.shape];
+        leaves the counters in ``last_ode_stats``, the log in ``last_ode_log`` and the final state in ``last_ode_state``."""
+        extra = set(model_kwargs) - {"x_cond", "x_cond_mask", "y"}
+        if extra:
+            raise TypeError(f"unexpected model kwargs {sorted(extra)}")
+        for name in ("x_cond", "x_cond_mask"):
+            if name not in model_kwargs:
+                raise TypeError(f"missing model kwarg {name!r}")
+        dev = init.device
+        for name, ten in model_kwargs.items():
+            if ten is not None and ten.device != dev:
+                raise RuntimeError(f"Expected all tensors to be on the same device, but {name} is on {ten.device} and the state is on {dev}")
+        if int(self.attempts_per_poll) < 1:
+            raise ValueError(f"attempts_per_poll must be at least 1, got {self.attempts_per_poll}")
+        lib = _lib.load()
+        net.ensure_packed(dev)
+        # persistent input buffers for calls the library may replay as a hipGraph (see run_fused); the solver state lives in the workspace
+        replay = net.graph_replay_enabled(tokens=int(init.shape[0]) * int(init.shape[1]) * int(init.shape[2]))
+        x = net.staged("state", init, torch.float32, dev, persistent=replay)
+        xc = net.staged("x_cond", model_kwargs["x_cond"], torch.float32, dev, persistent=replay)
+        xm = net.staged("x_cond_mask", model_kwargs["x_cond_mask"], torch.int64, dev, persistent=replay)
+        yv = model_kwargs.get("y")
+        if yv is not None:
+            yv = net.staged("y", yv, torch.float32, dev, persistent=replay)
+        io, keep = net.make_io(x, xc, xm, yv)
+        n_out = len(grid)
+        out = torch.empty((n_out,) + tuple(x.shape), dtype=torch.float32, device=dev)
+        ws = net.workspace(io.B, io.T, io.L, dev, need=lib.lsl_dopri_workspace_bytes(net._handle, io.B, io.T, io.L, n_out))
+        tr = self.transport
+        desc = _lib.DopriDesc(_lib.Dopri.PATHS[tr.path_type.name], _lib.Dopri.PREDICTIONS[tr.model_type.name], int(bool(reverse)),
+                              min(int(self.ode_max_steps), _lib.Dopri.MAX_ATTEMPTS), float(rtol), float(atol))
+        times = (C.c_double * n_out)(*[float(g) for g in grid])
+
+        def controller():
+            raw = _lib.to_host(ws[_lib.Dopri.CTL_OFFSET:_lib.Dopri.CTL_OFFSET + C.sizeof(_lib.DopriCtl)])
+            return _lib.DopriCtl.from_buffer_copy(raw.tobytes())
+
+        _lib.call(dev, "lsl_dopri_begin", net._handle, C.byref(io), C.byref(desc), times, n_out, out.data_ptr(), ws.data_ptr(), ws.numel())
+        ctl = controller()
+        while not ctl.done:
+            _lib.call(dev, "lsl_dopri_advance", net._handle, C.byref(io), int(self.attempts_per_poll), ws.data_ptr(), ws.numel())
+            ctl = controller()
+        net.last_path = "hip"
+        self.last_path = "dopri5-device"
+        attempts = ctl.accepted + ctl.rejected
+        self.last_ode_stats = {"nfe": ctl.nfe, "accepted": ctl.accepted, "rejected": ctl.rejected}
+        self.last_ode_log = torch.zeros(0, 4, dtype=torch.float64)
+        if attempts:
+            rows = _lib.to_host(ws[_lib.Dopri.LOG_OFFSET:_lib.Dopri.LOG_OFFSET + 32 * attempts])
+            self.last_ode_log = torch.from_numpy(rows.copy()).view(torch.float64).reshape(attempts, 4)
+        self.last_ode_state = ws[_lib.Dopri.STATE_OFFSET:_lib.Dopri.STATE_OFFSET + 4 * x.numel()].view(torch.float32).reshape(x.shape).clone()
+        del keep
+        if ctl.status == _lib.Dopri.STATUS_MAX_STEPS:
+            raise RuntimeError("dopri5: max_steps reached")
+        if ctl.status == _lib.Dopri.STATUS_NON_FINITE:
+            raise RuntimeError("dopri5: the error ratio is not finite (NaN or Inf in the state or in the network's output)")
+        return out if out.dtype == init.dtype else out.to(init.dtype)
+
+    def _sample_ode_dopri5(self, *, num_steps, atol, rtol, reverse, method="dopri5", controller="host"):
         """The reference's default ODE sampler (transport.py:486-494, integrators.py:67-78 with method "dopri5"): adaptive steps, the solution
         reported at linspace(t0, t1, num_steps).  Every network evaluation runs on the HIP path (LatentSIV3.forward); the stage
         combinations and the error norm are a handful of element-wise device operations per step."""
@@ -876,6 +955,11 @@ class Sampler:
         grid = [float(g) for g in torch.linspace(t0, t1, num_steps)]
 
         def _sample(init, model, **model_kwargs):
+            if controller == "device":
+                net = resolve_backbone(model)
+                if net is None or not init.is_cuda:
+                    raise RuntimeError("fused sampling requested but the model is not a lam_slide_amd.LatentSIV3 on a GPU")
+                return self.run_dopri_device(net, init, grid, rtol, atol, reverse, model_kwargs)
             self.last_path = method
 
             def f(t, x):
@@ -883,7 +967,7 @@ class Sampler:
                 return self._vel(x, tv, model, **model_kwargs)[0]
 
             if method == "dopri5":
-                ys, self.last_ode_stats = dopri5_solve(f, init, grid, rtol, atol)
+                ys, self.last_ode_stats = dopri5_solve(f, init, grid, rtol, atol, max_steps=self.ode_max_steps)
             else:  # (torchdiffeq's fixed-grid midpoint / heun3 / rk4: one step per output interval)
                 ys = fixed_grid_rk_solve(f, init, grid, method)
             return torch.stack(ys)
