@@ -52,7 +52,8 @@ extern "C" {
  * 6, later still: lsl_weighted_moments_workspace_bytes, lsl_weighted_moments, lsl_affine_weights, lsl_project_wide added the same way.
  * 6, later still: lsl_msm_active_set, lsl_msm_reversible_step, lsl_msm_transition_matrix added the same way.
  * 6, later still: lsl_superpose, lsl_atom_rmsf_workspace_bytes, lsl_atom_rmsf added the same way.
- * 6, later still: lsl_dopri_workspace_bytes, lsl_dopri_begin, lsl_dopri_advance, lsl_debug_dopri_coeffs added the same way. */
+ * 6, later still: lsl_dopri_workspace_bytes, lsl_dopri_begin, lsl_dopri_advance, lsl_debug_dopri_coeffs added the same way.
+ * 6, later still: lsl_forward_jvp_workspace_bytes, lsl_forward_jvp, lsl_dot_rows added the same way. */
 #define LSL_VERSION 6
 
 typedef struct lsl_model lsl_model;
@@ -202,6 +203,30 @@ size_t lsl_workspace_bytes(const lsl_model *m, int32_t B, int32_t T, int32_t L);
 
 /* LatentSIV3.forward: io->out = network(io->x, io->t, io->x_cond, io->mask, io->y). */
 int lsl_forward(lsl_model *m, const lsl_io *io, void *workspace, size_t workspace_bytes, void *stream);
+
+/* The tangent pass of the network (forward mode): what Sampler.sample_ode_likelihood needs of the drift's divergence, eps . (J eps) for a
+ * probe eps (modules/transport/transport.py:432-443 obtains the same scalar by autograd).  csrc/k_jvp.hip.h, DESIGN.md 6.2.
+ *   io as for lsl_forward: io->t per trajectory, io->out receives the network output with the bits lsl_forward produces for the same
+ *   arguments on the same handle; x_tangent, out_tangent: device f32 [B,T,L,C]; out_tangent = (d network / d x)(io->x) . x_tangent.  io->x and
+ *   x_tangent are not modified.  The conditioning (t, y, x_cond, mask) has no tangent.
+ *   Numerics: the tangent operands of linear1, linear2 and the two attention products are bf16 with fp32 accumulation like their primal
+ *   twins, everything else fp32.  The tangent stream is linear operation by operation: a zero tangent gives zeros, and negating or doubling
+ *   x_tangent negates or doubles out_tangent bit for bit.  No float atomics, fixed summation orders: a trajectory's tangent has the same bits
+ *   alone, in any batch and at any pass size.
+ *   The pass runs the default decomposition of the general path: a handle in the tail or ln_fuse form or in linear-attention mode is
+ *   refused with -21 and a message that names the setter to call; the trajectory-resident path and hipGraph replay are not used.  Every
+ *   shape lsl_forward accepts in softmax mode is accepted.  A tangent pass holds half the tokens of a forward pass (its scratch per token is
+ *   about three times a forward's); the workspace is the forward's scratch of that pass size plus the tangent stream's.
+ *   Returns -1 for a null pointer, -3 for B, T or L <= 0 or a workspace smaller than lsl_forward_jvp_workspace_bytes says (both before
+ *   anything touches a GPU), -21 as above.  A refused call enqueues nothing. */
+size_t lsl_forward_jvp_workspace_bytes(const lsl_model *m, int32_t B, int32_t T, int32_t L);
+int lsl_forward_jvp(lsl_model *m, const lsl_io *io, const float *x_tangent, float *out_tangent, void *workspace, size_t workspace_bytes,
+                    void *stream);
+/* out[b] = sum_e a[b,e] * b[b,e] over per_trajectory elements (device f32 in, device f64 [B] out): fp64 sums of the exact fp32 products in a
+ * fixed order (slabs of LSL_SI_SLAB elements, then the slab partials in order; no atomics): a trajectory's bits are the same in any batch.
+ * scratch: device, at least B * ceil(per_trajectory / LSL_SI_SLAB) doubles.  B <= 65535, per_trajectory <= 2^31. */
+int lsl_dot_rows(const float *a, const float *b, int32_t B, uint64_t per_trajectory, double *out, void *scratch, size_t scratch_bytes,
+                 void *stream);
 
 /* Stochastic-interpolant objective without gradients: Transport.training_losses (modules/transport/transport.py:116-156), the loss every
  * validation_step evaluates through Loss.forward (second_stage/md17.py:221) before it samples.  For every path (path.py:21-206), prediction

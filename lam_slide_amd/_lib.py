@@ -52,6 +52,7 @@ EXPORTED = (
     "lsl_superpose", "lsl_atom_rmsf_workspace_bytes", "lsl_atom_rmsf",
     "lsl_profile_enable", "lsl_profile_read", "lsl_randn", "lsl_rk_lincomb", "lsl_rk_dense", "lsl_rk_error_ratio",
     "lsl_dopri_workspace_bytes", "lsl_dopri_begin", "lsl_dopri_advance", "lsl_debug_dopri_coeffs",
+    "lsl_forward_jvp_workspace_bytes", "lsl_forward_jvp", "lsl_dot_rows",
     "lsl_decoder_create", "lsl_decoder_destroy", "lsl_decode_workspace_bytes", "lsl_decode",
     "lsl_encoder_create", "lsl_encoder_destroy", "lsl_encode_workspace_bytes", "lsl_encode",
     "lsl_decode_heads", "lsl_class_loss_sums", "lsl_class_loss_final",
@@ -248,6 +249,10 @@ def load() -> C.CDLL:
         C.c_void_p, C.c_size_t, C.c_void_p]
     lib.lsl_debug_head.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(StepEx), C.c_void_p, C.c_uint64,
                                    C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+    lib.lsl_forward_jvp_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+    lib.lsl_forward_jvp_workspace_bytes.restype = C.c_size_t
+    lib.lsl_forward_jvp.argtypes = [C.c_void_p, C.POINTER(IO), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.lsl_dot_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.lsl_si_loss_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
     lib.lsl_si_loss_workspace_bytes.restype = C.c_size_t
     lib.lsl_si_loss.argtypes = [C.c_void_p, C.POINTER(IO), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]

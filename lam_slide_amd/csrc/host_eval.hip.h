@@ -251,10 +251,21 @@ AttnArgs attention_args(const lsl_model *m, const Workspace &ws, const PassPlan 
     return aa;
 }
 
+// The tangent pass (lsl_forward_jvp, host_jvp.hip.h) rides on the primal launches of an evaluation: run_embed / run_block / run_eval call these
+// between their own launches, which stay what they are - the primal half of a tangent pass is the evaluation itself, launch for launch.
+struct EvalTangent {
+    virtual int embedded() = 0;  // ws.h holds the state embedding, in front of the LayerNorm of normalize models
+    virtual int normed(int bi, const float *mbase) = 0;  // ws.a holds sub-block bi's linear1 operand (mbase: its shift | scale | gate rows)
+    virtual int attended(int bi, const float *mbase, float premul, int pdiv, int pmod) = 0;  // ws.qkv and ws.z are written, ws.h is not yet updated
+    virtual int head(const float *fm) = 0;  // the output head has read ws.h (fm: the final shift | scale rows)
+    virtual ~EvalTangent() = default;
+};
+
 // one ParallelMLPAttentionV2 sub-block on ws.h (in place): LN+modulate -> linear1 -> attention -> linear2; which kernels: the plan.
 // a_tap (lsl_debug_block_ex; debug plans only, where the LayerNorm launch always runs): receives ws.a, linear1's operand, right behind the
 // LayerNorm launch - on a tail handle k_tail overwrites ws.a with the NEXT sub-block's operand (TailArgs::a_next aliases A)
-int run_block(lsl_model *m, const Workspace &ws, const PassPlan &p, int bi, const float *mods, hipStream_t st, void *a_tap = nullptr) {
+int run_block(lsl_model *m, const Workspace &ws, const PassPlan &p, int bi, const float *mods, hipStream_t st, void *a_tap = nullptr,
+              EvalTangent *tg = nullptr) {
     const lsl_model_desc &d = m->d;
     const lsl_block_weights &bw = m->blocks[bi];
     const int D = d.hidden, n = p.n, tpt = p.T * p.L, mod_stride = p.mod_stride, temporal = bi & 1;
@@ -270,6 +281,8 @@ int run_block(lsl_model *m, const Workspace &ws, const PassPlan &p, int bi, cons
         m->prof.end(3, st);
         if (a_tap) hipMemcpyAsync(a_tap, ws.a, (size_t)n * D * 2, hipMemcpyDeviceToDevice, st);
     }
+    if (tg)
+        if (int rc = tg->normed(bi, mbase)) return rc;
     m->prof.begin(0, st);
     if (p.lin1_ts) {
         const Lin1Args la{(const u16 *)bw.w1, lnf ? (const u16 *)ws.h : ws.a, bw.b1, ws.rope_qk + (size_t)(2 * bi) * ws.rope_qk_stride,
@@ -290,6 +303,8 @@ int run_block(lsl_model *m, const Workspace &ws, const PassPlan &p, int bi, cons
         LSL_CHECK_LAUNCH("block");
         return 0;
     }
+    if (tg)
+        if (int rc = tg->attended(bi, mbase, premul, pdiv, pmod)) return rc;
     m->prof.begin(1, st);
     if (p.lin2 == Lin2Kind::tail) {  // up-projection -> GELU -> down-projection + out-projection + gated residual + the next sub-block's LayerNorm + modulate
         const bool next = bi + 1 < 2 * d.depth;
@@ -336,7 +351,7 @@ StepUpdate step_update(const EvalArgs &e) {
 
 // The state embedding of an evaluation: ws.h = x_in(x) + ws.cond_emb, with what the pass plan attaches to it (ln_fuse handles: the rows'
 // statistics for the first sub-block's linear1; normalize models: the in-place LayerNorm).  h_tap (lsl_debug_embed): ws.h in front of the LayerNorm.
-int run_embed(lsl_model *m, const Workspace &ws, const PassPlan &p, const float *x, hipStream_t st, float *h_tap = nullptr) {
+int run_embed(lsl_model *m, const Workspace &ws, const PassPlan &p, const float *x, hipStream_t st, float *h_tap = nullptr, EvalTangent *tg = nullptr) {
     const lsl_model_desc &d = m->d;
     const int D = d.hidden, n = p.n;
     m->prof.begin(5, st);
@@ -345,6 +360,8 @@ int run_embed(lsl_model *m, const Workspace &ws, const PassPlan &p, const float 
                     &m->prof);
     if (p.emb_stats) hipLaunchKernelGGL(k_ln_finalize, dim3((n + 255) / 256), dim3(256), 0, st, ws.lnstat, ws.lnparts, D / 256, p.npad, n, 256.0f);
     if (h_tap) hipMemcpyAsync(h_tap, ws.h, (size_t)n * D * 4, hipMemcpyDeviceToDevice, st);
+    if (tg)
+        if (int rc = tg->embedded()) return rc;
     if (d.normalize) { DISPATCH_D(D, launch_ln_inplace_t, ws.h, n, 1e-5f, st); }
     m->prof.end(5, st);
     LSL_CHECK_LAUNCH("embed");
@@ -364,7 +381,7 @@ int run_head(lsl_model *m, const float *h, const float *fm, int mod_stride, int 
 }
 
 // One evaluation for a pass: embeds x, runs the sub-blocks and the head (write the network output, or fuse the record's update into it)
-int run_eval(lsl_model *m, const Workspace &ws, const PassPlan &p, const EvalArgs &e, hipStream_t st) {
+int run_eval(lsl_model *m, const Workspace &ws, const PassPlan &p, const EvalArgs &e, hipStream_t st, EvalTangent *tg = nullptr) {
     const lsl_model_desc &d = m->d;
     const int D = d.hidden, n = p.n;
     const lsl_step_ex r = e.rec ? *e.rec : lsl_step_ex{};
@@ -375,11 +392,12 @@ int run_eval(lsl_model *m, const Workspace &ws, const PassPlan &p, const EvalArg
     if (e.mods_ready && shared) mods = e.mods_ready;
     else rc = run_mods(m, ws, e.t, r.t, e.have_y ? ws.yemb : nullptr, shared ? 1 : p.bc, ws.vec, ws.mods, st);
     if (rc) return rc;
-    if ((rc = run_embed(m, ws, p, e.x, st))) return rc;
+    if ((rc = run_embed(m, ws, p, e.x, st, nullptr, tg))) return rc;
     for (int bi = 0; bi < 2 * d.depth; ++bi)
-        if ((rc = run_block(m, ws, p, bi, mods, st))) return rc;
+        if ((rc = run_block(m, ws, p, bi, mods, st, nullptr, tg))) return rc;
     const float *fm = mods + (size_t)d.depth * 6 * D;  // adaLN: shift, scale
-    return run_head(m, ws.h, fm, p.mod_stride, n, p.T * p.L, e, st);
+    if ((rc = run_head(m, ws.h, fm, p.mod_stride, n, p.T * p.L, e, st))) return rc;
+    return tg ? tg->head(fm) : 0;
 }
 
 int prepare_pass(lsl_model *m, const Workspace &ws, const float *x_cond, const int64_t *mask, const float *y, int bc, int T,

@@ -578,6 +578,53 @@ struct EpiLinear2 {
     }
 };
 
+// plain epilogue: out[n][f] = acc (+ bias[f]), fp32, row stride ld.  The raw linear1 products of the tangent pass (host_jvp.hip.h): the pre-norm
+// q / k and the pre-GELU mlp values of the primal rows (with the bias) and of the tangent rows (bias == nullptr: no bias enters the tangent
+// stream).  Same staging and store shape as EpiLinear2.
+struct EpiPlain {
+    const float *bias;  // [F rounded up to 256], or nullptr
+    float *out;         // [N][ld]
+    int ld;
+    int probe;  // bit5: streaming stores (set by the launcher)
+
+    static constexpr bool lds_bias = false;
+
+    template <int WF, int WT>
+    static constexpr size_t wave_stage_bytes() { return (size_t)32 * WT * 4; }
+    template <int MI, int NJ>
+    static constexpr int min_store_ops() { return MI * NJ * 4; }
+
+    template <int MI, int NJ>
+    __device__ __forceinline__ void run(f32x16 (&acc)[MI][NJ], char *stage, int f_wave, int n_wave, int lane, int F, int N) const {
+        constexpr int WT = NJ * 32;
+        const int r = lane & 31, hf = lane >> 5;
+        const int chunk = lane & 7;
+#pragma unroll
+        for (int i = 0; i < MI; ++i) {
+            const int f0 = f_wave + i * 32;
+            if (f0 >= F) continue;  // wave-uniform
+#pragma unroll
+            for (int j = 0; j < NJ; ++j)
+#pragma unroll
+                for (int q4 = 0; q4 < 4; ++q4) {
+                    const float4 v = make_float4(acc[i][j][4 * q4], acc[i][j][4 * q4 + 1], acc[i][j][4 * q4 + 2], acc[i][j][4 * q4 + 3]);
+                    *reinterpret_cast<float4 *>(stage + stage_off(j * 32 + r, 2 * q4 + hf)) = v;
+                }
+            __builtin_amdgcn_sched_barrier(0);
+            const int f = f0 + 4 * chunk;
+            const float4 b = bias ? *reinterpret_cast<const float4 *>(bias + f) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 2
+            for (int row0 = 0; row0 < WT; row0 += 8) {
+                const int row = row0 + (lane >> 3), n = n_wave + row;
+                float4 a = *reinterpret_cast<const float4 *>(stage + stage_off(row, chunk));
+                if (n < N) {
+                    if (bias) a = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+                    store16(out + (size_t)n * ld + f, __builtin_bit_cast(u32x4, a), probe & 32);
+                }
+            }
+        }
+    }
+};
 
 // The piece form of an epilogue (Epi::fetch / Epi::piece, written for k_gemm_pp.hip.h) run back to back as the epilogue of the
 // one-tile-at-a-time kernel: 4 KiB of staging per wave instead of 8, which is what lets a PERSISTENT 256 x 256 kernel hold two

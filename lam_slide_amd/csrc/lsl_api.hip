@@ -24,6 +24,7 @@
 #include "k_small.hip.h"
 #include "k_dopri5.hip.h"
 #include "k_resident.hip.h"
+#include "k_jvp.hip.h"
 #ifdef LSL_EXPERIMENTS  // measured-and-rejected structures, built only by tools/build_experiments.sh (never in the product library)
 #include "k_gemm_pp.hip.h"        // tools/experiments/ (on the include path of tools/build_experiments.sh only)
 #include "k_gemm_drain.hip.h"
@@ -31,6 +32,7 @@
 #endif
 
 #include "host_eval.hip.h"  // (on top of host_launch.hip.h and host_common.hip.h)
+#include "host_jvp.hip.h"
 
 LSL_UNIT_INFO;
 
@@ -231,6 +233,51 @@ int lsl_forward(lsl_model *m, const lsl_io *io, void *workspace, size_t workspac
     CallPlans plans;
     if (int rc = plan_call(m, ws, io, chunk, m->MODW, plans)) return rc;  // (per-trajectory times: a modulation row per trajectory)
     return forward_passes(m, io, ws, plans, chunk, st);
+} LSL_API_CATCH
+
+// ---- the tangent pass (host_jvp.hip.h, k_jvp.hip.h): the general path, eagerly - no trajectory-resident kernel, no hipGraph replay ----
+size_t lsl_forward_jvp_workspace_bytes(const lsl_model *m, int32_t B, int32_t T, int32_t L) {
+    if (!m || B <= 0 || T <= 0 || L <= 0) return 0;
+    return jvp_workspace_need(m, B, T, L);
+}
+
+int lsl_forward_jvp(lsl_model *m, const lsl_io *io, const float *x_tangent, float *out_tangent, void *workspace, size_t workspace_bytes,
+                    void *stream) try {
+    int chunk = 0;
+    if (int rc = check_jvp(m, io, x_tangent, out_tangent, workspace, workspace_bytes, &chunk)) return rc;
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    hipStream_t st = (hipStream_t)stream;
+    const Workspace ws = carve(m, (char *)workspace, chunk, io->T, io->L);
+    const JvpWorkspace jw = carve_jvp(m, (char *)workspace + align_up(ws.bytes, 256), chunk, io->T, io->L);
+    CallPlans plans;
+    if (int rc = plan_call(m, ws, io, chunk, m->MODW, plans)) return rc;  // (before the first launch: a refused call enqueues nothing)
+    run_tables(m, ws, io->T, io->L, st);
+    return for_each_pass(m, ws, io, chunk, st, [&](const Pass &ps) {
+        EvalArgs e;
+        e.x = io->x + ps.elem;
+        e.out = io->out + ps.elem;
+        e.t = io->t + ps.b0;
+        e.have_y = ps.y != nullptr;
+        const PassPlan &plan = plans.of(ps.bc);
+        JvpPass tangent(m, ws, jw, plan, x_tangent + ps.elem, out_tangent + ps.elem, st);
+        return run_eval(m, ws, plan, e, st, &tangent);
+    });
+} LSL_API_CATCH
+
+int lsl_dot_rows(const float *a, const float *b, int32_t B, uint64_t per_trajectory, double *out, void *scratch, size_t scratch_bytes,
+                 void *stream) try {
+    static_assert(LSL_SI_SLAB % 256 == 0, "k_dot_rows_partial: whole rounds of 256 threads per slab");
+    if (!a || !b || !out) return fail(-1, "null argument");
+    if (B <= 0 || per_trajectory == 0) return fail(-3, "B and per_trajectory must be positive");
+    if (B > 65535 || per_trajectory > ((uint64_t)1 << 31)) return fail(-3, "at most 65535 trajectories of at most 2^31 elements");
+    const size_t slabs = (size_t)((per_trajectory + LSL_SI_SLAB - 1) / LSL_SI_SLAB), need = (size_t)B * slabs * sizeof(double);
+    if (!scratch || scratch_bytes < need) return fail(-4, "scratch too small: need %zu bytes, got %zu", need, scratch_bytes);
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_dot_rows_partial, dim3((unsigned)slabs, (unsigned)B), dim3(256), 0, st, (double *)scratch, a, b, (unsigned long long)per_trajectory);
+    hipLaunchKernelGGL(k_dot_rows_final, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, out, (const double *)scratch, (int)B, (int)slabs);
+    LSL_CHECK_LAUNCH("lsl_dot_rows");
+    return 0;
 } LSL_API_CATCH
 
 // ---- stochastic-interpolant objective (kernels: k_siloss.hip.h, through lsl_si_mix_launch / lsl_si_reduce_launch above) ----

@@ -321,3 +321,51 @@ class LatentSIV3(nn.Module):
         self.last_path = "hip"
         del keep
         return out.to(x.dtype)
+
+    def jvp_supported(self) -> Optional[str]:
+        """``None`` when :meth:`jvp` can serve this model object, else the reason it cannot (the library's tangent pass differentiates
+        softmax attention on the default decomposition of a sub-block).  The forms are the native handle's: ask after ``ensure_packed``
+        (before it, only what ``set_tail`` / ``set_ln_fuse`` were told is known, not the defaults of LSL_TAIL / LSL_LN_FUSE)."""
+        if self.attention_mode != "scaled_dot_product":
+            return f"attention_mode {self.attention_mode!r}: the tangent pass differentiates softmax attention only"
+        if self._tail or (self._tail is None and self.tail):
+            return "the tail form is set: the tangent pass runs the default decomposition (set_tail(False))"
+        if self._ln_fuse or (self._ln_fuse is None and self.ln_fuse):
+            return "the ln_fuse form is set: the tangent pass runs the default decomposition (set_ln_fuse(False))"
+        return None
+
+    @torch.no_grad()
+    def jvp(self, x: Tensor, t: Tensor, x_cond: Tensor, x_cond_mask: Tensor, y: Tensor = None, *, tangent: Tensor):
+        """``(out, out_tangent)``: the network output ``out = forward(x, t, ...)`` (the same bits) and its directional derivative
+        ``out_tangent = (d out / d x)(x) . tangent`` by one forward-mode pass of the library (``lsl_forward_jvp``: no activation tape, no
+        weight gradients).  ``tangent`` is shaped like ``x``; the conditioning has no tangent.  Linear in ``tangent`` bit for bit
+        (zero, sign, powers of two); a trajectory's result does not depend on the batch or the pass size.  GPU only, one device, nothing
+        requiring grad; a model in linear-attention mode or in the tail / ln_fuse form raises ``ValueError`` (the library's -21)."""
+        self._require_gpu(x)
+        if x.dim() != 4:
+            raise ValueError(f"x must be [B, T, L, C], got {tuple(x.shape)}")
+        if tuple(tangent.shape) != tuple(x.shape):
+            raise ValueError(f"tangent must be shaped like x {tuple(x.shape)}, got {tuple(tangent.shape)}")
+        for name, ten in (("t", t), ("tangent", tangent)):
+            if ten.device != x.device:
+                raise RuntimeError(f"Expected all tensors to be on the same device, but {name} is on {ten.device} and x is on {x.device}")
+        if not _lib.device_form(x, tangent):
+            raise ValueError("jvp takes float32 GPU tensors on one device, none requiring grad (the library's result carries no grad_fn)")
+        B = x.shape[0]
+        tt = t.detach().float()
+        if tt.dim() == 0 or tuple(tt.shape) == (1,):
+            tt = tt.reshape(1).expand(B)
+        if tuple(tt.shape) != (B,):
+            raise ValueError(f"t must have shape ({B},) (or be a scalar), got {tuple(t.shape)}")
+        tt = tt.contiguous()
+        self.ensure_packed(x.device)
+        xin = self.staged("state", x, torch.float32, x.device)
+        xt = self.staged("tangent", tangent, torch.float32, x.device)
+        out, out_t = torch.empty_like(xin), torch.empty_like(xin)
+        io, keep = self.make_io(xin, x_cond, x_cond_mask, y, tt, out)
+        need = _lib.load().lsl_forward_jvp_workspace_bytes(self._handle, io.B, io.T, io.L)
+        ws = self._scratch.get(x.device, need)
+        _lib.call(x.device, "lsl_forward_jvp", self._handle, C.byref(io), xt.data_ptr(), out_t.data_ptr(), ws.data_ptr(), ws.numel())
+        self.last_path = "hip-jvp"
+        del keep
+        return out, out_t

@@ -188,6 +188,11 @@ class Transport:
         var = s * s - rev * ds * s
         return -1.0 / var, rev / var
 
+    def prior_logp(self, z: Tensor) -> Tensor:
+        """Log-density of the standard normal prior per sample of a batched ``z`` (transport.py:62-67): ``-N/2 log 2 pi - sum(z^2) / 2`` over
+        the N elements of a sample, shape [B], in z's dtype, on z's device."""
+        n = z[0].numel()
+        return -0.5 * n * math.log(2.0 * math.pi) - z.reshape(z.shape[0], -1).pow(2).sum(dim=1) / 2.0
 
     # ---- the stochastic-interpolant objective without gradients (transport.py:103-156) ---------------------------------------------
     def sample(self, x1: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
@@ -311,6 +316,23 @@ def si_reduce(pred: Tensor, x1: Tensor, x0: Tensor, rows: Tensor) -> Tensor:
     _lib.call(dev, "lsl_si_reduce", pred.data_ptr(), x1.data_ptr(), x0.data_ptr(), table.data_ptr(), B, per, loss.data_ptr(), scratch.data_ptr(),
               scratch.numel() * 4)
     return loss
+
+
+def dot_rows(a: Tensor, b: Tensor) -> Tensor:
+    """``out[i] = sum(a[i] * b[i])`` over everything behind the first axis, float64 [B], on the device (``lsl_dot_rows``): fp64 sums of the
+    exact fp32 products in a fixed order, so a row's bits are the same alone and in any batch.  Contiguous float32 GPU tensors of one shape."""
+    if not a.is_cuda:
+        raise RuntimeError("dot_rows runs on the GPU (HIP kernel); there is no CPU fallback")
+    if a.shape != b.shape or a.dim() < 1 or a.device != b.device or a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise ValueError("a and b must be float32 tensors of one shape on one device")
+    a, b = a.contiguous(), b.contiguous()
+    B = a.shape[0]
+    per = a[0].numel()
+    dev = a.device
+    out = torch.empty(B, dtype=torch.float64, device=dev)
+    scratch = torch.empty(B * ((per + _lib.SI_SLAB - 1) // _lib.SI_SLAB), dtype=torch.float64, device=dev)
+    _lib.call(dev, "lsl_dot_rows", a.data_ptr(), b.data_ptr(), B, per, out.data_ptr(), scratch.data_ptr(), scratch.numel() * 8)
+    return out
 
 
 class CreateTransport:
@@ -973,6 +995,106 @@ class Sampler:
             return torch.stack(ys)
 
         return _sample
+
+    def sample_ode_likelihood(self, *, sampling_method="dopri5", num_steps=50, atol=1e-6, rtol=1e-3, eps=None):
+        """``fn(x, model, **model_kwargs) -> (logp, z)`` as the reference's ``Sampler.sample_ode_likelihood`` (transport.py:413-473): the
+        probability-flow ODE from the data ``x`` to the prior with the log-density change beside it, the divergence of the drift estimated by
+        Hutchinson's ``eps . (J eps)`` with a Rademacher probe.  The drift is evaluated at ``1 - t``; the augmented right-hand side is
+        ``(-drift, vx N + vm eps . j)`` with ``j = (d net / d x) eps`` and ``N`` the elements of a sample (the drift is ``vx x + vm net`` and
+        ``eps_i = +-1``); ``z`` is the last state and ``logp = prior_logp(z) - delta_logp``.
+
+        The augmented state is one flat vector ``[x.flatten() | logp]`` solved by :func:`dopri5_solve`, :func:`fixed_grid_rk_solve` or Euler
+        steps on ``linspace(t0, t1, num_steps)``: torchdiffeq's flattening of a tuple state with equal tolerances (the RMS error norm runs over
+        all ``B N + B`` elements).  ``eps`` (this package's extra): ``None`` draws ``torch.randint(2, x.size(), dtype=torch.float,
+        device=x.device) * 2 - 1`` at every drift evaluation (the reference's draw, in its order); a tensor is used at every evaluation (a
+        deterministic ODE); a callable ``(shape, device) -> Tensor`` is called at every evaluation.
+
+        A ``lam_slide_amd.LatentSIV3`` on a GPU behind ``model`` (softmax attention, default form) runs the device path: one tangent pass of the
+        library per evaluation (``LatentSIV3.jvp``) and ``lsl_dot_rows`` (``last_path == "likelihood-device"``); one the device path cannot
+        serve raises ``NotImplementedError``.  Any other callable runs the reference's autograd expression in torch
+        (``"likelihood-generic"``): autograd through ``model`` gives the divergence term of every evaluation; as in the reference (no
+        ``create_graph``) the state, the drift and that term leave the evaluation detached, so ``logp`` carries no graph to the caller's
+        parameters.  ``last_ode_stats["nfe"]`` counts the drift evaluations."""
+        tr = self.transport
+        fixed = sampling_method in FIXED_GRID_RK_METHODS
+        if sampling_method not in ("dopri5", "euler") and not fixed:
+            raise NotImplementedError(f"ODE solver {sampling_method!r}: 'euler', 'midpoint', 'heun3', 'rk4' and adaptive 'dopri5' are implemented")
+        t0, t1 = tr.check_interval(tr.train_eps, tr.sample_eps, sde=False, eval=True, reverse=False, last_step_size=0.0)
+        grid = [float(g) for g in torch.linspace(t0, t1, num_steps)]
+
+        def draw(xs: Tensor) -> Tensor:
+            if eps is None:
+                return torch.randint(2, xs.size(), dtype=torch.float, device=xs.device) * 2 - 1
+            e = eps(tuple(xs.shape), xs.device) if callable(eps) else eps
+            if tuple(e.shape) != tuple(xs.shape):
+                raise ValueError(f"eps must be shaped like the state {tuple(xs.shape)}, got {tuple(e.shape)}")
+            return e
+
+        def _sample_fn(x, model, **model_kwargs):
+            B, shape, n_el = x.shape[0], tuple(x.shape), x[0].numel()
+            net = resolve_backbone(model)
+            if net is not None:
+                if x.is_cuda:
+                    net.ensure_packed(x.device)  # (the handle's forms - LSL_TAIL / LSL_LN_FUSE defaults included - exist once it does)
+                why = "the state is not on a GPU" if not x.is_cuda else net.jvp_supported()
+                if why is None and not _lib.device_form(x):
+                    why = "the state must be float32 and must not require grad (the tangent pass is forward mode without a tape)"
+                if why is not None:
+                    raise NotImplementedError(f"sample_ode_likelihood on a lam_slide_amd.LatentSIV3 needs the library's tangent pass: {why}")
+                extra = set(model_kwargs) - {"x_cond", "x_cond_mask", "y"}
+                if extra:
+                    raise TypeError(f"unexpected model kwargs {sorted(extra)}")
+                for name in ("x_cond", "x_cond_mask"):
+                    if name not in model_kwargs:
+                        raise TypeError(f"missing model kwarg {name!r}")
+            self.last_path = "likelihood-device" if net is not None else "likelihood-generic"
+            count = [0]
+
+            def rhs(t: float, state: Tensor) -> Tensor:
+                count[0] += 1
+                xs = state[:B * n_el].reshape(shape)
+                tf = _f32(1.0 - t)
+                tv = torch.full((B,), tf, dtype=torch.float32, device=x.device)
+                try:
+                    vx, vm = tr.velocity_coeffs(tf)
+                except ZeroDivisionError:
+                    raise ZeroDivisionError(f"sample_ode_likelihood: the {tr.path_type.name} path with {tr.model_type.name} prediction has no finite "
+                                            f"velocity at time {tf} (sigma = 0 there; the reference's expression returns NaN): its interval "
+                                            f"[{t0}, {t1}] evaluates the drift at 1 - t") from None
+                e = draw(xs)
+                if net is not None:
+                    out, jt = net.jvp(xs.contiguous(), tv, model_kwargs["x_cond"], model_kwargs["x_cond_mask"], model_kwargs.get("y"),
+                                      tangent=e.to(device=x.device, dtype=torch.float32))
+                    drift = vx * xs + vm * out
+                    dlogp = (vx * n_el + vm * dot_rows(e.to(device=x.device, dtype=torch.float32), jt)).to(state.dtype)
+                else:
+                    e = e.to(xs)
+                    with torch.enable_grad():
+                        xg = xs.detach().requires_grad_(True)
+                        drift = vx * xg + vm * model(xg, tv.to(xs.dtype), **model_kwargs)
+                        grad = torch.autograd.grad(torch.sum(drift * e), xg)[0]
+                    dlogp = torch.sum(grad * e, dim=tuple(range(1, xs.dim())))
+                    drift = drift.detach()
+                return torch.cat([-drift.reshape(-1), dlogp.reshape(-1).to(state.dtype)])
+
+            y0 = torch.cat([x.detach().reshape(-1), torch.zeros(B, dtype=x.dtype, device=x.device)])
+            if sampling_method == "dopri5":
+                ys, stats = dopri5_solve(rhs, y0, grid, rtol, atol, max_steps=self.ode_max_steps)
+                last = ys[-1]
+                self.last_ode_stats = dict(stats)
+            elif fixed:
+                last = fixed_grid_rk_solve(rhs, y0, grid, sampling_method)[-1]
+            else:
+                last = y0
+                for ta, tb in zip(grid[:-1], grid[1:]):
+                    last = last + (tb - ta) * rhs(ta, last)
+            if sampling_method != "dopri5":
+                self.last_ode_stats = {"nfe": count[0], "accepted": len(grid) - 1, "rejected": 0}
+            z = last[:B * n_el].reshape(shape)
+            delta_logp = last[B * n_el:]
+            return tr.prior_logp(z) - delta_logp, z
+
+        return _sample_fn
 
     def sample_sde(self, *, sampling_method="Euler", diffusion_form="SBDM", diffusion_norm=1.0, last_step="Mean",
                    last_step_size=0.04, num_steps=250, noise: Optional[Tensor] = None):
