@@ -53,7 +53,8 @@ extern "C" {
  * 6, later still: lsl_msm_active_set, lsl_msm_reversible_step, lsl_msm_transition_matrix added the same way.
  * 6, later still: lsl_superpose, lsl_atom_rmsf_workspace_bytes, lsl_atom_rmsf added the same way.
  * 6, later still: lsl_dopri_workspace_bytes, lsl_dopri_begin, lsl_dopri_advance, lsl_debug_dopri_coeffs added the same way.
- * 6, later still: lsl_forward_jvp_workspace_bytes, lsl_forward_jvp, lsl_dot_rows added the same way. */
+ * 6, later still: lsl_forward_jvp_workspace_bytes, lsl_forward_jvp, lsl_dot_rows added the same way.
+ * 6, later still: lsl_dopri_each_workspace_bytes, lsl_dopri_each_begin, lsl_dopri_each_advance added the same way. */
 #define LSL_VERSION 6
 
 typedef struct lsl_model lsl_model;
@@ -668,6 +669,47 @@ size_t lsl_dopri_workspace_bytes(const lsl_model *m, int32_t B, int32_t T, int32
 int lsl_dopri_begin(lsl_model *m, const lsl_io *io, const lsl_dopri_desc *desc, const double *grid, int32_t n_out, float *out, void *workspace,
                     size_t workspace_bytes, void *stream);
 int lsl_dopri_advance(lsl_model *m, const lsl_io *io, int32_t n_attempts, void *workspace, size_t workspace_bytes, void *stream);
+
+/* The same solver with one step controller per trajectory: a call on B trajectories is B independent adaptive solves.  Each trajectory has
+ * its own lsl_dopri_ctl record (time, step size, decision, output cursor, counters, status), its own error norm over its [T,L,C] elements and
+ * its own log; the network is evaluated once per stage for all of them, at one time per trajectory (io->t's [B] form).  Trajectory b of a call
+ * has the bits of lsl_dopri_begin / lsl_dopri_advance on that trajectory alone (B = 1): the kernels give a trajectory the launch shape, the
+ * element order and the reductions of that call (csrc/k_dopri5.hip.h).  A trajectory that is done (its last output time reached, a
+ * non-finite error ratio, max_steps attempts) changes nothing any more - its state, its rows of `out` and its record stay - while the others
+ * go on; the network still evaluates its rows.  max_steps bounds each trajectory's attempts.
+ *
+ * The workspace (lsl_dopri_each_workspace_bytes) starts with what a caller reads back:
+ *   LSL_DOPRI_EACH_SUMMARY_OFFSET             lsl_dopri_each_summary: written behind begin and behind every attempt; the one small copy of a poll
+ *   LSL_DOPRI_EACH_CTL_OFFSET                 lsl_dopri_ctl[B], record b at + b * sizeof of the record (128 bytes); the fields mean what they
+ *                                             mean above, for trajectory b; `out` is begin's out
+ *   LSL_DOPRI_EACH_LOG_OFFSET(B)              fp64 [B][log_rows][4]: row a of trajectory b = (t, dt, ratio, accepted) of its attempt a, for
+ *                                             a < min(accepted + rejected, log_rows); later attempts are counted, not logged; log_rows >= 0
+ *   LSL_DOPRI_EACH_STATE_OFFSET(B, log_rows)  fp32 [B,T,L,C]: the current states (trajectory b at its own time lsl_dopri_ctl.t)
+ * behind them the buffers of lsl_dopri_begin (nine state-sized ones, the time vector, two reduction scratches of
+ * B * ceil(T L C / 256, at most 2048) floats, the network's workspace, the output times).
+ *
+ *   lsl_dopri_each_begin    as lsl_dopri_begin; out: device [n_out][B,T,L,C], trajectory b's rows written as its own accepted steps cover
+ *                           the output times.  B <= 65535, log_rows <= LSL_DOPRI_MAX_ATTEMPTS.
+ *   lsl_dopri_each_advance  n_attempts attempts of every trajectory that is not done; same io and workspace as the begin call on this
+ *                           handle (which recorded n_out and log_rows for it; -3 without one).  Enqueue as many as convenient, read the
+ *                           summary, repeat while !done.  Replayed as a hipGraph under the rule of lsl_dopri_advance.
+ * Argument checks, error codes and "a refused call enqueues nothing" as above. */
+#define LSL_DOPRI_EACH_SUMMARY_OFFSET 0
+#define LSL_DOPRI_EACH_CTL_OFFSET 256
+#define LSL_DOPRI_EACH_LOG_OFFSET(B) (256 + 256 * ((128 * (size_t)(B) + 255) / 256))
+#define LSL_DOPRI_EACH_STATE_OFFSET(B, log_rows) (LSL_DOPRI_EACH_LOG_OFFSET(B) + 256 * ((32 * (size_t)(B) * (size_t)(log_rows) + 255) / 256))
+typedef struct lsl_dopri_each_summary {
+    int32_t B;            /* trajectories of the call */
+    int32_t n_done;       /* trajectories whose record has done = 1 */
+    int32_t n_failed;     /* of those, the ones with status != LSL_DOPRI_OK */
+    int32_t max_attempts; /* the largest accepted + rejected over the trajectories */
+    int32_t done;         /* 1 = n_done == B: further attempts change nothing */
+} lsl_dopri_each_summary;
+size_t lsl_dopri_each_workspace_bytes(const lsl_model *m, int32_t B, int32_t T, int32_t L, int32_t n_out, int32_t log_rows);
+int lsl_dopri_each_begin(lsl_model *m, const lsl_io *io, const lsl_dopri_desc *desc, const double *grid, int32_t n_out, float *out,
+                         int32_t log_rows, void *workspace, size_t workspace_bytes, void *stream);
+int lsl_dopri_each_advance(lsl_model *m, const lsl_io *io, int32_t n_attempts, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Test hook: out[i] = (vx, vm) of the drift vx y + vm net(y, t) at the fp32 times t[0..n), fp64, as the kernels of lsl_dopri_* evaluate them */
 int lsl_debug_dopri_coeffs(int32_t path_type, int32_t model_type, const float *t, int32_t n, double *out, void *stream);
 

@@ -52,6 +52,7 @@ EXPORTED = (
     "lsl_superpose", "lsl_atom_rmsf_workspace_bytes", "lsl_atom_rmsf",
     "lsl_profile_enable", "lsl_profile_read", "lsl_randn", "lsl_rk_lincomb", "lsl_rk_dense", "lsl_rk_error_ratio",
     "lsl_dopri_workspace_bytes", "lsl_dopri_begin", "lsl_dopri_advance", "lsl_debug_dopri_coeffs",
+    "lsl_dopri_each_workspace_bytes", "lsl_dopri_each_begin", "lsl_dopri_each_advance",
     "lsl_forward_jvp_workspace_bytes", "lsl_forward_jvp", "lsl_dot_rows",
     "lsl_decoder_create", "lsl_decoder_destroy", "lsl_decode_workspace_bytes", "lsl_decode",
     "lsl_encoder_create", "lsl_encoder_destroy", "lsl_encode_workspace_bytes", "lsl_encode",
@@ -141,6 +142,10 @@ class DopriCtl(C.Structure):  # lsl_dopri_ctl
                                  "model_type", "reverse")]
 
 
+class DopriEachSummary(C.Structure):  # lsl_dopri_each_summary
+    _fields_ = [(n, C.c_int32) for n in ("B", "n_done", "n_failed", "max_attempts", "done")]
+
+
 class Dopri:
     """The constants of lsl_dopri_* (include/lsl_api.h; tests/test_dopri5_controller.py holds them against the header)."""
     MAX_ATTEMPTS = 100000  # LSL_DOPRI_MAX_ATTEMPTS
@@ -148,6 +153,16 @@ class Dopri:
     PATHS = {"LINEAR": 0, "GVP": 1, "VP": 2}  # LSL_PATH_*
     PREDICTIONS = {"VELOCITY": 0, "DATA": 1, "NOISE": 2, "SCORE": 3}  # LSL_PRED_*
     STATUS_MAX_STEPS, STATUS_NON_FINITE = 1, 2  # lsl_dopri_ctl.status
+    # lsl_dopri_each_*: the head of the workspace (tests/test_dopri5_each.py holds these against the header's macros)
+    EACH_SUMMARY_OFFSET, EACH_CTL_OFFSET, EACH_CTL_STRIDE, EACH_MAX_B = 0, 256, 128, 65535
+
+    @staticmethod
+    def each_log_offset(B: int) -> int:  # LSL_DOPRI_EACH_LOG_OFFSET
+        return 256 + 256 * ((128 * int(B) + 255) // 256)
+
+    @staticmethod
+    def each_state_offset(B: int, log_rows: int) -> int:  # LSL_DOPRI_EACH_STATE_OFFSET
+        return Dopri.each_log_offset(B) + 256 * ((32 * int(B) * int(log_rows) + 255) // 256)
 
 
 # The translation units of the library and the compile options each adds to BASE_FLAGS: a unit per family of entry points (the sampling
@@ -308,6 +323,11 @@ def load() -> C.CDLL:
     lib.lsl_dopri_begin.argtypes = [C.c_void_p, C.POINTER(IO), C.POINTER(DopriDesc), C.POINTER(C.c_double), C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
                                     C.c_void_p]
     lib.lsl_dopri_advance.argtypes = [C.c_void_p, C.POINTER(IO), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.lsl_dopri_each_workspace_bytes.argtypes = [C.c_void_p] + [C.c_int32] * 5
+    lib.lsl_dopri_each_workspace_bytes.restype = C.c_size_t
+    lib.lsl_dopri_each_begin.argtypes = [C.c_void_p, C.POINTER(IO), C.POINTER(DopriDesc), C.POINTER(C.c_double), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                         C.c_size_t, C.c_void_p]
+    lib.lsl_dopri_each_advance.argtypes = [C.c_void_p, C.POINTER(IO), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.lsl_debug_dopri_coeffs.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     lib.lsl_profile_enable.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     lib.lsl_profile_read.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32)]

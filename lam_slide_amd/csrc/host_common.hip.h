@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <map>
 #include <vector>
 
 #include "../../include/lsl_api.h"
@@ -51,6 +52,10 @@ struct lsl_model {
     bool ln_fuse = false;  // LayerNorm + modulate inside linear1's activation load (k_lin1.hip.h LNF): lsl_model_set_ln_fuse, a property of the HANDLE
     bool tail = false;  // the back half of every sub-block runs k_tail (k_tail.hip.h): a property of the HANDLE (lsl_model_set_tail), never of the batch
     GraphCache graphs;  // hipGraph replay of lsl_sample / lsl_sample_ex calls whose arguments repeat (host_graph.hip.h)
+    struct DopriEachCall {
+        int32_t B, T, L, n_out, log_rows;
+    };
+    std::map<const void *, DopriEachCall> dopri_each;  // by workspace: what lsl_dopri_each_begin laid it out for (lsl_dopri_each_advance carves by it)
 };
 
 namespace {

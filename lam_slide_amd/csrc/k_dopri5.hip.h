@@ -8,6 +8,13 @@
 // error norm's fixed reduction.  Coefficients that carry the step size are formed in fp64 (dt * beta) and rounded to fp32 once, as the host
 // loop hands them to lsl_rk_lincomb.  Times, the drift coefficients (vx, vm) and the controller run in fp64, products rounded one by one
 // (dp_mul) so that the expressions of Transport.velocity_coeffs / _Schedule are followed rounding for rounding.
+//
+// Two forms of every kernel, one copy of each (template parameter EACH):
+//   batch (EACH = false, lsl_dopri_begin / lsl_dopri_advance): one controller record, one solve of n = B T L C elements, gridDim.y = 1.
+//   per trajectory (EACH = true, lsl_dopri_each_*): B records, B solves of n = T L C elements each.  gridDim.y = B: a workgroup works on
+//     the elements of trajectory blockIdx.y alone, under that trajectory's record, with the launch shape in x, the element assignment, the
+//     per-element arithmetic and the reductions of a B = 1 batch call - so trajectory b has the bits of that call on [b:b+1].  A finished
+//     or failed trajectory's workgroups return at once.  k_dp_apply_each, one workgroup, moves every record on and writes the summary.
 #pragma once
 #include "../../include/lsl_api.h"
 #include "k_small.hip.h"
@@ -117,17 +124,44 @@ __global__ void k_dp_grid(double *grid, DpGridChunk chunk, int off, int count) {
     if ((int)threadIdx.x < count) grid[off + threadIdx.x] = chunk.g[threadIdx.x];
 }
 
+// The solve a workgroup belongs to: the index of its record, the offset of its first element in the state arrays, and the elements of one
+// output slice out[j] (n elements per solve)
+template <bool EACH>
+__device__ __forceinline__ unsigned dp_solve() {
+    return EACH ? blockIdx.y : 0u;
+}
+template <bool EACH>
+__device__ __forceinline__ unsigned long long dp_base(unsigned long long n) {
+    return EACH ? (unsigned long long)blockIdx.y * n : 0ull;
+}
+template <bool EACH>
+__device__ __forceinline__ unsigned long long dp_slice(unsigned long long n) {
+    return EACH ? (unsigned long long)gridDim.y * n : n;
+}
+// the network's time of the next evaluation, written by the first workgroup of a solve: every trajectory's entry (batch), the solve's own
+template <bool EACH>
+__device__ __forceinline__ void dp_set_time(float *tvec, int B, float v) {
+    if (blockIdx.x != 0) return;
+    if (EACH) {
+        if (threadIdx.x == 0) tvec[blockIdx.y] = v;
+    } else
+        for (int b = threadIdx.x; b < B; b += 256) tvec[b] = v;
+}
+
 // Begin: y = stage = y0, out[j] = y0 for the n_lead leading output times, the network's time vector at t0, the controller's first state
+template <bool EACH>
 __global__ void __launch_bounds__(256) k_dp_init(lsl_dopri_ctl *ctl, lsl_dopri_desc desc, float *out, int n_out, int n_lead, double t0, float *y, float *stage,
                                                  const float *y0, float *tvec, int B, unsigned long long n) {
-    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) {
+    const unsigned long long base = dp_base<EACH>(n), slice = dp_slice<EACH>(n);
+    for (unsigned long long i = base + (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < base + n; i += (unsigned long long)gridDim.x * 256) {
         const float v = y0[i];
         y[i] = v;
         stage[i] = v;
-        for (int j = 0; j < n_lead; ++j) out[(unsigned long long)j * n + i] = v;
+        for (int j = 0; j < n_lead; ++j) out[(unsigned long long)j * slice + i] = v;
     }
     if (blockIdx.x != 0) return;
-    for (int b = threadIdx.x; b < B; b += 256) tvec[b] = dp_net_time(t0, 0.0, 0.0, desc.reverse);
+    dp_set_time<EACH>(tvec, B, dp_net_time(t0, 0.0, 0.0, desc.reverse));
+    ctl += dp_solve<EACH>();
     if (threadIdx.x == 0) {
         lsl_dopri_ctl c = {};
         c.t = c.t_lo = t0;
@@ -145,17 +179,23 @@ __global__ void __launch_bounds__(256) k_dp_init(lsl_dopri_ctl *ctl, lsl_dopri_d
 }
 
 // k[i] = drift of the evaluation at t + alpha dt on the stage state (begin: f0 and the evaluation of Hairer's rule)
+template <bool EACH>
 __global__ void __launch_bounds__(256) k_dp_drift(const lsl_dopri_ctl *ctl, float *k, const float *stage, const float *net, double alpha, unsigned long long n) {
-    const DpDrift drift(ctl, alpha);
-    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) k[i] = drift(stage[i], net[i]);
+    const DpDrift drift(ctl + dp_solve<EACH>(), alpha);
+    const unsigned long long base = dp_base<EACH>(n);
+    for (unsigned long long i = base + (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < base + n; i += (unsigned long long)gridDim.x * 256)
+        k[i] = drift(stage[i], net[i]);
 }
 
 // Hairer's initial step (Hairer, Norsett, Wanner I, II.4), one workgroup.  FIRST: d0 = |y|, d1 = |f0| in the error norm -> dt = h0, ratio = d1.
 // Second: d2 = |f1 - f0| / h0 -> dt = min(100 h0, h1); a grid that ends at t0 is done, max_steps = 0 is a failure.
-template <bool FIRST>
+template <bool FIRST, bool EACH>
 __global__ void __launch_bounds__(256) k_dp_first_step(lsl_dopri_ctl *ctl, const float *part0, const float *part1, int n_partial, const double *grid,
                                                        unsigned long long n) {
     __shared__ double red[256];
+    ctl += dp_solve<EACH>();
+    part0 += (size_t)dp_solve<EACH>() * n_partial;
+    part1 += (size_t)dp_solve<EACH>() * n_partial;
     const double r0 = (double)rk_error_root(red, part0, n_partial, n);
     __syncthreads();
     const double r1 = FIRST ? (double)rk_error_root(red, part1, n_partial, n) : 0.0;
@@ -181,47 +221,58 @@ __global__ void __launch_bounds__(256) k_dp_first_step(lsl_dopri_ctl *ctl, const
 // The launch between two network evaluations.  k_prev != nullptr: k_prev = drift of the evaluation at t + alpha_prev dt (stage state and
 // network output still in place); then stage = the terms' combination (y + sum_j fp32(dt beta_j) k_j) and the time vector of the next
 // evaluation, t + alpha dt.
+template <bool EACH>
 __global__ void __launch_bounds__(256) k_dp_stage(const lsl_dopri_ctl *ctl, float *stage, const float *net, float *k_prev, DpTerms terms, double alpha_prev,
                                                   double alpha, float *tvec, int B, unsigned long long n) {
+    ctl += dp_solve<EACH>();
     if (ctl->done) return;
+    const unsigned long long base = dp_base<EACH>(n);
     const RkTerms r = dp_terms(terms, ctl->dt);
     if (k_prev) {
         const DpDrift drift(ctl, alpha_prev);
-        for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) {
+        for (unsigned long long i = base + (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < base + n; i += (unsigned long long)gridDim.x * 256) {
             k_prev[i] = drift(stage[i], net[i]);
             stage[i] = rk_sum(r, i);
         }
     } else {
-        for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) stage[i] = rk_sum(r, i);
+        for (unsigned long long i = base + (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < base + n; i += (unsigned long long)gridDim.x * 256)
+            stage[i] = rk_sum(r, i);
     }
-    if (blockIdx.x == 0)
-        for (int b = threadIdx.x; b < B; b += 256) tvec[b] = dp_net_time(ctl->t, ctl->dt, alpha, ctl->reverse);
+    dp_set_time<EACH>(tvec, B, dp_net_time(ctl->t, ctl->dt, alpha, ctl->reverse));
 }
 
 // Behind the last evaluation: k_last = its drift (the stage state is the 5th-order solution y1), then k_rk_error_partial's sums of
 // ((sum_j fp32(dt c_err_j) k_j) / (atol + rtol max(|y|, |y1|)))^2 in k_rk_error_partial's launch shape
+// (per trajectory: partial[b][gridDim.x], the blocks, the element assignment and the tree of a B = 1 call)
+template <bool EACH>
 __global__ void __launch_bounds__(256) k_dp_error(const lsl_dopri_ctl *ctl, float *partial, const float *y, const float *stage, const float *net, float *k_last,
                                                   DpTerms err, unsigned long long n) {
+    ctl += dp_solve<EACH>();
     if (ctl->done) return;
     __shared__ float red[256];
+    const unsigned long long base = dp_base<EACH>(n);
     const RkTerms r = dp_terms(err, ctl->dt);
     const DpDrift drift(ctl, 1.0);
     const float atol = (float)ctl->atol, rtol = (float)ctl->rtol;
     float s = 0.0f;
-    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) {
+    for (unsigned long long i = base + (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < base + n; i += (unsigned long long)gridDim.x * 256) {
         k_last[i] = drift(stage[i], net[i]);
         s = rk_error_add(s, r, y, stage, atol, rtol, i);
     }
     const float total = block_tree_sum(red, s);
-    if (threadIdx.x == 0) partial[blockIdx.x] = total;
+    if (threadIdx.x == 0) partial[(size_t)dp_solve<EACH>() * gridDim.x + blockIdx.x] = total;
 }
 
 // The decision of the attempt, one workgroup: ratio (k_rk_error_final's value), accept iff ratio <= 1, the step size that follows, the output
-// times an accepted step covers, the attempt's row of the log.  Writes decision fields only; k_dp_apply moves the controller on.
-__global__ void __launch_bounds__(256) k_dp_control(lsl_dopri_ctl *ctl, double *log, const float *partial, int n_partial, const double *grid, unsigned long long n) {
+// times an accepted step covers, the attempt's row of the log (log[solve][log_rows][4]; attempts beyond log_rows are counted, not logged).
+// Writes decision fields only; k_dp_apply moves the controller on.
+template <bool EACH>
+__global__ void __launch_bounds__(256) k_dp_control(lsl_dopri_ctl *ctl, double *log, int log_rows, const float *partial, int n_partial, const double *grid,
+                                                    unsigned long long n) {
+    ctl += dp_solve<EACH>();
     if (ctl->done) return;
     __shared__ double red[256];
-    const double ratio = (double)rk_error_root(red, partial, n_partial, n);
+    const double ratio = (double)rk_error_root(red, partial + (size_t)dp_solve<EACH>() * n_partial, n_partial, n);
     if (threadIdx.x != 0) return;
     const double t = ctl->t, dt = ctl->dt;
     const int accept = ratio <= 1.0;
@@ -236,7 +287,9 @@ __global__ void __launch_bounds__(256) k_dp_control(lsl_dopri_ctl *ctl, double *
     ctl->t_new = t_new;
     ctl->dt_next = dp_mul(dt, factor);
     ctl->out_end = j;
-    double *row = log + 4 * (size_t)(ctl->accepted + ctl->rejected);
+    const int a = ctl->accepted + ctl->rejected;
+    if (a >= log_rows) return;
+    double *row = log + 4 * ((size_t)dp_solve<EACH>() * log_rows + a);
     row[0] = t;
     row[1] = dt;
     row[2] = ratio;
@@ -245,22 +298,25 @@ __global__ void __launch_bounds__(256) k_dp_control(lsl_dopri_ctl *ctl, double *
 
 // An accepted step, element-wise: the mid-point and the dense-output coefficients of dopri5_solve (each sum in its list order; the mid-point
 // passes through `mid`, the network output's buffer), every pending output time of the step by rk_poly4, then y <- y1, k_1 <- k_7
+template <bool EACH>
 __global__ void __launch_bounds__(256) k_dp_commit(const lsl_dopri_ctl *ctl, const double *grid, float *y, const float *y1, float *mid, float *k_first,
                                                    const float *k_last, DpTerms t_mid, DpTerms t_a, DpTerms t_b, DpTerms t_c, DpTerms t_d,
                                                    unsigned long long n) {
+    ctl += dp_solve<EACH>();
     if (ctl->done || !ctl->accept) return;
+    const unsigned long long base = dp_base<EACH>(n), slice = dp_slice<EACH>(n);
     const double dt = ctl->dt, t_lo = ctl->t, t_new = ctl->t_new;
     const int j0 = ctl->next_out, j1 = ctl->out_end;
     float *out = ctl->out;
     const RkTerms rm = dp_terms(t_mid, dt), ra = dp_terms(t_a, dt), rb = dp_terms(t_b, dt), rc = dp_terms(t_c, dt), rd = dp_terms(t_d, dt);
     const bool flat = !(t_new > t_lo);  // (a step that did not move the time: the state itself, as the host loop returns it)
-    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) {
+    for (unsigned long long i = base + (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < base + n; i += (unsigned long long)gridDim.x * 256) {
         const float yn = y1[i];
         if (j0 < j1) {
             mid[i] = rk_sum(rm, i);
             const float a = rk_sum(ra, i), b = rk_sum(rb, i), c = rk_sum(rc, i), d = rk_sum(rd, i), e = y[i];
             for (int j = j0; j < j1; ++j)
-                out[(unsigned long long)j * n + i] = flat ? yn : rk_poly4(a, b, c, d, e, (float)((grid[j] - t_lo) / (t_new - t_lo)));
+                out[(unsigned long long)j * slice + i] = flat ? yn : rk_poly4(a, b, c, d, e, (float)((grid[j] - t_lo) / (t_new - t_lo)));
         }
         y[i] = yn;
         k_first[i] = k_last[i];
@@ -269,7 +325,7 @@ __global__ void __launch_bounds__(256) k_dp_commit(const lsl_dopri_ctl *ctl, con
 
 // The controller moves on, one thread: an accepted step advances the time and the output cursor; the next step size; the counters; done at
 // the last output time, on a non-finite ratio, and when another attempt would exceed max_steps
-__global__ void k_dp_apply(lsl_dopri_ctl *ctl, const double *grid) {
+__device__ inline void dp_apply(lsl_dopri_ctl *ctl, const double *grid) {
     if (ctl->done) return;
     ctl->nfe += 6;
     if (!isfinite(ctl->ratio)) {
@@ -291,6 +347,32 @@ __global__ void k_dp_apply(lsl_dopri_ctl *ctl, const double *grid) {
         ctl->status = LSL_DOPRI_MAX_STEPS;
         ctl->done = 1;
     }
+}
+__global__ void k_dp_apply(lsl_dopri_ctl *ctl, const double *grid) { dp_apply(ctl, grid); }
+
+// The per-trajectory form's last kernel of an attempt, one workgroup: every record moves on (APPLY; a thread per record, 256 at a time), then
+// the summary the host polls - how many trajectories are done, how many of them failed, the largest number of attempts.  Integer counts in
+// LDS; the begin call runs it with APPLY = false for the summary of the first state.
+template <bool APPLY>
+__global__ void __launch_bounds__(256) k_dp_apply_each(lsl_dopri_ctl *ctl, const double *grid, lsl_dopri_each_summary *summary, int B) {
+    __shared__ int n_done, n_failed, most;
+    if (threadIdx.x == 0) n_done = n_failed = most = 0;
+    __syncthreads();
+    for (int b = threadIdx.x; b < B; b += 256) {
+        if (APPLY) dp_apply(ctl + b, grid);
+        if (ctl[b].done) atomicAdd(&n_done, 1);
+        if (ctl[b].status != LSL_DOPRI_OK) atomicAdd(&n_failed, 1);
+        atomicMax(&most, ctl[b].accepted + ctl[b].rejected);
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    lsl_dopri_each_summary s;
+    s.B = B;
+    s.n_done = n_done;
+    s.n_failed = n_failed;
+    s.max_attempts = most;
+    s.done = n_done == B;
+    *summary = s;
 }
 
 // lsl_debug_dopri_coeffs: out[i] = (vx, vm) at the fp32 time t[i]

@@ -616,15 +616,17 @@ __device__ __forceinline__ float rk_error_add(float s, const RkTerms &k, const f
 // the launch shape of the error norm's partial sums (fixed for a given n: the sum's order is part of the contract)
 inline unsigned rk_error_blocks(unsigned long long n) { return (unsigned)(n + 255 < 2048ull * 256 ? (n + 255) / 256 : 2048); }
 // partial[b] = sum over block b's elements of (err[i] / (atol + rtol max(|y0[i]|, |y1[i]|)))^2, err = sum_j c[j] k[j]: fixed grid-stride
-// assignment, per-thread sums in element order, fixed tree over the block (deterministic)
+// assignment, per-thread sums in element order, fixed tree over the block (deterministic).  gridDim.y states of n elements each, one behind
+// the other (partial[blockIdx.y][gridDim.x]): each gets the sums of a launch on it alone
 __global__ void __launch_bounds__(256) k_rk_error_partial(float *partial, const float *y0, const float *y1, RkTerms k, float atol, float rtol,
                                                           unsigned long long n) {
     __shared__ float red[256];
+    const unsigned long long base = (unsigned long long)blockIdx.y * n;
     float s = 0.0f;
-    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256)
+    for (unsigned long long i = base + (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < base + n; i += (unsigned long long)gridDim.x * 256)
         s = rk_error_add(s, k, y0, y1, atol, rtol, i);
     const float total = block_tree_sum(red, s);
-    if (threadIdx.x == 0) partial[blockIdx.x] = total;
+    if (threadIdx.x == 0) partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = total;
 }
 // sqrt(sum_b partial[b] / n) on every thread of a 256-thread workgroup (red: 256 doubles of LDS)
 __device__ __forceinline__ float rk_error_root(double *red, const float *partial, int n_partial, unsigned long long n) {

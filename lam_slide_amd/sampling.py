@@ -173,7 +173,9 @@ class SecondStageSampler:
         ``sample`` K times in sequence (second_stage/pedestrian.py:193-204, nba.py:205-217, md17.py:157-166); trajectories are
         independent, so the K samples are folded into the batch: [B,...] -> [K*B,...] with the conditioning computed once.
         inits: optional [K,B,T,L,C] initial noises.  Returns [K,B,T,L,C]; sample k equals ``sample_latents(latents, init=inits[k])``
-        bit for bit (batch independence)."""
+        bit for bit (batch independence) - with a fixed-grid method, or adaptive ``dopri5`` with ``step_control="trajectory"`` in
+        ``sampling_kwargs``; ``dopri5``'s default step control chooses one step for the whole batch, so a sample's steps then depend on
+        its batch companions."""
         B = latents.shape[0]
         x_cond, mask = setup_conditioning(latents, self.cond_idx, self.mask_cond_mean)
         xc = x_cond.unsqueeze(0).expand(K, *x_cond.shape).reshape(K * B, *x_cond.shape[1:]).contiguous()
@@ -211,7 +213,9 @@ def sample_sharded(sample_fn: Callable[[Tensor, int], Tensor], latents: Tensor, 
     ``dst`` closes the job (BASELINE north_star: "a single RCCL gather over xGMI at the end"; with backend "nccl" it
     is RCCL).  ``sample_fn(local_latents, first_global_index) -> local_final``.  Rank ``dst`` returns the full result in
     the original order, every other rank ``None`` - nobody needs the other shards back, and a gather moves 1 / world
-    of what an all_gather does.  ``dst=None``: every rank gets the full result (an all_gather)."""
+    of what an all_gather does.  ``dst=None``: every rank gets the full result (an all_gather).  A shard computes what the unsharded call
+    computes for its trajectories with a fixed-grid method, or with adaptive ``dopri5`` under ``step_control="trajectory"``; the default
+    step control of ``dopri5`` takes its error norm over the whole batch of a call, so its steps depend on the shard."""
     if not (dist.is_available() and dist.is_initialized()):
         return sample_fn(latents, 0)
     world, rank = dist.get_world_size(group), dist.get_rank(group)

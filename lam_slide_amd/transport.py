@@ -563,7 +563,7 @@ def dopri5_solve(f: Callable[[float, Tensor], Tensor], y0: Tensor, grid: Sequenc
     for tn in [float(g) for g in grid[1:]]:
         while tn > t:
             if accepted + rejected >= max_steps:
-                raise RuntimeError("dopri5: max_steps reached")
+                raise RuntimeError(DOPRI_MAX_STEPS_MESSAGE)
             k = [fy]
             yi = y
             for a, beta in zip(_DP_ALPHA, _DP_BETA):
@@ -593,6 +593,123 @@ def dopri5_solve(f: Callable[[float, Tensor], Tensor], y0: Tensor, grid: Sequenc
         e, d, c, b, a = coeff
         out.append(ops.poly4(a, b, c, d, e, (tn - t_lo) / (t - t_lo)))
     return out, {"nfe": nfe, "accepted": accepted, "rejected": rejected}
+
+
+DOPRI_MAX_STEPS_MESSAGE = "dopri5: max_steps reached"
+DOPRI_NON_FINITE_MESSAGE = "dopri5: the error ratio is not finite (NaN or Inf in the state or in the network's output)"
+
+
+def dopri_each_failure(max_steps_rows: Sequence[int], non_finite_rows: Sequence[int]) -> Optional[str]:
+    """The message of a per-trajectory solve some of whose trajectories failed (None: none did): the messages of the batch solve, each with
+    the indices of its trajectories."""
+    parts = [f"{msg} (trajectories {list(rows)})" for msg, rows in ((DOPRI_MAX_STEPS_MESSAGE, max_steps_rows), (DOPRI_NON_FINITE_MESSAGE, non_finite_rows))
+             if len(rows)]
+    return "; ".join(parts) if parts else None
+
+
+def dopri5_solve_each(f: Callable[[Sequence[float], Tensor], Tensor], y0: Tensor, grid: Sequence[float], rtol: float, atol: float,
+                      max_steps: int = 100000) -> Tuple[List[Tensor], Dict[str, Any]]:
+    """:func:`dopri5_solve` with one step controller per trajectory (row of ``y0``), in lock step: the host restatement of the library's
+    ``lsl_dopri_each_*`` loop.  ``f(times, y)`` takes one time per row; every row has its own time, step size, accept / reject decision and
+    output cursor, an attempt evaluates ``f`` once per stage for all rows, and a row that is finished (or failed) is carried along unchanged
+    - ``f`` still sees its state, at its last time.  Every row's stage combinations, error norm (over that row alone) and dense output are
+    computed on the row's slice with the expressions of ``dopri5_solve``, so with an ``f`` whose rows are independent, row ``b`` equals
+    ``dopri5_solve`` on ``y0[b:b+1]`` exactly.  A row stops alone at ``max_steps`` attempts or on a non-finite error ratio; the others go
+    on, and the call raises once all have stopped.  Returns the outputs and ``{"nfe", "accepted", "rejected"}`` as per-row lists, ``"attempts"``
+    (the largest count), ``"passes"`` (evaluations of ``f``) and ``"log"``: per row a float64 [attempts, 4] tensor of (t, dt, ratio,
+    accepted)."""
+    y0 = y0.contiguous()
+    B = int(y0.shape[0])
+    rows = range(B)
+    ops = _RkOps(y0)
+    grid = [float(g) for g in grid]
+    t0 = grid[0]
+
+    def row(x, b):
+        return x[b:b + 1]
+
+    def each(fn, keep, live):  # fn(b) -> [1, ...] for the live rows, the rows of `keep` for the others
+        return torch.cat([fn(b) if live[b] else row(keep, b) for b in rows])
+
+    def norm(b, ya, yb, terms):
+        return ops.error_ratio(row(ya, b), row(yb, b), [(c, row(x, b)) for c, x in terms], atol, rtol)
+
+    everyone = [True] * B
+    f0 = f([t0] * B, y0)
+    d0, d1 = [norm(b, y0, y0, [(1.0, y0)]) for b in rows], [norm(b, y0, y0, [(1.0, f0)]) for b in rows]
+    h0 = [1e-6 if d0[b] < 1e-5 or d1[b] < 1e-5 else 0.01 * d0[b] / d1[b] for b in rows]
+    f1 = f([t0 + h for h in h0], each(lambda b: ops.lincomb([(1.0, row(y0, b)), (h0[b], row(f0, b))]), y0, everyone))
+    passes = 2
+    d2 = [norm(b, y0, y0, [(1.0, f1), (-1.0, f0)]) / h0[b] for b in rows]
+    dt = [min(100 * h0[b], max(1e-6, h0[b] * 1e-3) if d1[b] <= 1e-15 and d2[b] <= 1e-15 else (0.01 / max(d1[b], d2[b])) ** (1.0 / 5.0)) for b in rows]
+
+    t, t_lo, y, fy = [t0] * B, [t0] * B, y0, f0
+    coeff: List[Any] = [None] * B
+    outs = [[row(y0, b)] for b in rows]  # per row: its output slices so far
+    nfe, accepted, rejected = [2] * B, [0] * B, [0] * B
+    log: List[List[Tuple[float, float, float, float]]] = [[] for _ in rows]
+    hit_limit, non_finite = [], []
+
+    def flush(b):  # the output times row b's current step covers; is the row still live?
+        while len(outs[b]) < len(grid) and not grid[len(outs[b])] > t[b]:
+            if coeff[b] is None or t[b] <= t_lo[b]:
+                outs[b].append(row(y, b))
+            else:
+                e, d, c, bb, a = coeff[b]
+                outs[b].append(ops.poly4(a, bb, c, d, e, (grid[len(outs[b])] - t_lo[b]) / (t[b] - t_lo[b])))
+        if len(outs[b]) == len(grid):
+            return False
+        if accepted[b] + rejected[b] >= max_steps:
+            hit_limit.append(b)
+            return False
+        return True
+
+    live = [flush(b) for b in rows]
+    while any(live):
+        k = [fy]
+        yi = y
+        for a, beta in zip(_DP_ALPHA, _DP_BETA):
+            yi = each(lambda b: ops.lincomb([(1.0, row(y, b))] + [(dt[b] * c, row(kj, b)) for c, kj in zip(beta, k) if c != 0.0]), yi, live)
+            k.append(f([t[b] + a * dt[b] if live[b] else t[b] for b in rows], yi))
+        passes += 6
+        y1 = yi
+        ratio = [norm(b, y, y1, [(dt[b] * c, kj) for c, kj in zip(_DP_C_ERR, k) if c != 0.0]) if live[b] else 0.0 for b in rows]
+        take = [live[b] and ratio[b] <= 1.0 for b in rows]
+        for b in rows:
+            if not live[b]:
+                continue
+            nfe[b] += 6
+            log[b].append((t[b], dt[b], ratio[b], float(take[b])))
+            if take[b]:
+                y_mid = ops.lincomb([(1.0, row(y, b))] + [(dt[b] * c, row(kj, b)) for c, kj in zip(_DP_C_MID, k) if c != 0.0])
+                yb, y1b, fa, fb, h = row(y, b), row(y1, b), row(k[0], b), row(k[-1], b), dt[b]
+                coeff[b] = (yb, ops.lincomb([(h, fa)]),
+                            ops.lincomb([(h, fb), (-4 * h, fa), (-11.0, yb), (-5.0, y1b), (16.0, y_mid)]),
+                            ops.lincomb([(5 * h, fa), (-3 * h, fb), (18.0, yb), (14.0, y1b), (-32.0, y_mid)]),
+                            ops.lincomb([(2 * h, fb), (-2 * h, fa), (-8.0, y1b), (-8.0, yb), (16.0, y_mid)]))
+                t_lo[b], t[b] = t[b], t[b] + h
+                accepted[b] += 1
+            else:
+                rejected[b] += 1
+        y = each(lambda b: row(y1, b), y, take)
+        fy = each(lambda b: row(k[-1], b), fy, take)
+        for b in rows:
+            if not live[b]:
+                continue
+            if not math.isfinite(ratio[b]):
+                non_finite.append(b)
+                live[b] = False
+                continue
+            dt[b] = dt[b] * 10.0 if ratio[b] == 0.0 else dt[b] * min(10.0, max(0.9 / ratio[b] ** 0.2, 1.0 if ratio[b] < 1.0 else 0.2))
+            live[b] = flush(b)
+    stats = {"nfe": nfe, "accepted": accepted, "rejected": rejected, "attempts": max(a + r for a, r in zip(accepted, rejected)), "passes": passes,
+             "log": [torch.tensor(rows_b, dtype=torch.float64).reshape(-1, 4) for rows_b in log], "state": y}
+    failure = dopri_each_failure(sorted(hit_limit), sorted(non_finite))
+    if failure:
+        err = RuntimeError(failure)
+        err.stats = stats
+        raise err
+    return [torch.cat([outs[b][j] for b in rows]) for j in range(len(grid))], stats
 
 
 
@@ -657,8 +774,12 @@ class Sampler:
         # profiles/dopri5_cost.txt): at the peptide and md17 shapes an attempt is 4-6 ms of device work, 2 / 4 / 8 are within 0.3 % of
         # each other and at most 0.6 % ahead of 1 - so the smallest of them, whose idle attempt at the end of a call costs least
         self.attempts_per_poll = 2
-        self.last_ode_stats: Optional[Dict[str, int]] = None
-        self.last_ode_log: Optional[Tensor] = None    # controller="device": float64 [attempts, 4] rows (t, dt, ratio, accepted)
+        # step_control="trajectory": the rows of a trajectory's log that are kept (attempts beyond them are counted, not logged).  128 rows
+        # are 4 KiB a trajectory - 16 MiB of workspace at B = 4096 - and more than twice the attempts of a solve at the default tolerances
+        self.ode_log_rows = 128
+        self.last_ode_stats: Optional[Dict[str, Any]] = None  # (step_control="trajectory": per-trajectory lists, "attempts", "network_passes")
+        # controller="device": float64 [attempts, 4] rows (t, dt, ratio, accepted); step_control="trajectory": a list of B such tensors
+        self.last_ode_log: Any = None
         self.last_ode_state: Optional[Tensor] = None  # controller="device": the state at the end of the last accepted step
 
     def next_call_seed(self, draw: bool = True) -> int:
@@ -863,18 +984,33 @@ class Sampler:
         return v + g * (sx * x + sm * out), g
 
     # ---- reference API --------------------------------------------------------------------------------------
-    def sample_ode(self, *, sampling_method="dopri5", num_steps=50, atol=1e-6, rtol=1e-3, reverse=False, controller="host"):
+    def sample_ode(self, *, sampling_method="dopri5", num_steps=50, atol=1e-6, rtol=1e-3, reverse=False, controller="host", step_control="batch"):
         """``controller`` (this package's extra, adaptive ``dopri5`` only): ``"host"`` keeps the step controller in Python around the
         library's network and Runge-Kutta calls (:func:`dopri5_solve`); ``"device"`` runs the whole solve inside the library
         (``lsl_dopri_begin`` / ``lsl_dopri_advance``: controller state in device memory, attempts replayed as a hipGraph, the host reads the
-        controller once per ``attempts_per_poll`` attempts) and needs a ``lam_slide_amd.LatentSIV3`` on a GPU behind ``model``.  Either way
-        the error norm runs over the whole state, as in torchdiffeq: the steps of a trajectory depend on the batch it is sampled in."""
+        controller once per ``attempts_per_poll`` attempts) and needs a ``lam_slide_amd.LatentSIV3`` on a GPU behind ``model``.
+
+        ``step_control`` (this package's extra, adaptive ``dopri5`` only): ``"batch"``, the default, is torchdiffeq's rule - one controller
+        whose error norm runs over the whole state, so the steps of a trajectory depend on the batch it is sampled in.  ``"trajectory"``
+        gives every trajectory (row of the initial state) a controller of its own - time, step size, decisions, error norm over that
+        trajectory alone - and evaluates the network once per stage for all of them, at one time per trajectory: trajectory ``b`` of the
+        call is the ``"batch"`` call on ``[b:b+1]``, bit for bit with ``controller="device"`` (``lsl_dopri_each_*``, ``last_path ==
+        "dopri5-device-each"``) and exactly with ``controller="host"`` on CPU tensors (:func:`dopri5_solve_each`; ``model`` then receives
+        a different time per row).  ``last_ode_stats`` holds per-trajectory lists of ``nfe`` / ``accepted`` / ``rejected``, ``attempts``
+        (the largest count) and ``network_passes``; ``last_ode_log`` a list of per-trajectory logs of at most ``ode_log_rows`` rows.  A
+        trajectory that fails (``ode_max_steps`` attempts, a non-finite error ratio) stops alone; the call raises once all have stopped
+        and names the failed trajectories."""
         if controller not in ("host", "device"):
             raise ValueError(f"controller must be 'host' or 'device', got {controller!r}")
+        if step_control not in ("batch", "trajectory"):
+            raise ValueError(f"step_control must be 'batch' or 'trajectory', got {step_control!r}")
         if controller == "device" and sampling_method != "dopri5":
             raise ValueError(f"controller='device' is the adaptive dopri5 solver's; {sampling_method!r} has no step controller")
+        if step_control == "trajectory" and sampling_method != "dopri5":
+            raise ValueError(f"step_control='trajectory' is the adaptive dopri5 solver's; {sampling_method!r} has no step controller")
         if sampling_method == "dopri5" or sampling_method in FIXED_GRID_RK_METHODS:
-            return self._sample_ode_dopri5(num_steps=num_steps, atol=atol, rtol=rtol, reverse=reverse, method=sampling_method, controller=controller)
+            return self._sample_ode_dopri5(num_steps=num_steps, atol=atol, rtol=rtol, reverse=reverse, method=sampling_method, controller=controller,
+                                           each=step_control == "trajectory")
         if sampling_method != "euler":
             # Other torchdiffeq solvers: not implemented here.  When this class stands in for the reference's Sampler (dropin.install) and
             # was given the reference's own Transport object, hand the call to the class it replaced instead of breaking a flow that worked
@@ -911,6 +1047,95 @@ class Sampler:
         """The adaptive solve inside the library: ``lsl_dopri_begin``, then ``lsl_dopri_advance`` in chunks of ``attempts_per_poll`` attempts
         with one read of the controller record (128 bytes, the one synchronisation) behind each.  Returns float32 [len(grid), *init.shape];
         leaves the counters in ``last_ode_stats``, the log in ``last_ode_log`` and the final state in ``last_ode_state``."""
+        lib, dev, x, io, keep = self._dopri_device_inputs(net, init, model_kwargs)
+        n_out = len(grid)
+        out = torch.empty((n_out,) + tuple(x.shape), dtype=torch.float32, device=dev)
+        ws = net.workspace(io.B, io.T, io.L, dev, need=lib.lsl_dopri_workspace_bytes(net._handle, io.B, io.T, io.L, n_out))
+        desc, times = self._dopri_desc(grid, rtol, atol, reverse)
+
+        def controller():
+            raw = _lib.to_host(ws[_lib.Dopri.CTL_OFFSET:_lib.Dopri.CTL_OFFSET + C.sizeof(_lib.DopriCtl)])
+            return _lib.DopriCtl.from_buffer_copy(raw.tobytes())
+
+        _lib.call(dev, "lsl_dopri_begin", net._handle, C.byref(io), C.byref(desc), times, n_out, out.data_ptr(), ws.data_ptr(), ws.numel())
+        ctl = controller()
+        while not ctl.done:
+            _lib.call(dev, "lsl_dopri_advance", net._handle, C.byref(io), int(self.attempts_per_poll), ws.data_ptr(), ws.numel())
+            ctl = controller()
+        net.last_path = "hip"
+        self.last_path = "dopri5-device"
+        attempts = ctl.accepted + ctl.rejected
+        self.last_ode_stats = {"nfe": ctl.nfe, "accepted": ctl.accepted, "rejected": ctl.rejected}
+        self.last_ode_log = torch.zeros(0, 4, dtype=torch.float64)
+        if attempts:
+            rows = _lib.to_host(ws[_lib.Dopri.LOG_OFFSET:_lib.Dopri.LOG_OFFSET + 32 * attempts])
+            self.last_ode_log = torch.from_numpy(rows.copy()).view(torch.float64).reshape(attempts, 4)
+        self.last_ode_state = ws[_lib.Dopri.STATE_OFFSET:_lib.Dopri.STATE_OFFSET + 4 * x.numel()].view(torch.float32).reshape(x.shape).clone()
+        del keep
+        if ctl.status == _lib.Dopri.STATUS_MAX_STEPS:
+            raise RuntimeError(DOPRI_MAX_STEPS_MESSAGE)
+        if ctl.status == _lib.Dopri.STATUS_NON_FINITE:
+            raise RuntimeError(DOPRI_NON_FINITE_MESSAGE)
+        return out if out.dtype == init.dtype else out.to(init.dtype)
+
+    def run_dopri_device_each(self, net: LatentSIV3, init: Tensor, grid: Sequence[float], rtol: float, atol: float, reverse: bool,
+                              model_kwargs: Dict[str, Any]) -> Tensor:
+        """``run_dopri_device`` with one controller per trajectory (``lsl_dopri_each_begin`` / ``lsl_dopri_each_advance``): the host reads
+        the summary record (20 bytes) once per ``attempts_per_poll`` attempts until every trajectory is done, then the B controller records,
+        the logs (``ode_log_rows`` rows a trajectory) and the states.  ``last_ode_stats``: per-trajectory lists ``nfe`` / ``accepted`` /
+        ``rejected``, ``attempts`` (the largest count: the attempts the call ran) and ``network_passes`` (evaluations of the network on
+        the batch); ``last_ode_log``: a list of B float64 [min(attempts_b, ode_log_rows), 4] tensors; ``last_ode_state``: every
+        trajectory's state at the end of its last accepted step.  Trajectories that failed are named in the error, raised once all
+        have stopped."""
+        lib, dev, x, io, keep = self._dopri_device_inputs(net, init, model_kwargs)
+        D = _lib.Dopri
+        B, n_out, log_rows = int(io.B), len(grid), int(self.ode_log_rows)
+        if not 0 <= log_rows <= D.MAX_ATTEMPTS:
+            raise ValueError(f"ode_log_rows must be in 0..{D.MAX_ATTEMPTS}, got {self.ode_log_rows}")
+        if B > D.EACH_MAX_B:
+            raise ValueError(f"step_control='trajectory' takes at most {D.EACH_MAX_B} trajectories a call, got {B}")
+        out = torch.empty((n_out,) + tuple(x.shape), dtype=torch.float32, device=dev)
+        ws = net.workspace(io.B, io.T, io.L, dev, need=lib.lsl_dopri_each_workspace_bytes(net._handle, io.B, io.T, io.L, n_out, log_rows))
+        desc, times = self._dopri_desc(grid, rtol, atol, reverse)
+
+        def summary():
+            raw = _lib.to_host(ws[D.EACH_SUMMARY_OFFSET:D.EACH_SUMMARY_OFFSET + C.sizeof(_lib.DopriEachSummary)])
+            return _lib.DopriEachSummary.from_buffer_copy(raw.tobytes())
+
+        _lib.call(dev, "lsl_dopri_each_begin", net._handle, C.byref(io), C.byref(desc), times, n_out, out.data_ptr(), log_rows, ws.data_ptr(), ws.numel())
+        state = summary()
+        while not state.done:
+            _lib.call(dev, "lsl_dopri_each_advance", net._handle, C.byref(io), int(self.attempts_per_poll), ws.data_ptr(), ws.numel())
+            state = summary()
+        net.last_path = "hip"
+        self.last_path = "dopri5-device-each"
+        raw = _lib.to_host(ws[D.EACH_CTL_OFFSET:D.EACH_CTL_OFFSET + D.EACH_CTL_STRIDE * B]).tobytes()
+        ctl = [_lib.DopriCtl.from_buffer_copy(raw, D.EACH_CTL_STRIDE * b) for b in range(B)]
+        self.last_ode_stats = {"nfe": [c.nfe for c in ctl], "accepted": [c.accepted for c in ctl], "rejected": [c.rejected for c in ctl],
+                               "attempts": int(state.max_attempts), "network_passes": 2 + 6 * int(state.max_attempts)}
+        self.last_ode_log = [torch.zeros(0, 4, dtype=torch.float64) for _ in ctl]
+        if log_rows:
+            rows = _lib.to_host(ws[D.each_log_offset(B):D.each_log_offset(B) + 32 * B * log_rows])
+            logs = torch.from_numpy(rows.copy()).view(torch.float64).reshape(B, log_rows, 4)
+            self.last_ode_log = [logs[b, :min(c.accepted + c.rejected, log_rows)].clone() for b, c in enumerate(ctl)]
+        at = D.each_state_offset(B, log_rows)
+        self.last_ode_state = ws[at:at + 4 * x.numel()].view(torch.float32).reshape(x.shape).clone()
+        del keep
+        failure = dopri_each_failure([b for b, c in enumerate(ctl) if c.status == D.STATUS_MAX_STEPS],
+                                     [b for b, c in enumerate(ctl) if c.status == D.STATUS_NON_FINITE])
+        if failure:
+            raise RuntimeError(failure)
+        return out if out.dtype == init.dtype else out.to(init.dtype)
+
+    def _dopri_desc(self, grid, rtol, atol, reverse):
+        """The solver's description and output times as the library takes them"""
+        tr = self.transport
+        desc = _lib.DopriDesc(_lib.Dopri.PATHS[tr.path_type.name], _lib.Dopri.PREDICTIONS[tr.model_type.name], int(bool(reverse)),
+                              min(int(self.ode_max_steps), _lib.Dopri.MAX_ATTEMPTS), float(rtol), float(atol))
+        return desc, (C.c_double * len(grid))(*[float(g) for g in grid])
+
+    def _dopri_device_inputs(self, net: LatentSIV3, init: Tensor, model_kwargs: Dict[str, Any]):
+        """The checks and the staged inputs of a device solve: (library, device, state, the call's lsl_io, what it keeps alive)"""
         extra = set(model_kwargs) - {"x_cond", "x_cond_mask", "y"}
         if extra:
             raise TypeError(f"unexpected model kwargs {sorted(extra)}")
@@ -934,40 +1159,9 @@ class Sampler:
         if yv is not None:
             yv = net.staged("y", yv, torch.float32, dev, persistent=replay)
         io, keep = net.make_io(x, xc, xm, yv)
-        n_out = len(grid)
-        out = torch.empty((n_out,) + tuple(x.shape), dtype=torch.float32, device=dev)
-        ws = net.workspace(io.B, io.T, io.L, dev, need=lib.lsl_dopri_workspace_bytes(net._handle, io.B, io.T, io.L, n_out))
-        tr = self.transport
-        desc = _lib.DopriDesc(_lib.Dopri.PATHS[tr.path_type.name], _lib.Dopri.PREDICTIONS[tr.model_type.name], int(bool(reverse)),
-                              min(int(self.ode_max_steps), _lib.Dopri.MAX_ATTEMPTS), float(rtol), float(atol))
-        times = (C.c_double * n_out)(*[float(g) for g in grid])
+        return lib, dev, x, io, keep
 
-        def controller():
-            raw = _lib.to_host(ws[_lib.Dopri.CTL_OFFSET:_lib.Dopri.CTL_OFFSET + C.sizeof(_lib.DopriCtl)])
-            return _lib.DopriCtl.from_buffer_copy(raw.tobytes())
-
-        _lib.call(dev, "lsl_dopri_begin", net._handle, C.byref(io), C.byref(desc), times, n_out, out.data_ptr(), ws.data_ptr(), ws.numel())
-        ctl = controller()
-        while not ctl.done:
-            _lib.call(dev, "lsl_dopri_advance", net._handle, C.byref(io), int(self.attempts_per_poll), ws.data_ptr(), ws.numel())
-            ctl = controller()
-        net.last_path = "hip"
-        self.last_path = "dopri5-device"
-        attempts = ctl.accepted + ctl.rejected
-        self.last_ode_stats = {"nfe": ctl.nfe, "accepted": ctl.accepted, "rejected": ctl.rejected}
-        self.last_ode_log = torch.zeros(0, 4, dtype=torch.float64)
-        if attempts:
-            rows = _lib.to_host(ws[_lib.Dopri.LOG_OFFSET:_lib.Dopri.LOG_OFFSET + 32 * attempts])
-            self.last_ode_log = torch.from_numpy(rows.copy()).view(torch.float64).reshape(attempts, 4)
-        self.last_ode_state = ws[_lib.Dopri.STATE_OFFSET:_lib.Dopri.STATE_OFFSET + 4 * x.numel()].view(torch.float32).reshape(x.shape).clone()
-        del keep
-        if ctl.status == _lib.Dopri.STATUS_MAX_STEPS:
-            raise RuntimeError("dopri5: max_steps reached")
-        if ctl.status == _lib.Dopri.STATUS_NON_FINITE:
-            raise RuntimeError("dopri5: the error ratio is not finite (NaN or Inf in the state or in the network's output)")
-        return out if out.dtype == init.dtype else out.to(init.dtype)
-
-    def _sample_ode_dopri5(self, *, num_steps, atol, rtol, reverse, method="dopri5", controller="host"):
+    def _sample_ode_dopri5(self, *, num_steps, atol, rtol, reverse, method="dopri5", controller="host", each=False):
         """The reference's default ODE sampler (transport.py:486-494, integrators.py:67-78 with method "dopri5"): adaptive steps, the solution
         reported at linspace(t0, t1, num_steps).  Every network evaluation runs on the HIP path (LatentSIV3.forward); the stage
         combinations and the error norm are a handful of element-wise device operations per step."""
@@ -981,13 +1175,34 @@ class Sampler:
                 net = resolve_backbone(model)
                 if net is None or not init.is_cuda:
                     raise RuntimeError("fused sampling requested but the model is not a lam_slide_amd.LatentSIV3 on a GPU")
-                return self.run_dopri_device(net, init, grid, rtol, atol, reverse, model_kwargs)
+                run = self.run_dopri_device_each if each else self.run_dopri_device
+                return run(net, init, grid, rtol, atol, reverse, model_kwargs)
             self.last_path = method
 
             def f(t, x):
                 tv = torch.ones(x.size(0), device=x.device) * (_f32(1 - t) if reverse else t)
                 return self._vel(x, tv, model, **model_kwargs)[0]
 
+            if each:
+                self.last_path = "dopri5-each"
+
+                def f_each(ts, x):  # one time per trajectory: the model on the batch, the drift row by row with each row's coefficients
+                    tv = torch.tensor([_f32(1 - t) if reverse else t for t in ts], dtype=torch.float32, device=x.device)
+                    out = model(x, tv, **model_kwargs)
+                    return torch.cat([self._vel(x[b:b + 1], tv[b:b + 1], lambda *a, **k: out[b:b + 1])[0] for b in range(x.size(0))])
+
+                stats = None
+                try:
+                    ys, stats = dopri5_solve_each(f_each, init, grid, rtol, atol, max_steps=self.ode_max_steps)
+                except RuntimeError as err:
+                    stats = getattr(err, "stats", None)
+                    raise
+                finally:
+                    if stats is not None:
+                        self.last_ode_log, self.last_ode_state = stats.pop("log"), stats.pop("state")
+                        stats["network_passes"] = stats.pop("passes")
+                        self.last_ode_stats = stats
+                return torch.stack(ys)
             if method == "dopri5":
                 ys, self.last_ode_stats = dopri5_solve(f, init, grid, rtol, atol, max_steps=self.ode_max_steps)
             else:  # (torchdiffeq's fixed-grid midpoint / heun3 / rk4: one step per output interval)
