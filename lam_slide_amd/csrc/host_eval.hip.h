@@ -578,4 +578,28 @@ int for_each_pass(lsl_model *m, const Workspace &ws, const lsl_io *io, int chunk
     return 0;
 }
 
+// the passes of one network evaluation at per-trajectory times: io->out = network(io->x, io->t, ...) (lsl_forward, the middle of lsl_si_loss,
+// every evaluation of lsl_dopri_*)
+int forward_passes(lsl_model *m, const lsl_io *io, const Workspace &ws, const CallPlans &plans, int chunk, hipStream_t st) {
+    run_tables(m, ws, io->T, io->L, st);
+    return for_each_pass(m, ws, io, chunk, st, [&](const Pass &ps) {
+        EvalArgs e;
+        e.x = io->x + ps.elem;
+        e.out = io->out + ps.elem;
+        e.t = io->t + ps.b0;
+        e.have_y = ps.y != nullptr;
+        return run_eval(m, ws, plans.of(ps.bc), e, st);
+    });
+}
+
+// Whether a unit of n_evals network evaluations per trajectory goes through the handle's GraphCache (host_graph.hip.h; the rule is described
+// in lsl_sample_ex)
+bool graph_gate(const lsl_model *m, const lsl_io *io, int chunk, int n_evals) {
+    static const int use_graph = env_int("LSL_GRAPH", 1);
+    const int passes = (io->B + chunk - 1) / chunk;
+    const long est_launches = (long)passes * n_evals * (8L * m->d.depth + 6);
+    const bool launch_bound = (size_t)chunk * io->T * io->L <= 65536;
+    return use_graph && (launch_bound || use_graph >= 2) && m->prof.kernel < 0 && est_launches <= 4096;
+}
+
 }  // namespace

@@ -5,7 +5,11 @@
 #pragma once
 
 struct GraphCache {
-    using Key = std::vector<unsigned char>;
+    struct Key : std::vector<unsigned char> {  // the bytes of everything a call's enqueued launches depend on
+        void put(const void *p, size_t bytes) { insert(end(), (const unsigned char *)p, (const unsigned char *)p + bytes); }
+        template <class T>
+        void put(const T &value) { put(&value, sizeof(value)); }  // (a pointer: the pointer itself)
+    };
     struct Entry {
         Key key;
         hipGraphExec_t exec = nullptr;

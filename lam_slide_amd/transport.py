@@ -27,6 +27,9 @@ from torch import Tensor
 
 from . import _lib
 from .latent_si import LatentSIV3
+# the solvers (ode.py); their names stay importable from here
+from .ode import (DOPRI_MAX_STEPS_MESSAGE, DOPRI_NON_FINITE_MESSAGE, FIXED_GRID_RK_METHODS, _DP_ALPHA, _DP_BETA, _DP_C_ERR, _DP_C_MID,  # noqa: F401
+                  _RkOps, _f32, _rms, dopri5_solve, dopri5_solve_each, dopri_each_failure, fixed_grid_rk_solve)
 
 
 class _ByName(enum.Enum):
@@ -257,19 +260,12 @@ class Transport:
         return {"pred": pred, "loss": loss, "xt": xt}
 
     def _si_loss_fused(self, net: "LatentSIV3", x1: Tensor, t: Tensor, x0: Tensor, rows: Tensor, model_kwargs: Dict[str, Any]) -> Dict[str, Tensor]:
-        extra = set(model_kwargs) - {"x_cond", "x_cond_mask", "y"}
-        if extra:
-            raise TypeError(f"unexpected model kwargs {sorted(extra)}")
-        for name in ("x_cond", "x_cond_mask"):
-            if name not in model_kwargs:
-                raise TypeError(f"missing model kwarg {name!r}")
+        check_model_kwargs(model_kwargs)  # (where its tensors are: make_io below)
         dev = x1.device
         B = x1.shape[0]
         if tuple(x0.shape) != tuple(x1.shape) or tuple(t.shape) != (B,):
             raise ValueError(f"x0 must be shaped like x1 {tuple(x1.shape)} and t ({B},), got {tuple(x0.shape)} and {tuple(t.shape)}")
-        for name, ten in (("t", t), ("x0", x0)):
-            if ten.device != dev:
-                raise RuntimeError(f"Expected all tensors to be on the same device, but {name} is on {ten.device} and x1 is on {dev}")
+        same_device((("t", t), ("x0", x0)), dev, "x1")
         net.ensure_packed(dev)
         x1 = x1.detach()
         x0 = x0.detach().float().contiguous()
@@ -460,291 +456,54 @@ def resolve_backbone(model: Callable) -> Optional[LatentSIV3]:
     return None
 
 
-def _f32(v: float) -> float:
-    return float(torch.tensor(v, dtype=torch.float32))
+def same_device(named, dev, anchor: str) -> None:
+    """The reference's device-mismatch error for the first of ``named`` = (name, tensor or None) pairs that is not on ``dev``, the device of
+    what ``anchor`` names"""
+    for name, ten in named:
+        if ten is not None and ten.device != dev:
+            raise RuntimeError(f"Expected all tensors to be on the same device, but {name} is on {ten.device} and {anchor} is on {dev}")
 
 
-# ---- adaptive Dormand-Prince 5(4), the reference's default ODE method (transport.py:486-494: torchdiffeq.odeint(method="dopri5")) ----------
-# torchdiffeq is a third-party dependency that is neither vendored in the reference nor installed here (parity unpinned); this
-# restates its published algorithm (Dormand-Prince / Shampine tableau, Hairer's initial step, RMS error norm over the whole state, step
-# factor clamp(0.9 err^-1/5, 0.2 .. 10), first-same-as-last, 4th-order dense output through the midpoint weights) so that the default
-# configuration of the reference runs on the HIP network without it.  The network evaluations - all the cost - go through `f`.
-_DP_ALPHA = (1 / 5, 3 / 10, 4 / 5, 8 / 9, 1.0, 1.0)
-_DP_BETA = ((1 / 5,), (3 / 40, 9 / 40), (44 / 45, -56 / 15, 32 / 9), (19372 / 6561, -25360 / 2187, 64448 / 6561, -212 / 729),
-            (9017 / 3168, -355 / 33, 46732 / 5247, 49 / 176, -5103 / 18656), (35 / 384, 0.0, 500 / 1113, 125 / 192, -2187 / 6784, 11 / 84))
-_DP_C_ERR = (35 / 384 - 1951 / 21600, 0.0, 500 / 1113 - 22642 / 50085, 125 / 192 - 451 / 720, -2187 / 6784 + 12231 / 42400,
-             11 / 84 - 649 / 6300, -1 / 60)
-_DP_C_MID = (6025192743 / 30085553152 / 2, 0.0, 51252292925 / 65400821598 / 2, -2691868925 / 45128329728 / 2,
-             187940372067 / 1594534317056 / 2, -1776094331 / 19743644256 / 2, 11237099 / 235043384 / 2)
+def check_model_kwargs(model_kwargs: Dict[str, Any], dev=None, then: Optional[Callable[[], Any]] = None) -> None:
+    """The check of the conditioning every library path takes as ``model_kwargs``, in this order: unexpected keys, (``then()``: what a
+    caller has always checked at this point,) missing ``x_cond`` / ``x_cond_mask``, and - given the state's device ``dev`` - tensors
+    elsewhere."""
+    extra = set(model_kwargs) - {"x_cond", "x_cond_mask", "y"}
+    if extra:
+        raise TypeError(f"unexpected model kwargs {sorted(extra)}")
+    if then is not None:
+        then()
+    for name in ("x_cond", "x_cond_mask"):
+        if name not in model_kwargs:
+            raise TypeError(f"missing model kwarg {name!r}")
+    if dev is not None:
+        same_device(model_kwargs.items(), dev, "the state")
 
 
-def _rms(v: Tensor) -> float:
-    return float(v.double().pow(2).mean().sqrt())
+def stage_inputs(net: LatentSIV3, init: Tensor, model_kwargs: Dict[str, Any], dev, fresh: bool):
+    """The state and the conditioning of a sampling call as the library takes them: (state, the call's lsl_io, what it keeps alive, replay).
+    ``fresh``: the library updates the state in place, so it gets a private copy.  ``replay``: the library may replay the call as a hipGraph
+    (``graph_replay_enabled``), so every input lies in a persistent buffer (see ``LatentSIV3.staged``)."""
+    replay = net.graph_replay_enabled(tokens=int(init.shape[0]) * int(init.shape[1]) * int(init.shape[2]))
+    x = net.staged("state", init, torch.float32, dev, fresh=fresh, persistent=replay)
+    xc = net.staged("x_cond", model_kwargs["x_cond"], torch.float32, dev, persistent=replay)
+    xm = net.staged("x_cond_mask", model_kwargs["x_cond_mask"], torch.int64, dev, persistent=replay)
+    yv = model_kwargs.get("y")
+    if yv is not None:
+        yv = net.staged("y", yv, torch.float32, dev, persistent=replay)
+    io, keep = net.make_io(x, xc, xm, yv)
+    return x, io, keep, replay
 
 
-class _RkOps:
-    """The arithmetic of a Runge-Kutta step on whole states: linear combinations, the controller's error ratio, the quartic dense output.
-    fp32 CUDA tensors go through the library (``lsl_rk_lincomb`` / ``lsl_rk_error_ratio`` / ``lsl_rk_dense``: one launch per combination, terms
-    added in list order, deterministic reduction); anything else (CPU tensors of the host-logic tests, other dtypes) through torch operations
-    in the same order.  ``terms`` = [(coefficient, tensor), ...] with at most 8 entries."""
-
-    def __init__(self, like: Tensor):
-        self.hip = like.is_cuda and like.dtype == torch.float32
-        if self.hip:
-            _lib.load()  # (LibraryMissing is raised here, where Sampler._vel catches it)
-            self.dev = like.device
-            self.scratch = torch.empty(_lib.RK_SCRATCH_BYTES // 4, dtype=torch.float32, device=like.device)
-            self.ratio = torch.empty(1, dtype=torch.float32, device=like.device)
-
-    def _pack(self, terms):
-        xs = [x.contiguous() for _, x in terms]
-        ptrs = (C.c_void_p * len(xs))(*[x.data_ptr() for x in xs])
-        cs = (C.c_float * len(xs))(*[float(c) for c, _ in terms])
-        return xs, ptrs, cs
-
-    def lincomb(self, terms) -> Tensor:
-        if not self.hip:
-            rnd = _f32 if terms[0][1].dtype == torch.float32 else float  # (the kernels take fp32 coefficients)
-            acc = terms[0][1] * rnd(terms[0][0])
-            for c, x in terms[1:]:
-                acc = acc + x * rnd(c)
-            return acc
-        xs, ptrs, cs = self._pack(terms)
-        out = torch.empty_like(xs[0])
-        _lib.call(self.dev, "lsl_rk_lincomb", out.data_ptr(), ptrs, cs, len(xs), out.numel())
-        return out
-
-    def error_ratio(self, y0: Tensor, y1: Tensor, terms, atol: float, rtol: float) -> float:
-        """sqrt(mean((sum_j c_j k_j / (atol + rtol max(|y0|, |y1|)))^2)) as a host scalar (the one device sync of a step)."""
-        if not self.hip:
-            return _rms(self.lincomb(terms) / (atol + rtol * torch.maximum(y0.abs(), y1.abs())))
-        xs, ptrs, cs = self._pack(terms)
-        y0, y1 = y0.contiguous(), y1.contiguous()
-        _lib.call(self.dev, "lsl_rk_error_ratio", self.ratio.data_ptr(), y0.data_ptr(), y1.data_ptr(), ptrs, cs, len(xs), float(atol), float(rtol),
-                  y0.numel(), self.scratch.data_ptr())
-        return float(self.ratio.item())
-
-    def poly4(self, a: Tensor, b: Tensor, c: Tensor, d: Tensor, e: Tensor, x: float) -> Tensor:
-        if not self.hip:
-            xf = _f32(x) if e.dtype == torch.float32 else float(x)
-            return e + xf * (d + xf * (c + xf * (b + xf * a)))
-        out = torch.empty_like(e)
-        _lib.call(self.dev, "lsl_rk_dense", out.data_ptr(), a.data_ptr(), b.data_ptr(), c.data_ptr(), d.data_ptr(), e.data_ptr(), float(x), out.numel())
-        return out
-
-
-def dopri5_solve(f: Callable[[float, Tensor], Tensor], y0: Tensor, grid: Sequence[float], rtol: float, atol: float,
-                 max_steps: int = 100000) -> Tuple[List[Tensor], Dict[str, int]]:
-    """Solution of y' = f(t, y) at the (increasing) times `grid`, grid[0] being the initial time: [y(grid[0]), ..., y(grid[-1])] and
-    counters.  Steps are chosen by the error controller alone and run past the output times; outputs are interpolated.  An output time
-    that does not exceed the current time (repeated grid points, a single-point grid) returns the current state.  Time arithmetic runs in
-    Python float64 (torchdiffeq keeps t in the dtype of the state's time tensor: accepted-step sequences agree in accuracy class, not in
-    the last bit).  The state arithmetic of a step is ten launches of the library's Runge-Kutta kernels (`_RkOps`: six stage states, the
-    error ratio, and for an accepted step the mid-point and three dense-output coefficients); the error ratio is the one host scalar, and the
-    one device sync, of a step."""
-    y0 = y0.contiguous()
-    ops = _RkOps(y0)
-    t0 = float(grid[0])
-    f0 = f(t0, y0)
-    nfe = 1
-    # initial step (Hairer, Norsett, Wanner I, II.4), order 4 estimate; scale = atol + |y0| rtol
-    d0, d1 = ops.error_ratio(y0, y0, [(1.0, y0)], atol, rtol), ops.error_ratio(y0, y0, [(1.0, f0)], atol, rtol)
-    h0 = 1e-6 if d0 < 1e-5 or d1 < 1e-5 else 0.01 * d0 / d1
-    f1 = f(t0 + h0, ops.lincomb([(1.0, y0), (h0, f0)]))
-    nfe += 1
-    d2 = ops.error_ratio(y0, y0, [(1.0, f1), (-1.0, f0)], atol, rtol) / h0
-    h1 = max(1e-6, h0 * 1e-3) if d1 <= 1e-15 and d2 <= 1e-15 else (0.01 / max(d1, d2)) ** (1.0 / 5.0)
-    dt = min(100 * h0, h1)
-
-    out = [y0]
-    t, y, fy = t0, y0, f0
-    t_lo, coeff = t0, None  # dense output of the last accepted step [t_lo, t]
-    accepted = rejected = 0
-    for tn in [float(g) for g in grid[1:]]:
-        while tn > t:
-            if accepted + rejected >= max_steps:
-                raise RuntimeError(DOPRI_MAX_STEPS_MESSAGE)
-            k = [fy]
-            yi = y
-            for a, beta in zip(_DP_ALPHA, _DP_BETA):
-                yi = ops.lincomb([(1.0, y)] + [(dt * b, kj) for b, kj in zip(beta, k) if b != 0.0])
-                k.append(f(t + a * dt, yi))
-            nfe += 6
-            y1 = yi  # the last stage IS the 5th-order solution (beta[-1] = c_sol): first same as last
-            ratio = ops.error_ratio(y, y1, [(dt * c, kj) for c, kj in zip(_DP_C_ERR, k) if c != 0.0], atol, rtol)
-            if ratio <= 1.0:
-                y_mid = ops.lincomb([(1.0, y)] + [(dt * c, kj) for c, kj in zip(_DP_C_MID, k) if c != 0.0])
-                fa, fb = k[0], k[-1]
-                coeff = (y, ops.lincomb([(dt, fa)]),
-                         ops.lincomb([(dt, fb), (-4 * dt, fa), (-11.0, y), (-5.0, y1), (16.0, y_mid)]),
-                         ops.lincomb([(5 * dt, fa), (-3 * dt, fb), (18.0, y), (14.0, y1), (-32.0, y_mid)]),
-                         ops.lincomb([(2 * dt, fb), (-2 * dt, fa), (-8.0, y1), (-8.0, y), (16.0, y_mid)]))
-                t_lo, t, y, fy = t, t + dt, y1, k[-1]
-                accepted += 1
-            else:
-                rejected += 1
-            if ratio == 0.0:
-                dt = dt * 10.0
-            else:
-                dt = dt * min(10.0, max(0.9 / ratio ** 0.2, 1.0 if ratio < 1.0 else 0.2))
-        if coeff is None or t <= t_lo:  # an output time at (or before) the current time with no accepted step to interpolate: the state itself
-            out.append(y)
-            continue
-        e, d, c, b, a = coeff
-        out.append(ops.poly4(a, b, c, d, e, (tn - t_lo) / (t - t_lo)))
-    return out, {"nfe": nfe, "accepted": accepted, "rejected": rejected}
-
-
-DOPRI_MAX_STEPS_MESSAGE = "dopri5: max_steps reached"
-DOPRI_NON_FINITE_MESSAGE = "dopri5: the error ratio is not finite (NaN or Inf in the state or in the network's output)"
-
-
-def dopri_each_failure(max_steps_rows: Sequence[int], non_finite_rows: Sequence[int]) -> Optional[str]:
-    """The message of a per-trajectory solve some of whose trajectories failed (None: none did): the messages of the batch solve, each with
-    the indices of its trajectories."""
-    parts = [f"{msg} (trajectories {list(rows)})" for msg, rows in ((DOPRI_MAX_STEPS_MESSAGE, max_steps_rows), (DOPRI_NON_FINITE_MESSAGE, non_finite_rows))
-             if len(rows)]
-    return "; ".join(parts) if parts else None
-
-
-def dopri5_solve_each(f: Callable[[Sequence[float], Tensor], Tensor], y0: Tensor, grid: Sequence[float], rtol: float, atol: float,
-                      max_steps: int = 100000) -> Tuple[List[Tensor], Dict[str, Any]]:
-    """:func:`dopri5_solve` with one step controller per trajectory (row of ``y0``), in lock step: the host restatement of the library's
-    ``lsl_dopri_each_*`` loop.  ``f(times, y)`` takes one time per row; every row has its own time, step size, accept / reject decision and
-    output cursor, an attempt evaluates ``f`` once per stage for all rows, and a row that is finished (or failed) is carried along unchanged
-    - ``f`` still sees its state, at its last time.  Every row's stage combinations, error norm (over that row alone) and dense output are
-    computed on the row's slice with the expressions of ``dopri5_solve``, so with an ``f`` whose rows are independent, row ``b`` equals
-    ``dopri5_solve`` on ``y0[b:b+1]`` exactly.  A row stops alone at ``max_steps`` attempts or on a non-finite error ratio; the others go
-    on, and the call raises once all have stopped.  Returns the outputs and ``{"nfe", "accepted", "rejected"}`` as per-row lists, ``"attempts"``
-    (the largest count), ``"passes"`` (evaluations of ``f``) and ``"log"``: per row a float64 [attempts, 4] tensor of (t, dt, ratio,
-    accepted)."""
-    y0 = y0.contiguous()
-    B = int(y0.shape[0])
-    rows = range(B)
-    ops = _RkOps(y0)
-    grid = [float(g) for g in grid]
-    t0 = grid[0]
-
-    def row(x, b):
-        return x[b:b + 1]
-
-    def each(fn, keep, live):  # fn(b) -> [1, ...] for the live rows, the rows of `keep` for the others
-        return torch.cat([fn(b) if live[b] else row(keep, b) for b in rows])
-
-    def norm(b, ya, yb, terms):
-        return ops.error_ratio(row(ya, b), row(yb, b), [(c, row(x, b)) for c, x in terms], atol, rtol)
-
-    everyone = [True] * B
-    f0 = f([t0] * B, y0)
-    d0, d1 = [norm(b, y0, y0, [(1.0, y0)]) for b in rows], [norm(b, y0, y0, [(1.0, f0)]) for b in rows]
-    h0 = [1e-6 if d0[b] < 1e-5 or d1[b] < 1e-5 else 0.01 * d0[b] / d1[b] for b in rows]
-    f1 = f([t0 + h for h in h0], each(lambda b: ops.lincomb([(1.0, row(y0, b)), (h0[b], row(f0, b))]), y0, everyone))
-    passes = 2
-    d2 = [norm(b, y0, y0, [(1.0, f1), (-1.0, f0)]) / h0[b] for b in rows]
-    dt = [min(100 * h0[b], max(1e-6, h0[b] * 1e-3) if d1[b] <= 1e-15 and d2[b] <= 1e-15 else (0.01 / max(d1[b], d2[b])) ** (1.0 / 5.0)) for b in rows]
-
-    t, t_lo, y, fy = [t0] * B, [t0] * B, y0, f0
-    coeff: List[Any] = [None] * B
-    outs = [[row(y0, b)] for b in rows]  # per row: its output slices so far
-    nfe, accepted, rejected = [2] * B, [0] * B, [0] * B
-    log: List[List[Tuple[float, float, float, float]]] = [[] for _ in rows]
-    hit_limit, non_finite = [], []
-
-    def flush(b):  # the output times row b's current step covers; is the row still live?
-        while len(outs[b]) < len(grid) and not grid[len(outs[b])] > t[b]:
-            if coeff[b] is None or t[b] <= t_lo[b]:
-                outs[b].append(row(y, b))
-            else:
-                e, d, c, bb, a = coeff[b]
-                outs[b].append(ops.poly4(a, bb, c, d, e, (grid[len(outs[b])] - t_lo[b]) / (t[b] - t_lo[b])))
-        if len(outs[b]) == len(grid):
-            return False
-        if accepted[b] + rejected[b] >= max_steps:
-            hit_limit.append(b)
-            return False
-        return True
-
-    live = [flush(b) for b in rows]
-    while any(live):
-        k = [fy]
-        yi = y
-        for a, beta in zip(_DP_ALPHA, _DP_BETA):
-            yi = each(lambda b: ops.lincomb([(1.0, row(y, b))] + [(dt[b] * c, row(kj, b)) for c, kj in zip(beta, k) if c != 0.0]), yi, live)
-            k.append(f([t[b] + a * dt[b] if live[b] else t[b] for b in rows], yi))
-        passes += 6
-        y1 = yi
-        ratio = [norm(b, y, y1, [(dt[b] * c, kj) for c, kj in zip(_DP_C_ERR, k) if c != 0.0]) if live[b] else 0.0 for b in rows]
-        take = [live[b] and ratio[b] <= 1.0 for b in rows]
-        for b in rows:
-            if not live[b]:
-                continue
-            nfe[b] += 6
-            log[b].append((t[b], dt[b], ratio[b], float(take[b])))
-            if take[b]:
-                y_mid = ops.lincomb([(1.0, row(y, b))] + [(dt[b] * c, row(kj, b)) for c, kj in zip(_DP_C_MID, k) if c != 0.0])
-                yb, y1b, fa, fb, h = row(y, b), row(y1, b), row(k[0], b), row(k[-1], b), dt[b]
-                coeff[b] = (yb, ops.lincomb([(h, fa)]),
-                            ops.lincomb([(h, fb), (-4 * h, fa), (-11.0, yb), (-5.0, y1b), (16.0, y_mid)]),
-                            ops.lincomb([(5 * h, fa), (-3 * h, fb), (18.0, yb), (14.0, y1b), (-32.0, y_mid)]),
-                            ops.lincomb([(2 * h, fb), (-2 * h, fa), (-8.0, y1b), (-8.0, yb), (16.0, y_mid)]))
-                t_lo[b], t[b] = t[b], t[b] + h
-                accepted[b] += 1
-            else:
-                rejected[b] += 1
-        y = each(lambda b: row(y1, b), y, take)
-        fy = each(lambda b: row(k[-1], b), fy, take)
-        for b in rows:
-            if not live[b]:
-                continue
-            if not math.isfinite(ratio[b]):
-                non_finite.append(b)
-                live[b] = False
-                continue
-            dt[b] = dt[b] * 10.0 if ratio[b] == 0.0 else dt[b] * min(10.0, max(0.9 / ratio[b] ** 0.2, 1.0 if ratio[b] < 1.0 else 0.2))
-            live[b] = flush(b)
-    stats = {"nfe": nfe, "accepted": accepted, "rejected": rejected, "attempts": max(a + r for a, r in zip(accepted, rejected)), "passes": passes,
-             "log": [torch.tensor(rows_b, dtype=torch.float64).reshape(-1, 4) for rows_b in log], "state": y}
-    failure = dopri_each_failure(sorted(hit_limit), sorted(non_finite))
-    if failure:
-        err = RuntimeError(failure)
-        err.stats = stats
-        raise err
-    return [torch.cat([outs[b][j] for b in rows]) for j in range(len(grid))], stats
-
-
-
-# ---- torchdiffeq's other fixed-grid explicit methods (integrators.py:119 passes any `method` through) ------------------------------------
-# Restated from the published schemes, as torchdiffeq's fixed_grid.py / rk_common.py define them (parity unpinned like dopri5: the package is
-# absent): the grid is the output grid itself, one step per interval.  "rk4" is torchdiffeq's default fourth-order step, the 3/8 rule.
-FIXED_GRID_RK_METHODS = ("midpoint", "heun3", "rk4")
-
-
-def fixed_grid_rk_solve(f: Callable[[float, Tensor], Tensor], y0: Tensor, grid: Sequence[float], method: str) -> List[Tensor]:
-    """[y(grid[0]), ..., y(grid[-1])] of y' = f(t, y) with one explicit Runge-Kutta step of `method` per grid interval; stage states and
-    the update through `_RkOps` (library kernels for fp32 CUDA states)."""
-    if method not in FIXED_GRID_RK_METHODS:
-        raise NotImplementedError(f"fixed-grid method {method!r}")
-    y = y0.contiguous()
-    ops = _RkOps(y)
-    out = [y]
-    ts = [float(g) for g in grid]
-    for t0, t1 in zip(ts[:-1], ts[1:]):
-        dt = t1 - t0
-        k1 = f(t0, y)
-        if method == "midpoint":
-            k2 = f(t0 + dt / 2, ops.lincomb([(1.0, y), (dt / 2, k1)]))
-            y = ops.lincomb([(1.0, y), (dt, k2)])
-        elif method == "heun3":
-            k2 = f(t0 + dt / 3, ops.lincomb([(1.0, y), (dt / 3, k1)]))
-            k3 = f(t0 + 2 * dt / 3, ops.lincomb([(1.0, y), (2 * dt / 3, k2)]))
-            y = ops.lincomb([(1.0, y), (dt / 4, k1), (3 * dt / 4, k3)])
-        else:  # rk4: 3/8 rule
-            k2 = f(t0 + dt / 3, ops.lincomb([(1.0, y), (dt / 3, k1)]))
-            k3 = f(t0 + 2 * dt / 3, ops.lincomb([(1.0, y), (dt, k2), (-dt / 3, k1)]))
-            k4 = f(t1, ops.lincomb([(1.0, y), (dt, k1), (-dt, k2), (dt, k3)]))
-            y = ops.lincomb([(1.0, y), (dt / 8, k1), (3 * dt / 8, k2), (3 * dt / 8, k3), (dt / 8, k4)])
-        out.append(y)
-    return out
+def _dopri_head(each: bool, B: int, log_rows: int) -> Dict[str, Any]:
+    """Where a device solve's caller finds things: the entry points' common name, ``last_path``, the record polled between chunks of
+    attempts, and the offsets of the controller record(s), the log(s) and the state in the workspace (include/lsl_api.h)."""
+    D = _lib.Dopri
+    if each:
+        return {"entry": "lsl_dopri_each", "path": "dopri5-device-each", "polled": _lib.DopriEachSummary, "polled_at": D.EACH_SUMMARY_OFFSET,
+                "ctl_at": D.EACH_CTL_OFFSET, "ctl_stride": D.EACH_CTL_STRIDE, "log_at": D.each_log_offset(B), "state_at": D.each_state_offset(B, log_rows)}
+    return {"entry": "lsl_dopri", "path": "dopri5-device", "polled": _lib.DopriCtl, "polled_at": D.CTL_OFFSET, "ctl_at": D.CTL_OFFSET, "ctl_stride": 0,
+            "log_at": D.LOG_OFFSET, "state_at": D.STATE_OFFSET}
 
 
 class Sampler:
@@ -806,6 +565,14 @@ class Sampler:
             steps.append((te, 1.0 + dt * vx, dt * vm, 0.0))
         return steps, grid
 
+    def sde_drift_coeffs(self, t: float, diffusion_form: str, diffusion_norm: float) -> Tuple[float, float, float]:
+        """(dx, dm, g): the SDE's drift at time t is dx x + dm net(x, t) - velocity plus g times the score - under the diffusion coefficient g"""
+        tr = self.transport
+        vx, vm = tr.velocity_coeffs(t)
+        sx, sm = tr.score_coeffs(t)
+        g = tr.schedule.diffusion(t, diffusion_form, diffusion_norm)
+        return vx + g * sx, vm + g * sm, g
+
     def sde_steps(self, *, diffusion_form, diffusion_norm, last_step, last_step_size, num_steps):
         tr = self.transport
         if last_step is None:
@@ -816,23 +583,16 @@ class Sampler:
         grid = torch.linspace(t0, t1, num_steps)
         dt = float(grid[1] - grid[0])
         sch = tr.schedule
-
-        def drift(t):
-            vx, vm = tr.velocity_coeffs(t)
-            sx, sm = tr.score_coeffs(t)
-            g = sch.diffusion(t, diffusion_form, diffusion_norm)
-            return vx + g * sx, vm + g * sm, g
-
         steps = []
         for i in range(num_steps - 1):
             ti = float(grid[i])
-            dx, dm, g = drift(ti)
+            dx, dm, g = self.sde_drift_coeffs(ti, diffusion_form, diffusion_norm)
             steps.append((ti, 1.0 + dt * dx, dt * dm, math.sqrt(2 * g) * math.sqrt(dt)))
         t1f = _f32(t1)
         if last_step is None:
             pass
         elif last_step == "Mean":
-            dx, dm, _ = drift(t1f)
+            dx, dm, _ = self.sde_drift_coeffs(t1f, diffusion_form, diffusion_norm)
             steps.append((t1f, 1.0 + last_step_size * dx, last_step_size * dm, 0.0))
         elif last_step == "Euler":
             vx, vm = tr.velocity_coeffs(t1f)
@@ -855,21 +615,13 @@ class Sampler:
         (dt K1 = x_p - x_hat).  Returned with the EM table's last step appended (same last-step rule as Euler-Maruyama)."""
         em, grid = self.sde_steps(diffusion_form=diffusion_form, diffusion_norm=diffusion_norm, last_step=last_step,
                                   last_step_size=last_step_size, num_steps=num_steps)
-        tr, sch = self.transport, self.transport.schedule
         dt = float(grid[1] - grid[0])
-
-        def drift(t):
-            vx, vm = tr.velocity_coeffs(t)
-            sx, sm = tr.score_coeffs(t)
-            g = sch.diffusion(t, diffusion_form, diffusion_norm)
-            return vx + g * sx, vm + g * sm, g
-
         rec = []
         for i in range(num_steps - 1):
             ti = float(grid[i])
             tn = _f32(_f32(ti) + _f32(dt))  # t_cur + dt in fp32, as the reference forms it
-            dx, dm, g = drift(ti)
-            dx2, dm2, _ = drift(tn)
+            dx, dm, g = self.sde_drift_coeffs(ti, diffusion_form, diffusion_norm)
+            dx2, dm2, _ = self.sde_drift_coeffs(tn, diffusion_form, diffusion_norm)
             rec.append((ti, 1.0, 0.0, math.sqrt(2 * g) * math.sqrt(dt), 0.0, _lib.STEP_NO_NETWORK | _lib.STEP_SAVE, i, -1))
             rec.append((ti, 1.0 + dt * dx, dt * dm, 0.0, 0.0, 0, 0, -1))
             rec.append((tn, 0.5 + 0.5 * dt * dx2, 0.5 * dt * dm2, 0.0, 0.5, 0, 0, i))
@@ -883,18 +635,9 @@ class Sampler:
                   noise: Optional[Tensor] = None, duplicate_last: bool = False, records=None) -> SampleResult:
         """``steps``: plain (t, ax, am, aw) records -> lsl_sample; ``records``: extended ones (heun_records) -> lsl_sample_ex, with
         ``steps`` then only giving the number of kept states."""
-        extra = set(model_kwargs) - {"x_cond", "x_cond_mask", "y"}
-        if extra:
-            raise TypeError(f"unexpected model kwargs {sorted(extra)}")
-        net._require_gpu(init)
-        lib = _lib.load()
         dev = init.device
-        for name in ("x_cond", "x_cond_mask"):
-            if name not in model_kwargs:
-                raise TypeError(f"missing model kwarg {name!r}")
-        for name, ten in model_kwargs.items():
-            if ten is not None and ten.device != dev:
-                raise RuntimeError(f"Expected all tensors to be on the same device, but {name} is on {ten.device} and the state is on {dev}")
+        check_model_kwargs(model_kwargs, dev, then=lambda: net._require_gpu(init))
+        lib = _lib.load()
         # The call's noise-stream seed is drawn only when the call uses device noise (an Euler-Maruyama step without an explicit noise
         # tensor).  ODE calls and SDE calls with stored noise leave torch's global generator untouched, like the reference.
         table = records if records is not None else steps
@@ -902,15 +645,8 @@ class Sampler:
         call_seed = self.next_call_seed(draw=needs_device_noise)
         self.last_seed = call_seed if needs_device_noise else None
         net.ensure_packed(dev)
-        # the state is updated in place by the library: always a private copy (persistent buffers only for calls the library may replay as a hipGraph, see staged())
-        replay = net.graph_replay_enabled(tokens=int(init.shape[0]) * int(init.shape[1]) * int(init.shape[2]))
-        x = net.staged("state", init, torch.float32, dev, fresh=True, persistent=replay)
-        xc = net.staged("x_cond", model_kwargs["x_cond"], torch.float32, dev, persistent=replay)
-        xm = net.staged("x_cond_mask", model_kwargs["x_cond_mask"], torch.int64, dev, persistent=replay)
-        yv = model_kwargs.get("y")
-        if yv is not None:
-            yv = net.staged("y", yv, torch.float32, dev, persistent=replay)
-        io, keep = net.make_io(x, xc, xm, yv)
+        # the state is updated in place by the library: always a private copy
+        x, io, keep, replay = stage_inputs(net, init, model_kwargs, dev, fresh=True)
         ws = net.workspace(io.B, io.T, io.L, dev)
         if records is None:
             arr = (_lib.Step * len(steps))(*[_lib.Step(*s) for s in steps])
@@ -1044,85 +780,79 @@ class Sampler:
 
     def run_dopri_device(self, net: LatentSIV3, init: Tensor, grid: Sequence[float], rtol: float, atol: float, reverse: bool,
                          model_kwargs: Dict[str, Any]) -> Tensor:
-        """The adaptive solve inside the library: ``lsl_dopri_begin``, then ``lsl_dopri_advance`` in chunks of ``attempts_per_poll`` attempts
-        with one read of the controller record (128 bytes, the one synchronisation) behind each.  Returns float32 [len(grid), *init.shape];
-        leaves the counters in ``last_ode_stats``, the log in ``last_ode_log`` and the final state in ``last_ode_state``."""
-        lib, dev, x, io, keep = self._dopri_device_inputs(net, init, model_kwargs)
-        n_out = len(grid)
-        out = torch.empty((n_out,) + tuple(x.shape), dtype=torch.float32, device=dev)
-        ws = net.workspace(io.B, io.T, io.L, dev, need=lib.lsl_dopri_workspace_bytes(net._handle, io.B, io.T, io.L, n_out))
-        desc, times = self._dopri_desc(grid, rtol, atol, reverse)
-
-        def controller():
-            raw = _lib.to_host(ws[_lib.Dopri.CTL_OFFSET:_lib.Dopri.CTL_OFFSET + C.sizeof(_lib.DopriCtl)])
-            return _lib.DopriCtl.from_buffer_copy(raw.tobytes())
-
-        _lib.call(dev, "lsl_dopri_begin", net._handle, C.byref(io), C.byref(desc), times, n_out, out.data_ptr(), ws.data_ptr(), ws.numel())
-        ctl = controller()
-        while not ctl.done:
-            _lib.call(dev, "lsl_dopri_advance", net._handle, C.byref(io), int(self.attempts_per_poll), ws.data_ptr(), ws.numel())
-            ctl = controller()
-        net.last_path = "hip"
-        self.last_path = "dopri5-device"
-        attempts = ctl.accepted + ctl.rejected
-        self.last_ode_stats = {"nfe": ctl.nfe, "accepted": ctl.accepted, "rejected": ctl.rejected}
-        self.last_ode_log = torch.zeros(0, 4, dtype=torch.float64)
-        if attempts:
-            rows = _lib.to_host(ws[_lib.Dopri.LOG_OFFSET:_lib.Dopri.LOG_OFFSET + 32 * attempts])
-            self.last_ode_log = torch.from_numpy(rows.copy()).view(torch.float64).reshape(attempts, 4)
-        self.last_ode_state = ws[_lib.Dopri.STATE_OFFSET:_lib.Dopri.STATE_OFFSET + 4 * x.numel()].view(torch.float32).reshape(x.shape).clone()
-        del keep
-        if ctl.status == _lib.Dopri.STATUS_MAX_STEPS:
-            raise RuntimeError(DOPRI_MAX_STEPS_MESSAGE)
-        if ctl.status == _lib.Dopri.STATUS_NON_FINITE:
-            raise RuntimeError(DOPRI_NON_FINITE_MESSAGE)
-        return out if out.dtype == init.dtype else out.to(init.dtype)
+        """The adaptive solve inside the library with one controller for the batch (``_run_dopri_device``)."""
+        return self._run_dopri_device(net, init, grid, rtol, atol, reverse, model_kwargs, each=False)
 
     def run_dopri_device_each(self, net: LatentSIV3, init: Tensor, grid: Sequence[float], rtol: float, atol: float, reverse: bool,
                               model_kwargs: Dict[str, Any]) -> Tensor:
-        """``run_dopri_device`` with one controller per trajectory (``lsl_dopri_each_begin`` / ``lsl_dopri_each_advance``): the host reads
-        the summary record (20 bytes) once per ``attempts_per_poll`` attempts until every trajectory is done, then the B controller records,
-        the logs (``ode_log_rows`` rows a trajectory) and the states.  ``last_ode_stats``: per-trajectory lists ``nfe`` / ``accepted`` /
-        ``rejected``, ``attempts`` (the largest count: the attempts the call ran) and ``network_passes`` (evaluations of the network on
-        the batch); ``last_ode_log``: a list of B float64 [min(attempts_b, ode_log_rows), 4] tensors; ``last_ode_state``: every
-        trajectory's state at the end of its last accepted step.  Trajectories that failed are named in the error, raised once all
-        have stopped."""
-        lib, dev, x, io, keep = self._dopri_device_inputs(net, init, model_kwargs)
+        """The adaptive solve inside the library with one controller per trajectory (``_run_dopri_device``)."""
+        return self._run_dopri_device(net, init, grid, rtol, atol, reverse, model_kwargs, each=True)
+
+    def _run_dopri_device(self, net: LatentSIV3, init: Tensor, grid: Sequence[float], rtol: float, atol: float, reverse: bool,
+                          model_kwargs: Dict[str, Any], each: bool) -> Tensor:
+        """The adaptive solve inside the library: ``lsl_dopri[_each]_begin``, then ``lsl_dopri[_each]_advance`` in chunks of
+        ``attempts_per_poll`` attempts with one read of the polled record (``_dopri_head``: the controller record, 128 bytes, or the summary
+        of the per-trajectory form, 20 bytes - the one synchronisation) behind each, until it says done; then the controller record(s), the
+        log(s) and the state.  Returns float32 [len(grid), *init.shape].
+
+        Batch form: ``last_ode_stats`` holds the counters, ``last_ode_log`` a float64 [attempts, 4] tensor.  ``each``: per-trajectory lists
+        ``nfe`` / ``accepted`` / ``rejected``, ``attempts`` (the largest count: the attempts the call ran) and ``network_passes``
+        (evaluations of the network on the batch); ``last_ode_log`` a list of B float64 [min(attempts_b, ode_log_rows), 4] tensors;
+        trajectories that failed are named in the error, raised once all have stopped.  ``last_ode_state``: the state (every trajectory's)
+        at the end of the last accepted step."""
+        check_model_kwargs(model_kwargs, init.device)
+        if int(self.attempts_per_poll) < 1:
+            raise ValueError(f"attempts_per_poll must be at least 1, got {self.attempts_per_poll}")
+        lib, dev = _lib.load(), init.device
+        net.ensure_packed(dev)
+        # (the solver state lives in the workspace: no private copy of the initial state)
+        x, io, keep, _ = stage_inputs(net, init, model_kwargs, dev, fresh=False)
         D = _lib.Dopri
-        B, n_out, log_rows = int(io.B), len(grid), int(self.ode_log_rows)
-        if not 0 <= log_rows <= D.MAX_ATTEMPTS:
+        B, n_out, log_rows = int(io.B), len(grid), int(self.ode_log_rows) if each else D.MAX_ATTEMPTS
+        if each and not 0 <= log_rows <= D.MAX_ATTEMPTS:
             raise ValueError(f"ode_log_rows must be in 0..{D.MAX_ATTEMPTS}, got {self.ode_log_rows}")
-        if B > D.EACH_MAX_B:
+        if each and B > D.EACH_MAX_B:
             raise ValueError(f"step_control='trajectory' takes at most {D.EACH_MAX_B} trajectories a call, got {B}")
+        head = _dopri_head(each, B, log_rows)
+        layout = (n_out, log_rows) if each else (n_out,)
         out = torch.empty((n_out,) + tuple(x.shape), dtype=torch.float32, device=dev)
-        ws = net.workspace(io.B, io.T, io.L, dev, need=lib.lsl_dopri_each_workspace_bytes(net._handle, io.B, io.T, io.L, n_out, log_rows))
+        ws = net.workspace(io.B, io.T, io.L, dev, need=getattr(lib, head["entry"] + "_workspace_bytes")(net._handle, io.B, io.T, io.L, *layout))
         desc, times = self._dopri_desc(grid, rtol, atol, reverse)
 
-        def summary():
-            raw = _lib.to_host(ws[D.EACH_SUMMARY_OFFSET:D.EACH_SUMMARY_OFFSET + C.sizeof(_lib.DopriEachSummary)])
-            return _lib.DopriEachSummary.from_buffer_copy(raw.tobytes())
+        def records(cls, at, count=1, stride=0):
+            raw = _lib.to_host(ws[at:at + max(stride * count, C.sizeof(cls))]).tobytes()
+            return [cls.from_buffer_copy(raw, stride * i) for i in range(count)]
 
-        _lib.call(dev, "lsl_dopri_each_begin", net._handle, C.byref(io), C.byref(desc), times, n_out, out.data_ptr(), log_rows, ws.data_ptr(), ws.numel())
-        state = summary()
-        while not state.done:
-            _lib.call(dev, "lsl_dopri_each_advance", net._handle, C.byref(io), int(self.attempts_per_poll), ws.data_ptr(), ws.numel())
-            state = summary()
+        _lib.call(dev, head["entry"] + "_begin", net._handle, C.byref(io), C.byref(desc), times, *layout[:1], out.data_ptr(), *layout[1:], ws.data_ptr(),
+                  ws.numel())
+        polled, = records(head["polled"], head["polled_at"])
+        while not polled.done:
+            _lib.call(dev, head["entry"] + "_advance", net._handle, C.byref(io), int(self.attempts_per_poll), ws.data_ptr(), ws.numel())
+            polled, = records(head["polled"], head["polled_at"])
         net.last_path = "hip"
-        self.last_path = "dopri5-device-each"
-        raw = _lib.to_host(ws[D.EACH_CTL_OFFSET:D.EACH_CTL_OFFSET + D.EACH_CTL_STRIDE * B]).tobytes()
-        ctl = [_lib.DopriCtl.from_buffer_copy(raw, D.EACH_CTL_STRIDE * b) for b in range(B)]
-        self.last_ode_stats = {"nfe": [c.nfe for c in ctl], "accepted": [c.accepted for c in ctl], "rejected": [c.rejected for c in ctl],
-                               "attempts": int(state.max_attempts), "network_passes": 2 + 6 * int(state.max_attempts)}
-        self.last_ode_log = [torch.zeros(0, 4, dtype=torch.float64) for _ in ctl]
+        self.last_path = head["path"]
+        if each:
+            ctl = records(_lib.DopriCtl, head["ctl_at"], B, head["ctl_stride"])
+            self.last_ode_stats = {"nfe": [c.nfe for c in ctl], "accepted": [c.accepted for c in ctl], "rejected": [c.rejected for c in ctl],
+                                   "attempts": int(polled.max_attempts), "network_passes": 2 + 6 * int(polled.max_attempts)}
+        else:  # (the polled record is the controller's)
+            ctl = [polled]
+            self.last_ode_stats = {"nfe": polled.nfe, "accepted": polled.accepted, "rejected": polled.rejected}
+            log_rows = polled.accepted + polled.rejected  # (every attempt has its row: the rows to read)
+        logs = [torch.zeros(0, 4, dtype=torch.float64) for _ in ctl]
         if log_rows:
-            rows = _lib.to_host(ws[D.each_log_offset(B):D.each_log_offset(B) + 32 * B * log_rows])
-            logs = torch.from_numpy(rows.copy()).view(torch.float64).reshape(B, log_rows, 4)
-            self.last_ode_log = [logs[b, :min(c.accepted + c.rejected, log_rows)].clone() for b, c in enumerate(ctl)]
-        at = D.each_state_offset(B, log_rows)
-        self.last_ode_state = ws[at:at + 4 * x.numel()].view(torch.float32).reshape(x.shape).clone()
+            rows = _lib.to_host(ws[head["log_at"]:head["log_at"] + 32 * len(ctl) * log_rows])
+            table = torch.from_numpy(rows.copy()).view(torch.float64).reshape(len(ctl), log_rows, 4)
+            logs = [table[b, :min(c.accepted + c.rejected, log_rows)].clone() for b, c in enumerate(ctl)]
+        self.last_ode_log = logs if each else logs[0]
+        self.last_ode_state = ws[head["state_at"]:head["state_at"] + 4 * x.numel()].view(torch.float32).reshape(x.shape).clone()
         del keep
-        failure = dopri_each_failure([b for b, c in enumerate(ctl) if c.status == D.STATUS_MAX_STEPS],
-                                     [b for b, c in enumerate(ctl) if c.status == D.STATUS_NON_FINITE])
+        hit_limit = [b for b, c in enumerate(ctl) if c.status == D.STATUS_MAX_STEPS]
+        non_finite = [b for b, c in enumerate(ctl) if c.status == D.STATUS_NON_FINITE]
+        if each:
+            failure = dopri_each_failure(hit_limit, non_finite)
+        else:
+            failure = DOPRI_MAX_STEPS_MESSAGE if hit_limit else DOPRI_NON_FINITE_MESSAGE if non_finite else None
         if failure:
             raise RuntimeError(failure)
         return out if out.dtype == init.dtype else out.to(init.dtype)
@@ -1133,33 +863,6 @@ class Sampler:
         desc = _lib.DopriDesc(_lib.Dopri.PATHS[tr.path_type.name], _lib.Dopri.PREDICTIONS[tr.model_type.name], int(bool(reverse)),
                               min(int(self.ode_max_steps), _lib.Dopri.MAX_ATTEMPTS), float(rtol), float(atol))
         return desc, (C.c_double * len(grid))(*[float(g) for g in grid])
-
-    def _dopri_device_inputs(self, net: LatentSIV3, init: Tensor, model_kwargs: Dict[str, Any]):
-        """The checks and the staged inputs of a device solve: (library, device, state, the call's lsl_io, what it keeps alive)"""
-        extra = set(model_kwargs) - {"x_cond", "x_cond_mask", "y"}
-        if extra:
-            raise TypeError(f"unexpected model kwargs {sorted(extra)}")
-        for name in ("x_cond", "x_cond_mask"):
-            if name not in model_kwargs:
-                raise TypeError(f"missing model kwarg {name!r}")
-        dev = init.device
-        for name, ten in model_kwargs.items():
-            if ten is not None and ten.device != dev:
-                raise RuntimeError(f"Expected all tensors to be on the same device, but {name} is on {ten.device} and the state is on {dev}")
-        if int(self.attempts_per_poll) < 1:
-            raise ValueError(f"attempts_per_poll must be at least 1, got {self.attempts_per_poll}")
-        lib = _lib.load()
-        net.ensure_packed(dev)
-        # persistent input buffers for calls the library may replay as a hipGraph (see run_fused); the solver state lives in the workspace
-        replay = net.graph_replay_enabled(tokens=int(init.shape[0]) * int(init.shape[1]) * int(init.shape[2]))
-        x = net.staged("state", init, torch.float32, dev, persistent=replay)
-        xc = net.staged("x_cond", model_kwargs["x_cond"], torch.float32, dev, persistent=replay)
-        xm = net.staged("x_cond_mask", model_kwargs["x_cond_mask"], torch.int64, dev, persistent=replay)
-        yv = model_kwargs.get("y")
-        if yv is not None:
-            yv = net.staged("y", yv, torch.float32, dev, persistent=replay)
-        io, keep = net.make_io(x, xc, xm, yv)
-        return lib, dev, x, io, keep
 
     def _sample_ode_dopri5(self, *, num_steps, atol, rtol, reverse, method="dopri5", controller="host", each=False):
         """The reference's default ODE sampler (transport.py:486-494, integrators.py:67-78 with method "dopri5"): adaptive steps, the solution
@@ -1256,12 +959,7 @@ class Sampler:
                     why = "the state must be float32 and must not require grad (the tangent pass is forward mode without a tape)"
                 if why is not None:
                     raise NotImplementedError(f"sample_ode_likelihood on a lam_slide_amd.LatentSIV3 needs the library's tangent pass: {why}")
-                extra = set(model_kwargs) - {"x_cond", "x_cond_mask", "y"}
-                if extra:
-                    raise TypeError(f"unexpected model kwargs {sorted(extra)}")
-                for name in ("x_cond", "x_cond_mask"):
-                    if name not in model_kwargs:
-                        raise TypeError(f"missing model kwarg {name!r}")
+                check_model_kwargs(model_kwargs)  # (where its tensors are: LatentSIV3.jvp)
             self.last_path = "likelihood-device" if net is not None else "likelihood-generic"
             count = [0]
 

@@ -2,6 +2,7 @@
 controller per trajectory (``dopri5_solve_each``) against ``dopri5_solve`` on every trajectory alone, the keyword's dispatch and errors, the
 binding of lsl_dopri_each_* against the header, and the argument checks of the library that need no device."""
 import ctypes as C
+import math
 import os
 import re
 
@@ -166,3 +167,76 @@ def test_refused_calls_enqueue_nothing_and_say_why():
         assert lib.lsl_dopri_each_advance(handle, C.byref(io), 1, p, need, None) == -3 and "lsl_dopri_each_begin" in _lib.last_error()
     finally:
         lib.lsl_model_destroy(handle)
+
+
+# ---- the one lock-step loop behind both solvers (lam_slide_amd/ode.py): what differs between the two forms, and what must not ----
+def _cos_rhs(bad=None, bad_calls=(), bad_rows=slice(None)):
+    """y' = cos(t) per row (independent of y, so a non-finite stage leaves later evaluations finite), as (f_batch, f_each, times): both
+    count their calls together and return ``bad`` in ``bad_rows`` on the calls (1-based) in ``bad_calls``; times[i] is call i's time(s)."""
+    times = []
+
+    def f_each(ts, y):
+        times.append(list(ts))
+        out = torch.cos(torch.tensor(ts, dtype=y.dtype)).reshape(-1, 1, 1).expand_as(y).clone()
+        if len(times) in bad_calls:
+            out[bad_rows] = bad
+        return out
+
+    return (lambda t, y: f_each([t] * y.shape[0], y)), f_each, times
+
+
+def test_batch_form_recovers_from_an_infinite_error_ratio():
+    """torchdiffeq's rule, kept by the batch form: +inf in the seventh evaluation of the first attempt (it enters the error estimate alone, so the
+    ratio is inf, not nan) is a rejected attempt followed by a step of 0.2 times the first, and the solve finishes."""
+    from lam_slide_amd.transport import dopri5_solve
+    y0 = torch.tensor([1.0, 2.0], dtype=torch.float64).reshape(2, 1, 1)
+    f, _, times = _cos_rhs(bad=float("inf"), bad_calls=(8,))  # calls 1, 2: the initial step; 3 .. 8: the first attempt
+    grid = [0.0, 0.4, 1.0]
+    ys, stats = dopri5_solve(f, y0, grid, 1e-6, 1e-9)
+    assert stats["rejected"] >= 1 and stats["accepted"] >= 1 and stats["nfe"] == len(times) == 2 + 6 * (stats["accepted"] + stats["rejected"])
+    # the sixth evaluation of an attempt is at t + dt; both attempts start at t = 0, the second because the first was rejected
+    dt_first, dt_second = times[6][0], times[12][0]
+    assert dt_first > 0.0 and dt_second == dt_first * 0.2, (dt_first, dt_second)
+    assert times[8][0] == dt_second * 0.2  # (alpha_1 = 1 / 5 of the new step, from the old time)
+    for t, y in zip(grid, ys):  # y = y0 + sin(t): the controller holds 1e-6 |y| + 1e-9 a step, over a handful of steps
+        assert torch.isfinite(y).all() and (y - (y0 + math.sin(t))).abs().max() < 1e-5, t
+
+
+def test_nan_ends_the_batch_form_at_max_steps_and_stops_one_trajectory_alone():
+    """NaN from the first attempt on in row 0, max_steps = 4.  Batch form: every attempt is rejected, "max_steps reached".  Per-trajectory
+    form: row 0 stops on its first attempt and is named; row 1 goes on and finishes - its counters, log and state are those of its solo
+    solves (a failed call returns no outputs: ``err.stats`` is what it leaves)."""
+    from lam_slide_amd.transport import DOPRI_MAX_STEPS_MESSAGE, DOPRI_NON_FINITE_MESSAGE, dopri5_solve, dopri5_solve_each
+    y0 = torch.tensor([1.0, 2.0], dtype=torch.float64).reshape(2, 1, 1)
+    grid, rtol, atol = [0.0, 0.3, 0.5], 1e-3, 1e-6
+    every_attempt = range(3, 1000)
+    f, _, times = _cos_rhs(bad=float("nan"), bad_calls=every_attempt, bad_rows=slice(0, 1))
+    with pytest.raises(RuntimeError) as batch:
+        dopri5_solve(f, y0, grid, rtol, atol, max_steps=4)
+    assert str(batch.value) == DOPRI_MAX_STEPS_MESSAGE and len(times) == 2 + 6 * 4
+    _, f_each, times = _cos_rhs(bad=float("nan"), bad_calls=every_attempt, bad_rows=slice(0, 1))
+    with pytest.raises(RuntimeError) as each:
+        dopri5_solve_each(f_each, y0, grid, rtol, atol, max_steps=4)
+    assert str(each.value) == f"{DOPRI_NON_FINITE_MESSAGE} (trajectories [0])"
+    stats = each.value.stats
+    assert (stats["accepted"][0], stats["rejected"][0]) == (0, 1) and math.isnan(stats["log"][0][0, 2]) and torch.equal(stats["state"][0], y0[0])
+    f_solo, f_solo_each, _ = _cos_rhs()
+    solo, solo_stats = dopri5_solve(f_solo, y0[1:2], grid, rtol, atol, max_steps=4)
+    solo_each, solo_each_stats = dopri5_solve_each(f_solo_each, y0[1:2], grid, rtol, atol, max_steps=4)
+    assert 1 <= solo_stats["accepted"] + solo_stats["rejected"] <= 4 and stats["attempts"] == solo_each_stats["attempts"]
+    assert {k: stats[k][1] for k in ("nfe", "accepted", "rejected")} == solo_stats
+    assert torch.equal(stats["log"][1], solo_each_stats["log"][0]) and torch.equal(stats["state"][1:2], solo_each_stats["state"])
+    assert all(torch.equal(a, b) for a, b in zip(solo, solo_each))
+
+
+def test_one_trajectory_solved_each_is_the_batch_solve():
+    """B = 1: the two wrappers run the one loop on the same single group - equal outputs bit for bit, equal counters."""
+    from lam_slide_amd.transport import dopri5_solve, dopri5_solve_each
+    y0 = torch.tensor([[[1.5]]], dtype=torch.float64)
+    grid, rtol, atol = [0.0, 0.0, 0.7, 2.0], 1e-7, 1e-9
+    k = 6.0
+    ys, stats = dopri5_solve(lambda t, y: math.sin(k * t) * y, y0, grid, rtol, atol)
+    ys_each, stats_each = dopri5_solve_each(lambda ts, y: math.sin(k * ts[0]) * y, y0, grid, rtol, atol)
+    assert len(ys) == len(ys_each) == len(grid) and all(torch.equal(a, b) and a.shape == y0.shape for a, b in zip(ys, ys_each))
+    assert stats == {key: stats_each[key][0] for key in ("nfe", "accepted", "rejected")} and stats["rejected"] + stats["accepted"] > 3
+    assert stats_each["passes"] == stats["nfe"] and stats_each["attempts"] == len(stats_each["log"][0]) == stats["accepted"] + stats["rejected"]
