@@ -54,7 +54,8 @@ extern "C" {
  * 6, later still: lsl_superpose, lsl_atom_rmsf_workspace_bytes, lsl_atom_rmsf added the same way.
  * 6, later still: lsl_dopri_workspace_bytes, lsl_dopri_begin, lsl_dopri_advance, lsl_debug_dopri_coeffs added the same way.
  * 6, later still: lsl_forward_jvp_workspace_bytes, lsl_forward_jvp, lsl_dot_rows added the same way.
- * 6, later still: lsl_dopri_each_workspace_bytes, lsl_dopri_each_begin, lsl_dopri_each_advance added the same way. */
+ * 6, later still: lsl_dopri_each_workspace_bytes, lsl_dopri_each_begin, lsl_dopri_each_advance added the same way.
+ * 6, later still: lsl_dopri_logp_workspace_bytes, lsl_dopri_logp_begin, lsl_dopri_logp_advance, lsl_rademacher added the same way. */
 #define LSL_VERSION 6
 
 typedef struct lsl_model lsl_model;
@@ -709,6 +710,44 @@ size_t lsl_dopri_each_workspace_bytes(const lsl_model *m, int32_t B, int32_t T, 
 int lsl_dopri_each_begin(lsl_model *m, const lsl_io *io, const lsl_dopri_desc *desc, const double *grid, int32_t n_out, float *out,
                          int32_t log_rows, void *workspace, size_t workspace_bytes, void *stream);
 int lsl_dopri_each_advance(lsl_model *m, const lsl_io *io, int32_t n_attempts, void *workspace, size_t workspace_bytes, void *stream);
+
+/* The adaptive solve of Sampler.sample_ode_likelihood on the device: the same solver on the augmented vector [x | logp],
+ * with one tangent pass (lsl_forward_jvp's) per evaluation.  each = 0: one controller, a vector of B T L C + B elements, the logp entries
+ * behind all of x (the layout the host path concatenates); each = 1: a controller per trajectory, B vectors of T L C + 1 elements, trajectory
+ * b with the bits of the each = 0 call on [b:b+1].  Launch shapes and the error norm's summation order are those of lsl_rk_error_ratio on
+ * the concatenated vector.  The right-hand side at solver time s = t + alpha dt, with tn = (float)(1 - s) and (vx, vm) at (double)tn:
+ *   k_x[i]    = -(fp32(vx) x[i] + fp32(vm) net[i])         net = network(x, tn)
+ *   k_logp[b] = (float)(vx T L C + vm dot_b)               dot_b = sum_e eps[b,e] j[b,e] (lsl_dot_rows' order), j = (d net / d x) eps
+ * The probe eps: a device tensor [B,T,L,C] read in place at every evaluation, or (eps = NULL) drawn on the device in front of every tangent
+ * pass: trajectory b's evaluation e, element i is lsl_rademacher's value for (probe_seeds[b], e, i), e being the evaluation count of the
+ * trajectory's record (begin: 0 and 1; stage s of an attempt: nfe + s), i the index inside the trajectory.  probe_seeds: device uint64 [B],
+ * copied at begin.  Exactly one of eps / probe_seeds is given.
+ *
+ * The workspace (lsl_dopri_logp_workspace_bytes) starts with the records of lsl_dopri_begin (each = 0) or lsl_dopri_each_begin (each = 1) at
+ * the same offsets, read back the same way; with so = LSL_DOPRI_STATE_OFFSET or LSL_DOPRI_EACH_STATE_OFFSET(B, log_rows):
+ *   so                                            fp32 [B,T,L,C]: the current x
+ *   LSL_DOPRI_LOGP_SIDE_OFFSET(so, B T L C)       fp32 [B]: the current logp (the accumulated change of the log-density)
+ * desc->reverse must be 1 (the drift is evaluated at 1 - t); the records carry reverse = 1 | LSL_DOPRI_NEGATED: the network's time is
+ * reversed AND the x drift is negated, the side elements are integrated beside it - the record of an augmented solve.  The bit is
+ * informational, for whoever reads a record back: no kernel tests it (lsl_dopri_logp_* always negate), and setting it in the desc of another
+ * entry point is refused like any reverse value but 0 and 1.
+ * One workspace layout per (B, T, L, n_out, each, log_rows): the state-sized probe buffer is part of it whether the probe is drawn or given.
+ *   lsl_dopri_logp_begin    as lsl_dopri_[each_]begin; out: device [n_out][B,T,L,C], out_logp: device [n_out][B] (0 at the leading output
+ *                           times).  each = 0: log_rows is not used (LSL_DOPRI_MAX_ATTEMPTS rows).  B <= 65535.
+ *   lsl_dopri_logp_advance  as lsl_dopri_each_advance: same io and workspace as the begin call on this handle (-3 without one); eps, where
+ *                           given, is read again.  Attempts are enqueued eagerly (the tangent pass is not replayed as a hipGraph).
+ * The tangent pass keeps its refusals (-21: tail, ln_fuse, linear attention); a path x prediction pair without a finite velocity on the
+ * interval ends with LSL_DOPRI_NON_FINITE.  Argument checks, error codes and "a refused call enqueues nothing" as above. */
+#define LSL_DOPRI_NEGATED 2 /* bit of lsl_dopri_ctl.reverse */
+#define LSL_DOPRI_LOGP_SIDE_OFFSET(state_offset, n_state) ((state_offset) + 256 * ((4 * (size_t)(n_state) + 255) / 256))
+size_t lsl_dopri_logp_workspace_bytes(const lsl_model *m, int32_t B, int32_t T, int32_t L, int32_t n_out, int32_t each, int32_t log_rows);
+int lsl_dopri_logp_begin(lsl_model *m, const lsl_io *io, const lsl_dopri_desc *desc, const double *grid, int32_t n_out, float *out, float *out_logp,
+                         int32_t each, int32_t log_rows, const float *eps, const uint64_t *probe_seeds, void *workspace, size_t workspace_bytes,
+                         void *stream);
+int lsl_dopri_logp_advance(lsl_model *m, const lsl_io *io, int32_t n_attempts, void *workspace, size_t workspace_bytes, void *stream);
+/* out[i] = +1 or -1 for (seed, eval_index, i), i < n: the Philox4x32-10 stream of lsl_randn (counter = (i / 4, eval_index, 0), key = seed), the
+ * top bit of word i % 4.  The probe draw of lsl_dopri_logp_*. */
+int lsl_rademacher(float *out, uint64_t n, uint64_t seed, uint32_t eval_index, void *stream);
 
 /* Test hook: out[i] = (vx, vm) of the drift vx y + vm net(y, t) at the fp32 times t[0..n), fp64, as the kernels of lsl_dopri_* evaluate them */
 int lsl_debug_dopri_coeffs(int32_t path_type, int32_t model_type, const float *t, int32_t n, double *out, void *stream);

@@ -53,6 +53,7 @@ EXPORTED = (
     "lsl_profile_enable", "lsl_profile_read", "lsl_randn", "lsl_rk_lincomb", "lsl_rk_dense", "lsl_rk_error_ratio",
     "lsl_dopri_workspace_bytes", "lsl_dopri_begin", "lsl_dopri_advance", "lsl_debug_dopri_coeffs",
     "lsl_dopri_each_workspace_bytes", "lsl_dopri_each_begin", "lsl_dopri_each_advance",
+    "lsl_dopri_logp_workspace_bytes", "lsl_dopri_logp_begin", "lsl_dopri_logp_advance", "lsl_rademacher",
     "lsl_forward_jvp_workspace_bytes", "lsl_forward_jvp", "lsl_dot_rows",
     "lsl_decoder_create", "lsl_decoder_destroy", "lsl_decode_workspace_bytes", "lsl_decode",
     "lsl_encoder_create", "lsl_encoder_destroy", "lsl_encode_workspace_bytes", "lsl_encode",
@@ -163,6 +164,12 @@ class Dopri:
     @staticmethod
     def each_state_offset(B: int, log_rows: int) -> int:  # LSL_DOPRI_EACH_STATE_OFFSET
         return Dopri.each_log_offset(B) + 256 * ((32 * int(B) * int(log_rows) + 255) // 256)
+
+    NEGATED = 2  # LSL_DOPRI_NEGATED: the bit of lsl_dopri_ctl.reverse an augmented solve (lsl_dopri_logp_*) sets
+
+    @staticmethod
+    def logp_side_offset(state_offset: int, n_state: int) -> int:  # LSL_DOPRI_LOGP_SIDE_OFFSET
+        return int(state_offset) + 256 * ((4 * int(n_state) + 255) // 256)
 
 
 # The translation units of the library and the compile options each adds to BASE_FLAGS: a unit per family of entry points (the sampling
@@ -328,6 +335,12 @@ def load() -> C.CDLL:
     lib.lsl_dopri_each_begin.argtypes = [C.c_void_p, C.POINTER(IO), C.POINTER(DopriDesc), C.POINTER(C.c_double), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                          C.c_size_t, C.c_void_p]
     lib.lsl_dopri_each_advance.argtypes = [C.c_void_p, C.POINTER(IO), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.lsl_dopri_logp_workspace_bytes.argtypes = [C.c_void_p] + [C.c_int32] * 6
+    lib.lsl_dopri_logp_workspace_bytes.restype = C.c_size_t
+    lib.lsl_dopri_logp_begin.argtypes = [C.c_void_p, C.POINTER(IO), C.POINTER(DopriDesc), C.POINTER(C.c_double), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                         C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.lsl_dopri_logp_advance.argtypes = [C.c_void_p, C.POINTER(IO), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.lsl_rademacher.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p]
     lib.lsl_debug_dopri_coeffs.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     lib.lsl_profile_enable.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     lib.lsl_profile_read.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32)]

@@ -56,6 +56,12 @@ struct lsl_model {
         int32_t B, T, L, n_out, log_rows;
     };
     std::map<const void *, DopriEachCall> dopri_each;  // by workspace: what lsl_dopri_each_begin laid it out for (lsl_dopri_each_advance carves by it)
+    struct DopriLogpCall {
+        int32_t B, T, L, n_out, log_rows, each;
+        const float *eps;  // the caller's probe, or null: drawn on the device
+        float *out_logp;
+    };
+    std::map<const void *, DopriLogpCall> dopri_logp;  // the same for lsl_dopri_logp_begin / lsl_dopri_logp_advance
 };
 
 namespace {

@@ -188,4 +188,21 @@ int check_jvp(const lsl_model *m, const lsl_io *io, const float *x_tangent, cons
     return 0;
 }
 
+// The passes of one tangent evaluation (lsl_forward_jvp, every evaluation of lsl_dopri_logp_*): io->out = network(io->x, io->t, ...),
+// out_tangent = its Jacobian in x applied to x_tangent
+int jvp_passes(lsl_model *m, const lsl_io *io, const Workspace &ws, const JvpWorkspace &jw, const CallPlans &plans, int chunk, const float *x_tangent,
+               float *out_tangent, hipStream_t st) {
+    run_tables(m, ws, io->T, io->L, st);
+    return for_each_pass(m, ws, io, chunk, st, [&](const Pass &ps) {
+        EvalArgs e;
+        e.x = io->x + ps.elem;
+        e.out = io->out + ps.elem;
+        e.t = io->t + ps.b0;
+        e.have_y = ps.y != nullptr;
+        const PassPlan &plan = plans.of(ps.bc);
+        JvpPass tangent(m, ws, jw, plan, x_tangent + ps.elem, out_tangent + ps.elem, st);
+        return run_eval(m, ws, plan, e, st, &tangent);
+    });
+}
+
 }  // namespace

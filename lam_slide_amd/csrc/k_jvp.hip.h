@@ -371,8 +371,9 @@ __global__ void __launch_bounds__(256) k_gate_update_jvp(float *ht, const float 
 // ---- lsl_dot_rows: out[b] = sum_e a[b][e] b[b][e] in fp64 from the exact products of the fp32 values.  A trajectory is cut into slabs of
 // LSL_SI_SLAB elements (4096, a constant of the header); inside a slab thread i adds elements i + 256 j in j order and the 256 threads' sums go through the
 // halving tree; a trajectory's slabs are added in slab order.  No atomics: a trajectory's bits are the same in any batch.
-__global__ void __launch_bounds__(256) k_dot_rows_partial(double *partial, const float *a, const float *b, unsigned long long per) {
-    __shared__ double red[256];
+// The two fragments (k_dopri5.hip.h's k_dp_dot / k_dp_klogp run the same ones): slab blockIdx.x of trajectory blockIdx.y by a 256-thread
+// workgroup, and a trajectory's slab partials in slab order
+__device__ __forceinline__ void dot_rows_slab(double *red, double *partial, const float *a, const float *b, unsigned long long per) {
     const unsigned long long base = (unsigned long long)blockIdx.y * per, e0 = (unsigned long long)blockIdx.x * LSL_SI_SLAB;
     double s = 0.0;
 #pragma unroll 4
@@ -383,12 +384,20 @@ __global__ void __launch_bounds__(256) k_dot_rows_partial(double *partial, const
     s = block_tree_sum(red, s);
     if (threadIdx.x == 0) partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
 }
+__device__ __forceinline__ double dot_rows_total(const double *partial, int b, int slabs) {
+    double s = 0.0;
+    for (int k = 0; k < slabs; ++k) s += partial[(size_t)b * slabs + k];
+    return s;
+}
+__global__ void __launch_bounds__(256) k_dot_rows_partial(double *partial, const float *a, const float *b, unsigned long long per) {
+    __shared__ double red[256];
+    dot_rows_slab(red, partial, a, b, per);
+}
 // (one thread per trajectory adds its slab partials serially - the documented order.  A likelihood state has a few hundred slabs at most
 // (peptide: 375); the 2^19 slabs of the largest trajectory the entry point admits would be a long serial chain.)
 __global__ void k_dot_rows_final(double *out, const double *partial, int B, int slabs) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    double s = 0.0;
-    for (int k = 0; k < slabs; ++k) s += partial[(size_t)b * slabs + k];
+    const double s = dot_rows_total(partial, b, slabs);
     out[b] = s;
 }

@@ -105,6 +105,14 @@ __device__ __forceinline__ float philox_normal(unsigned long long seed, unsigned
     __sincosf(6.283185307179586f * u2, &sn, &cs);
     return (elem & 1) ? rad * sn : rad * cs;
 }
+// A Rademacher draw from the same counters: +-1 for (seed, step, element) by the top bit of the element's output word
+// (counter = (elem/4 lo, elem/4 hi, step, 0), key = (seed lo, seed hi), word elem % 4)
+__device__ __forceinline__ float philox_sign(unsigned long long seed, unsigned step, unsigned long long elem) {
+    const unsigned long long blk = elem >> 2;
+    unsigned c[4] = {(unsigned)blk, (unsigned)(blk >> 32), step, 0u};
+    philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32));
+    return (c[elem & 3] >> 31) ? -1.0f : 1.0f;
+}
 
 // ---- a record's update of one state element (lsl_step_ex):  xn = ax x + am m;  += aw w[e];  += as saved[e];  x, trace, save_out <- xn, the
 // terms added in this order.  e is the element's index in the launch's state (x, noise, trace, saved and save_out all point at the launch's first

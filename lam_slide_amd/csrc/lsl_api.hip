@@ -239,17 +239,7 @@ int lsl_forward_jvp(lsl_model *m, const lsl_io *io, const float *x_tangent, floa
     const JvpWorkspace jw = carve_jvp(m, (char *)workspace + align_up(ws.bytes, 256), chunk, io->T, io->L);
     CallPlans plans;
     if (int rc = plan_call(m, ws, io, chunk, m->MODW, plans)) return rc;  // (before the first launch: a refused call enqueues nothing)
-    run_tables(m, ws, io->T, io->L, st);
-    return for_each_pass(m, ws, io, chunk, st, [&](const Pass &ps) {
-        EvalArgs e;
-        e.x = io->x + ps.elem;
-        e.out = io->out + ps.elem;
-        e.t = io->t + ps.b0;
-        e.have_y = ps.y != nullptr;
-        const PassPlan &plan = plans.of(ps.bc);
-        JvpPass tangent(m, ws, jw, plan, x_tangent + ps.elem, out_tangent + ps.elem, st);
-        return run_eval(m, ws, plan, e, st, &tangent);
-    });
+    return jvp_passes(m, io, ws, jw, plans, chunk, x_tangent, out_tangent, st);
 } LSL_API_CATCH
 
 int lsl_dot_rows(const float *a, const float *b, int32_t B, uint64_t per_trajectory, double *out, void *scratch, size_t scratch_bytes,
@@ -505,6 +495,37 @@ int lsl_dopri_each_advance(lsl_model *m, const lsl_io *io, int32_t n_attempts, v
     if (call == m->dopri_each.end() || call->second.B != io->B || call->second.T != io->T || call->second.L != io->L)
         return fail(-3, "no lsl_dopri_each_begin on this handle laid this workspace out for B, T, L = %d, %d, %d", io->B, io->T, io->L);
     return dopri_advance(m, io, n_attempts, true, call->second.n_out, call->second.log_rows, workspace, workspace_bytes, stream);
+} LSL_API_CATCH
+
+// ---- the augmented solve of sample_ode_likelihood: the vector [x | logp], an evaluation = a tangent pass (host_dopri.hip.h) ----
+size_t lsl_dopri_logp_workspace_bytes(const lsl_model *m, int32_t B, int32_t T, int32_t L, int32_t n_out, int32_t each, int32_t log_rows) {
+    if (!m || B <= 0 || B > DOPRI_EACH_MAX_B || T <= 0 || L <= 0 || n_out <= 0 || log_rows < 0 || log_rows > LSL_DOPRI_MAX_ATTEMPTS) return 0;
+    return dopri_carve(m, nullptr, B, T, L, n_out, each != 0, each ? log_rows : LSL_DOPRI_MAX_ATTEMPTS, true).bytes;
+}
+
+int lsl_dopri_logp_begin(lsl_model *m, const lsl_io *io, const lsl_dopri_desc *desc, const double *grid, int32_t n_out, float *out, float *out_logp,
+                         int32_t each, int32_t log_rows, const float *eps, const uint64_t *probe_seeds, void *workspace, size_t workspace_bytes,
+                         void *stream) try {
+    const DopriLogp logp{eps, (const unsigned long long *)probe_seeds, out_logp};
+    return dopri_begin(m, io, desc, grid, n_out, out, each != 0, each ? log_rows : LSL_DOPRI_MAX_ATTEMPTS, workspace, workspace_bytes, stream, &logp);
+} LSL_API_CATCH
+
+int lsl_dopri_logp_advance(lsl_model *m, const lsl_io *io, int32_t n_attempts, void *workspace, size_t workspace_bytes, void *stream) try {
+    if (!m || !io) return fail(-1, "null model or io");
+    const auto call = m->dopri_logp.find(workspace);
+    if (call == m->dopri_logp.end() || call->second.B != io->B || call->second.T != io->T || call->second.L != io->L)
+        return fail(-3, "no lsl_dopri_logp_begin on this handle laid this workspace out for B, T, L = %d, %d, %d", io->B, io->T, io->L);
+    const DopriLogp logp{call->second.eps, nullptr, call->second.out_logp};
+    return dopri_advance(m, io, n_attempts, call->second.each != 0, call->second.n_out, call->second.log_rows, workspace, workspace_bytes, stream, &logp);
+} LSL_API_CATCH
+
+int lsl_rademacher(float *out, uint64_t n, uint64_t seed, uint32_t eval_index, void *stream) try {
+    DeviceGuard dev_guard_((hipStream_t)stream);
+    if (!out && n) return fail(-1, "null argument");
+    if (!n) return 0;
+    hipLaunchKernelGGL(k_rademacher, dim3(rk_grid(n)), dim3(256), 0, (hipStream_t)stream, out, (unsigned long long)n, (unsigned long long)seed, (unsigned)eval_index);
+    LSL_CHECK_LAUNCH("lsl_rademacher");
+    return 0;
 } LSL_API_CATCH
 
 int lsl_debug_dopri_coeffs(int32_t path_type, int32_t model_type, const float *t, int32_t n, double *out, void *stream) try {

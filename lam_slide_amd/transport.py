@@ -495,15 +495,20 @@ def stage_inputs(net: LatentSIV3, init: Tensor, model_kwargs: Dict[str, Any], de
     return x, io, keep, replay
 
 
-def _dopri_head(each: bool, B: int, log_rows: int) -> Dict[str, Any]:
+def _dopri_head(each: bool, B: int, log_rows: int, logp: bool = False) -> Dict[str, Any]:
     """Where a device solve's caller finds things: the entry points' common name, ``last_path``, the record polled between chunks of
-    attempts, and the offsets of the controller record(s), the log(s) and the state in the workspace (include/lsl_api.h)."""
+    attempts, and the offsets of the controller record(s), the log(s) and the state in the workspace (include/lsl_api.h).  ``logp``: the
+    augmented solve of ``sample_ode_likelihood`` (``lsl_dopri_logp_*``: the same records at the same offsets)."""
     D = _lib.Dopri
     if each:
-        return {"entry": "lsl_dopri_each", "path": "dopri5-device-each", "polled": _lib.DopriEachSummary, "polled_at": D.EACH_SUMMARY_OFFSET,
+        head = {"entry": "lsl_dopri_each", "path": "dopri5-device-each", "polled": _lib.DopriEachSummary, "polled_at": D.EACH_SUMMARY_OFFSET,
                 "ctl_at": D.EACH_CTL_OFFSET, "ctl_stride": D.EACH_CTL_STRIDE, "log_at": D.each_log_offset(B), "state_at": D.each_state_offset(B, log_rows)}
-    return {"entry": "lsl_dopri", "path": "dopri5-device", "polled": _lib.DopriCtl, "polled_at": D.CTL_OFFSET, "ctl_at": D.CTL_OFFSET, "ctl_stride": 0,
-            "log_at": D.LOG_OFFSET, "state_at": D.STATE_OFFSET}
+    else:
+        head = {"entry": "lsl_dopri", "path": "dopri5-device", "polled": _lib.DopriCtl, "polled_at": D.CTL_OFFSET, "ctl_at": D.CTL_OFFSET, "ctl_stride": 0,
+                "log_at": D.LOG_OFFSET, "state_at": D.STATE_OFFSET}
+    if logp:
+        head.update(entry="lsl_dopri_logp", path="likelihood-device-solve-each" if each else "likelihood-device-solve")
+    return head
 
 
 class Sampler:
@@ -540,6 +545,8 @@ class Sampler:
         # controller="device": float64 [attempts, 4] rows (t, dt, ratio, accepted); step_control="trajectory": a list of B such tensors
         self.last_ode_log: Any = None
         self.last_ode_state: Optional[Tensor] = None  # controller="device": the state at the end of the last accepted step
+        self.last_ode_logp_state: Optional[Tensor] = None  # sample_ode_likelihood(controller="device"): the logp part of that state, float32 [B]
+        self.last_delta_logp: Optional[Tensor] = None  # sample_ode_likelihood: the integrated change of the log-density, [B] (logp = prior_logp(z) - it)
 
     def next_call_seed(self, draw: bool = True) -> int:
         """Seed of this call's device-noise stream.  The call counter advances on every call (ranks of a sharded run stay in step even
@@ -789,7 +796,7 @@ class Sampler:
         return self._run_dopri_device(net, init, grid, rtol, atol, reverse, model_kwargs, each=True)
 
     def _run_dopri_device(self, net: LatentSIV3, init: Tensor, grid: Sequence[float], rtol: float, atol: float, reverse: bool,
-                          model_kwargs: Dict[str, Any], each: bool) -> Tensor:
+                          model_kwargs: Dict[str, Any], each: bool, logp: Optional[Dict[str, Any]] = None):
         """The adaptive solve inside the library: ``lsl_dopri[_each]_begin``, then ``lsl_dopri[_each]_advance`` in chunks of
         ``attempts_per_poll`` attempts with one read of the polled record (``_dopri_head``: the controller record, 128 bytes, or the summary
         of the per-trajectory form, 20 bytes - the one synchronisation) behind each, until it says done; then the controller record(s), the
@@ -799,7 +806,11 @@ class Sampler:
         ``nfe`` / ``accepted`` / ``rejected``, ``attempts`` (the largest count: the attempts the call ran) and ``network_passes``
         (evaluations of the network on the batch); ``last_ode_log`` a list of B float64 [min(attempts_b, ode_log_rows), 4] tensors;
         trajectories that failed are named in the error, raised once all have stopped.  ``last_ode_state``: the state (every trajectory's)
-        at the end of the last accepted step."""
+        at the end of the last accepted step.
+
+        ``logp`` (``sample_ode_likelihood``): the augmented solve ``lsl_dopri_logp_*`` on ``[x | logp]`` with ``{"eps": the probe tensor or
+        None, "seeds": one integer per trajectory where the probe is drawn on the device}``.  Returns ``(out, out_logp)``, float32
+        [len(grid), *init.shape] and [len(grid), B]; ``last_ode_logp_state`` holds the logp part of the state beside ``last_ode_state``."""
         check_model_kwargs(model_kwargs, init.device)
         if int(self.attempts_per_poll) < 1:
             raise ValueError(f"attempts_per_poll must be at least 1, got {self.attempts_per_poll}")
@@ -813,9 +824,29 @@ class Sampler:
             raise ValueError(f"ode_log_rows must be in 0..{D.MAX_ATTEMPTS}, got {self.ode_log_rows}")
         if each and B > D.EACH_MAX_B:
             raise ValueError(f"step_control='trajectory' takes at most {D.EACH_MAX_B} trajectories a call, got {B}")
-        head = _dopri_head(each, B, log_rows)
+        head = _dopri_head(each, B, log_rows, logp is not None)
         layout = (n_out, log_rows) if each else (n_out,)
         out = torch.empty((n_out,) + tuple(x.shape), dtype=torch.float32, device=dev)
+        begin_args = (*layout[:1], out.data_ptr(), *layout[1:])
+        if logp is not None:
+            if B > D.EACH_MAX_B:
+                raise ValueError(f"the likelihood solve takes at most {D.EACH_MAX_B} trajectories a call, got {B}")
+            layout = (n_out, int(each), log_rows)
+            out_logp = torch.empty((n_out, B), dtype=torch.float32, device=dev)
+            probe = logp.get("eps")
+            seeds = None
+            if probe is not None:
+                if tuple(probe.shape) != tuple(x.shape):
+                    raise ValueError(f"eps must be shaped like the state {tuple(x.shape)}, got {tuple(probe.shape)}")
+                same_device([("eps", probe)], dev, "the state")
+                probe = probe.detach().to(torch.float32).contiguous()
+            else:
+                if len(logp["seeds"]) != B:
+                    raise ValueError(f"probe_seeds must hold one integer per trajectory ({B}), got {len(logp['seeds'])}")
+                wrapped = [(int(v) & _MASK64) - (1 << 64) if (int(v) & _MASK64) >> 63 else int(v) & _MASK64 for v in logp["seeds"]]
+                seeds = torch.tensor(wrapped, dtype=torch.int64).to(dev)  # (the bits of the unsigned seeds)
+            begin_args = (n_out, out.data_ptr(), out_logp.data_ptr(), int(each), log_rows, probe.data_ptr() if probe is not None else None,
+                          seeds.data_ptr() if seeds is not None else None)
         ws = net.workspace(io.B, io.T, io.L, dev, need=getattr(lib, head["entry"] + "_workspace_bytes")(net._handle, io.B, io.T, io.L, *layout))
         desc, times = self._dopri_desc(grid, rtol, atol, reverse)
 
@@ -823,8 +854,7 @@ class Sampler:
             raw = _lib.to_host(ws[at:at + max(stride * count, C.sizeof(cls))]).tobytes()
             return [cls.from_buffer_copy(raw, stride * i) for i in range(count)]
 
-        _lib.call(dev, head["entry"] + "_begin", net._handle, C.byref(io), C.byref(desc), times, *layout[:1], out.data_ptr(), *layout[1:], ws.data_ptr(),
-                  ws.numel())
+        _lib.call(dev, head["entry"] + "_begin", net._handle, C.byref(io), C.byref(desc), times, *begin_args, ws.data_ptr(), ws.numel())
         polled, = records(head["polled"], head["polled_at"])
         while not polled.done:
             _lib.call(dev, head["entry"] + "_advance", net._handle, C.byref(io), int(self.attempts_per_poll), ws.data_ptr(), ws.numel())
@@ -846,6 +876,9 @@ class Sampler:
             logs = [table[b, :min(c.accepted + c.rejected, log_rows)].clone() for b, c in enumerate(ctl)]
         self.last_ode_log = logs if each else logs[0]
         self.last_ode_state = ws[head["state_at"]:head["state_at"] + 4 * x.numel()].view(torch.float32).reshape(x.shape).clone()
+        if logp is not None:
+            side_at = D.logp_side_offset(head["state_at"], x.numel())
+            self.last_ode_logp_state = ws[side_at:side_at + 4 * B].view(torch.float32).clone()
         del keep
         hit_limit = [b for b, c in enumerate(ctl) if c.status == D.STATUS_MAX_STEPS]
         non_finite = [b for b, c in enumerate(ctl) if c.status == D.STATUS_NON_FINITE]
@@ -855,6 +888,8 @@ class Sampler:
             failure = DOPRI_MAX_STEPS_MESSAGE if hit_limit else DOPRI_NON_FINITE_MESSAGE if non_finite else None
         if failure:
             raise RuntimeError(failure)
+        if logp is not None:
+            return (out if out.dtype == init.dtype else out.to(init.dtype)), out_logp
         return out if out.dtype == init.dtype else out.to(init.dtype)
 
     def _dopri_desc(self, grid, rtol, atol, reverse):
@@ -914,7 +949,20 @@ class Sampler:
 
         return _sample
 
-    def sample_ode_likelihood(self, *, sampling_method="dopri5", num_steps=50, atol=1e-6, rtol=1e-3, eps=None):
+    def _prior_logp_rows(self, z: Tensor) -> Tensor:
+        """``Transport.prior_logp(z)`` for the forms of ``sample_ode_likelihood`` whose trajectories do not depend on the batch: on float32
+        GPU tensors the sum of squares is ``dot_rows(z, z)`` - fp64, a fixed order per row - where a torch reduction may choose its order by
+        the shape of the batch; the value, rounded once to ``z``'s dtype, is the same number to within that rounding."""
+        if not _lib.device_form(z):
+            return self.transport.prior_logp(z)
+        try:
+            sq = dot_rows(z, z)
+        except _lib.LibraryMissing:  # (an arbitrary callable on a GPU needs no library)
+            return self.transport.prior_logp(z)
+        return (-0.5 * z[0].numel() * math.log(2.0 * math.pi) - sq / 2.0).to(z.dtype)
+
+    def sample_ode_likelihood(self, *, sampling_method="dopri5", num_steps=50, atol=1e-6, rtol=1e-3, eps=None, controller="host", step_control="batch",
+                              probe_seeds=None):
         """``fn(x, model, **model_kwargs) -> (logp, z)`` as the reference's ``Sampler.sample_ode_likelihood`` (transport.py:413-473): the
         probability-flow ODE from the data ``x`` to the prior with the log-density change beside it, the divergence of the drift estimated by
         Hutchinson's ``eps . (J eps)`` with a Rademacher probe.  The drift is evaluated at ``1 - t``; the augmented right-hand side is
@@ -932,9 +980,32 @@ class Sampler:
         serve raises ``NotImplementedError``.  Any other callable runs the reference's autograd expression in torch
         (``"likelihood-generic"``): autograd through ``model`` gives the divergence term of every evaluation; as in the reference (no
         ``create_graph``) the state, the drift and that term leave the evaluation detached, so ``logp`` carries no graph to the caller's
-        parameters.  ``last_ode_stats["nfe"]`` counts the drift evaluations."""
+        parameters.  ``last_ode_stats["nfe"]`` counts the drift evaluations.
+
+        ``controller`` / ``step_control`` (this package's extras, adaptive ``dopri5`` only; the defaults run the path above bit for bit), as
+        in :meth:`sample_ode`.  ``step_control="trajectory"`` solves ``B`` vectors ``[x_b | logp_b]`` with a step controller each, so that a
+        trajectory's ``logp`` does not depend on its batch companions; with ``controller="host"`` through :func:`dopri5_solve_each` (one time
+        per row; in torch on CPU tensors and any callable).  ``controller="device"`` runs the whole augmented solve inside the library
+        (``lsl_dopri_logp_*``, DESIGN.md 6.2.1: a tangent pass per evaluation, the controller in device memory; ``last_path ==
+        "likelihood-device-solve"`` / ``"likelihood-device-solve-each"``): trajectory ``b`` of the per-trajectory call has the bits of the
+        batch-form call on ``[b:b+1]``.  It takes ``eps`` as a tensor or ``None`` - then the probe of trajectory ``b`` is drawn on the
+        device from ``probe_seeds[b]`` (one integer per trajectory; default ``mix_seed(next_call_seed(), b)``), its evaluation count and
+        the element's index, so it does not depend on the batch either; a callable ``eps`` raises ``NotImplementedError``.
+        ``last_ode_stats`` / ``last_ode_log`` / ``last_ode_state`` (and ``last_ode_logp_state``) are filled as by :meth:`sample_ode`."""
         tr = self.transport
         fixed = sampling_method in FIXED_GRID_RK_METHODS
+        if controller not in ("host", "device"):
+            raise ValueError(f"controller must be 'host' or 'device', got {controller!r}")
+        if step_control not in ("batch", "trajectory"):
+            raise ValueError(f"step_control must be 'batch' or 'trajectory', got {step_control!r}")
+        if controller == "device" and sampling_method != "dopri5":
+            raise ValueError(f"controller='device' is the adaptive dopri5 solver's; {sampling_method!r} has no step controller")
+        if step_control == "trajectory" and sampling_method != "dopri5":
+            raise ValueError(f"step_control='trajectory' is the adaptive dopri5 solver's; {sampling_method!r} has no step controller")
+        if controller == "device" and callable(eps):
+            raise NotImplementedError("sample_ode_likelihood(controller='device') takes eps as a tensor or None (drawn on the device): a callable "
+                                      "probe would need the host at every evaluation")
+        each = step_control == "trajectory"
         if sampling_method not in ("dopri5", "euler") and not fixed:
             raise NotImplementedError(f"ODE solver {sampling_method!r}: 'euler', 'midpoint', 'heun3', 'rk4' and adaptive 'dopri5' are implemented")
         t0, t1 = tr.check_interval(tr.train_eps, tr.sample_eps, sde=False, eval=True, reverse=False, last_step_size=0.0)
@@ -948,6 +1019,58 @@ class Sampler:
                 raise ValueError(f"eps must be shaped like the state {tuple(xs.shape)}, got {tuple(e.shape)}")
             return e
 
+        def _solve_each(x, model, net, model_kwargs):
+            """The host restatement of the per-trajectory augmented solve: :func:`dopri5_solve_each` on rows ``[x_b | logp_b]``, one time per
+            row, the right-hand side of ``rhs`` below row by row with each row's coefficients"""
+            B, shape, n_el = x.shape[0], tuple(x.shape), x[0].numel()
+            wide = (B,) + (1,) * (x.dim() - 1)
+
+            def rhs_each(ts: Sequence[float], state: Tensor) -> Tensor:
+                xs = state[:, :n_el].reshape(shape)
+                tfs = [_f32(1.0 - t) for t in ts]
+                tv = torch.tensor(tfs, dtype=torch.float32, device=x.device)
+                try:
+                    coeffs = [tr.velocity_coeffs(tf) for tf in tfs]
+                except ZeroDivisionError:
+                    raise ZeroDivisionError(f"sample_ode_likelihood: the {tr.path_type.name} path with {tr.model_type.name} prediction has no finite "
+                                            f"velocity at one of the times {tfs} (sigma = 0 there; the reference's expression returns NaN): its "
+                                            f"interval [{t0}, {t1}] evaluates the drift at 1 - t") from None
+                e = draw(xs)
+                if net is not None:
+                    e = e.to(device=x.device, dtype=torch.float32)
+                    out, jt = net.jvp(xs.contiguous(), tv, model_kwargs["x_cond"], model_kwargs["x_cond_mask"], model_kwargs.get("y"), tangent=e)
+                    dots = dot_rows(e, jt)
+                    drift = torch.cat([vx * xs[b:b + 1] + vm * out[b:b + 1] for b, (vx, vm) in enumerate(coeffs)])
+                    dlogp = torch.cat([(vx * n_el + vm * dots[b:b + 1]).to(state.dtype) for b, (vx, vm) in enumerate(coeffs)])
+                else:
+                    e = e.to(xs)
+                    vx = torch.tensor([c[0] for c in coeffs], dtype=xs.dtype, device=xs.device).reshape(wide)
+                    vm = torch.tensor([c[1] for c in coeffs], dtype=xs.dtype, device=xs.device).reshape(wide)
+                    with torch.enable_grad():
+                        xg = xs.detach().requires_grad_(True)
+                        drift = vx * xg + vm * model(xg, tv.to(xs.dtype), **model_kwargs)
+                        grad = torch.autograd.grad(torch.sum(drift * e), xg)[0]
+                    dlogp = torch.stack([torch.sum(grad[b] * e[b]) for b in range(B)])
+                    drift = drift.detach()
+                return torch.cat([-drift.reshape(B, n_el), dlogp.reshape(B, 1).to(state.dtype)], dim=1)
+
+            y0 = torch.cat([x.detach().reshape(B, n_el), torch.zeros(B, 1, dtype=x.dtype, device=x.device)], dim=1)
+            stats = None
+            try:
+                ys, stats = dopri5_solve_each(rhs_each, y0, grid, rtol, atol, max_steps=self.ode_max_steps)
+            except RuntimeError as err:
+                stats = getattr(err, "stats", None)
+                raise
+            finally:
+                if stats is not None:
+                    self.last_ode_log, state = stats.pop("log"), stats.pop("state")
+                    self.last_ode_state, self.last_ode_logp_state = state[:, :n_el].reshape(shape), state[:, n_el]
+                    stats["network_passes"] = stats.pop("passes")
+                    self.last_ode_stats = stats
+            z = ys[-1][:, :n_el].reshape(shape).contiguous()
+            self.last_delta_logp = ys[-1][:, n_el]
+            return self._prior_logp_rows(z) - ys[-1][:, n_el], z
+
         def _sample_fn(x, model, **model_kwargs):
             B, shape, n_el = x.shape[0], tuple(x.shape), x[0].numel()
             net = resolve_backbone(model)
@@ -960,7 +1083,20 @@ class Sampler:
                 if why is not None:
                     raise NotImplementedError(f"sample_ode_likelihood on a lam_slide_amd.LatentSIV3 needs the library's tangent pass: {why}")
                 check_model_kwargs(model_kwargs)  # (where its tensors are: LatentSIV3.jvp)
-            self.last_path = "likelihood-device" if net is not None else "likelihood-generic"
+            if controller == "device":
+                if net is None:
+                    raise RuntimeError("fused sampling requested but the model is not a lam_slide_amd.LatentSIV3 on a GPU")
+                seeds = None
+                if eps is None:
+                    call_seed = self.next_call_seed() if probe_seeds is None else None
+                    seeds = [mix_seed(call_seed, b) for b in range(B)] if probe_seeds is None else [int(v) for v in probe_seeds]
+                out, out_logp = self._run_dopri_device(net, x.detach(), grid, rtol, atol, True, model_kwargs, each=each, logp={"eps": eps, "seeds": seeds})
+                z = out[-1]
+                self.last_delta_logp = out_logp[-1]
+                return self._prior_logp_rows(z) - out_logp[-1].to(z.dtype), z
+            self.last_path = ("likelihood-device" if net is not None else "likelihood-generic") + ("-each" if each else "")
+            if each:
+                return _solve_each(x, model, net, model_kwargs)
             count = [0]
 
             def rhs(t: float, state: Tensor) -> Tensor:
@@ -1005,6 +1141,7 @@ class Sampler:
                 self.last_ode_stats = {"nfe": count[0], "accepted": len(grid) - 1, "rejected": 0}
             z = last[:B * n_el].reshape(shape)
             delta_logp = last[B * n_el:]
+            self.last_delta_logp = delta_logp
             return tr.prior_logp(z) - delta_logp, z
 
         return _sample_fn
